@@ -61,7 +61,29 @@ def parse_args(argv=None):
                     help="distinct reads of the end-to-end block (host seed lookup + upload + engine + TSV formatting, measured after the timed region; 0 = skip)")
     ap.add_argument("--rehearse", action="store_true",
                     help="control-flow rehearsal WITHOUT the engine (CPU, gloo): launch, rendezvous, barrier, gather, max-over-ranks, one JSON line; value is null")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the placement records of batch 0's last timed step (rank 0) as DIR/<field>.npy, one float64 "
+                         "array per field the step computes, over the reads it placed (DIR/read_index.npy: which reads); the inputs are seeded, so two "
+                         "builds can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+def dump_outputs(d, recs, fix_root_loglik):
+    """one float64 array per field of the placement records (integer fields are exact in float64), over the placed reads: an unplaced
+    read (c_node < 0) has no placement and NaN in every number.  root_loglik is computed only under hu_opts.fix_root_loglik (NaN otherwise)"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    placed = np.nonzero(recs["c_node"] >= 0)[0]
+    np.save(os.path.join(d, "read_index.npy"), placed.astype(np.float64))
+    for name in recs.dtype.names:
+        if name == "root_loglik" and not fix_root_loglik:
+            continue
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(recs[name][placed], np.float64))
 
 
 def cpu_quota():
@@ -341,6 +363,7 @@ def main():
 
     timed_ms = [dict() for _ in range(nb)]
     timed_n = [0] * nb
+    last_out = [None] * nb                  # each batch's placement records from its last step
 
     def run_steps(i, steps):
         out = None
@@ -350,6 +373,7 @@ def main():
             for k, v in batches[i].timings().items():       # HIP events on this batch's stream, every timed step
                 timed_ms[i][k] = timed_ms[i].get(k, 0.0) + v
             timed_n[i] += 1
+        last_out[i] = out
         return out
 
     def run(total):
@@ -364,7 +388,7 @@ def main():
     list(pool.map(lambda i: run_steps(i, 1), range(nb)))
     run(args.warmup)
     for i in range(nb):
-        timed_ms[i].clear(); timed_n[i] = 0
+        timed_ms[i].clear(); timed_n[i] = 0; last_out[i] = None
     barrier()
     cpu0 = os.times()
     t1 = time.perf_counter()
@@ -379,6 +403,9 @@ def main():
     dt = max_over_ranks(dt_local)
     total_reads = args.batch * args.steps * world
     value = total_reads / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out[0], opts.fix_root_loglik)        # batch 0 runs a timed step whenever --steps >= 1
+        log("outputs of batch 0's last timed step written to %s" % args.dump_outputs)
 
     # ---- per-kernel device times (HIP events on the batch's stream)
     # (a) inside the timed region: the kernels of the other batches in flight share the GPU (elapsed-with-contention)

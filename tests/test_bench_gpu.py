@@ -75,3 +75,28 @@ def test_paired_line_and_the_stable_order_as_the_timed_region():
     assert j2["config"]["seed_order"] == "stable" and j2["cpu_baseline"]["oracle_seed_order"].startswith("TIE_STABLE") and j2["cpu_baseline"]["unexplained_best_branch_diffs"] == 0
     sr2 = j2["seed_order_reference"]
     assert sr2["reads_compared"] == 96 and sr2["unexplained_best_branch_diffs"] == 0 and sr2["candidate_set_differs"] == 0 and sr2["oracle_seed_order"].startswith("TIE_LIBSTDCXX"), sr2
+
+
+def test_dump_outputs_are_the_timed_steps_records_and_repeat_exactly(tmp_path):
+    """--dump-outputs DIR: the placement records of the timed path's last step, one float64 array per field it computes, over the reads it
+    placed (read_index.npy); every number finite; the inputs are seeded, so a second run writes the same numbers; --steps is the number of
+    timed steps the line reports"""
+    import numpy as np
+    from hmmufotu_amd.engine import PLACE_DTYPE
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        j = _run(["--cpu-sample", "0", "--e2e-reads", "0", "--dump-outputs", str(d)] + SMALL)
+        assert j["steps"] == 4 and j["ms_per_step"] > 0
+    names = ["read_index"] + [n for n in PLACE_DTYPE.names if n != "root_loglik"]      # root_loglik: only under hu_opts.fix_root_loglik
+    assert sorted(f.name for f in dirs[0].iterdir()) == sorted(n + ".npy" for n in names)
+    got = [{n: np.load(str(d / (n + ".npy"))) for n in names} for d in dirs]
+    n_placed = len(got[0]["read_index"])
+    assert 48 < n_placed <= 96
+    assert np.array_equal(got[0]["read_index"], np.unique(got[0]["read_index"])) and got[0]["read_index"].max() < 96
+    for n in names:
+        a, b = got[0][n], got[1][n]
+        assert a.dtype == np.float64 and a.shape == (n_placed,), (n, a.dtype, a.shape)
+        assert np.isfinite(a).all(), n
+        assert np.array_equal(a, b), n
+    assert (got[0]["c_node"] >= 0).all()
+    assert sum(f.stat().st_size for f in dirs[0].iterdir()) < 64 << 20

@@ -652,11 +652,17 @@ def test_tree_pre_evaluation(model, dg_k, pi):
         assert np.abs(h - oh).max() < 1e-12 and np.abs(h - db.height).max() < 1e-12
 
 
+def cli_msa_text():
+    """the leaf rows of test_cli_end_to_end's database as the alignment its <DB>.csfm is built from"""
+    db = get_db(120, 700, "GTR", dg_k=4)
+    return "".join(">n%d\n%s\n" % (u, "".join("ACGT"[x] if x >= 0 else "-" for x in db.seq[u])) for u in np.nonzero(db.is_leaf)[0])
+
+
 def test_cli_end_to_end(tmp_path):
     """hmmufotu-amd <DB> <reads.fasta>: DB files in the reference's formats, host seed index, batched
     engine, TSV — identical to driving the ABI from Python with the same seeds; FASTQ + PE too"""
     E = _engine()
-    import os, subprocess
+    import gzip, hashlib, os, subprocess
     from hmmufotu_amd import synth
     db = get_db(120, 700, "GTR", dg_k=4)
     cli = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "hmmufotu_amd", "bin", "hmmufotu-amd")
@@ -703,21 +709,20 @@ def test_cli_end_to_end(tmp_path):
     assert outm.returncode == 0 and "2 device(s) x 2 batches in flight" in outm.stderr, outm.stderr
     assert [l for l in outm.stdout.split("\n") if l and not l.startswith("#")][1:] == want
     assert subprocess.run([cli, pre, fa, "--gpus", "9"], capture_output=True).returncode != 0          # more devices than the box has
-    # with the database's own <DB>.csfm beside it (written here by the reference's libcds + libdivsufsort, oracle/_ref/csfm_ref, from the
-    # leaf rows): the CLI reads it instead of rebuilding the index; these reads come from single leaves, so the assignments are the same
-    ref_writer = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "csfm_ref")
-    if os.path.exists(ref_writer):
-        msa = str(tmp_path / "msa.fasta")
-        with open(msa, "w") as f:
-            for u in leaves:
-                f.write(">n%d\n%s\n" % (u, "".join("ACGT"[x] if x >= 0 else "-" for x in db.seq[u])))
-        assert subprocess.run([ref_writer, msa, pre + ".csfm"], capture_output=True).returncode == 0
-        outc = subprocess.run([cli, pre, fa, "-s", "1", "-v"], capture_output=True, text=True, timeout=300)
-        assert outc.returncode == 0 and "seed index read from the .csfm" in outc.stderr, outc.stderr
-        assert [l for l in outc.stdout.split("\n") if l and not l.startswith("#")][1:] == want
-        outn = subprocess.run([cli, pre, fa, "-s", "1", "-v", "--no-csfm"], capture_output=True, text=True, timeout=300)
-        assert outn.returncode == 0 and "seed index built" in outn.stderr
-        os.remove(pre + ".csfm")
+    # with the database's own <DB>.csfm beside it (written by the reference's libcds + libdivsufsort, oracle/_ref/csfm_ref, from the
+    # leaf rows; stored as tests/golden/cli_db.csfm.gz by tests/golden/make_ref_seq_golden.py): the CLI reads it instead of rebuilding
+    # the index; these reads come from single leaves, so the assignments are the same
+    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    with np.load(os.path.join(gold, "ref_seq.npz")) as z:
+        assert hashlib.sha256(cli_msa_text().encode()).hexdigest() == str(z["cli_msa_sha256"])      # the rows the stored index was built from
+    with gzip.open(os.path.join(gold, "cli_db.csfm.gz"), "rb") as fi, open(pre + ".csfm", "wb") as fo:
+        fo.write(fi.read())
+    outc = subprocess.run([cli, pre, fa, "-s", "1", "-v"], capture_output=True, text=True, timeout=300)
+    assert outc.returncode == 0 and "seed index read from the .csfm" in outc.stderr, outc.stderr
+    assert [l for l in outc.stdout.split("\n") if l and not l.startswith("#")][1:] == want
+    outn = subprocess.run([cli, pre, fa, "-s", "1", "-v", "--no-csfm"], capture_output=True, text=True, timeout=300)
+    assert outn.returncode == 0 and "seed index built" in outn.stderr
+    os.remove(pre + ".csfm")
     # -S <seed>: seed hits drawn from all occurrences (CSFMIndex::locateOne) — reproducible, whatever the batching; same lines as the ABI
     # driven from Python with the same draws
     outs = [subprocess.run([cli, pre, fa, "-s", "1", "-S", "7", "--batch", bs], capture_output=True, text=True, timeout=300) for bs in ("16", "5")]
