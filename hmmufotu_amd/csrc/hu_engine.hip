@@ -25,6 +25,7 @@
 #include "hu_kern_blk.h"
 #include "hu_kern_refsort.h"
 #include "hu_kern_rank.h"
+#include "hu_kern_anneal.h"
 
 #define HIPCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { \
 	hu_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return HU_ERR_DEVICE; } } while(0)
@@ -160,6 +161,14 @@ struct hu_db {
 	int64_t hbmBytes = 0;
 	int32_t* dAnnoId = nullptr;    /* [nNodes] class of the node's taxon annotation (calcQValues sums by taxon name) */
 	double* dLlTab = nullptr;      /* [csLen + 1] the final loglik placeSeq returns for a region of k columns: k sequential additions of log(sum_i pi_i e) */
+	/* the primer scan (hu_anneal_batch), built on its first call: the planes store node codes -1 and -2 alike as v = 0, so a database
+	 * with any -1 gets one more plane, [WQ][nNodesPad] uint4 of "code == -1" in scan order; leafMask: one bit per node, neighbors.size() == 1 */
+	bool hasInvalidCode = false;
+	std::mutex annealMu;
+	bool annealReady = false;
+	uint4* dInvPlane = nullptr;
+	unsigned long long* dLeafMask = nullptr;
+	std::vector<int32_t> colPos;    /* CS column -> scan position (the inverse of HuDbDev::posCol) */
 };
 
 template<class X> static int dev_alloc(hu_db* db, X** p, size_t n) {
@@ -292,6 +301,7 @@ extern "C" int hu_db_create(const hu_profile_desc* prof, const hu_tree_desc* tre
 			const int8_t* s = &db->seq[(size_t) i * L];
 			for(int cc = 0; cc < L; ++cc) {
 				const int code = s[cc];
+				if(code == -1) db->hasInvalidCode = true;
 				if(code < 0) continue;
 				const int c = colPos[cc];
 				const int q = c >> 7, w = (c >> 5) & 3; const uint32_t bit = 1u << (c & 31);
@@ -878,6 +888,7 @@ struct hu_batch {
 	int nFullRedo = 0;          /* sequences of the last align call whose banded DP found no path: full DP, one launch */
 	DBuf<double> dRedoScr; DBuf<HuReadDesc> dRedoDesc; DBuf<HuVitOut> dRedoVit;    /* the redo launches' own scratch: kept (an allocation or a release stalls every stream of the device) */
 	PinnedVec<HuAlnDev> hAlns;
+	DBuf<int32_t> dAnRow, dAnThr, dAnTileQ; DBuf<int2> dAnReg; DBuf<uint32_t> dAnMasks; DBuf<unsigned long long> dAnHits;      /* hu_anneal_batch */
 	PinnedVec<int32_t> hStart, hEnd, hSeedCnt, hSeedId;
 	PinnedVec<uint32_t> hSeedDN;
 	PinnedVec<HuEstOut> hEst;
@@ -2762,3 +2773,190 @@ extern "C" int hu_batch_get_placements(hu_batch* b, hu_place_rec* best) try {
 	memcpy(best, b->best.data(), b->best.size() * sizeof(hu_place_rec));
 	return HU_OK;
 } catch(...) { return hu_catch_all("hu_batch_get_placements"); }
+
+/* ------------------------------------------------------------------------------ primer scan (hmmufotu-anneal) */
+extern "C" int64_t hu_anneal_max_mismatch(double max_dist, int32_t len) {
+	if(len < 1) return -1;
+	int64_t d = std::min<int64_t>(len, max_dist >= 0 ? (int64_t) std::min(std::floor(max_dist * len), (double) len) + 1 : 0);
+	while(d >= 0 && !(static_cast<double>(d) / len <= max_dist)) --d;      /* pDist <= maxDist, src/hmmufotu-anneal.cpp:272-273 */
+	return d;
+}
+extern "C" const char* hu_anneal_header(void) {
+	return "id\tdescription\tsequence\tstrand\tCS_start\tCS_end\talignment\ttotal_nodes\ttotal_leaves\thit_nodes\thit_leaves\tefficiency_nodes\tefficiency_leaves";
+}
+extern "C" int hu_anneal_match_table(uint8_t* out) {
+	if(!out) return HU_ERR_ARG;
+	for(int c = 0; c < 256; ++c) out[c] = (uint8_t) hu_anneal_accept((unsigned char) c);
+	return HU_OK;
+}
+
+/* the per-database part, once: leaf flags, the scan position of every column, the plane of code -1 when the database has that code */
+/* PTUNode::isLeaf (src/PhyloTreeUnrooted.h:199): one neighbour, so a root with a single child is a leaf */
+static std::vector<char> leaf_flags(const hu_db* db) {
+	const int n = db->dev.nNodes;
+	std::vector<int32_t> deg(n, 0);
+	for(int i = 0; i < n; ++i) if(db->parent[i] >= 0) { deg[i]++; deg[db->parent[i]]++; }
+	std::vector<char> leaf(n);
+	for(int i = 0; i < n; ++i) leaf[i] = deg[i] == 1;
+	return leaf;
+}
+
+static int anneal_prepare(hu_db* db) {
+	std::lock_guard<std::mutex> lk(db->annealMu);
+	if(db->annealReady) return HU_OK;
+	const HuDbDev& d = db->dev;
+	const int n = d.nNodes, L = d.csLen;
+	const size_t np = (size_t) d.nNodesPad;
+	int rc;
+	const std::vector<char> isLeaf = leaf_flags(db);
+	std::vector<unsigned long long> leaf(np / 64, 0ull);
+	for(int i = 0; i < n; ++i) if(isLeaf[i]) leaf[i >> 6] |= 1ull << (i & 63);
+	if((rc = dev_upload(db, &db->dLeafMask, leaf.data(), leaf.size())) != HU_OK) return rc;
+	std::vector<int32_t> colPos(L, -1);
+	{
+		int p = 0;
+		for(int k = 1; k <= d.K; ++k) colPos[db->prof.p2cs[k] - 1] = p++;
+		for(int c = 0; c < L; ++c) if(colPos[c] < 0) colPos[c] = p++;
+	}
+	if(db->hasInvalidCode) {
+		std::vector<uint4> pl((size_t) d.WQ * np, make_uint4(0, 0, 0, 0));
+		for(int i = 0; i < n; ++i) {
+			const int8_t* sq = &db->seq[(size_t) i * L];
+			for(int cc = 0; cc < L; ++cc) if(sq[cc] == -1) {
+				const int c = colPos[cc];
+				(&pl[(size_t)(c >> 7) * np + i].x)[(c >> 5) & 3] |= 1u << (c & 31);
+			}
+		}
+		if((rc = dev_upload(db, &db->dInvPlane, pl.data(), pl.size())) != HU_OK) return rc;
+	}
+	db->colPos.swap(colPos);
+	db->annealReady = true;
+	return HU_OK;
+}
+
+/* buildGlobalAlign writes a matched base as PrimarySeq::charAt gives it, in the case it was read, and an inserted one lower-cased
+ * (src/BandedHMMP7.cpp:1035-1046); the batch's rows hold the upper-case bases the DP ran on.  For each primer whose text has lower-case
+ * letters, the M states of its trace are walked: state k takes the k-th upper-case letter of the region, and that letter is lower-cased
+ * where the base it came from was read in lower case.  The rows then hold the reference's alignment string. */
+static int anneal_restore_case(hu_batch* b, const int32_t* row_of_primer, int n, const char* const* as_read) {
+	const int L = b->db->dev.csLen;
+	std::vector<char> trace, reg;
+	for(int i = 0; i < n; ++i) {
+		const int r = row_of_primer[i];
+		if(r < 0 || !as_read[i]) continue;
+		const char* t = as_read[i];
+		const HuReadDesc& rd = b->hDescs[r];
+		const size_t len = strlen(t);
+		if(len != (size_t) rd.len) { hu_set_error("hu_anneal_batch: the text of primer %d has %zu letters, its row %d %d", i, len, r, rd.len); return HU_ERR_ARG; }
+		bool lower = false;
+		for(size_t j = 0; j < len; ++j) {
+			if(toupper((unsigned char) t[j]) != (unsigned char) b->hBases[rd.baseOff + j]) { hu_set_error("hu_anneal_batch: the text of primer %d is not the bases of row %d", i, r); return HU_ERR_ARG; }
+			lower |= islower((unsigned char) t[j]) != 0;
+		}
+		if(!lower) continue;
+		const HuVitOut& v = b->hVit[r];
+		const HuAlnDev& a = b->hAlns[r];
+		const int c0 = a.csStart - 1, w = a.csEnd - a.csStart + 1;
+		trace.resize((size_t) std::max(v.traceLen, 1)); reg.resize((size_t) w);
+		char* row = b->dRows.p + (size_t) r * L + c0;
+		HIPCHK(hipMemcpyAsync(trace.data(), b->dTraces.p + rd.traceOff, (size_t) v.traceLen, hipMemcpyDeviceToHost, b->stream));
+		HIPCHK(hipMemcpyAsync(reg.data(), row, (size_t) w, hipMemcpyDeviceToHost, b->stream));
+		HIPCHK(hu_wait(b->stream));
+		int j = a.seqStart - 1, c = 0;     /* 0-based read position of the next state, next region column */
+		for(int k = 0; k < v.traceLen; ++k) {
+			if(trace[k] == 'I') { ++j; continue; }
+			if(trace[k] != 'M') continue;
+			while(c < w && !isupper((unsigned char) reg[c])) ++c;
+			if(c >= w || j < 0 || j >= rd.len) { hu_set_error("hu_anneal_batch: the trace of row %d does not fit its alignment", r); return HU_ERR_STATE; }
+			if(islower((unsigned char) t[j])) reg[c] = (char) tolower((unsigned char) reg[c]);
+			++c; ++j;
+		}
+		HIPCHK(hipMemcpyAsync(row, reg.data(), (size_t) w, hipMemcpyHostToDevice, b->stream));
+		HIPCHK(hu_wait(b->stream));
+	}
+	return HU_OK;
+}
+
+extern "C" int hu_anneal_batch(hu_batch* b, const int32_t* row_of_primer, int n, const char* const* as_read, double max_dist, int64_t* hit_nodes, int64_t* hit_leaves) try {
+	if(!b || n < 0 || (n > 0 && (!row_of_primer || !hit_nodes || !hit_leaves))) { hu_set_error("hu_anneal_batch: bad argument"); return HU_ERR_ARG; }
+	if(!(max_dist >= 0)) { hu_set_error("hu_anneal_batch: max_dist must be >= 0"); return HU_ERR_ARG; }
+	if(b->state < ST_ALIGNED || b->fromCodes) { hu_set_error("hu_anneal_batch: no aligned reads"); return HU_ERR_STATE; }
+	hu_db* db = b->db;
+	const HuDbDev& d = db->dev;
+	if(d.winStart != 0 || d.winLen != d.csLen) { hu_set_error("hu_anneal_batch: the database holds a column window; anneal needs the whole database"); return HU_ERR_ARG; }
+	if(d.nNodesPad / 256 > 65535) { hu_set_error("hu_anneal_batch: too many nodes for one launch"); return HU_ERR_ARG; }
+	for(int i = 0; i < n; ++i) {
+		const int r = row_of_primer[i];
+		if(r >= b->nSeq || (r >= 0 && (b->hAlns[r].status != HU_READ_OK || b->hAlns[r].csStart < 1 || b->hAlns[r].csEnd < b->hAlns[r].csStart || b->hAlns[r].csEnd > d.csLen))) {
+			hu_set_error("hu_anneal_batch: primer %d names row %d, which is not an aligned row of the batch", i, r); return HU_ERR_ARG;
+		}
+	}
+	HIPCHK(hipSetDevice(db->device));
+	int rc;
+	if((rc = anneal_prepare(db)) != HU_OK) return rc;
+	if(n == 0) return HU_OK;
+	if(as_read && (rc = anneal_restore_case(b, row_of_primer, n, as_read)) != HU_OK) return rc;
+	constexpr int T = HU_ANNEAL_TILE;
+	const int tiles = (n + T - 1) / T, WQ = d.WQ;
+	/* slots in order of region start: the primers of a tile then share their few quads (in input order a tile of scattered primers
+	 * spans ~25 quads, and every primer of it is scored over all of them) */
+	std::vector<int32_t> slotOf(n), rowOf(n);
+	for(int i = 0; i < n; ++i) slotOf[i] = i;
+	auto key = [&](int i) { const int r = row_of_primer[i]; return r < 0 ? INT32_MAX : b->hAlns[r].csStart; };
+	std::stable_sort(slotOf.begin(), slotOf.end(), [&](int x, int y) { return key(x) < key(y); });
+	for(int s = 0; s < n; ++s) rowOf[s] = row_of_primer[slotOf[s]];
+	std::vector<int32_t> thr(n, -1), tileQ((size_t) tiles * (WQ + 2), 0);
+	std::vector<int2> reg(n, make_int2(0, -1));
+	std::vector<char> used(WQ);
+	int nMask = 0, maxNq = 0;
+	for(int tile = 0; tile < tiles; ++tile) {
+		std::fill(used.begin(), used.end(), 0);
+		for(int s = tile * T; s < std::min(n, tile * T + T); ++s) {
+			const int r = rowOf[s];
+			if(r < 0) continue;
+			const int c0 = b->hAlns[r].csStart - 1, c1 = b->hAlns[r].csEnd - 1;
+			reg[s] = make_int2(c0, c1);
+			thr[s] = (int32_t) hu_anneal_max_mismatch(max_dist, c1 - c0 + 1);
+			for(int c = c0; c <= c1; ++c) used[db->colPos[c] >> 7] = 1;
+		}
+		int32_t* tq = &tileQ[(size_t) tile * (WQ + 2)];
+		tq[0] = nMask;
+		for(int q = 0; q < WQ; ++q) if(used[q]) tq[2 + tq[1]++] = q;
+		nMask += tq[1];
+		maxNq = std::max(maxNq, (int) tq[1]);
+	}
+	if((rc = b->dAnRow.ensure(n)) != HU_OK || (rc = b->dAnThr.ensure(n)) != HU_OK || (rc = b->dAnReg.ensure(n)) != HU_OK ||
+	   (rc = b->dAnTileQ.ensure(tileQ.size())) != HU_OK || (rc = b->dAnMasks.ensure((size_t) std::max(nMask, 1) * T * 32)) != HU_OK ||
+	   (rc = b->dAnHits.ensure((size_t) n * 2)) != HU_OK) return rc;
+	HIPCHK(hipMemcpyAsync(b->dAnRow.p, rowOf.data(), (size_t) n * 4, hipMemcpyHostToDevice, b->stream));
+	HIPCHK(hipMemcpyAsync(b->dAnThr.p, thr.data(), (size_t) n * 4, hipMemcpyHostToDevice, b->stream));
+	HIPCHK(hipMemcpyAsync(b->dAnReg.p, reg.data(), (size_t) n * sizeof(int2), hipMemcpyHostToDevice, b->stream));
+	HIPCHK(hipMemcpyAsync(b->dAnTileQ.p, tileQ.data(), tileQ.size() * 4, hipMemcpyHostToDevice, b->stream));
+	HIPCHK(hipMemsetAsync(b->dAnHits.p, 0, (size_t) n * 2 * sizeof(unsigned long long), b->stream));
+	(void) hipGetLastError();
+	if(maxNq > 0) {
+		k_anneal_masks<<<dim3((unsigned) tiles, (unsigned) maxNq), 128, 0, b->stream>>>(d, b->dRows.p, b->dAnRow.p, b->dAnReg.p, n, b->dAnTileQ.p, b->dAnMasks.p);
+		HIPCHK(hipGetLastError());
+		const dim3 grid((unsigned) tiles, (unsigned)(d.nNodesPad / 256));
+		if(db->dInvPlane) k_anneal_scan<true><<<grid, 256, 0, b->stream>>>(d, db->dInvPlane, db->dLeafMask, b->dAnMasks.p, b->dAnTileQ.p, b->dAnThr.p, n, b->dAnHits.p);
+		else k_anneal_scan<false><<<grid, 256, 0, b->stream>>>(d, nullptr, db->dLeafMask, b->dAnMasks.p, b->dAnTileQ.p, b->dAnThr.p, n, b->dAnHits.p);
+		HIPCHK(hipGetLastError());
+	}
+	std::vector<unsigned long long> h((size_t) n * 2);
+	HIPCHK(hipMemcpyAsync(h.data(), b->dAnHits.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
+	HIPCHK(hu_wait(b->stream));
+	for(int s = 0; s < n; ++s) {
+		const int i = slotOf[s];
+		const bool ok = rowOf[s] >= 0;
+		hit_nodes[i] = ok ? (int64_t) h[(size_t) s * 2] : -1;
+		hit_leaves[i] = ok ? (int64_t) h[(size_t) s * 2 + 1] : -1;
+	}
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_anneal_batch"); }
+
+extern "C" int hu_db_num_leaves(const hu_db* db, int64_t* n_leaves) try {
+	if(!db || !n_leaves) return HU_ERR_ARG;
+	const std::vector<char> leaf = leaf_flags(db);
+	*n_leaves = std::count(leaf.begin(), leaf.end(), (char) 1);
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_db_num_leaves"); }

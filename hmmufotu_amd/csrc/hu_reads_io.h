@@ -58,7 +58,7 @@ struct LineIn {
 		}
 	}
 };
-static bool next_read(LineIn& in, bool fastq, Read& r) {
+static bool next_read(LineIn& in, bool fastq, Read& r, bool keepCase = false) {
 	std::string line;
 	r = Read();
 	bool got = false;
@@ -82,14 +82,19 @@ static bool next_read(LineIn& in, bool fastq, Read& r) {
 	while(e < line.size() && blank(line[e])) ++e;
 	r.desc = line.substr(e);
 	while(!r.seq.empty() && (r.seq.back() == '\r' || r.seq.back() == '\n')) r.seq.pop_back();
-	for(char& c : r.seq) c = (char) toupper((unsigned char) c);
+	if(!keepCase) for(char& c : r.seq) c = (char) toupper((unsigned char) c);
 	return true;
 }
-static std::string revcom(const std::string& s) { /* IUPACNucl complements (src/IUPACNucl.cpp:52-71) */
+static std::string revcom(const std::string& s) { /* IUPACNucl complements (src/IUPACNucl.cpp:52-71); a lower-case letter keeps its case (IUPACNucl.h:73-75) */
 	std::string r(s.rbegin(), s.rend());
-	for(char& c : r) switch(c) {
+	for(char& ch : r) {
+		const bool lower = islower((unsigned char) ch) != 0;
+		char c = lower ? (char) toupper((unsigned char) ch) : ch;
+		switch(c) {
 		case 'A': c = 'T'; break; case 'T': c = 'A'; break; case 'C': c = 'G'; break; case 'G': c = 'C'; break; case 'U': c = 'A'; break;
 		case 'Y': c = 'R'; break; case 'R': c = 'Y'; break; case 'K': c = 'M'; break; case 'M': c = 'K'; break;
 		case 'B': c = 'V'; break; case 'V': c = 'B'; break; case 'D': c = 'H'; break; case 'H': c = 'D'; break; default: break; }
+		ch = lower ? (char) tolower((unsigned char) c) : c;
+	}
 	return r;
 }

@@ -119,6 +119,29 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
+def anneal_max_mismatch(max_dist: float, length: int) -> int:
+    """the hit threshold of hu_anneal_batch: the largest d with d / length <= max_dist in double precision, -1 if none"""
+    lib = load_library()
+    lib.hu_anneal_max_mismatch.restype = C.c_int64
+    return int(lib.hu_anneal_max_mismatch(C.c_double(max_dist), C.c_int32(length)))
+
+
+def anneal_match_table() -> np.ndarray:
+    """[256] uint8: the node codes each alignment byte matches (bit 0..3 = A C G T, bit 4 = gap -2, bit 5 = invalid -1)"""
+    t = np.zeros(256, np.uint8)
+    _chk(load_library().hu_anneal_match_table(_p(t, C.c_uint8)))
+    return t
+
+
+_COMPL = str.maketrans("ACGTUYRKMBVDHacgtuyrkmbvdh", "TGCAARYMKVBHDtgcaarymkvbhd")
+
+
+def revcom_as_read(s: str) -> str:
+    """PrimarySeq::revcom (src/PrimarySeq.h:229-231): IUPACNucl complements, a lower-case letter complemented in lower case
+    (src/IUPACNucl.h:73-75), every other character kept"""
+    return s[::-1].translate(_COMPL)
+
+
 def device_count() -> int:
     return int(load_library().hu_device_count())
 
@@ -353,6 +376,60 @@ class Database:
                                               _p(out["p2cs"], C.c_int32), _p(out["entry_cost"], C.c_double), _p(out["exit_cost"], C.c_double)))
         return out
 
+    def num_leaves(self) -> int:
+        """PTUnrooted::numLeaves: nodes with one neighbour, a root with a single child included"""
+        v = C.c_int64()
+        _chk(load_library().hu_db_num_leaves(self.h, C.byref(v)))
+        return int(v.value)
+
+    def anneal(self, primers, identity=0.9, strand=3, batch=4096):
+        """hmmufotu-anneal (src/hmmufotu-anneal.cpp:246-290): per primer (IUPAC letters in either case, kept as given), its strand ('+', '-'),
+        the CS region and alignment of the chosen strand, and the hit counts of nodes and leaves at `identity`; None for a primer with no
+        alignment (a letter outside IUPAC included).  Strand choice on the host: the reverse complement (case kept letter by letter)
+        replaces the forward alignment only at a strictly lower cost.  The Viterbi scores use the upper-cased bases; a matched lower-case
+        base stays lower-case in the alignment, as the reference writes it."""
+        max_dist = 1 - float(identity)
+        if not max_dist >= 0:
+            raise ValueError("-i|--identity must between 0 and 1")
+        if strand not in (1, 2, 3):
+            raise ValueError("-s|--strand must be 1, 2 or 3")
+        opts = default_opts(align_mode="global")
+        n_leaves = self.num_leaves()
+        out = []
+        for i0 in range(0, len(primers), batch):
+            part = list(primers[i0:i0 + batch])
+            n = len(part)
+            seqs = (part if strand & 1 else []) + ([revcom_as_read(p) for p in part] if strand & 2 else [])
+            b = Batch(self, len(seqs))
+            try:
+                b.set_reads([t.upper() for t in seqs], None)
+                b.align(opts)
+                recs = b.alignments(want_align=False)["recs"]
+                chosen = np.full(n, -1, np.int32)
+                strands = ["."] * n
+                for i in range(n):
+                    cost, rev0 = np.inf, 0
+                    if strand & 1:
+                        strands[i] = "+"
+                        if recs[i]["status"] == 1:
+                            chosen[i], cost = i, recs[i]["cost"]
+                        rev0 = n
+                    if strand & 2 and recs[rev0 + i]["status"] == 1 and recs[rev0 + i]["cost"] < cost:
+                        chosen[i], strands[i] = rev0 + i, "-"
+                hn, hl = b.anneal(chosen, max_dist, [seqs[r] if r >= 0 else None for r in chosen])
+                rows = b.alignments()["align"]      # after the scan: in the case the primers were read
+            finally:
+                b.close()
+            for i in range(n):
+                r = int(chosen[i])
+                if r < 0:
+                    out.append(None)
+                    continue
+                s0, s1 = int(recs[r]["cs_start"]), int(recs[r]["cs_end"])
+                out.append(dict(strand=strands[i], cs_start=s0, cs_end=s1, alignment=rows[r][s0 - 1:s1], n_nodes=self.n_nodes,
+                                n_leaves=n_leaves, hit_nodes=int(hn[i]), hit_leaves=int(hl[i])))
+        return out
+
     def close(self):
         if self.h:
             load_library().hu_db_destroy(self.h)
@@ -566,6 +643,16 @@ class Batch:
         cd = np.zeros((n, L), np.int8); s = np.zeros(n, np.int32); e = np.zeros(n, np.int32)
         _chk(load_library().hu_batch_get_codes(self.h, _p(cd, C.c_int8), _p(s, C.c_int32), _p(e, C.c_int32)))
         return cd, s, e
+
+    def anneal(self, row_of_primer, max_dist, as_read=None):
+        """hu_anneal_batch: (hit_nodes, hit_leaves) per primer for its chosen aligned row (negative: skipped, -1).  as_read: per primer the
+        text of its row in the case it was read (None: the row's upper-case bases); the rows take that case."""
+        rows = np.ascontiguousarray(row_of_primer, np.int32)
+        n = len(rows)
+        hn = np.zeros(n, np.int64); hl = np.zeros(n, np.int64)
+        txt = (C.c_char_p * n)(*[t.encode("latin1") if t is not None else None for t in as_read]) if as_read is not None else None
+        _chk(load_library().hu_anneal_batch(self.h, _p(rows, C.c_int32), C.c_int(n), txt, C.c_double(max_dist), _p(hn, C.c_int64), _p(hl, C.c_int64)))
+        return hn, hl
 
     def pdist(self, read: int):
         d = np.zeros(self.db.n_nodes, np.int32); N = np.zeros(self.db.n_nodes, np.int32)

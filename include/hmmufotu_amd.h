@@ -439,6 +439,30 @@ int hu_batch_wall(hu_batch* b, double* ms4);
  * the kernel's LDS index, ~9 M nodes: said once on stderr) — so that a rate quoted for the mode is never silently a host-path rate */
 int hu_batch_refsort_stats(hu_batch* b, int32_t* left_to_host, int32_t* whole_batch_on_host);
 
+/* ---- primer coverage (hmmufotu-anneal) --------------------------------------------------
+ * The node scan of src/hmmufotu-anneal.cpp:246-290: for each primer, the nodes (all of them, the root included) whose sequence is within
+ * max_dist of the primer's alignment, SeqUtils::pDist(aln.align, node seq, csStart - 1, csEnd - 1) (src/SeqUtils.cpp:77-85): the share
+ * of the region's columns, gaps included, where DegenAlphabet::isMatch(align char, node code) fails.  Among them the leaves, nodes with
+ * one neighbour (a root with a single child is one).
+ * Runs on a batch that hu_align_batch has aligned: the caller aligns each primer (GLOBAL mode, no vpaths: alignSeq(hmm, read),
+ * src/HmmUFOtu_main.cpp:107-125), and for the reverse strand its reverse complement as another row, and chooses the strand on the host
+ * from the rows' costs (the reverse one only when its cost is strictly lower, :253-265).  row_of_primer[i] is the chosen row of primer i;
+ * a negative row skips the primer (both outputs -1).  as_read (may be NULL) gives per primer the text of its chosen row in the case the
+ * primer was read (for the reverse row: reversed and complemented case by case, IUPACNucl::getComplementSymbol); the row's bases must
+ * be that text upper-cased.  The reference writes a matched base into the alignment as read, so a lower-case one is an invalid symbol
+ * there: the batch's rows take the text's case before the scan, and hu_batch_get_alignments returns them so afterwards.
+ * HU_ERR_ARG: a row that is not an aligned row of the batch, a text that is not its bases, max_dist < 0, or a database that keeps a
+ * column window (hu_db_load_window). */
+int hu_anneal_batch(hu_batch* b, const int32_t* row_of_primer, int n, const char* const* as_read, double max_dist, int64_t* hit_nodes, int64_t* hit_leaves);
+/* the hit threshold of a region of len columns: the largest d with (double) d / len <= max_dist, -1 if none */
+int64_t hu_anneal_max_mismatch(double max_dist, int32_t len);
+/* the match rule per alignment byte: bit 0..3 = node code 0..3 (A C G T), bit 4 = node code -2 (gap), bit 5 = node code -1 */
+int hu_anneal_match_table(uint8_t* out /* [256] */);
+/* ANNEAL_HEADER of src/hmmufotu-anneal.cpp:52: the first line of an anneal report */
+const char* hu_anneal_header(void);
+/* PTUnrooted::numLeaves: nodes with one neighbour (src/PhyloTreeUnrooted.h:199) */
+int hu_db_num_leaves(const hu_db* db, int64_t* n_leaves);
+
 #ifdef __cplusplus
 }
 #endif
