@@ -26,6 +26,7 @@
 #include "hu_kern_refsort.h"
 #include "hu_kern_rank.h"
 #include "hu_kern_anneal.h"
+#include "hu_kern_build.h"
 
 #define HIPCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { \
 	hu_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return HU_ERR_DEVICE; } } while(0)
@@ -759,6 +760,122 @@ extern "C" int hu_tree_evaluate(int32_t n, int32_t cs_len, const int32_t* parent
 	}
 	return HU_OK;
 } catch(...) { return hu_catch_all("hu_tree_evaluate"); }
+
+/* ------------------------------------------------------------------------------ database build (hmmufotu-build) */
+/* encode(toupper(c)) of the MSA's alphabet, IUPACNucl (src/MSA.h:380-381, src/IUPACNucl.cpp:34-50, src/DegenAlphabet.cpp:51-63):
+ * A C G T -> 0..3, a degenerate letter -> the first base of its expansion, '-' '.' '_' -> -2, anything else -> -1 */
+static void msa_encode_table(int8_t* t) {
+	static const char* degen = "UTMARAWASCYCKGVAHADABCNA";   /* pairs: letter, first base of its expansion */
+	for(int c = 0; c < 256; ++c) {
+		const int u = (c >= 'a' && c <= 'z') ? c - 32 : c;
+		int8_t v = (u == '-' || u == '.' || u == '_') ? -2 : -1;
+		for(int b = 0; b < 4; ++b) if(u == "ACGT"[b]) v = (int8_t) b;
+		for(int k = 0; degen[k]; k += 2) if(u == degen[k]) v = (int8_t)(strchr("ACGT", degen[k + 1]) - "ACGT");
+		t[c] = v;
+	}
+}
+extern "C" int hu_msa_encode_table(int8_t* out) {
+	if(!out) return HU_ERR_ARG;
+	msa_encode_table(out);
+	return HU_OK;
+}
+
+extern "C" int hu_msa_stats(int device, int64_t n_seq, int64_t cs_len, const char* msa, int32_t* res_count, int32_t* gap_count,
+		int32_t* start, int32_t* end, int32_t* len, double* seq_weight, double* res_wcount, double* gap_wcount) try {
+	if(n_seq < 1 || cs_len < 1 || n_seq > INT32_MAX || cs_len > INT32_MAX || !msa || !res_count || !gap_count || !start || !end || !len || !seq_weight || !res_wcount || !gap_wcount) {
+		hu_set_error("hu_msa_stats: bad argument"); return HU_ERR_ARG;
+	}
+	if(hu_device_count() <= 0) { hu_set_error("no gfx950 device visible: the engine has no CPU path"); return HU_ERR_DEVICE; }
+	HIPCHK(hipSetDevice(device));
+	const int64_t N = n_seq, L = cs_len;
+	const size_t bytes = (size_t) N * L;
+	int8_t enc[256]; msa_encode_table(enc);
+	char* dMsa = nullptr; int8_t* dEnc = nullptr; int32_t *dRes = nullptr, *dGap = nullptr, *dSt = nullptr, *dEn = nullptr, *dLen = nullptr;
+	double *dInv = nullptr, *dW = nullptr, *dWRes = nullptr, *dWGap = nullptr;
+	HuScope guard([&] { (void) hipFree(dMsa); (void) hipFree(dEnc); (void) hipFree(dRes); (void) hipFree(dGap); (void) hipFree(dSt); (void) hipFree(dEn);
+		(void) hipFree(dLen); (void) hipFree(dInv); (void) hipFree(dW); (void) hipFree(dWRes); (void) hipFree(dWGap); });
+	#define MCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { hu_set_error("%s failed: %s", #call, hipGetErrorString(e_)); return HU_ERR_DEVICE; } } while(0)
+	{
+		size_t freeB = 0, totB = 0;
+		MCHK(hipMemGetInfo(&freeB, &totB));
+		const size_t need = bytes + (size_t) L * (4 * 4 + 4 + 4 * 8 + 4 * 8 + 8) + (size_t) N * (3 * 4 + 8) + 256;
+		if(need > freeB) { hu_set_error("hu_msa_stats: the alignment needs %.3f GB of device memory, %.3f GB are free", need / 1e9, freeB / 1e9); return HU_ERR_NOMEM; }
+	}
+	MCHK(hipMalloc((void**) &dMsa, bytes)); MCHK(hipMalloc((void**) &dEnc, 256));
+	MCHK(hipMalloc((void**) &dRes, (size_t) L * 16)); MCHK(hipMalloc((void**) &dGap, (size_t) L * 4));
+	MCHK(hipMalloc((void**) &dSt, (size_t) N * 4)); MCHK(hipMalloc((void**) &dEn, (size_t) N * 4)); MCHK(hipMalloc((void**) &dLen, (size_t) N * 4));
+	MCHK(hipMalloc((void**) &dInv, (size_t) L * 32)); MCHK(hipMalloc((void**) &dW, (size_t) N * 8));
+	MCHK(hipMalloc((void**) &dWRes, (size_t) L * 32)); MCHK(hipMalloc((void**) &dWGap, (size_t) L * 8));
+	MCHK(hipMemcpy(dMsa, msa, bytes, hipMemcpyHostToDevice)); MCHK(hipMemcpy(dEnc, enc, 256, hipMemcpyHostToDevice));
+	MCHK(hipMemset(dRes, 0, (size_t) L * 16)); MCHK(hipMemset(dGap, 0, (size_t) L * 4));
+	HuMsaDev m; m.msa = dMsa; m.nSeq = N; m.csLen = L; m.enc = dEnc;
+	(void) hipGetLastError();
+	const unsigned gx = (unsigned)((L + 255) / 256);
+	const int64_t rowsPer = 512;
+	const int64_t chunks = (N + rowsPer - 1) / rowsPer;
+	for(int64_t a = 0; a < chunks; a += 65535) {
+		HuMsaDev ma = m; ma.msa = dMsa + (size_t) a * rowsPer * L; ma.nSeq = N - a * rowsPer;
+		k_msa_col_counts<<<dim3(gx, (unsigned) std::min<int64_t>(65535, chunks - a)), 256>>>(ma, rowsPer, dRes, dGap);
+	}
+	MCHK(hipGetLastError());
+	MCHK(hipMemcpy(res_count, dRes, (size_t) L * 16, hipMemcpyDeviceToHost)); MCHK(hipMemcpy(gap_count, dGap, (size_t) L * 4, hipMemcpyDeviceToHost));
+	/* pssw(b, j) = (number of residues seen at j) * resCount(b, j), src/MSA.cpp:260-262 */
+	std::vector<double> inv((size_t) L * 4, 0.0);
+	for(int64_t j = 0; j < L; ++j) {
+		int nz = 0;
+		for(int b = 0; b < 4; ++b) nz += res_count[b * L + j] != 0;
+		for(int b = 0; b < 4; ++b) if(res_count[b * L + j]) inv[b * L + j] = 1.0 / (double)((int64_t) nz * res_count[b * L + j]);
+	}
+	MCHK(hipMemcpy(dInv, inv.data(), (size_t) L * 32, hipMemcpyHostToDevice));
+	k_msa_seq_weight<<<(unsigned)((N + 63) / 64), 64>>>(m, dInv, dSt, dEn, dLen, dW);
+	MCHK(hipGetLastError());
+	MCHK(hipMemcpy(start, dSt, (size_t) N * 4, hipMemcpyDeviceToHost)); MCHK(hipMemcpy(end, dEn, (size_t) N * 4, hipMemcpyDeviceToHost));
+	MCHK(hipMemcpy(len, dLen, (size_t) N * 4, hipMemcpyDeviceToHost)); MCHK(hipMemcpy(seq_weight, dW, (size_t) N * 8, hipMemcpyDeviceToHost));
+	/* seqWeight *= numSeq / seqWeight.sum(): the reference's sum is an Eigen reduction; here it is serial in i */
+	double tot = 0;
+	for(int64_t i = 0; i < N; ++i) tot += seq_weight[i];
+	const double scale = (double) N / tot;
+	for(int64_t i = 0; i < N; ++i) seq_weight[i] *= scale;
+	MCHK(hipMemcpy(dW, seq_weight, (size_t) N * 8, hipMemcpyHostToDevice));
+	k_msa_wcounts<<<gx, 256>>>(m, dW, dWRes, dWGap);
+	MCHK(hipGetLastError());
+	MCHK(hipMemcpy(res_wcount, dWRes, (size_t) L * 32, hipMemcpyDeviceToHost)); MCHK(hipMemcpy(gap_wcount, dWGap, (size_t) L * 8, hipMemcpyDeviceToHost));
+	#undef MCHK
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_msa_stats"); }
+
+extern "C" int hu_tree_count_mutations(int device, int32_t n_nodes, int32_t cs_len, const int32_t* parent, const double* up_dev, int32_t* counts) try {
+	if(n_nodes < 2 || cs_len < 1 || !parent || !up_dev || !counts) { hu_set_error("hu_tree_count_mutations: bad argument"); return HU_ERR_ARG; }
+	for(int32_t i = 0; i < n_nodes; ++i) if(parent[i] >= n_nodes) { hu_set_error("parent of node %d out of range", i); return HU_ERR_ARG; }
+	if(hu_device_count() <= 0) { hu_set_error("no gfx950 device visible: the engine has no CPU path"); return HU_ERR_DEVICE; }
+	HIPCHK(hipSetDevice(device));
+	const int32_t n = n_nodes; const int64_t L = cs_len;
+	int8_t* dSt = nullptr; int32_t *dPar = nullptr, *dCnt = nullptr;
+	HuScope guard([&] { (void) hipFree(dSt); (void) hipFree(dPar); (void) hipFree(dCnt); });
+	#define MCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { hu_set_error("%s failed: %s", #call, hipGetErrorString(e_)); return HU_ERR_DEVICE; } } while(0)
+	{
+		size_t freeB = 0, totB = 0;
+		MCHK(hipMemGetInfo(&freeB, &totB));
+		const size_t need = (size_t) n * L + (size_t) n * 4 + (size_t) L * 4;
+		if(need > freeB) { hu_set_error("hu_tree_count_mutations: the node states need %.3f GB of device memory, %.3f GB are free", need / 1e9, freeB / 1e9); return HU_ERR_NOMEM; }
+	}
+	MCHK(hipMalloc((void**) &dSt, (size_t) n * L)); MCHK(hipMalloc((void**) &dPar, (size_t) n * 4)); MCHK(hipMalloc((void**) &dCnt, (size_t) L * 4));
+	MCHK(hipMemcpy(dPar, parent, (size_t) n * 4, hipMemcpyHostToDevice)); MCHK(hipMemset(dCnt, 0, (size_t) L * 4));
+	(void) hipGetLastError();
+	const unsigned gx = (unsigned)((L + 255) / 256);
+	for(int32_t a = 0; a < n; a += 65535)
+		k_mut_state<<<dim3(gx, (unsigned) std::min(65535, n - a)), 256>>>(up_dev + (size_t) a * L * 4, L, dSt + (size_t) a * L);
+	const int32_t nodesPer = 256;
+	const int32_t chunks = (n + nodesPer - 1) / nodesPer;
+	for(int32_t a = 0; a < chunks; a += 65535) {
+		const int32_t u0 = a * nodesPer;
+		k_mut_count<<<dim3(gx, (unsigned) std::min(65535, chunks - a)), 256>>>(dSt, dPar, n, L, nodesPer, u0, dCnt);
+	}
+	MCHK(hipGetLastError());
+	MCHK(hipMemcpy(counts, dCnt, (size_t) L * 4, hipMemcpyDeviceToHost));
+	#undef MCHK
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_tree_count_mutations"); }
 
 /* ------------------------------------------------------------------------------ batch */
 

@@ -215,6 +215,61 @@ def tree_evaluate(parent, blen, seq, model: ModelDesc, up_ptr: int, down_ptr: in
     return seq, h
 
 
+def msa_encode_table() -> np.ndarray:
+    """hu_msa_encode_table: encode(toupper(c)) of the MSA's IUPACNucl alphabet for every byte (0..3 residue, a degenerate letter as
+    the first base of its expansion, -2 gap, -1 other)"""
+    t = np.zeros(256, np.int8)
+    _chk(load_library().hu_msa_encode_table(_p(t, C.c_int8)))
+    return t
+
+
+def msa_stats(rows, device=0) -> dict:
+    """hu_msa_stats on an alignment (list of equal-length str/bytes rows, or a uint8 [n][L] array): the raw and weighted column
+    counts, the per-sequence start / end / length and the normalised sequence weights of the reference's MSA.
+    keep marks the columns MSA::prune keeps (at least one residue)."""
+    if isinstance(rows, np.ndarray):
+        a = np.ascontiguousarray(rows, np.uint8)
+    else:
+        b = [r.encode() if isinstance(r, str) else bytes(r) for r in rows]
+        if not b or any(len(r) != len(b[0]) for r in b):
+            raise EngineError("msa_stats: rows must be non-empty and of equal length")
+        a = np.frombuffer(b"".join(b), np.uint8).reshape(len(b), len(b[0]))
+    n, L = a.shape
+    out = dict(res_count=np.zeros((4, L), np.int32), gap_count=np.zeros(L, np.int32), start=np.zeros(n, np.int32), end=np.zeros(n, np.int32),
+               len=np.zeros(n, np.int32), seq_weight=np.zeros(n), res_wcount=np.zeros((4, L)), gap_wcount=np.zeros(L))
+    _chk(load_library().hu_msa_stats(C.c_int(device), C.c_int64(n), C.c_int64(L), a.ctypes.data_as(C.c_char_p),
+                                     _p(out["res_count"], C.c_int32), _p(out["gap_count"], C.c_int32), _p(out["start"], C.c_int32),
+                                     _p(out["end"], C.c_int32), _p(out["len"], C.c_int32), _p(out["seq_weight"], C.c_double),
+                                     _p(out["res_wcount"], C.c_double), _p(out["gap_wcount"], C.c_double)))
+    out["keep"] = out["res_count"].sum(axis=0) > 0
+    return out
+
+
+def tree_count_mutations(parent, cs_len: int, up_ptr: int, device=0) -> np.ndarray:
+    """hu_tree_count_mutations: per column, the non-root nodes whose inferred state differs from their parent's, from the DEVICE
+    fixed-rate up buffer at up_ptr ([n][cs_len][4] float64, as tree_evaluate leaves it with win_len 0)"""
+    parent = np.ascontiguousarray(parent, np.int32)
+    cnt = np.zeros(cs_len, np.int32)
+    _chk(load_library().hu_tree_count_mutations(C.c_int(device), C.c_int32(len(parent)), C.c_int32(cs_len), _p(parent, C.c_int32),
+                                                C.c_void_p(int(up_ptr)), _p(cnt, C.c_int32)))
+    return cnt
+
+
+def dg_model(K: int, alpha: float):
+    """hu_dg_model: the discrete-Gamma breaks [K + 1] and rates [K] of DiscreteGammaModel(K, alpha)"""
+    b = np.zeros(K + 1); r = np.zeros(K)
+    _chk(load_library().hu_dg_model(C.c_int32(K), C.c_double(alpha), _p(b, C.c_double), _p(r, C.c_double)))
+    return b, r
+
+
+def dg_estimate_shape(x) -> float:
+    """hu_dg_estimate_shape: the moment estimate of the Gamma shape from per-site mutation counts (+inf below 2 sites)"""
+    lib = load_library()
+    lib.hu_dg_estimate_shape.restype = C.c_double
+    x = np.ascontiguousarray(x, np.float64)
+    return float(lib.hu_dg_estimate_shape(C.c_int64(len(x)), _p(x, C.c_double)))
+
+
 def write_ptu(path, parent, blen, seq, up, down, height, model: ModelDesc, names=None, annos=None, anno_dist=None, model_text=None,
               dg_alpha=0.0, dg_breaks=None, msgs_on_device=False):
     """hu_ptu_write: the database file in the reference's .ptu format; up / down are [n][cs_len][4] arrays, or device pointers (ints)

@@ -208,6 +208,32 @@ int hu_tree_evaluate(int32_t n_nodes, int32_t cs_len, const int32_t* parent, con
 int hu_ptu_write(const char* path, const hu_tree_desc* tree, const char* const* names, const char* const* annos, const hu_model_desc* model,
 		const char* model_text, double dg_alpha, const double* dg_breaks);
 
+/* ---- build statistics (the MSA and mutation-count loops of hmmufotu-build) -------------------------
+ * MSA statistics on the device: MSA::updateRawCounts, updateSeqWeight and updateWeightedCounts (src/MSA.cpp:226-293) of the loaded
+ * alignment, msa = n_seq rows of cs_len bytes, row-major, as read (case kept).  Every byte is classified by encode(toupper(c)) of the
+ * MSA's IUPACNucl alphabet: hu_msa_encode_table gives that table (0..3 residue, a degenerate letter as the first base of its expansion,
+ * -2 gap, -1 anything else).  Outputs, all host:
+ *   res_count [4][cs_len], gap_count [cs_len]: raw counts; the columns with no residue are the ones MSA::prune drops (src/MSA.cpp:87-138);
+ *   start / end / len [n_seq]: first / last residue column (-1 if none), in the input's columns, and the residue count;
+ *   seq_weight [n_seq]: position-specific weights, each summed over columns in serial j order on the device, then scaled to sum n_seq
+ *     on the host with a serial sum (the reference's seqWeight.sum() is an Eigen reduction);
+ *   res_wcount [4][cs_len], gap_wcount [cs_len]: weighted counts, each summed over sequences in serial i order.
+ * Dropping columns without residues changes none of these for the columns that stay (pruned columns add no weight), so one call on the
+ * unpruned alignment gives the values the reference computes after prune(). */
+int hu_msa_encode_table(int8_t* out /* [256] */);
+int hu_msa_stats(int device, int64_t n_seq, int64_t cs_len, const char* msa, int32_t* res_count, int32_t* gap_count,
+		int32_t* start, int32_t* end, int32_t* len, double* seq_weight, double* res_wcount, double* gap_wcount);
+/* PhyloTreeUnrooted::estimateNumMutations (src/PhyloTreeUnrooted.cpp:1008-1016) for every column: the non-root nodes whose inferState
+ * differs from their parent's.  inferState is the first maximum (Eigen maxCoeff) of the node's own message, up[node], leaves included;
+ * a gap leaf's message is log pi (src/PhyloTreeUnrooted.h:1431-1437), so its state is the first maximum of pi.  up_dev: DEVICE [n_nodes][cs_len][4], the whole-column up buffer of hu_tree_evaluate with a
+ * fixed-rate model.  counts: host [cs_len].  Needs n_nodes x cs_len bytes of device scratch. */
+int hu_tree_count_mutations(int device, int32_t n_nodes, int32_t cs_len, const int32_t* parent, const double* up_dev, int32_t* counts);
+/* DiscreteGammaModel::setBreaks / setRates (src/DiscreteGammaModel.cpp:40-55), host only: breaks [K + 1] (last +inf), rates [K] (sum 1) */
+int hu_dg_model(int32_t K, double alpha, double* breaks, double* rates);
+/* DiscreteGammaModel::estimateShapeMoment (src/DiscreteGammaModel.cpp:92-98): mean^2 / (var - mean), sums in serial order; +inf when
+ * n < 2; <= 0 (or NaN) means near-invariant rates, which hmmufotu-build answers with the fixed-rate model (src/hmmufotu-build.cpp:437-446) */
+double hu_dg_estimate_shape(int64_t n, const double* X);
+
 /* ---- the tree of a .ptu without its messages (host only, no device): what the consumers of an assignment file need of the database —
  * hmmufotu-sum the nodes' taxon annotations (src/hmmufotu-sum.cpp:378-383), hmmufotu-jplace the topology, branch lengths and the order of
  * every node's children as PTUnrooted::load leaves it (src/hmmufotu-jplace.cpp:197, src/PhyloTreeUnrooted.cpp:1135-1157).  The 4 x csLen
