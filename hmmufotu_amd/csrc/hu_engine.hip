@@ -153,7 +153,6 @@ struct hu_db {
 	HuModelDev mdl;
 	hu_model_desc mdesc;
 	HuProfileHost prof;
-	std::vector<double> hT7, hEM, hEI;
 	std::vector<int32_t> parent, annoId;
 	std::vector<double> blen, height, annoDist;
 	std::vector<int8_t> seq;
@@ -965,7 +964,6 @@ struct hu_batch {
 	DBuf<int8_t> dCodes;
 	DBuf<int32_t> dStart, dEnd, dSeedCnt, dSeedId, dGiven, dPermCnt;
 	DBuf<uint16_t> dPerm;
-	PinnedVec<int32_t> hPermCnt;
 	DBuf<uint32_t> dRp, dPairs, dSeedDN, dParDN, dBmin, dRSpan, dTileSpan;     /* dRSpan / dTileSpan: uint2 per read / tile */
 	DBuf<int32_t> dTileQ, dSlotRead, dReadSlot;
 	DBuf<uint32_t> dRq;
@@ -997,28 +995,23 @@ struct hu_batch {
 	std::vector<char> hBases;
 	PinnedVec<HuVitOut> hVit;
 	int64_t cellsTotal = 0, cornerTotal = 0;   /* DP cells of all phases of all sequences / of their corner blocks (set with the reads) */
-	int nVitRedo = 0;           /* sequences of the last align call redone by the value-filing Viterbi */
 	int rMain = 0;              /* width split of the batch (plan_width_split): regions of at most rMain columns take the main launch; 0 = one launch for all */
+	int maxAll = 1, maxMain = 1;     /* the widest region of the batch / of the main launch's reads (plan_width_split) */
 	std::vector<int32_t> wideReads;     /* the reads beyond it */
 	std::vector<uint32_t> hWideOrd, hWideCand; DBuf<uint32_t> dWideOrd, dWideCand;      /* their (read, seed) slots and their candidates: the lists of the second launches */
 	PinnedVec<int32_t> hCandOffAll;   /* candidate offsets on the host when there are wide reads (scan_cands) */
-	int nFullRedo = 0;          /* sequences of the last align call whose banded DP found no path: full DP, one launch */
 	DBuf<double> dRedoScr; DBuf<HuReadDesc> dRedoDesc; DBuf<HuVitOut> dRedoVit;    /* the redo launches' own scratch: kept (an allocation or a release stalls every stream of the device) */
 	PinnedVec<HuAlnDev> hAlns;
 	DBuf<int32_t> dAnRow, dAnThr, dAnTileQ; DBuf<int2> dAnReg; DBuf<uint32_t> dAnMasks; DBuf<unsigned long long> dAnHits;      /* hu_anneal_batch */
 	PinnedVec<int32_t> hStart, hEnd, hSeedCnt, hSeedId;
 	PinnedVec<uint32_t> hSeedDN;
-	PinnedVec<HuEstOut> hEst;
 	PinnedVec<HuCand> hCands;
-	PinnedVec<HuPlaceOut> hPlaceOut;
 	std::vector<int64_t> candOffs;
 	std::vector<HostPlace> places;    /* candidates in filterPlacements order, all reads */
-	std::vector<HostPlace> tmpPlaces;
 	PinnedVec<hu_place_rec> best;      /* page-locked: a device-to-host copy into pageable memory makes the runtime wait (spinning) for the stream inside the call */
 	PinnedVec<int32_t> hMeta, hBail;   /* the same for the few words the host reads between stages */
 	PinnedVec<char> hRows;            /* alignment rows of the last format call */
 	std::vector<char> tsvBuf; std::vector<size_t> tsvOff, tsvLen; size_t tsvSize = 0;
-	int maxRegion = 0;
 };
 
 struct Timer {
@@ -1302,6 +1295,31 @@ extern "C" int hu_batch_set_aligned(hu_batch* b, int n, const int8_t* codes, con
 	return set_aligned_impl(b, n, codes, hipMemcpyHostToDevice, start, end);
 } catch(...) { return hu_catch_all("hu_batch_set_aligned"); }
 
+/* The fill of hu_align_batch, chosen once from the knobs and the batch's shape before any scratch is sized.  The LDS-staged wavefronts run while
+ * the (M, I, D) of three diagonals fit 96 KB (vlds); longer reads, and viterbi_hbm, take the HBM-staged kernel. */
+enum VitFill { VF_WAVE4, VF_WAVE4_DIAG1, VF_WAVE4_DIAG2, VF_WAVE8, VF_DEC2_256, VF_DEC2_512, VF_DEC, VF_VALUES, VF_HBM };
+struct VitPlan {
+	VitFill fill;
+	size_t lds;        /* dynamic LDS of the fill kernel */
+	int decRpl;        /* decision-byte layout for k_viterbi_trace_dec: rows per lane of k_viterbi_wave, 0 for the workgroup kernels */
+	bool wave() const { return fill <= VF_WAVE8; }
+	bool dec() const { return fill <= VF_DEC; }   /* one decision byte per cell; (M, I, D) only where a later phase looks */
+};
+static VitPlan plan_viterbi(const HuKnobs& kb, int maxLen, size_t vlds, int haloW) {
+	if(vlds > 96 * 1024 || kb.viterbi_hbm) return {VF_HBM, 0, 0};
+	if(kb.viterbi_values) return {VF_VALUES, vlds, 0};
+	const int mode = kb.viterbi_mode ? kb.viterbi_mode : (kb.viterbi_dec1 ? 1 : 0);   /* 1 = generic workgroup kernel, 2 = row-per-thread workgroup kernel */
+	if(mode == 0 && maxLen <= 512) { /* one wave per sequence, no barrier */
+		const size_t wl = (size_t) 3 * std::min(haloW, 512) * sizeof(double) + (size_t)(kb.vit_lds_pad > 0 && kb.vit_lds_pad <= 40 ? kb.vit_lds_pad : 0) * 1024;
+		if(maxLen > 256) return {VF_WAVE8, wl, 8};
+		return {kb.vw_diag == 1 ? VF_WAVE4_DIAG1 : kb.vw_diag == 2 ? VF_WAVE4_DIAG2 : VF_WAVE4, wl, 4};
+	}
+	const size_t vlds2 = vlds + (size_t) 3 * haloW * sizeof(double) + 32 * (maxLen <= 256 ? 256 : 512);
+	if(mode != 1 && maxLen <= 256 && vlds2 <= 96 * 1024) return {VF_DEC2_256, vlds2, 0};   /* one DP row per thread, nothing global inside the wavefront */
+	if(mode != 1 && maxLen <= 512 && vlds2 <= 96 * 1024) return {VF_DEC2_512, vlds2, 0};
+	return {VF_DEC, vlds, 0};
+}
+
 extern "C" int hu_align_batch(hu_batch* b, const hu_opts* o) try {
 	if(!b || !o) return HU_ERR_ARG;
 	if(b->state < ST_READS || b->fromCodes) { hu_set_error("hu_align_batch: no reads set"); return HU_ERR_STATE; }
@@ -1317,153 +1335,118 @@ extern "C" int hu_align_batch(hu_batch* b, const hu_opts* o) try {
 	b->hVit.resize(b->nSeq);
 	(void) hipGetLastError(); /* the HIP runtime is shared with torch: drop stale sticky errors that are not ours */
 	if(b->nSeq) {
-		int maxLen = 1;
-		for(int s = 0; s < b->nSeq; ++s) maxLen = std::max(maxLen, (int) b->hDescs[s].len);
+		int maxLen = 1, haloW = 2;
+		for(int s = 0; s < b->nSeq; ++s) {
+			maxLen = std::max(maxLen, (int) b->hDescs[s].len);
+			for(int r = 0; r < b->hDescs[s].nRegions; ++r) haloW = std::max(haloW, b->hDescs[s].reg[r].j1 - b->hDescs[s].reg[r].j0 + 3);
+		}
 		const int ldsRows = maxLen + 1;
-		bool usedDec = false;
-		int decRpl = 0;
 		const size_t vlds = (size_t) 9 * ldsRows * sizeof(double);
+		const VitPlan vp = plan_viterbi(kb, maxLen, vlds, haloW);
 		/* The one-wave kernel files (M, I, D) only of the corner blocks (a few cells per read); every other kernel keeps all three values of
 		 * every cell of every phase: 2-3 MB per 250-base read, 16 GB per batch of 8,192 — allocated only when such a kernel is going to run. */
-		const bool wavePath = vlds <= 96 * 1024 && !kb.viterbi_hbm && !kb.viterbi_values && !(kb.viterbi_mode ? kb.viterbi_mode : (kb.viterbi_dec1 ? 1 : 0)) && maxLen <= 512;
-		if((rc = b->dScratch.ensure((size_t)(wavePath ? b->cornerTotal : b->cellsTotal) * 3 + 1)) != HU_OK) return rc;
+		if((rc = b->dScratch.ensure((size_t)(vp.wave() ? b->cornerTotal : b->cellsTotal) * 3 + 1)) != HU_OK) return rc;
+		/* the value-filing Viterbi over n descriptors, each with its share of scr: a workgroup per sequence, the wavefront staged in LDS, every value
+		 * filed for the traceback (K + len steps of a barrier each instead of as many round trips to HBM by one wave: 30 - 100 ms for a handful of
+		 * 150-base reads), then the traceback.  Where the plan takes the HBM-staged kernel, which has no onlyStatus, no fill flags reads for a redo. */
+		auto fillValues = [&](const HuReadDesc* descs, unsigned n, double* scr, HuVitOut* outs, int onlyStatus) -> int {
+			if(vp.fill != VF_HBM) {
+				if(vlds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*) k_viterbi_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int) vlds));
+				k_viterbi_lds<<<n, HU_VIT_THREADS, vlds, b->stream>>>(d, descs, b->dBases.p, scr, b->dTraces.p, tNN, tNB, tEC, tCC, outs, ldsRows, onlyStatus);
+				k_viterbi_trace<<<(n + 63) / 64, 64, 0, b->stream>>>(d, descs, scr, b->dTraces.p, tNN, tNB, outs, (int) n);
+			}
+			else k_viterbi<<<n, 64, 0, b->stream>>>(d, descs, b->dBases.p, scr, b->dTraces.p, tNN, tNB, tEC, tCC, outs);
+			return HU_OK;
+		};
 		{
 			Timer t(b, HU_T_VITERBI);
-			if(vlds <= 96 * 1024 && !kb.viterbi_hbm) { /* LDS-staged wavefront; longer reads take the HBM-staged kernel */
-				if(!kb.viterbi_values) { /* one decision byte per cell; (M, I, D) only where a later phase looks */
-					if(vlds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*) k_viterbi_dec, hipFuncAttributeMaxDynamicSharedMemorySize, (int) vlds));
-					#define VD_ARGS d, b->dDescs.p, b->dBases.p, b->dScratch.p, b->dDec.p, tNN, tNB, tEC, tCC, b->dVit.p, ldsRows
-					int haloW = 2;
-					for(int s = 0; s < b->nSeq; ++s) for(int r = 0; r < b->hDescs[s].nRegions; ++r)
-						haloW = std::max(haloW, b->hDescs[s].reg[r].j1 - b->hDescs[s].reg[r].j0 + 3);
-					const size_t vlds2 = vlds + (size_t) 3 * haloW * sizeof(double) + 32 * (maxLen <= 256 ? 256 : 512);
-					const int mode = kb.viterbi_mode ? kb.viterbi_mode : (kb.viterbi_dec1 ? 1 : 0);   /* 1 = generic workgroup kernel, 2 = row-per-thread workgroup kernel */
-					const int haloWw = std::min(haloW, 512);
-					if(mode == 0 && maxLen <= 512) { /* one wave per sequence, no barrier */
-						const size_t wl = (size_t) 3 * haloWw * sizeof(double) + (size_t)(kb.vit_lds_pad > 0 && kb.vit_lds_pad <= 40 ? kb.vit_lds_pad : 0) * 1024;
-						const int dgv = kb.vw_diag;
-						if(maxLen <= 256 && dgv == 1) { k_viterbi_wave<4, 1><<<b->nSeq, 64, wl, b->stream>>>(d, b->dDescs.p, b->dBases.p, b->dScratch.p, b->dDec.p, tNN, tNB, tEC, tCC, b->dVit.p, haloWw); decRpl = 4; }
-						else if(maxLen <= 256 && dgv == 2) { k_viterbi_wave<4, 2><<<b->nSeq, 64, wl, b->stream>>>(d, b->dDescs.p, b->dBases.p, b->dScratch.p, b->dDec.p, tNN, tNB, tEC, tCC, b->dVit.p, haloWw); decRpl = 4; }
-						else if(maxLen <= 256) { k_viterbi_wave<4><<<b->nSeq, 64, wl, b->stream>>>(d, b->dDescs.p, b->dBases.p, b->dScratch.p, b->dDec.p, tNN, tNB, tEC, tCC, b->dVit.p, haloWw); decRpl = 4; }
-						else { k_viterbi_wave<8><<<b->nSeq, 64, wl, b->stream>>>(d, b->dDescs.p, b->dBases.p, b->dScratch.p, b->dDec.p, tNN, tNB, tEC, tCC, b->dVit.p, haloWw); decRpl = 8; }
-					}
-					else if(mode != 1 && maxLen <= 256 && vlds2 <= 96 * 1024) { /* one DP row per thread, nothing global inside the wavefront */
-						if(vlds2 > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*) k_viterbi_dec2<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) vlds2));
-						k_viterbi_dec2<256><<<b->nSeq, 256, vlds2, b->stream>>>(VD_ARGS, haloW);
-					}
-					else if(mode != 1 && maxLen <= 512 && vlds2 <= 96 * 1024) {
-						if(vlds2 > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*) k_viterbi_dec2<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) vlds2));
-						k_viterbi_dec2<512><<<b->nSeq, 512, vlds2, b->stream>>>(VD_ARGS, haloW);
-					}
-					else k_viterbi_dec<<<b->nSeq, HU_VIT_THREADS, vlds, b->stream>>>(VD_ARGS);
-					#undef VD_ARGS
-					k_viterbi_trace_dec<<<(b->nSeq + 63) / 64, 64, 0, b->stream>>>(d, b->dDescs.p, b->dDec.p, b->dTraces.p, b->dVit.p, b->nSeq, kb.viterbi_force_redo != 0, decRpl);
-					usedDec = true;
-				}
-				else {
-					if(vlds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*) k_viterbi_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int) vlds));
-					k_viterbi_lds<<<b->nSeq, HU_VIT_THREADS, vlds, b->stream>>>(d, b->dDescs.p, b->dBases.p, b->dScratch.p, b->dTraces.p, tNN, tNB, tEC, tCC, b->dVit.p, ldsRows, 0);
-					k_viterbi_trace<<<(b->nSeq + 63) / 64, 64, 0, b->stream>>>(d, b->dDescs.p, b->dScratch.p, b->dTraces.p, tNN, tNB, b->dVit.p, b->nSeq);
-				}
+			#define VD_ARGS d, b->dDescs.p, b->dBases.p, b->dScratch.p, b->dDec.p, tNN, tNB, tEC, tCC, b->dVit.p
+			const int haloWw = std::min(haloW, 512);
+			switch(vp.fill) {
+			case VF_WAVE4_DIAG1: k_viterbi_wave<4, 1><<<b->nSeq, 64, vp.lds, b->stream>>>(VD_ARGS, haloWw); break;
+			case VF_WAVE4_DIAG2: k_viterbi_wave<4, 2><<<b->nSeq, 64, vp.lds, b->stream>>>(VD_ARGS, haloWw); break;
+			case VF_WAVE4: k_viterbi_wave<4><<<b->nSeq, 64, vp.lds, b->stream>>>(VD_ARGS, haloWw); break;
+			case VF_WAVE8: k_viterbi_wave<8><<<b->nSeq, 64, vp.lds, b->stream>>>(VD_ARGS, haloWw); break;
+			case VF_DEC2_256:
+				if(vp.lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*) k_viterbi_dec2<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) vp.lds));
+				k_viterbi_dec2<256><<<b->nSeq, 256, vp.lds, b->stream>>>(VD_ARGS, ldsRows, haloW);
+				break;
+			case VF_DEC2_512:
+				if(vp.lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*) k_viterbi_dec2<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) vp.lds));
+				k_viterbi_dec2<512><<<b->nSeq, 512, vp.lds, b->stream>>>(VD_ARGS, ldsRows, haloW);
+				break;
+			case VF_DEC:
+				if(vp.lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*) k_viterbi_dec, hipFuncAttributeMaxDynamicSharedMemorySize, (int) vp.lds));
+				k_viterbi_dec<<<b->nSeq, HU_VIT_THREADS, vp.lds, b->stream>>>(VD_ARGS, ldsRows);
+				break;
+			case VF_VALUES: case VF_HBM:
+				if((rc = fillValues(b->dDescs.p, b->nSeq, b->dScratch.p, b->dVit.p, 0)) != HU_OK) return rc;
+				break;
 			}
-			else k_viterbi<<<b->nSeq, 64, 0, b->stream>>>(d, b->dDescs.p, b->dBases.p, b->dScratch.p, b->dTraces.p, tNN, tNB, tEC, tCC, b->dVit.p);
+			#undef VD_ARGS
+			if(vp.dec()) k_viterbi_trace_dec<<<(b->nSeq + 63) / 64, 64, 0, b->stream>>>(d, b->dDescs.p, b->dDec.p, b->dTraces.p, b->dVit.p, b->nSeq, kb.viterbi_force_redo != 0, vp.decRpl);
 		}
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipMemcpyAsync(b->hVit.data(), b->dVit.p, (size_t) b->nSeq * sizeof(HuVitOut), hipMemcpyDeviceToHost, b->stream));
 		HIPCHK(hu_wait(b->stream));
-		if(usedDec) { /* sequences whose traceback cannot trust the fill-time decisions: redo with every value filed */
-			int nRedo = 0;
-			for(int s = 0; s < b->nSeq; ++s) if(b->hVit[s].status == HU_READ_NEEDS_VALUES) nRedo++;
-			b->nVitRedo = nRedo;
-			if(nRedo && wavePath) { /* the batch holds corner scratch only: the few sequences to redo get a full-size scratch of their own, in launches of <= 48 M cells */
-				if(vlds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*) k_viterbi_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int) vlds));
-				std::vector<int> rs;
-				for(int s = 0; s < b->nSeq; ++s) if(b->hVit[s].status == HU_READ_NEEDS_VALUES) rs.push_back(s);
-				const int64_t cap = 48ll << 20;
-				for(size_t at = 0; at < rs.size();) {
-					std::vector<HuReadDesc> rdv; std::vector<HuVitOut> hv;
-					int64_t cells = 0; size_t e = at;
-					for(; e < rs.size(); ++e) {
-						HuReadDesc rd = b->hDescs[rs[e]];
-						int64_t c = 0;                         /* cells of all its phases, as build_regions laid them out */
-						for(int g = 0; g < rd.nRegions; ++g) if(rd.reg[g].j1 >= rd.reg[g].j0 && rd.reg[g].i1 >= rd.reg[g].i0) c += (int64_t)(rd.reg[g].j1 - rd.reg[g].j0 + 1) * (rd.reg[g].i1 - rd.reg[g].i0 + 1);
-						if(!rdv.empty() && cells + c > cap) break;
-						rd.scratchOff = cells; cells += c;
-						rdv.push_back(rd); hv.push_back(b->hVit[rs[e]]);
-					}
-					DBuf<double>& scr = b->dRedoScr; DBuf<HuReadDesc>& dd = b->dRedoDesc; DBuf<HuVitOut>& vo = b->dRedoVit;
-					if((rc = scr.ensure((size_t) cells * 3 + 1)) != HU_OK || (rc = dd.ensure(rdv.size())) != HU_OK || (rc = vo.ensure(rdv.size())) != HU_OK) return rc;
-					HIPCHK(hipMemcpyAsync(dd.p, rdv.data(), rdv.size() * sizeof(HuReadDesc), hipMemcpyHostToDevice, b->stream));
-					HIPCHK(hipMemcpyAsync(vo.p, hv.data(), hv.size() * sizeof(HuVitOut), hipMemcpyHostToDevice, b->stream));
-					k_viterbi_lds<<<(unsigned) rdv.size(), HU_VIT_THREADS, vlds, b->stream>>>(d, dd.p, b->dBases.p, scr.p, b->dTraces.p, tNN, tNB, tEC, tCC, vo.p, ldsRows, HU_READ_NEEDS_VALUES);
-					k_viterbi_trace<<<((unsigned) rdv.size() + 63) / 64, 64, 0, b->stream>>>(d, dd.p, scr.p, b->dTraces.p, tNN, tNB, vo.p, (int) rdv.size());
-					HIPCHK(hipGetLastError());
-					HIPCHK(hipMemcpyAsync(hv.data(), vo.p, hv.size() * sizeof(HuVitOut), hipMemcpyDeviceToHost, b->stream));
-					HIPCHK(hu_wait(b->stream));
-					for(size_t k = 0; k < rdv.size(); ++k) {
-						b->hVit[rs[at + k]] = hv[k];               /* the trace is written at the sequence's own traceOff */
-						HIPCHK(hipMemcpyAsync(b->dVit.p + rs[at + k], &b->hVit[rs[at + k]], sizeof(HuVitOut), hipMemcpyHostToDevice, b->stream));
-					}
-					HIPCHK(hu_wait(b->stream));
-					at = e;
+		bool hostVit = false;      /* hVit holds what dVit does not: it goes up once, before the row build */
+		/* the reads of rs again, each with the descriptor make() gives it (make returns its cells) and its share of the redo launches' scratch, in
+		 * launches of at most 48 M cells (1.2 GB of (M, I, D) scratch: ~130 reads of 250 bp against K = 1,400 each); their outputs come back to hVit.
+		 * A redo of the flagged reads (onlyStatus) takes their current outputs up first: k_viterbi_lds reads the status */
+		auto redoChunked = [&](const std::vector<int>& rs, auto&& make, int onlyStatus) -> int {
+			const int64_t cap = 48ll << 20;
+			std::vector<HuReadDesc> rdv; std::vector<HuVitOut> hv;
+			for(size_t at = 0; at < rs.size();) {
+				rdv.clear(); hv.clear();
+				int64_t cells = 0; size_t e = at;
+				for(; e < rs.size(); ++e) {
+					HuReadDesc rd = b->hDescs[rs[e]];
+					const int64_t c = make(rd);
+					if(!rdv.empty() && cells + c > cap) break;
+					rd.scratchOff = cells; cells += c;
+					rdv.push_back(rd); hv.push_back(b->hVit[rs[e]]);
 				}
+				DBuf<double>& scr = b->dRedoScr; DBuf<HuReadDesc>& dd = b->dRedoDesc; DBuf<HuVitOut>& vo = b->dRedoVit;
+				if((rc = scr.ensure((size_t) cells * 3 + 1)) != HU_OK || (rc = dd.ensure(rdv.size())) != HU_OK || (rc = vo.ensure(rdv.size())) != HU_OK) return rc;
+				HIPCHK(hipMemcpyAsync(dd.p, rdv.data(), rdv.size() * sizeof(HuReadDesc), hipMemcpyHostToDevice, b->stream));
+				if(onlyStatus) HIPCHK(hipMemcpyAsync(vo.p, hv.data(), hv.size() * sizeof(HuVitOut), hipMemcpyHostToDevice, b->stream));
+				if((rc = fillValues(dd.p, (unsigned) rdv.size(), scr.p, vo.p, onlyStatus)) != HU_OK) return rc;
+				HIPCHK(hipGetLastError());
+				HIPCHK(hipMemcpyAsync(hv.data(), vo.p, hv.size() * sizeof(HuVitOut), hipMemcpyDeviceToHost, b->stream));
+				HIPCHK(hu_wait(b->stream));
+				for(size_t k = 0; k < rdv.size(); ++k) b->hVit[rs[at + k]] = hv[k];     /* the trace is written at the sequence's own traceOff */
+				hostVit = true;
+				at = e;
 			}
-			else if(nRedo) {
-				if(vlds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*) k_viterbi_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int) vlds));
-				k_viterbi_lds<<<b->nSeq, HU_VIT_THREADS, vlds, b->stream>>>(d, b->dDescs.p, b->dBases.p, b->dScratch.p, b->dTraces.p, tNN, tNB, tEC, tCC, b->dVit.p, ldsRows, HU_READ_NEEDS_VALUES);
-				k_viterbi_trace<<<(b->nSeq + 63) / 64, 64, 0, b->stream>>>(d, b->dDescs.p, b->dScratch.p, b->dTraces.p, tNN, tNB, b->dVit.p, b->nSeq);
+			return HU_OK;
+		};
+		if(vp.dec()) { /* sequences whose traceback cannot trust the fill-time decisions: redo with every value filed */
+			std::vector<int> rs;
+			for(int s = 0; s < b->nSeq; ++s) if(b->hVit[s].status == HU_READ_NEEDS_VALUES) rs.push_back(s);
+			if(!rs.empty() && vp.wave()) { /* the batch holds corner scratch only: the few sequences to redo get a full-size scratch of their own */
+				auto cellsOf = [](HuReadDesc& rd) {      /* cells of all its phases, as build_regions laid them out */
+					int64_t c = 0;
+					for(int g = 0; g < rd.nRegions; ++g) if(rd.reg[g].j1 >= rd.reg[g].j0 && rd.reg[g].i1 >= rd.reg[g].i0) c += (int64_t)(rd.reg[g].j1 - rd.reg[g].j0 + 1) * (rd.reg[g].i1 - rd.reg[g].i0 + 1);
+					return c;
+				};
+				if((rc = redoChunked(rs, cellsOf, HU_READ_NEEDS_VALUES)) != HU_OK) return rc;
+			}
+			else if(!rs.empty()) {
+				if((rc = fillValues(b->dDescs.p, b->nSeq, b->dScratch.p, b->dVit.p, HU_READ_NEEDS_VALUES)) != HU_OK) return rc;
 				HIPCHK(hipGetLastError());
 				HIPCHK(hipMemcpyAsync(b->hVit.data(), b->dVit.p, (size_t) b->nSeq * sizeof(HuVitOut), hipMemcpyDeviceToHost, b->stream));
 				HIPCHK(hu_wait(b->stream));
 			}
 		}
-		/* banded version failed -> regular HMM (src/HmmUFOtu_main.cpp:89-93): all such sequences in ONE launch, each with a
-		 * full-DP descriptor of its own (same bases, same trace slot) and its share of one temporary scratch */
+		/* banded version failed -> regular HMM (src/HmmUFOtu_main.cpp:89-93): each such sequence with a full-DP descriptor of its own
+		 * (same bases, same trace slot) */
 		std::vector<int> redo;
 		for(int s = 0; s < b->nSeq; ++s) if(b->hVit[s].status == HU_READ_NEEDS_FULL && !(b->hDescs[s].nRegions == 1 && !b->hDescs[s].reg[0].band)) redo.push_back(s);
-		b->nFullRedo = (int) redo.size();
-		/* launches of at most 48 M cells (1.2 GB of (M, I, D) scratch): ~130 reads of 250 bp against K = 1,400 each */
-		const int64_t cellCap = 48ll << 20;
-		for(size_t at = 0; at < redo.size();) {
-			std::vector<HuReadDesc> rdv;
-			int64_t cells = 0;
-			size_t e = at;
-			for(; e < redo.size(); ++e) {
-				HuReadDesc rd = b->hDescs[redo[e]];
-				build_regions(b->db, rd.len, nullptr, rd);
-				const int64_t c = rd.scratchOff;
-				if(!rdv.empty() && cells + c > cellCap) break;
-				rd.scratchOff = cells; cells += c;
-				rdv.push_back(rd);
-			}
-			DBuf<double>& scr = b->dRedoScr; DBuf<HuReadDesc>& dd = b->dRedoDesc; DBuf<HuVitOut>& vo = b->dRedoVit;
-			if((rc = scr.ensure((size_t) cells * 3 + 1)) != HU_OK || (rc = dd.ensure(rdv.size())) != HU_OK || (rc = vo.ensure(rdv.size())) != HU_OK) return rc;
-			std::vector<HuVitOut> hv(rdv.size());
-			HIPCHK(hipMemcpyAsync(dd.p, rdv.data(), rdv.size() * sizeof(HuReadDesc), hipMemcpyHostToDevice, b->stream));
-			if(vlds <= 96 * 1024 && !kb.viterbi_hbm) { /* a workgroup per sequence, the wavefront staged in LDS, every value filed for the traceback: K + len steps of a barrier
-			                                           * each instead of as many round trips to HBM by one wave (30 - 100 ms for a handful of 150-base reads) */
-				if(vlds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*) k_viterbi_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int) vlds));
-				k_viterbi_lds<<<(unsigned) rdv.size(), HU_VIT_THREADS, vlds, b->stream>>>(d, dd.p, b->dBases.p, scr.p, b->dTraces.p, tNN, tNB, tEC, tCC, vo.p, ldsRows, 0);
-				k_viterbi_trace<<<((unsigned) rdv.size() + 63) / 64, 64, 0, b->stream>>>(d, dd.p, scr.p, b->dTraces.p, tNN, tNB, vo.p, (int) rdv.size());
-			}
-			else k_viterbi<<<(unsigned) rdv.size(), 64, 0, b->stream>>>(d, dd.p, b->dBases.p, scr.p, b->dTraces.p, tNN, tNB, tEC, tCC, vo.p);
-			HIPCHK(hipGetLastError());
-			HIPCHK(hipMemcpyAsync(hv.data(), vo.p, hv.size() * sizeof(HuVitOut), hipMemcpyDeviceToHost, b->stream));
-			HIPCHK(hu_wait(b->stream));
-			for(size_t k = 0; k < rdv.size(); ++k) {
-				const int s = redo[at + k];
-				b->hVit[s] = hv[k];                     /* the trace is already written at the sequence's traceOff */
-				if(b->hVit[s].status == HU_READ_NEEDS_FULL) b->hVit[s].status = HU_READ_INVALID;
-				HIPCHK(hipMemcpyAsync(b->dVit.p + s, &b->hVit[s], sizeof(HuVitOut), hipMemcpyHostToDevice, b->stream));
-				b->hDescs[s].nRegions = -1; /* mark: full DP was used */
-			}
-			HIPCHK(hu_wait(b->stream));
-			at = e;
-		}
-		for(int s = 0; s < b->nSeq; ++s) if(b->hVit[s].status == HU_READ_NEEDS_FULL) {
-			b->hVit[s].status = HU_READ_INVALID;
-			HIPCHK(hipMemcpyAsync(b->dVit.p + s, &b->hVit[s], sizeof(HuVitOut), hipMemcpyHostToDevice, b->stream));
-		}
+		auto fullDp = [&](HuReadDesc& rd) { build_regions(b->db, rd.len, nullptr, rd); return rd.scratchOff; };
+		if((rc = redoChunked(redo, fullDp, 0)) != HU_OK) return rc;
+		for(int s : redo) b->hDescs[s].nRegions = -1; /* mark: full DP was used */
+		for(int s = 0; s < b->nSeq; ++s) if(b->hVit[s].status == HU_READ_NEEDS_FULL) { b->hVit[s].status = HU_READ_INVALID; hostVit = true; }
+		if(hostVit) HIPCHK(hipMemcpyAsync(b->dVit.p, b->hVit.data(), (size_t) b->nSeq * sizeof(HuVitOut), hipMemcpyHostToDevice, b->stream));
 		{
 			Timer t(b, HU_T_ALIGN_BUILD);
 			k_align_rows<<<b->nSeq, 64, 0, b->stream>>>(d, b->dDescs.p, b->dBases.p, b->dTraces.p, b->dVit.p, b->dRows.p, b->dAlns.p);
@@ -2023,13 +2006,15 @@ __global__ void k_seed_sortkeys(int n, const int32_t* __restrict__ seedCnt, cons
  * workgroups per CU) goes with the WIDEST region of the launch — and with seeds from the index instead of the truth a few reads per batch have
  * seeds that land far apart: regions of 2,000 - 6,000 columns beside 8,000 reads of ~800 (measured on the 1 M-read pool at 150 bases: 1 - 4 such
  * reads in five batches of eight, placement 23 ms instead of 5).  Those reads get a launch of their own: the class boundary above the
- * (W + 1)-th widest region, W <= 64, splits the batch when the widest region lies in a higher class. */
+ * (W + 1)-th widest region, W <= 64, splits the batch when the widest region lies in a higher class.  Split or not, it records the widest
+ * region of the batch and of the main launch, which size the kernels of both passes. */
 static void plan_width_split(hu_batch* b) {
-	b->rMain = 0; b->wideReads.clear();
-	if(!b->knob.width_split || b->n < 256 || (int) b->hStart.size() < b->n || (int) b->hEnd.size() < b->n) return;
+	b->rMain = 0; b->wideReads.clear(); b->maxAll = b->maxMain = 1;
+	if((int) b->hStart.size() < b->n || (int) b->hEnd.size() < b->n) return;
 	std::vector<int> R((size_t) b->n);
-	int maxAll = 0;
-	for(int r = 0; r < b->n; ++r) { R[r] = std::max(0, b->hEnd[r] - b->hStart[r] + 1); maxAll = std::max(maxAll, R[r]); }
+	for(int r = 0; r < b->n; ++r) { R[r] = std::max(0, b->hEnd[r] - b->hStart[r] + 1); b->maxAll = std::max(b->maxAll, R[r]); }
+	b->maxMain = b->maxAll;
+	if(!b->knob.width_split || b->n < 256) return;
 	const int W = std::min(64, b->n / 128);
 	std::vector<int> tmp(R);
 	std::nth_element(tmp.begin(), tmp.begin() + W, tmp.end(), std::greater<int>());
@@ -2037,10 +2022,16 @@ static void plan_width_split(hu_batch* b) {
 	static const int bounds[] = {512, 768, 1024, 1536, 2048, 3072};
 	int bound = 0;
 	for(int x : bounds) if(kth <= x) { bound = x; break; }
-	if(!bound || bound >= maxAll) return;
-	b->rMain = bound;
-	for(int r = 0; r < b->n; ++r) if(R[r] > bound) b->wideReads.push_back(r);
-	if(b->knob.trace) fprintf(stderr, "[hu] width split: %zu of %d reads beyond %d columns (widest %d) take a launch of their own\n", b->wideReads.size(), b->n, bound, maxAll);
+	if(!bound || bound >= b->maxAll) return;
+	b->rMain = bound; b->maxMain = 1;
+	for(int r = 0; r < b->n; ++r) { if(R[r] > bound) b->wideReads.push_back(r); else b->maxMain = std::max(b->maxMain, R[r]); }
+	if(b->knob.trace) fprintf(stderr, "[hu] width split: %zu of %d reads beyond %d columns (widest %d) take a launch of their own\n", b->wideReads.size(), b->n, bound, b->maxAll);
+}
+/* the database as a width pass sees it: pass 0 the regions of at most rMain columns, pass 1 the rest, through its list of slots / candidates */
+static HuDbDev width_pass_dev(const hu_batch* b, int pass, const uint32_t* wideList) {
+	HuDbDev dev = b->db->dev;
+	if(b->rMain) { dev.rLo = pass ? b->rMain : -1; dev.rHi = pass ? 0x7fffffff : b->rMain; dev.wideList = pass ? wideList : nullptr; }
+	return dev;
 }
 
 extern "C" int hu_estimate_batch(hu_batch* b, const hu_opts* o) try {
@@ -2054,8 +2045,6 @@ extern "C" int hu_estimate_batch(hu_batch* b, const hu_opts* o) try {
 	if(n) {
 		Timer t(b, HU_T_ESTIMATE);
 		plan_width_split(b);
-		int maxAll = 1, maxMain = 1;
-		for(int r = 0; r < b->n; ++r) { const int R = b->hEnd[r] - b->hStart[r] + 1; maxAll = std::max(maxAll, R); if(!b->rMain || R <= b->rMain) maxMain = std::max(maxMain, R); }
 		const bool stream = b->knob.streaming_sep != 0;
 		if(b->rMain) { /* the wide reads' (read, seed) slots: the second launch's list */
 			b->hWideOrd.clear();
@@ -2064,9 +2053,8 @@ extern "C" int hu_estimate_batch(hu_batch* b, const hu_opts* o) try {
 			HIPCHK(hipMemcpyAsync(b->dWideOrd.p, b->hWideOrd.data(), b->hWideOrd.size() * 4, hipMemcpyHostToDevice, b->stream));
 		}
 		for(int pass = 0; pass < (b->rMain ? 2 : 1); ++pass) { /* pass 1: the reads beyond rMain, on the kernel their width asks for */
-			const int maxR = pass ? maxAll : maxMain;
-			HuDbDev dev = b->db->dev;
-			if(b->rMain) { dev.rLo = pass ? b->rMain : -1; dev.rHi = pass ? 0x7fffffff : b->rMain; dev.wideList = pass ? b->dWideOrd.p : nullptr; }
+			const int maxR = pass ? b->maxAll : b->maxMain;
+			const HuDbDev dev = width_pass_dev(b, pass, b->dWideOrd.p);
 			#define EST_ARGS dev, b->db->mdl, b->dCodes.p, b->dStart.p, b->dEnd.p, b->dParDN.p, b->dSeedCnt.p, b->dSeedId.p, b->dSeedDN.p, o->weighted, b->dEst.p
 			const unsigned eg = pass ? (unsigned) b->hWideOrd.size() : (unsigned) b->n * HU_MAX_SEEDS;
 			/* launch order of the table-driven kernels: by seed node */
@@ -2253,8 +2241,6 @@ extern "C" int hu_place_batch(hu_batch* b, const hu_opts* o) try {
 	(void) hipGetLastError();
 	if(nc) {
 		Timer t(b, HU_T_PLACE);
-		int maxAll = 1, maxMain = 1;
-		for(int r = 0; r < b->n; ++r) { const int R = b->hEnd[r] - b->hStart[r] + 1; maxAll = std::max(maxAll, R); if(!b->rMain || R <= b->rMain) maxMain = std::max(maxMain, R); }
 		int passes = 1;
 		if(b->rMain) { /* the candidates of the wide reads: the second launch's list (plan_width_split) */
 			b->hWideCand.clear();
@@ -2267,9 +2253,8 @@ extern "C" int hu_place_batch(hu_batch* b, const hu_opts* o) try {
 			}
 		}
 		for(int pass = 0; pass < passes; ++pass) { /* pass 1: the candidates of the reads beyond rMain, on the kernel their width asks for */
-			const int maxR = pass ? maxAll : maxMain;
-			HuDbDev dev = b->db->dev;
-			if(b->rMain) { dev.rLo = pass ? b->rMain : -1; dev.rHi = pass ? 0x7fffffff : b->rMain; dev.wideList = pass ? b->dWideCand.p : nullptr; }
+			const int maxR = pass ? b->maxAll : b->maxMain;
+			const HuDbDev dev = width_pass_dev(b, pass, b->dWideCand.p);
 			const unsigned grid = pass ? (unsigned) b->hWideCand.size() : (unsigned) nc;
 			const int spt2 = (maxR + 127) / 128, spt4 = (maxR + 255) / 256;  /* sites per thread with 2 / 4 waves per candidate */
 			const bool stream = b->knob.streaming_sep != 0 || spt4 > 12;
