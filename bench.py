@@ -14,6 +14,12 @@ rank; started plainly with --gpus N > 1 it launches the N ranks itself (python -
 127.0.0.1) BEFORE anything touches the GPU, forwards rank 0's JSON line and exits with the launcher's code.
 A WORLD_SIZE that disagrees with --gpus is an error, never a silent one-rank run.
 
+A plain run does what the headline figure needs: it builds the database, uploads the reads, warms up, times the K
+steps, writes --dump-outputs and prints the line.  --full also measures and checks the rest, before and after the
+timed region: the CPU baseline and its parity with the GPU (--cpu-sample), the other seed order as a side block, the
+end-to-end block (--e2e-reads), and the per-kernel isolated times with the roofline.  The timed region is the same in
+both.
+
 Other workloads of BASELINE.json (parity cases, kept out of the headline line): --read-len 150 --dg-k 0 (cfg2),
 --paired --read-len 250 (cfg4 shape), --leaves 200000 --paired --read-len 300 (cfg5), --uniform-starts (SURVEY
 §8d: read starts uniform over the resident window instead of one amplicon window).
@@ -51,14 +57,17 @@ def parse_args(argv=None):
     ap.add_argument("--amplicon-cols", type=int, default=0, help="CS columns of the simulated amplicon (0: from the read length)")
     ap.add_argument("--uniform-starts", action="store_true", help="read starts uniform over the resident window (SURVEY §8d second run)")
     ap.add_argument("--partial-frac", type=float, default=0.0, help="fraction of the leaves that lose a prefix or suffix (partial reference sequences)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="reads for the CPU baseline (0 = skip, -1 = about 30 s worth on the CPUs the process may use)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline and its parity, the other seed order, "
+                         "the end-to-end block, per-kernel isolated times and the roofline")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="reads for the CPU baseline under --full (0 = skip, -1 = about 30 s worth on the CPUs the process may use)")
     ap.add_argument("--seed-order", choices=["stable", "reference"], default="reference",
                     help="hu_opts.seed_order of the timed region: 'reference' [default] = the first max_nseed of libstdc++'s std::sort on dist alone "
                          "(HU_SEED_ORDER_LIBSTDCXX: the reference binary's own tie permutation, src/HmmUFOtu_main.cpp:139 + src/hmmufotu.cpp:646-647, reproduced on the "
-                         "device by the pair scan + k_seed_refsort); 'stable' = (dist, node id) (distance-only scan + top-k).  The other order is measured after the "
-                         "timed region and reported as a side block (seed_order_stable / seed_order_reference)")
+                         "device by the pair scan + k_seed_refsort); 'stable' = (dist, node id) (distance-only scan + top-k).  Under --full the other order is measured "
+                         "after the timed region and reported as a side block (seed_order_stable / seed_order_reference)")
     ap.add_argument("--e2e-reads", type=int, default=int(os.environ.get("HU_BENCH_E2E_READS", 1 << 20)),
-                    help="distinct reads of the end-to-end block (host seed lookup + upload + engine + TSV formatting, measured after the timed region; 0 = skip)")
+                    help="distinct reads of the end-to-end block under --full (host seed lookup + upload + engine + TSV formatting, measured after the timed region; 0 = skip)")
     ap.add_argument("--rehearse", action="store_true",
                     help="control-flow rehearsal WITHOUT the engine (CPU, gloo): launch, rendezvous, barrier, gather, max-over-ranks, one JSON line; value is null")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -276,7 +285,7 @@ def main():
             all_reads.append(reads); all_vps.append(np.stack([synth.read_vpaths(db.hmm, r) for r in reads]))
     # ---- end-to-end pool: --e2e-reads DISTINCT reads of the headline shape as one byte buffer (drawn from the log-space messages, like the batches)
     e2e_pool = None
-    if rank == 0 and world == 1 and args.e2e_reads > 0 and not args.paired:
+    if args.full and rank == 0 and world == 1 and args.e2e_reads > 0 and not args.paired:
         tp = time.time()
         e2e_pool = synth_gpu.simulate_pool_gpu(db, up, down, args.e2e_reads, args.read_len, seed=777, amplicon_start=amp_start, amplicon_cols=amp_cols, device=dev)
         log("end-to-end pool: %d distinct reads, %.1f MB (%.0fs)" % (len(e2e_pool[1]) - 1, e2e_pool[0].nbytes / 1e6, time.time() - tp))
@@ -287,7 +296,7 @@ def main():
     # window (40-200 GB) — which is what lets the leg run on the 400 k-node database of config 5.  Phase B (after the timed region) runs the
     # rest of the task on those rows.  The same scan also yields the seed list under the reference's literal std::sort (tie-mode report).
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_sample != 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample != 0:
         try:
             from oracle import oracle_py as O
             cores = max(1, min(O.max_threads(), cpu_quota()))
@@ -414,120 +423,8 @@ def main():
         for k, v in timed_ms[i].items():
             acc[k] = acc.get(k, 0.0) + v
     acc = {k: v / max(1, sum(timed_n)) for k, v in acc.items()}
-    # (b) one batch alone on the GPU: the kernel's own cost, what the roofline fraction is quoted on
-    B = batches[0]
-    iso = {}
-    nprof = 3
-    wall = {}
-    for _ in range(nprof):
-        B.assign(opts)
-        for k, v in B.timings().items():
-            iso[k] = iso.get(k, 0.0) + v / nprof
-        for k, v in B.wall().items():
-            wall[k] = wall.get(k, 0.0) + v / nprof
-    cd, st, en = B.codes()
-    ok = en >= st
-    R = float((en[ok] - st[ok] + 1).mean())
-    best = B.placements()
-    cand = B.candidates()
-    _, cplaces = B.candidate_places()        # fetched now: the end-to-end block below reuses the batch objects
-    C = float(np.diff(cand["offs"]).mean())
-    place_iters = dict(outer_mean=float((cand["iters"] & 255).mean()), outer_max=int((cand["iters"] & 255).max()),
-                       em_mean=float((cand["iters"] >> 8).mean()), em_max=int((cand["iters"] >> 8).max()))
-    S = 50
-    peak = 8000.0
-    nread = int(ok.sum())
-    nseq = nread * (2 if args.paired else 1)
-    Rsum = float((en[ok] - st[ok] + 1).sum())
-    Wp = args.read_len + 60
-    # algorithmic bytes per launch (SURVEY.md §8d per-unit figures x units of one launch)
     ref_order = args.seed_order == "reference"
-    pair_bytes = 4 if (args.paired or args.read_len > 255) else 2       # the (d, N) pair row of the reference-order mode: 16-bit pairs while no read has more than 255 bases
-    alg = dict(viterbi=nseq * (args.read_len + 136.0 * Wp), seed_pdist=(D.n_nodes - 1) * Rsum,
-               seed_topk=(float(pair_bytes) * (D.n_nodes - 1) * nread if ref_order else 4.0 * D.n_nodes * nread),      # k_seed_refsort: the pair row once
-               estimate=S * 65.0 * Rsum, place=C * 64.0 * Rsum)
-    # measured HBM traffic + VALU issue per kernel: from the newest committed PMC summary that was taken on THIS workload
-    # (rocprofv3 --pmc passes of this same command, profiles/make_pmc_summary.py); tagged with its source, null otherwise
-    stages = ("viterbi", "seed_pdist", "seed_topk", "estimate", "place")
-    pmc_prefix = dict(viterbi=("k_viterbi_wave", "k_viterbi_dec2", "k_viterbi_dec", "k_viterbi_lds", "k_viterbi"),
-                      seed_pdist=("k_seed_pdist2", "k_seed_pdist") if ref_order else ("k_seed_dscan4", "k_seed_dscan", "k_seed_pdist2", "k_seed_pdist"),
-                      seed_topk=("k_seed_refsort",) if ref_order else ("k_seed_topk_straight", "k_seed_topk_d", "k_seed_topk"),
-                      estimate=("k_estimate_prod", "k_estimate_blk", "k_estimate"), place=("k_place_blk", "k_place_pair", "k_place"))
-    workload_key = dict(leaves=args.leaves, cs_len=args.cs_len, read_len=args.read_len, batch=args.batch, dg_k=args.dg_k, paired=bool(args.paired),
-                        uniform_starts=bool(args.uniform_starts), win=args.win)
-    if not ref_order:
-        workload_key["seed_order"] = "stable"
-    if args.partial_frac:
-        workload_key["partial_frac"] = args.partial_frac
-    pmc, pmc_src, pmc_hash = {}, None, None
-    src_hash = kernel_source_hash()
-    pdir = os.path.join(ROOT, "profiles")
-    for f in sorted((x for x in os.listdir(pdir) if x.endswith("_pmc_summary.json")), reverse=True):
-        try:
-            j = json.load(open(os.path.join(pdir, f)))
-            if j.get("workload") == workload_key:
-                pmc, pmc_src, pmc_hash = j["kernels"], "profiles/" + f, j.get("kernel_source_hash")
-                break
-        except Exception:
-            pass
-
-    pmc_stale = bool(pmc) and pmc_hash != src_hash       # counters of other kernel sources than the ones running: quoted, but tagged
-
-    def pmc_entry(stage):
-        for pre in pmc_prefix[stage]:
-            for name in sorted(pmc):
-                if name.startswith(pre) and not name[len(pre):len(pre) + 1].isalnum() and name[len(pre):len(pre) + 1] != "_":
-                    return name, pmc[name]
-        return pmc_prefix[stage][0], {}
-
-    kern = []
-    for k in stages:
-        name, ent = pmc_entry(k)
-        tr = ent.get("hbm_bytes_per_launch")
-        # algorithmic_over_hbm_peak: the contract's figure (SURVEY.md section 8d bytes / isolated time / 8 TB/s).  Above 1 it is NOT a bandwidth anybody measured: the kernel does the
-        # reference's work on fewer bytes (bit-planes, sixteen reads per node tile, L2 sharing); what the chip really moved and issued are the two fields after it
-        e = dict(stage=k, kernel=name, ms_isolated=round(iso[k], 3), ms_in_timed_region=round(acc[k], 3), algorithmic_bytes=alg[k],
-                 algorithmic_GBps=alg[k] / (iso[k] * 1e-3) / 1e9, algorithmic_over_hbm_peak=alg[k] / (iso[k] * 1e-3) / 1e9 / peak,
-                 traffic=tr, hbm_measured_frac=(tr / (iso[k] * 1e-3) / 1e9 / peak if tr else None))
-        if ent.get("valu_issue_cycles_per_launch"):       # typed instruction counts x measured issue cycles (profiles/isa_cost.py), over 1,024 SIMDs
-            e["valu_issue_frac"] = ent["valu_issue_cycles_per_launch"] / 1024.0 / (iso[k] * 1e-3 * ent.get("clock_hz", 2.37e9))   # 2.37 GHz: measured, profiles/r02d_clocks.json
-        kern.append(e)
-    dom = max(kern, key=lambda x: x["ms_isolated"])
-    # What binds the dominant kernel is FP64 VALU issue at the occupancy its per-site state allows, not HBM: `bound` says so.
-    # `frac` stays the contract's number (algorithmic bytes / isolated time / HBM peak); the two measured roofs sit beside it.
-    dfrac = dom["algorithmic_over_hbm_peak"]
-    roof = dict(bound="valu_fp64_issue", kernel=dom["kernel"], achieved=dom["algorithmic_GBps"], peak=peak, unit="GB/s", frac=dfrac, traffic=dom["traffic"],
-                ms=dom["ms_isolated"], timing="HIP events on the batch's stream, one batch in flight (the kernel's own cost)",
-                ms_in_timed_region=dom["ms_in_timed_region"], frac_in_timed_region=dom["algorithmic_bytes"] / (dom["ms_in_timed_region"] * 1e-3) / 1e9 / peak,
-                hbm_measured_frac=dom["hbm_measured_frac"], valu_issue_frac=dom.get("valu_issue_frac"), traffic_source=pmc_src,
-                pmc_kernel_source_hash=pmc_hash, kernel_source_hash=src_hash, pmc_stale=pmc_stale,
-                hbm_roof=dict(achieved=dom["algorithmic_GBps"], peak=peak, unit="GB/s", frac=dfrac, measured_frac=dom["hbm_measured_frac"]),
-                valu_roof=dict(frac=dom.get("valu_issue_frac"), unit="issue cycles of the kernel's vector instructions / (1,024 SIMDs x clock x isolated time)"),
-                note="frac = ALGORITHMIC bytes of the dominant kernel (SURVEY.md section 8d per-unit figure x the launch's units: FP64 messages once per candidate) / its isolated "
-                     "time / 8 TB/s; traffic = PMC bytes of the same launch.  The kernel is bound by FP64 vector issue at the occupancy its per-site state allows (valu_roof), not "
-                     "by HBM.  BASELINE.json's '>= 50 % HBM-bandwidth utilisation' is NOT met at configs 2-4 and cannot be by this formulation: after the bit-plane / tiling / "
-                     "eigenbasis reformulations every kernel of the path is VALU-issue-bound (roofline_path.path_valu_issue_frac), and the path moves ~a fifth of the HBM peak "
-                     "(roofline_path.hbm_measured_frac).  pmc_stale = the PMC summary was taken on other kernel sources than are running now.")
-    if dfrac > 1:      # (a seed-scan kernel dominates, e.g. config 5 in the reference's seed order)
-        roof["frac_above_1"] = ("the dominant kernel here is the node scan, whose ALGORITHMIC bytes (one int8 site per node, column and read, no reuse credited: SURVEY.md section 8d) are "
-                                "not bytes anybody moves: it reads three bit-planes per 32 sites once per tile of sixteen reads.  frac is kept as the contract defines it; "
-                                "hbm_measured_frac and valu_issue_frac say how busy the chip is")
-    bytes_per_read = (D.n_nodes - 1) * R + S * 65 * R + C * 64 * R + (2 if args.paired else 1) * (args.read_len + 136 * Wp) + args.cs_len + 128
-    step_traffic = sum(k["traffic"] for k in kern) if all(k["traffic"] for k in kern) else None
-    # every vector instruction of a step, priced at its measured issue cost, over what 1,024 SIMDs could issue in the step's time: how busy the chip's VALUs are, the roof
-    # that binds the path.  The per-step kernels of this seed order from the PMC summary (one-time kernels and the other order's seed kernels left out)
-    one_time = ("k_alleq_init", "k_node_cover", "k_pack_msgs", "k_col_planes", "k_tree_", "k_pairs_of_read", "k_sort_desc_test")
-    other_seed = ("k_seed_dscan", "k_seed_topk_straight", "k_seed_topk_d") if ref_order else ("k_seed_pdist2", "k_seed_refsort", "k_ref_pivots", "k_take_nan_rows")
-    issue_cycles = sum(v.get("valu_issue_cycles_per_launch", 0.0) for name_, v in pmc.items() if not name_.startswith(one_time) and not name_.startswith(other_seed))
-    clock_hz = next((v.get("clock_hz") for v in pmc.values() if v.get("clock_hz")), 2.37e9)
-    path = dict(algorithmic_bytes_per_read=bytes_per_read, algorithmic_GBps_equivalent=bytes_per_read * value / world / 1e9, mean_R=R, mean_candidates=C,
-                what="algorithmic bytes (SURVEY.md section 8d: int8 node sites streamed once per read, FP64 messages, no reuse credited) x reads/s.  An EQUIVALENT rate — "
-                     "%.0f x the HBM peak — not a bandwidth: the scan works on 3 bit-planes x 16 reads per node tile.  The measured roofs follow" % (bytes_per_read * value / world / 1e9 / peak),
-                hbm_measured_bytes_per_step=step_traffic,
-                hbm_measured_frac=(step_traffic / (dt / args.steps) / 1e9 / peak if step_traffic else None),
-                path_valu_issue_frac=(issue_cycles / 1024.0 / ((dt / args.steps) * clock_hz) if issue_cycles else None),
-                traffic_source=pmc_src, pmc_stale=pmc_stale)
-
+    # the headline line; --full adds the blocks below to it
     shape = "%s %d bp" % ("PE 2 x" if args.paired else "SE", args.read_len)
     free_b, total_b = torch.cuda.mem_get_info(local)
     out = dict(metric=metric, value=value, unit="reads/s" if not args.paired else "pairs/s",
@@ -541,13 +438,127 @@ def main():
                            db_hbm_gb=D.hbm_bytes / 1e9, message_window_cols=db.win[1], parallelism="read-sharded x%d" % world,
                            hbm_in_use_gb=(total_b - free_b) / 1e9, hbm_total_gb=total_b / 1e9),
                timed_region="the engine's whole per-read task on reads and seed paths already resident (hu_assign_batch + result fetch per step); the host seed "
-                            "lookup, FASTA parsing, the read upload (< 1 KB per read) and the TSV are outside it: `end_to_end` below measures them in this same process",
+                            "lookup, FASTA parsing, the read upload (< 1 KB per read) and the TSV are outside it: under --full `end_to_end` measures them in this same process",
                **({"engine_knobs": os.environ["HU_BENCH_KNOBS"]} if os.environ.get("HU_BENCH_KNOBS") else {}),
                host_cores_busy_per_rank=round(host_cores_busy, 1), host_cpus=os.cpu_count(), host_cpu_quota=cpu_quota(),
                rccl_ranks=rccl_ranks, rccl_error=rccl_error, backend=backend if (world > 1 or rccl_ranks) else None, gathered_records=(int(len(gathered)) if gathered is not None else None),
-               roofline=roof, roofline_kernels=kern, roofline_path=path,
-               kernel_ms={k: round(v, 3) for k, v in acc.items()}, kernel_ms_one_batch_in_flight={k: round(v, 3) for k, v in iso.items()},
-               host_wall_ms={k: round(float(v), 2) for k, v in wall.items()}, place_iterations=place_iters)
+               kernel_ms={k: round(v, 3) for k, v in acc.items()})
+
+    if args.full:
+        # (b) one batch alone on the GPU: the kernel's own cost, what the roofline fraction is quoted on
+        B = batches[0]
+        iso = {}
+        nprof = 3
+        wall = {}
+        for _ in range(nprof):
+            B.assign(opts)
+            for k, v in B.timings().items():
+                iso[k] = iso.get(k, 0.0) + v / nprof
+            for k, v in B.wall().items():
+                wall[k] = wall.get(k, 0.0) + v / nprof
+        cd, st, en = B.codes()
+        ok = en >= st
+        R = float((en[ok] - st[ok] + 1).mean())
+        best = B.placements()
+        cand = B.candidates()
+        _, cplaces = B.candidate_places()        # fetched now: the end-to-end block below reuses the batch objects
+        C = float(np.diff(cand["offs"]).mean())
+        place_iters = dict(outer_mean=float((cand["iters"] & 255).mean()), outer_max=int((cand["iters"] & 255).max()),
+                           em_mean=float((cand["iters"] >> 8).mean()), em_max=int((cand["iters"] >> 8).max()))
+        S = 50
+        peak = 8000.0
+        nread = int(ok.sum())
+        nseq = nread * (2 if args.paired else 1)
+        Rsum = float((en[ok] - st[ok] + 1).sum())
+        Wp = args.read_len + 60
+        # algorithmic bytes per launch (SURVEY.md §8d per-unit figures x units of one launch)
+        pair_bytes = 4 if (args.paired or args.read_len > 255) else 2       # the (d, N) pair row of the reference-order mode: 16-bit pairs while no read has more than 255 bases
+        alg = dict(viterbi=nseq * (args.read_len + 136.0 * Wp), seed_pdist=(D.n_nodes - 1) * Rsum,
+                   seed_topk=(float(pair_bytes) * (D.n_nodes - 1) * nread if ref_order else 4.0 * D.n_nodes * nread),      # k_seed_refsort: the pair row once
+                   estimate=S * 65.0 * Rsum, place=C * 64.0 * Rsum)
+        # measured HBM traffic + VALU issue per kernel: from the newest committed PMC summary that was taken on THIS workload
+        # (rocprofv3 --pmc passes of this same command, profiles/make_pmc_summary.py); tagged with its source, null otherwise
+        stages = ("viterbi", "seed_pdist", "seed_topk", "estimate", "place")
+        pmc_prefix = dict(viterbi=("k_viterbi_wave", "k_viterbi_dec2", "k_viterbi_dec", "k_viterbi_lds", "k_viterbi"),
+                          seed_pdist=("k_seed_pdist2", "k_seed_pdist") if ref_order else ("k_seed_dscan4", "k_seed_dscan", "k_seed_pdist2", "k_seed_pdist"),
+                          seed_topk=("k_seed_refsort",) if ref_order else ("k_seed_topk_straight", "k_seed_topk_d", "k_seed_topk"),
+                          estimate=("k_estimate_prod", "k_estimate_blk", "k_estimate"), place=("k_place_blk", "k_place_pair", "k_place"))
+        workload_key = dict(leaves=args.leaves, cs_len=args.cs_len, read_len=args.read_len, batch=args.batch, dg_k=args.dg_k, paired=bool(args.paired),
+                            uniform_starts=bool(args.uniform_starts), win=args.win)
+        if not ref_order:
+            workload_key["seed_order"] = "stable"
+        if args.partial_frac:
+            workload_key["partial_frac"] = args.partial_frac
+        pmc, pmc_src, pmc_hash = {}, None, None
+        src_hash = kernel_source_hash()
+        pdir = os.path.join(ROOT, "profiles")
+        for f in sorted((x for x in os.listdir(pdir) if x.endswith("_pmc_summary.json")), reverse=True):
+            try:
+                j = json.load(open(os.path.join(pdir, f)))
+                if j.get("workload") == workload_key:
+                    pmc, pmc_src, pmc_hash = j["kernels"], "profiles/" + f, j.get("kernel_source_hash")
+                    break
+            except Exception:
+                pass
+
+        pmc_stale = bool(pmc) and pmc_hash != src_hash       # counters of other kernel sources than the ones running: quoted, but tagged
+
+        def pmc_entry(stage):
+            for pre in pmc_prefix[stage]:
+                for name in sorted(pmc):
+                    if name.startswith(pre) and not name[len(pre):len(pre) + 1].isalnum() and name[len(pre):len(pre) + 1] != "_":
+                        return name, pmc[name]
+            return pmc_prefix[stage][0], {}
+
+        kern = []
+        for k in stages:
+            name, ent = pmc_entry(k)
+            tr = ent.get("hbm_bytes_per_launch")
+            # algorithmic_over_hbm_peak: the contract's figure (SURVEY.md section 8d bytes / isolated time / 8 TB/s).  Above 1 it is NOT a bandwidth anybody measured: the kernel does the
+            # reference's work on fewer bytes (bit-planes, sixteen reads per node tile, L2 sharing); what the chip really moved and issued are the two fields after it
+            e = dict(stage=k, kernel=name, ms_isolated=round(iso[k], 3), ms_in_timed_region=round(acc[k], 3), algorithmic_bytes=alg[k],
+                     algorithmic_GBps=alg[k] / (iso[k] * 1e-3) / 1e9, algorithmic_over_hbm_peak=alg[k] / (iso[k] * 1e-3) / 1e9 / peak,
+                     traffic=tr, hbm_measured_frac=(tr / (iso[k] * 1e-3) / 1e9 / peak if tr else None))
+            if ent.get("valu_issue_cycles_per_launch"):       # typed instruction counts x measured issue cycles (profiles/isa_cost.py), over 1,024 SIMDs
+                e["valu_issue_frac"] = ent["valu_issue_cycles_per_launch"] / 1024.0 / (iso[k] * 1e-3 * ent.get("clock_hz", 2.37e9))   # 2.37 GHz: measured, profiles/r02d_clocks.json
+            kern.append(e)
+        dom = max(kern, key=lambda x: x["ms_isolated"])
+        # What binds the dominant kernel is FP64 VALU issue at the occupancy its per-site state allows, not HBM: `bound` says so.
+        # `frac` stays the contract's number (algorithmic bytes / isolated time / HBM peak); the two measured roofs sit beside it.
+        dfrac = dom["algorithmic_over_hbm_peak"]
+        roof = dict(bound="valu_fp64_issue", kernel=dom["kernel"], achieved=dom["algorithmic_GBps"], peak=peak, unit="GB/s", frac=dfrac, traffic=dom["traffic"],
+                    ms=dom["ms_isolated"], timing="HIP events on the batch's stream, one batch in flight (the kernel's own cost)",
+                    ms_in_timed_region=dom["ms_in_timed_region"], frac_in_timed_region=dom["algorithmic_bytes"] / (dom["ms_in_timed_region"] * 1e-3) / 1e9 / peak,
+                    hbm_measured_frac=dom["hbm_measured_frac"], valu_issue_frac=dom.get("valu_issue_frac"), traffic_source=pmc_src,
+                    pmc_kernel_source_hash=pmc_hash, kernel_source_hash=src_hash, pmc_stale=pmc_stale,
+                    hbm_roof=dict(achieved=dom["algorithmic_GBps"], peak=peak, unit="GB/s", frac=dfrac, measured_frac=dom["hbm_measured_frac"]),
+                    valu_roof=dict(frac=dom.get("valu_issue_frac"), unit="issue cycles of the kernel's vector instructions / (1,024 SIMDs x clock x isolated time)"),
+                    note="frac = ALGORITHMIC bytes of the dominant kernel (SURVEY.md section 8d per-unit figure x the launch's units: FP64 messages once per candidate) / its isolated "
+                         "time / 8 TB/s; traffic = PMC bytes of the same launch.  The kernel is bound by FP64 vector issue at the occupancy its per-site state allows (valu_roof), not "
+                         "by HBM.  BASELINE.json's '>= 50 % HBM-bandwidth utilisation' is NOT met at configs 2-4 and cannot be by this formulation: after the bit-plane / tiling / "
+                         "eigenbasis reformulations every kernel of the path is VALU-issue-bound (roofline_path.path_valu_issue_frac), and the path moves ~a fifth of the HBM peak "
+                         "(roofline_path.hbm_measured_frac).  pmc_stale = the PMC summary was taken on other kernel sources than are running now.")
+        if dfrac > 1:      # (a seed-scan kernel dominates, e.g. config 5 in the reference's seed order)
+            roof["frac_above_1"] = ("the dominant kernel here is the node scan, whose ALGORITHMIC bytes (one int8 site per node, column and read, no reuse credited: SURVEY.md section 8d) are "
+                                    "not bytes anybody moves: it reads three bit-planes per 32 sites once per tile of sixteen reads.  frac is kept as the contract defines it; "
+                                    "hbm_measured_frac and valu_issue_frac say how busy the chip is")
+        bytes_per_read = (D.n_nodes - 1) * R + S * 65 * R + C * 64 * R + (2 if args.paired else 1) * (args.read_len + 136 * Wp) + args.cs_len + 128
+        step_traffic = sum(k["traffic"] for k in kern) if all(k["traffic"] for k in kern) else None
+        # every vector instruction of a step, priced at its measured issue cost, over what 1,024 SIMDs could issue in the step's time: how busy the chip's VALUs are, the roof
+        # that binds the path.  The per-step kernels of this seed order from the PMC summary (one-time kernels and the other order's seed kernels left out)
+        one_time = ("k_alleq_init", "k_node_cover", "k_pack_msgs", "k_col_planes", "k_tree_", "k_pairs_of_read", "k_sort_desc_test")
+        other_seed = ("k_seed_dscan", "k_seed_topk_straight", "k_seed_topk_d") if ref_order else ("k_seed_pdist2", "k_seed_refsort", "k_ref_pivots", "k_take_nan_rows")
+        issue_cycles = sum(v.get("valu_issue_cycles_per_launch", 0.0) for name_, v in pmc.items() if not name_.startswith(one_time) and not name_.startswith(other_seed))
+        clock_hz = next((v.get("clock_hz") for v in pmc.values() if v.get("clock_hz")), 2.37e9)
+        path = dict(algorithmic_bytes_per_read=bytes_per_read, algorithmic_GBps_equivalent=bytes_per_read * value / world / 1e9, mean_R=R, mean_candidates=C,
+                    what="algorithmic bytes (SURVEY.md section 8d: int8 node sites streamed once per read, FP64 messages, no reuse credited) x reads/s.  An EQUIVALENT rate — "
+                         "%.0f x the HBM peak — not a bandwidth: the scan works on 3 bit-planes x 16 reads per node tile.  The measured roofs follow" % (bytes_per_read * value / world / 1e9 / peak),
+                    hbm_measured_bytes_per_step=step_traffic,
+                    hbm_measured_frac=(step_traffic / (dt / args.steps) / 1e9 / peak if step_traffic else None),
+                    path_valu_issue_frac=(issue_cycles / 1024.0 / ((dt / args.steps) * clock_hz) if issue_cycles else None),
+                    traffic_source=pmc_src, pmc_stale=pmc_stale)
+        out.update(roofline=roof, roofline_kernels=kern, roofline_path=path, kernel_ms_one_batch_in_flight={k: round(v, 3) for k, v in iso.items()},
+                   host_wall_ms={k: round(float(v), 2) for k, v in wall.items()}, place_iterations=place_iters)
 
     # ---- the same task in the OTHER seed order, after the timed region, on the same resident batches.  The timed region runs the reference's own order
     # (HU_SEED_ORDER_LIBSTDCXX: what a g++-built reference binary outputs wherever nodes tie at the cut-off distance; cpu_baseline.tie_mode counts how often
@@ -555,7 +566,7 @@ def main():
     other = "stable" if ref_order else "reference"
     other_key = "seed_order_" + other
     best_oth = cand_oth = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             opts_oth = E.default_opts(seed_order=0 if ref_order else 1)
             nbr = nb

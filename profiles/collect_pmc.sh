@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-2 profile collection on the GPU box (gpurun):  bash profiles/collect_pmc.sh <tag> [bench.py workload flags]
-#   1. rocprofv3 --kernel-trace --stats of the DEFAULT bench command (+ the given workload flags): per-kernel durations
+#   1. rocprofv3 --kernel-trace --stats of the DEFAULT bench command with --full (+ the given workload flags): per-kernel durations
 #   2. four --pmc passes (counters only, no trace domain) of the same workload with ONE batch in flight, so that every
 #      dispatch runs alone and its counters are its own: FETCH_SIZE | WRITE_SIZE | SQ issue + L2 hit counters | VALU by type
 # Outputs under gpurun_out/<tag>/; profiles/make_pmc_summary.py turns them into the tracked summaries.
@@ -18,11 +18,11 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/$tag
 mkdir -p $out
 cd /tmp; export TMPDIR=/tmp
-short="--steps 2 --warmup 0 --cpu-sample 0 --inflight 1 --e2e-reads 0"
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o run -- python3 $root/bench.py --cpu-sample 0 --e2e-reads 0 "$@" > $out/bench_profiled.json 2> $out/stats.err || exit 1
+short="--full --steps 2 --warmup 0 --cpu-sample 0 --inflight 1 --e2e-reads 0"
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o run -- python3 $root/bench.py --full --cpu-sample 0 --e2e-reads 0 "$@" > $out/bench_profiled.json 2> $out/stats.err || exit 1
 echo "stats pass done"
 # the same with ONE batch in flight: every launch alone on the GPU -> the average duration bench.py's `roofline.ms` (isolated) must agree with
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats1 -o run -- python3 $root/bench.py --cpu-sample 0 --e2e-reads 0 --inflight 1 --steps 8 --warmup 2 "$@" > $out/bench_profiled_inflight1.json 2> $out/stats1.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats1 -o run -- python3 $root/bench.py --full --cpu-sample 0 --e2e-reads 0 --inflight 1 --steps 8 --warmup 2 "$@" > $out/bench_profiled_inflight1.json 2> $out/stats1.err || exit 1
 echo "stats (one batch in flight) pass done"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -o run -- python3 $root/bench.py $short "$@" > $out/fetch.json 2> $out/fetch.err || exit 1
 echo "fetch pass done"

@@ -65,7 +65,7 @@ for k in sorted(set(fe) | set(sq)):
         h, m = sq[k].get("TCC_HIT_sum", 0), sq[k].get("TCC_MISS_sum", 0)
         e["l2_hit_rate"] = h / (h + m) if h + m else None
     out[k] = e
-note = ("rocprofv3 --pmc passes of `python3 bench.py --steps 2 --warmup 0 --cpu-sample 0 --inflight 1 <workload flags>` (one batch in flight: every dispatch "
+note = ("rocprofv3 --pmc passes of `python3 bench.py --full --steps 2 --warmup 0 --cpu-sample 0 --inflight 1 <workload flags>` (one batch in flight: every dispatch "
         "alone on the GPU), counters averaged over a kernel's launches; see the header of profiles/make_pmc_summary.py for the corrections")
 json.dump(dict(note=note, workload=workload, bench_config=bench.get("config"), kernel_source_hash=(bench.get("roofline") or {}).get("kernel_source_hash"), kernels=out), open("profiles/%s_pmc_summary.json" % tag, "w"), indent=1)
 rows = list(csv.DictReader(open(os.path.join(d, "kernel_stats.csv"))))
@@ -97,7 +97,7 @@ class _KM(dict):
 km = _KM()
 with open("profiles/%s_summary.md" % tag, "w") as f:
     f.write("# %s: rocprofv3 --kernel-trace --stats + PMC passes\n\n" % tag)
-    f.write("Stats command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --cpu-sample 0 <workload flags>`; bench line of that (profiled) run: "
+    f.write("Stats command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --cpu-sample 0 <workload flags>`; bench line of that (profiled) run: "
             "%.0f %s, %.2f ms/step.  Workload: %s\n\n" % (bench["value"], bench["unit"], bench["ms_per_step"], bench["config"]["workload"]))
     f.write("| kernel | calls | rocprof avg ms, six batches in flight (+ the 3 isolated steps at the end) | rocprof avg ms, one batch in flight (`--inflight 1`) | bench.py HIP events: in the timed region / one batch alone | HBM GB per launch (PMC) | "
             "HBM GB/s alone (% of 8 TB/s) | VALU wave-instr per launch (FP64 share) | VALU issue: % of the SIMDs' cycles alone | VALU active / wave cycle | L2 hit |\n|---|---|---|---|---|---|---|---|---|---|---|\n")

@@ -23,7 +23,7 @@ with open('profiles/%s_kernel_stats_engine.csv' % tag, 'w') as f:
 km = b['kernel_ms']; iso = b.get('kernel_ms_one_batch_in_flight', {})
 with open('profiles/%s_summary.md' % tag, 'w') as f:
     f.write("# rocprofv3 --kernel-trace --stats, round 1 final kernels\n\n")
-    f.write("Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --cpu-sample 0` (defaults: %d warm-up + %d timed steps, "
+    f.write("Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --cpu-sample 0` (defaults: %d warm-up + %d timed steps, "
             "batches in flight as in the bench line, then 3 steps of one batch alone)\n\n" % (b['warmup'], b['steps']))
     f.write("1 x MI355X, %s.  bench line of the same (profiled) run: %.0f reads/s, %.1f ms/step.\n\n" % (b['config']['workload'], b['value'], b['ms_per_step']))
     f.write("| kernel | calls | rocprof avg ms (all calls) | share of per-read engine GPU time | bench.py HIP events of its stage, timed region (batches overlapping) | bench.py HIP events, one batch alone |\n|---|---|---|---|---|---|\n")

@@ -31,7 +31,7 @@ def test_two_ranks_launched_by_bench_itself():
 
 
 def test_single_rank_line_has_the_contract_fields_and_zero_unexplained_differences():
-    j = _run(["--cpu-sample", "96", "--e2e-reads", "500"] + SMALL)
+    j = _run(["--full", "--cpu-sample", "96", "--e2e-reads", "500"] + SMALL)
     assert j["n_gpus"] == 1 and j["unit"] == "reads/s" and j["dtype"] == "f64" and j["vs_baseline"] is None
     r = j["roofline"]
     assert set(("bound", "achieved", "peak", "unit", "frac", "traffic")) <= set(r) and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
@@ -63,7 +63,7 @@ def test_single_rank_line_has_the_contract_fields_and_zero_unexplained_differenc
 def test_paired_line_and_the_stable_order_as_the_timed_region():
     """--paired (BASELINE configs 4 / 5: two mates per unit, merged regions, 32-bit pairs) on a small database, and --seed-order stable as the timed
     region with the reference's order as the side block: both against the oracle in the same order, zero unexplained differences"""
-    j = _run(["--paired", "--read-len", "250", "--cpu-sample", "48", "--e2e-reads", "0", "--leaves", "600", "--cs-len", "2800", "--batch", "48", "--inflight", "2",
+    j = _run(["--full", "--paired", "--read-len", "250", "--cpu-sample", "48", "--e2e-reads", "0", "--leaves", "600", "--cs-len", "2800", "--batch", "48", "--inflight", "2",
               "--steps", "2", "--warmup", "1"])
     assert j["unit"] == "pairs/s" and j["value"] > 0 and j["config"]["seed_order"] == "reference"
     c = j["cpu_baseline"]
@@ -71,10 +71,23 @@ def test_paired_line_and_the_stable_order_as_the_timed_region():
     assert c["max_rel"]["outer_iteration_mismatches"] == 0 and c["max_rel"]["est_loglik"]["max_rel"] <= 1e-6
     sr = j["seed_order_stable"]
     assert sr["reads_compared"] == 48 and sr["unexplained_best_branch_diffs"] == 0 and sr["candidate_set_differs"] == 0, sr
-    j2 = _run(["--seed-order", "stable", "--cpu-sample", "96", "--e2e-reads", "0"] + SMALL)
+    j2 = _run(["--full", "--seed-order", "stable", "--cpu-sample", "96", "--e2e-reads", "0"] + SMALL)
     assert j2["config"]["seed_order"] == "stable" and j2["cpu_baseline"]["oracle_seed_order"].startswith("TIE_STABLE") and j2["cpu_baseline"]["unexplained_best_branch_diffs"] == 0
     sr2 = j2["seed_order_reference"]
     assert sr2["reads_compared"] == 96 and sr2["unexplained_best_branch_diffs"] == 0 and sr2["candidate_set_differs"] == 0 and sr2["oracle_seed_order"].startswith("TIE_LIBSTDCXX"), sr2
+
+
+def test_plain_line_is_the_headline_without_the_full_blocks():
+    """without --full the line carries the headline fields and the timed region's own figures (RCCL gather, per-kernel times of the
+    timed steps), and none of the blocks that take work of their own: CPU baseline, other seed order, end to end, isolated times, roofline"""
+    j = _run(SMALL)
+    assert j["n_gpus"] == 1 and j["unit"] == "reads/s" and j["dtype"] == "f64" and j["higher_is_better"] is True and j["vs_baseline"] is None
+    assert j["steps"] == 4 and j["warmup"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0
+    assert abs(j["value"] - 96 * 1e3 / j["ms_per_step"]) <= 1e-6 * j["value"]
+    assert j["rccl_ranks"] == 1 and j["gathered_records"] == 96 and j["kernel_ms"]
+    for k in ("cpu_baseline", "seed_order_stable", "seed_order_reference", "end_to_end", "roofline", "roofline_kernels", "roofline_path",
+              "kernel_ms_one_batch_in_flight", "host_wall_ms", "place_iterations"):
+        assert k not in j, k
 
 
 def test_dump_outputs_are_the_timed_steps_records_and_repeat_exactly(tmp_path):
