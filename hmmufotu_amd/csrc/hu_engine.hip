@@ -1420,9 +1420,11 @@ extern "C" int hu_align_batch(hu_batch* b, const hu_opts* o) try {
 			}
 			return HU_OK;
 		};
+		size_t nValues = 0;
 		if(vp.dec()) { /* sequences whose traceback cannot trust the fill-time decisions: redo with every value filed */
 			std::vector<int> rs;
 			for(int s = 0; s < b->nSeq; ++s) if(b->hVit[s].status == HU_READ_NEEDS_VALUES) rs.push_back(s);
+			nValues = rs.size();
 			if(!rs.empty() && vp.wave()) { /* the batch holds corner scratch only: the few sequences to redo get a full-size scratch of their own */
 				auto cellsOf = [](HuReadDesc& rd) {      /* cells of all its phases, as build_regions laid them out */
 					int64_t c = 0;
@@ -1445,6 +1447,10 @@ extern "C" int hu_align_batch(hu_batch* b, const hu_opts* o) try {
 		auto fullDp = [&](HuReadDesc& rd) { build_regions(b->db, rd.len, nullptr, rd); return rd.scratchOff; };
 		if((rc = redoChunked(redo, fullDp, 0)) != HU_OK) return rc;
 		for(int s : redo) b->hDescs[s].nRegions = -1; /* mark: full DP was used */
+		if(kb.trace) { /* the tests of the switching lengths match this line (tests/test_align_edges.py); names in VitFill's order */
+			static const char* const fillName[] = {"k_viterbi_wave<4>", "k_viterbi_wave<4, 1>", "k_viterbi_wave<4, 2>", "k_viterbi_wave<8>", "k_viterbi_dec2<256>", "k_viterbi_dec2<512>", "k_viterbi_dec", "k_viterbi_lds", "k_viterbi"};
+			fprintf(stderr, "[hu] align: %d sequences, longest %d, fill %s, %zu bytes of LDS, %zu redone for values, %zu by the full-DP fallback\n", b->nSeq, maxLen, fillName[vp.fill], vp.lds, nValues, redo.size());
+		}
 		for(int s = 0; s < b->nSeq; ++s) if(b->hVit[s].status == HU_READ_NEEDS_FULL) { b->hVit[s].status = HU_READ_INVALID; hostVit = true; }
 		if(hostVit) HIPCHK(hipMemcpyAsync(b->dVit.p, b->hVit.data(), (size_t) b->nSeq * sizeof(HuVitOut), hipMemcpyHostToDevice, b->stream));
 		{

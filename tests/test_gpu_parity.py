@@ -129,26 +129,47 @@ def test_align_parity(cfg):
     _check_alignments(E, db, H, [r.seq for r in reads], vps)
 
 
-def _check_alignments(E, db, H, seqs, vps):
+def _check_alignments(E, db, H, seqs, vps, opts=None, knobs=None, capfd=None):
+    """One batch through hu_align_batch against H.align, read by read.  opts: the engine's options (H must have been made for the same
+    align_mode); knobs: {name: value} set on the batch before the stage; capfd: pytest's fixture, to read what the stage writes to
+    stderr.  Returns (one dict per read of everything compared, that stderr text)."""
     from oracle import oracle_py as O
-    opts = E.default_opts()
-    D, B = _run_stages(E, db, seqs, vps, opts)
-    out = B.alignments(want_align=True, want_trace=True, trace_stride=db.hmm.K + max(len(s) for s in seqs) + 400)
-    cd, st, en = B.codes()
-    for i, seq in enumerate(seqs):
-        a = H.align(seq, vps[i])
-        rec = out["recs"][i]
-        assert a["ok"] and rec["status"] == 1, i
-        assert (rec["seq_start"], rec["seq_end"], rec["hmm_start"], rec["hmm_end"], rec["cs_start"], rec["cs_end"]) == \
-               (a["seqStart"], a["seqEnd"], a["hmmStart"], a["hmmEnd"], a["csStart"], a["csEnd"]), i
-        assert rec["cost"] == a["cost"], (i, rec["cost"], a["cost"])          # bit-exact
-        assert out["trace"][i] == a["trace"], i
-        assert out["align"][i] == a["align"], i
-        assert bool(rec["used_full"]) == a["usedFull"], i
-        ds = O.digitize(a["align"])
-        assert (cd[i] == ds).all(), i
-        assert st[i] == a["csStart"] - 1 and en[i] == a["csEnd"] - 1
-    B.close(); D.close()
+    opts = opts if opts is not None else E.default_opts()
+    D = E.Database.from_synth(db)
+    B = None
+    try:  # closed in order also when an assertion fails: left to the garbage collector, the database may go before its batch
+        B = E.Batch(D, max(len(seqs), 1))
+        for name, value in (knobs or {}).items():
+            B.set_knob(name, value)
+        B.set_reads(list(seqs), vps)
+        if capfd is not None:
+            capfd.readouterr()
+        B.align(opts)
+        err = capfd.readouterr().err if capfd is not None else ""
+        out = B.alignments(want_align=True, want_trace=True, trace_stride=db.hmm.K + max(len(s) for s in seqs) + 400)
+        cd, st, en = B.codes()
+        got = []
+        for i, seq in enumerate(seqs):
+            a = H.align(seq, vps[i])
+            rec = out["recs"][i]
+            assert a["ok"] and rec["status"] == 1, i
+            assert (rec["seq_start"], rec["seq_end"], rec["hmm_start"], rec["hmm_end"], rec["cs_start"], rec["cs_end"]) == \
+                   (a["seqStart"], a["seqEnd"], a["hmmStart"], a["hmmEnd"], a["csStart"], a["csEnd"]), i
+            assert rec["cost"] == a["cost"], (i, rec["cost"], a["cost"])          # bit-exact
+            assert out["trace"][i] == a["trace"], i
+            assert out["align"][i] == a["align"], i
+            assert bool(rec["used_full"]) == a["usedFull"], i
+            ds = O.digitize(a["align"])
+            assert (cd[i] == ds).all(), i
+            assert st[i] == a["csStart"] - 1 and en[i] == a["csEnd"] - 1
+            got.append(dict(status=int(rec["status"]), coords=tuple(int(rec[k]) for k in ("seq_start", "seq_end", "hmm_start", "hmm_end", "cs_start", "cs_end")),
+                            cost=float(rec["cost"]), trace=out["trace"][i], align=out["align"][i], used_full=bool(rec["used_full"]),
+                            codes=cd[i].tobytes(), start=int(st[i]), end=int(en[i])))
+    finally:
+        if B is not None:
+            B.close()
+        D.close()
+    return got, err
 
 
 def test_reads_longer_than_the_profile():
