@@ -27,6 +27,7 @@
 #include "hu_kern_rank.h"
 #include "hu_kern_anneal.h"
 #include "hu_kern_build.h"
+#include "hu_kern_otucs.h"
 
 #define HIPCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { \
 	hu_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return HU_ERR_DEVICE; } } while(0)
@@ -668,6 +669,11 @@ extern "C" const char* hu_db_get_annotation(const hu_db* db, int32_t node) try {
 	if(!db || node < 0 || node >= (int32_t) db->annos.size()) return "";
 	return db->annos[node].c_str();
 } catch(...) { (void) hu_catch_all("hu_db_get_annotation"); return ""; }
+extern "C" int hu_db_get_anno_dist(const hu_db* db, int32_t node, double* out) try {
+	if(!db || !out || node < 0 || node >= (int32_t) db->annoDist.size()) return HU_ERR_ARG;
+	*out = db->annoDist[node];
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_db_get_anno_dist"); }
 extern "C" int hu_db_get_model(const hu_db* db, hu_model_desc* out) try { if(!db || !out) return HU_ERR_ARG; *out = db->mdesc; return HU_OK; } catch(...) { return hu_catch_all("hu_db_get_model"); }
 
 __global__ void k_model_pr(HuModelDev mdl, int n, const double* __restrict__ t, double* __restrict__ P) {
@@ -3068,3 +3074,172 @@ extern "C" int hu_db_num_leaves(const hu_db* db, int64_t* n_leaves) try {
 	*n_leaves = std::count(leaf.begin(), leaf.end(), (char) 1);
 	return HU_OK;
 } catch(...) { return hu_catch_all("hu_db_num_leaves"); }
+
+/* ------------------------------------------------------------------------------ OTU consensus sequences (hmmufotu-sum -c) */
+struct hu_otucs {
+	hu_db* db = nullptr;
+	hipStream_t stream = nullptr;
+	std::vector<int32_t> slotOfNode;      /* [nNodes] -1: not seen */
+	int32_t nSlots = 0;
+	uint32_t* dTab = nullptr;             /* [capSlots][5][L] */
+	size_t capSlots = 0;
+	unsigned char* dCls = nullptr;        /* [256] byte -> plane */
+	PinnedVec<unsigned char> hStage;
+	DBuf<unsigned char> dStage; DBuf<HuOtucsRow> dRows; DBuf<int32_t> dOrder; DBuf<HuOtucsWork> dWork;
+	DBuf<int32_t> dNodes, dSlots; DBuf<char> dOut;
+	~hu_otucs() { if(dTab) (void) hipFree(dTab); if(dCls) (void) hipFree(dCls); if(stream) (void) hipStreamDestroy(stream); }
+};
+
+extern "C" int hu_otucs_create(hu_db* db, hu_otucs** out) try {
+	if(!db || !out) { hu_set_error("hu_otucs_create: null argument"); return HU_ERR_ARG; }
+	*out = nullptr;
+	const HuDbDev& d = db->dev;
+	if(d.winStart != 0 || d.winLen != d.csLen) { hu_set_error("hu_otucs_create: the database holds a column window; the consensus needs the whole database"); return HU_ERR_ARG; }
+	if(d.root != 0) { hu_set_error("hu_otucs_create: the database's stored root is node %d, not node 0: re-rooting the messages at node 0 (PTUnrooted::setRoot) is not provided", d.root); return HU_ERR_ARG; }
+	HIPCHK(hipSetDevice(db->device));
+	std::unique_ptr<hu_otucs> h(new hu_otucs);
+	h->db = db;
+	h->slotOfNode.assign((size_t) d.nNodes, -1);
+	HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+	int8_t enc[256]; unsigned char cls[256];
+	msa_encode_table(enc);
+	for(int c = 0; c < 256; ++c) cls[c] = enc[c] >= 0 ? (unsigned char) enc[c] : 4;
+	HIPCHK(hipMalloc((void**) &h->dCls, 256));
+	HIPCHK(hipMemcpy(h->dCls, cls, 256, hipMemcpyHostToDevice));
+	*out = h.release();
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_otucs_create"); }
+
+extern "C" void hu_otucs_free(hu_otucs* h) { if(h) { (void) hipSetDevice(h->db->device); delete h; } }
+
+/* room for nSlots OTUs: the table doubles, its counts move, the new part is zero */
+static int otucs_grow(hu_otucs* h, size_t nSlots) {
+	if(nSlots <= h->capSlots) return HU_OK;
+	const size_t per = (size_t) 5 * h->db->dev.csLen, cap = std::max<size_t>(std::max<size_t>(nSlots, h->capSlots * 2), 64);
+	uint32_t* nt = nullptr;
+	hipError_t e = hipMalloc((void**) &nt, cap * per * sizeof(uint32_t));
+	if(e != hipSuccess) { (void) hipGetLastError(); hu_set_error("hu_otucs_add: hipMalloc(%zu bytes) for the counts of %zu OTUs failed: %s", cap * per * sizeof(uint32_t), cap, hipGetErrorString(e)); return HU_ERR_NOMEM; }
+	HuScope guard([&] { if(nt) (void) hipFree(nt); });
+	if(h->capSlots) HIPCHK(hipMemcpyAsync(nt, h->dTab, h->capSlots * per * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
+	HIPCHK(hipMemsetAsync(nt + h->capSlots * per, 0, (cap - h->capSlots) * per * sizeof(uint32_t), h->stream));
+	HIPCHK(hu_wait(h->stream));
+	std::swap(nt, h->dTab);
+	h->capSlots = cap;
+	return HU_OK;
+}
+
+extern "C" int hu_otucs_add(hu_otucs* h, int64_t n_rows, const int32_t* node_of_row, const char* rows) try {
+	if(!h || n_rows < 0 || (n_rows > 0 && (!node_of_row || !rows))) { hu_set_error("hu_otucs_add: bad argument"); return HU_ERR_ARG; }
+	const HuDbDev& d = h->db->dev;
+	const int L = d.csLen;
+	const int64_t pitch16 = (L + 15) / 16;
+	if(n_rows * pitch16 > INT32_MAX) { hu_set_error("hu_otucs_add: %lld rows of %d columns are too many for one call", (long long) n_rows, L); return HU_ERR_ARG; }
+	for(int64_t i = 0; i < n_rows; ++i) if(node_of_row[i] < 0 || node_of_row[i] >= d.nNodes) {
+		hu_set_error("hu_otucs_add: row %lld names node %d, the database has %d", (long long) i, node_of_row[i], d.nNodes); return HU_ERR_ARG;
+	}
+	if(n_rows == 0) return HU_OK;
+	HIPCHK(hipSetDevice(h->db->device));
+	const size_t n = (size_t) n_rows;
+	/* the span of each row that holds anything but '-', widened to 16-byte bounds: only that crosses the bus (an amplicon read covers a
+	 * few hundred of the alignment's columns); k_otucs_count takes every column outside it as the gap it is */
+	std::vector<HuOtucsRow> meta(n);
+	parallel_for(n, [&](size_t i) {
+		const char* r = rows + i * (size_t) L;
+		int a = 0, e = L;
+		while(a < L && r[a] == '-') ++a;
+		while(e > a && r[e - 1] == '-') --e;
+		HuOtucsRow m{0, 0, 0, 0};
+		if(a < e) { m.c0 = a & ~15; m.c1 = std::min(L, (e + 15) & ~15); }
+		meta[i] = m;
+	});
+	int64_t tot16 = 0;
+	for(size_t i = 0; i < n; ++i) { meta[i].off16 = (int32_t) tot16; tot16 += (meta[i].c1 - meta[i].c0 + 15) / 16; }
+	/* slots at first sight; the batch's rows in slot order (a counting sort: the permutation alone, the rows stay) */
+	int32_t nSlots = h->nSlots;
+	std::vector<int32_t> slot(n);
+	for(size_t i = 0; i < n; ++i) {
+		int32_t& s = h->slotOfNode[node_of_row[i]];
+		if(s < 0) s = nSlots++;
+		slot[i] = s;
+	}
+	auto forget = [&] { for(size_t i = 0; i < n; ++i) if(slot[i] >= h->nSlots) h->slotOfNode[node_of_row[i]] = -1; };   /* a failed call leaves no trace */
+	bool done = false;
+	HuScope guard([&] { if(!done) forget(); });
+	int rc;
+	if((rc = otucs_grow(h, (size_t) nSlots)) != HU_OK) return rc;
+	std::vector<int32_t> first((size_t) nSlots + 1, 0), order(n);
+	for(size_t i = 0; i < n; ++i) first[slot[i] + 1]++;
+	for(int32_t s = 0; s < nSlots; ++s) first[s + 1] += first[s];
+	{
+		std::vector<int32_t> at(first.begin(), first.end() - 1);
+		for(size_t i = 0; i < n; ++i) order[at[slot[i]]++] = (int32_t) i;
+	}
+	std::vector<HuOtucsWork> work;
+	for(int32_t s = 0; s < nSlots; ++s)
+		for(int32_t b = first[s]; b < first[s + 1]; b += HU_OTUCS_CHUNK) work.push_back(HuOtucsWork{s, b, std::min(first[s + 1], b + HU_OTUCS_CHUNK), 0});
+	const size_t stageBytes = (size_t) tot16 * 16;
+	if(h->hStage.size() < stageBytes) h->hStage.resize(stageBytes + stageBytes / 8);
+	unsigned char* hs = h->hStage.data();
+	parallel_for(n, [&](size_t i) {
+		const HuOtucsRow& m = meta[i];
+		const size_t len = (size_t)(m.c1 - m.c0), padded = (len + 15) / 16 * 16;
+		if(!len) return;
+		unsigned char* dst = hs + (size_t) m.off16 * 16;
+		memcpy(dst, rows + i * (size_t) L + m.c0, len);
+		if(padded > len) memset(dst + len, '-', padded - len);
+	});
+	if((rc = h->dStage.ensure(std::max<size_t>(stageBytes, 16))) != HU_OK || (rc = h->dRows.ensure(n)) != HU_OK ||
+	   (rc = h->dOrder.ensure(n)) != HU_OK || (rc = h->dWork.ensure(work.size())) != HU_OK) return rc;
+	if(stageBytes) HIPCHK(hipMemcpyAsync(h->dStage.p, hs, stageBytes, hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemcpyAsync(h->dRows.p, meta.data(), n * sizeof(HuOtucsRow), hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemcpyAsync(h->dOrder.p, order.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemcpyAsync(h->dWork.p, work.data(), work.size() * sizeof(HuOtucsWork), hipMemcpyHostToDevice, h->stream));
+	(void) hipGetLastError();
+	const dim3 grid((unsigned) work.size(), (unsigned)((L + HU_OTUCS_BLOCK_COLS - 1) / HU_OTUCS_BLOCK_COLS));
+	k_otucs_count<<<grid, HU_OTUCS_THREADS, 0, h->stream>>>(h->dStage.p, h->dRows.p, h->dOrder.p, h->dWork.p, h->dCls, L, h->dTab);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hu_wait(h->stream));       /* the host buffers of this call are done with */
+	h->nSlots = nSlots;
+	done = true;
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_otucs_add"); }
+
+extern "C" int hu_otucs_counts(hu_otucs* h, int32_t node, uint32_t* freq, uint32_t* gap) try {
+	if(!h || !freq || !gap) { hu_set_error("hu_otucs_counts: null argument"); return HU_ERR_ARG; }
+	const int L = h->db->dev.csLen;
+	if(node < 0 || node >= h->db->dev.nNodes) { hu_set_error("hu_otucs_counts: node %d, the database has %d", node, h->db->dev.nNodes); return HU_ERR_ARG; }
+	const int32_t s = h->slotOfNode[node];
+	if(s < 0) { memset(freq, 0, (size_t) 4 * L * sizeof(uint32_t)); memset(gap, 0, (size_t) L * sizeof(uint32_t)); return HU_OK; }
+	HIPCHK(hipSetDevice(h->db->device));
+	const uint32_t* t = h->dTab + (size_t) s * 5 * L;
+	HIPCHK(hipMemcpyAsync(freq, t, (size_t) 4 * L * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(gap, t + (size_t) 4 * L, (size_t) L * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hu_wait(h->stream));
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_otucs_counts"); }
+
+extern "C" int hu_otucs_infer(hu_otucs* h, int32_t n, const int32_t* nodes, double eff_n, char* out) try {
+	if(!h || n < 0 || (n > 0 && (!nodes || !out))) { hu_set_error("hu_otucs_infer: bad argument"); return HU_ERR_ARG; }
+	if(!(eff_n >= 0) || std::isinf(eff_n)) { hu_set_error("hu_otucs_infer: eff_n must be non-negative and finite"); return HU_ERR_ARG; }
+	const HuDbDev& d = h->db->dev;
+	const int L = d.csLen;
+	for(int i = 0; i < n; ++i) if(nodes[i] < 0 || nodes[i] >= d.nNodes) { hu_set_error("hu_otucs_infer: entry %d names node %d, the database has %d", i, nodes[i], d.nNodes); return HU_ERR_ARG; }
+	if(n == 0) return HU_OK;
+	HIPCHK(hipSetDevice(h->db->device));
+	std::vector<int32_t> slots((size_t) n);
+	for(int i = 0; i < n; ++i) slots[i] = h->slotOfNode[nodes[i]];
+	const int piece = 4096;                   /* OTUs per launch: bounds the output buffer (and grid.y) */
+	int rc;
+	if((rc = h->dNodes.ensure((size_t) n)) != HU_OK || (rc = h->dSlots.ensure((size_t) n)) != HU_OK || (rc = h->dOut.ensure((size_t) std::min(n, piece) * L)) != HU_OK) return rc;
+	HIPCHK(hipMemcpyAsync(h->dNodes.p, nodes, (size_t) n * 4, hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemcpyAsync(h->dSlots.p, slots.data(), (size_t) n * 4, hipMemcpyHostToDevice, h->stream));
+	(void) hipGetLastError();
+	for(int o0 = 0; o0 < n; o0 += piece) {
+		const int m = std::min(piece, n - o0);
+		k_otucs_infer<<<dim3((unsigned)((L + 255) / 256), (unsigned) m), 256, 0, h->stream>>>(d, h->db->mdl, h->dNodes.p + o0, h->dSlots.p + o0, h->dTab, eff_n, h->dOut.p);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(out + (size_t) o0 * L, h->dOut.p, (size_t) m * L, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(hu_wait(h->stream));
+	}
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_otucs_infer"); }

@@ -692,3 +692,16 @@ extern "C" double hu_dg_estimate_shape(int64_t n, const double* X) {
 	q /= (n - 1);
 	return m * m / (q - m);
 }
+
+/* ---- the description of an OTU consensus record (src/hmmufotu-sum.cpp:448-452) ------------------------------------ */
+extern "C" int64_t hu_otucs_description(const char* db_name, const char* taxonomy, double anno_dist, int64_t read_count, int64_t sample_hits, char* out, int64_t cap) try {
+	if(!db_name || !taxonomy || (cap > 0 && !out)) { hu_set_error("hu_otucs_description: null argument"); return HU_ERR_ARG; }
+	/* boost::lexical_cast<std::string>(double) sets the stream's precision to 17 (lcast_precision: 2 + digits * 30103 / 100000) and
+	 * writes in the default floating format: printf's %.17g.  Taken from Boost's documented behaviour, not checked against a build. */
+	char num[64];
+	snprintf(num, sizeof num, "%.17g", anno_dist);
+	const std::string d = std::string("DBName=") + db_name + ";Taxonomy=\"" + taxonomy + "\";AnnoDist=" + num + ";ReadCount=" + std::to_string(read_count)
+		+ ";SampleHits=" + std::to_string(sample_hits);
+	if(cap > 0) { const size_t k = std::min<size_t>(d.size(), (size_t) cap - 1); memcpy(out, d.data(), k); out[k] = 0; }
+	return (int64_t) d.size();
+} catch(...) { return hu_catch_all("hu_otucs_description"); }

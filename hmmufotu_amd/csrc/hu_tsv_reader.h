@@ -93,4 +93,32 @@ inline std::vector<int32_t> cs_to_profile(int K, int L, const std::vector<int32_
 	return m;
 }
 
+
+/* the sample list of hmmufotu-sum -l (src/hmmufotu-sum.cpp:213-240): lines "name <tab> assignment file"; the files that are inputs are
+ * kept, in the list's order, under the list's names */
+inline bool read_sample_list(const std::string& listFn, std::vector<std::string>& inFiles, std::map<std::string, std::string>& fn2name) {
+	LineReader li;
+	if(!li.open(listFn)) return false;
+	inFiles.clear();
+	std::string line;
+	while(li.line(line)) {
+		if(!line.empty() && line[0] == '#') continue;
+		std::vector<std::string> f; Scanner::split(line, f);
+		if(f.size() >= 2 && fn2name.count(f[1])) { inFiles.push_back(f[1]); fn2name[f[1]] = f[0]; }
+	}
+	return true;
+}
+
+/* "a valid assignment" of the record the scanner stands on (src/hmmufotu-sum.cpp:374-382): taxon_id >= 0, Q_taxon >= minQ and the two
+ * identity filters (0: off); taxon receives atol(taxon_id) */
+struct Accept { double minQ = 0, minAln = 0, minHmm = 0; };
+inline bool accepted(const Scanner& sc, const Accept& f, const std::vector<int32_t>& cs2p, long& taxon) {
+	const int csStart = atoi(sc.get("CS_start").c_str()), csEnd = atoi(sc.get("CS_end").c_str());
+	const std::string& aln = sc.get("alignment");
+	taxon = atol(sc.get("taxon_id").c_str());
+	const double qTaxon = atof(sc.get("Q_taxon").c_str());
+	return taxon >= 0 && qTaxon >= f.minQ && (f.minAln == 0 || align_identity(aln, csStart - 1, csEnd - 1) >= f.minAln)
+		&& (f.minHmm == 0 || hmm_identity(cs2p, aln, csStart - 1, csEnd - 1) >= f.minHmm);
+}
+
 } // namespace hu_tsv

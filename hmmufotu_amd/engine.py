@@ -485,9 +485,85 @@ class Database:
                                 n_leaves=n_leaves, hit_nodes=int(hn[i]), hit_leaves=int(hl[i])))
         return out
 
+    def otu_consensus(self):
+        """hu_otucs_create: the accumulator of the OTU consensus sequences of hmmufotu-sum -c on this database"""
+        return OtuConsensus(self)
+
+    def anno_dist(self, node: int) -> float:
+        v = C.c_double()
+        _chk(load_library().hu_db_get_anno_dist(self.h, C.c_int32(node), C.byref(v)))
+        return float(v.value)
+
     def close(self):
         if self.h:
             load_library().hu_db_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def otucs_description(db_name: str, taxonomy: str, anno_dist: float, read_count: int, sample_hits: int) -> str:
+    """hu_otucs_description (host only): the description of an OTU's FASTA record as hmmufotu-sum -c writes it"""
+    lib = load_library()
+    lib.hu_otucs_description.restype = C.c_int64
+    args = (db_name.encode(), taxonomy.encode(), C.c_double(anno_dist), C.c_int64(read_count), C.c_int64(sample_hits))
+    need = int(lib.hu_otucs_description(*args, None, C.c_int64(0)))
+    if need < 0:
+        _chk(need)
+    buf = C.create_string_buffer(need + 1)
+    lib.hu_otucs_description(*args, buf, C.c_int64(need + 1))
+    return buf.value.decode()
+
+
+class OtuConsensus:
+    """Per-OTU column counts of accepted alignment rows and the consensus inferred from them (hu_otucs_*): the loop of
+    src/hmmufotu-sum.cpp:391-397 and PTUnrooted::inferPostCS.  The counts stay on the device of the database."""
+
+    def __init__(self, db: Database):
+        self.db = db
+        self.h = C.c_void_p()
+        _chk(load_library().hu_otucs_create(db.h, C.byref(self.h)))
+
+    def add(self, nodes, rows):
+        """nodes [n]: the rows' OTUs (node ids); rows: n alignment strings (str / bytes) of cs_len columns, or a uint8 [n][cs_len] array"""
+        nodes = np.ascontiguousarray(nodes, np.int32).ravel()
+        L = self.db.cs_len
+        if isinstance(rows, np.ndarray):
+            a = np.ascontiguousarray(rows, np.uint8)
+            if a.ndim != 2 or a.shape[1] != L:
+                raise EngineError("otu_consensus.add: rows must be [n][%d], got %s" % (L, a.shape,))
+        else:
+            b = [r.encode("latin1") if isinstance(r, str) else bytes(r) for r in rows]
+            for i, r in enumerate(b):
+                if len(r) != L:
+                    raise EngineError("otu_consensus.add: row %d has %d columns, the database %d" % (i, len(r), L))
+            a = np.frombuffer(b"".join(b), np.uint8).reshape(len(b), L)
+        if len(nodes) != a.shape[0]:
+            raise EngineError("otu_consensus.add: %d nodes for %d rows" % (len(nodes), a.shape[0]))
+        _chk(load_library().hu_otucs_add(self.h, C.c_int64(len(nodes)), _p(nodes, C.c_int32), a.ctypes.data_as(C.c_char_p)))
+
+    def counts(self, node: int):
+        """(freq [4][cs_len], gap [cs_len]) of one OTU, uint32"""
+        L = self.db.cs_len
+        freq = np.zeros((4, L), np.uint32); gap = np.zeros(L, np.uint32)
+        _chk(load_library().hu_otucs_counts(self.h, C.c_int32(node), _p(freq, C.c_uint32), _p(gap, C.c_uint32)))
+        return freq, gap
+
+    def infer(self, nodes, eff_n=2.0):
+        """the consensus of each OTU, a str of cs_len characters of ACGT and '-'"""
+        nodes = np.ascontiguousarray(nodes, np.int32).ravel()
+        L = self.db.cs_len
+        out = np.zeros((len(nodes), L), np.uint8)
+        _chk(load_library().hu_otucs_infer(self.h, C.c_int32(len(nodes)), _p(nodes, C.c_int32), C.c_double(eff_n), out.ctypes.data_as(C.c_char_p)))
+        return [bytes(r).decode("ascii") for r in out]
+
+    def close(self):
+        if self.h:
+            load_library().hu_otucs_free(self.h)
             self.h = None
 
     def __del__(self):

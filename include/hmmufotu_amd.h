@@ -489,6 +489,38 @@ const char* hu_anneal_header(void);
 /* PTUnrooted::numLeaves: nodes with one neighbour (src/PhyloTreeUnrooted.h:199) */
 int hu_db_num_leaves(const hu_db* db, int64_t* n_leaves);
 
+/* ---- OTU consensus sequences (hmmufotu-sum -c) ---------------------------
+ * What src/hmmufotu-sum.cpp:383-397 and :437-457 do with the accepted records of assignment files: per OTU (the node of a record's
+ * taxon_id) the column counts of its reads' alignments, then one consensus sequence per OTU from those counts and the node's message
+ * as a Dirichlet prior (PTUnrooted::inferPostCS, src/PhyloTreeUnrooted.cpp:1111-1125).  The counts stay on the device.  A handle is
+ * bound to a loaded database; several handles (and batches) may share one.  Calls on one handle are not concurrent.
+ * hu_otucs_create: HU_ERR_ARG for a database that keeps a column window (hu_db_load_window), and for one whose stored root is not
+ * node 0: the reference re-roots at node 0 first (ptu.setRoot(0), src/hmmufotu-sum.cpp:337), recomputing that node's message from its
+ * children, which is not provided; hmmufotu-build stores root 0. */
+typedef struct hu_otucs hu_otucs;
+int hu_otucs_create(hu_db* db, hu_otucs** out);
+void hu_otucs_free(hu_otucs* h);
+/* the loop of src/hmmufotu-sum.cpp:391-397 for n_rows accepted records: rows [n_rows][cs_len] bytes, the records' alignment strings as
+ * read; node_of_row [n_rows] their taxon_id.  Byte c of column j adds 1 to freq(b, j) of the row's OTU when b = encode(toupper(c)) of
+ * IUPACNucl (hu_msa_encode_table) is a residue, else to gap(j): gap symbols and every invalid byte alike.  May be called any number of
+ * times; the counts equal those of one call with all rows.  HU_ERR_ARG, before anything reaches the device, for a node outside
+ * [0, n_nodes); a failed call changes nothing. */
+int hu_otucs_add(hu_otucs* h, int64_t n_rows, const int32_t* node_of_row, const char* rows);
+/* the counts of one OTU: freq [4][cs_len] (A C G T), gap [cs_len]; all zero for a node no row has named */
+int hu_otucs_counts(hu_otucs* h, int32_t node, uint32_t* freq, uint32_t* gap);
+/* PTUnrooted::inferPostCS(node, freq, gap, effN) for n OTUs: out [n][cs_len] characters of ACGT and '-', no terminator.  Per column:
+ * pri = the node's message towards its parent (for node 0 the root message of the .ptu) as weights summing to 1 (inferWeight,
+ * src/PhyloTreeUnrooted.h:1590-1593), post = eff_n * pri + freq, post /= sum(post), and the symbol is '-' when sum(freq) < gap, else
+ * the first maximum of post.  eff_n = 0 turns the prior off.  HU_ERR_ARG for a node outside [0, n_nodes) or eff_n < 0. */
+int hu_otucs_infer(hu_otucs* h, int32_t n, const int32_t* nodes, double eff_n, char* out);
+/* host only: the description of an OTU's FASTA record (src/hmmufotu-sum.cpp:448-452),
+ *   DBName=<db_name>;Taxonomy="<taxonomy>";AnnoDist=<anno_dist>;ReadCount=<read_count>;SampleHits=<sample_hits>
+ * anno_dist as boost::lexical_cast<string>(double) writes it: 17 significant digits in ostream's general format, i.e. %.17g.  Returns
+ * the length (without the terminator) and writes at most cap bytes, terminator included; HU_ERR_ARG (negative) on a null argument. */
+int64_t hu_otucs_description(const char* db_name, const char* taxonomy, double anno_dist, int64_t read_count, int64_t sample_hits, char* out, int64_t cap);
+/* the annotation distance of a node (PTUNode::getAnnoDist), beside hu_db_get_annotation */
+int hu_db_get_anno_dist(const hu_db* db, int32_t node, double* out);
+
 #ifdef __cplusplus
 }
 #endif
