@@ -1,0 +1,303 @@
+// hmmufotu-amd-build: a <NAME>.ptu database from a reference MSA and its phylogenetic tree — the --no-hmm mode of hmmufotu-build
+// (src/hmmufotu-build.cpp:307-503 without the csfm, hmm and msa parts).  The host reads and joins the inputs; the wide loops run on
+// the device: the MSA column counts behind MSA::prune (hu_msa_stats), the tree evaluated at every root (hu_tree_evaluate), the
+// per-site mutation counts behind -V (hu_tree_count_mutations), the tree log-likelihood (hu_tree_loglik) and the gather of the
+// messages for the file (hu_ptu_write_stream).  Options and inputs are checked, and every input read and joined, before a device
+// is asked for.
+//   hmmufotu-amd-build <MSA-FILE> <TREE-FILE> --no-hmm -sm FILE [-n NAME] [--fmt fasta] [-a|--anno FILE] [-r|--root STR] [-V|--var]
+//                      [-k INT] [--device N] [-v]
+// Writes <NAME>.ptu only: no .msa and no .csfm (hmmufotu-amd rebuilds its seed index from the .ptu), and no .hmm — the profile comes
+// from a third-party trainer (HMMER3, hmmufotu-train-hmm) and is put beside the .ptu as <NAME>.hmm.
+#include <cerrno>
+#include <chrono>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <limits>
+#include <sstream>
+#include <unordered_map>
+#include <sys/stat.h>
+#include <unistd.h>
+#include "hu_reads_io.h"
+#include "../../include/hmmufotu_amd.h"
+
+/* src/hmmufotu-build.cpp:59-61 */
+static const int DEFAULT_DG_CATEGORY = 4, MIN_DG_CATEGORY = 2, MAX_DG_CATEGORY = 8;
+
+static void usage(const char* p) {
+	std::cerr << "Build the phylogenetic-tree database (.ptu) of an HmmUFOtu database from reference MSA and phylogenetic tree files\n"
+		"Usage:    " << p << "  <MSA-FILE> <TREE-FILE> --no-hmm -sm FILE [options]\n"
+		"MSA-FILE  FILE                   : multiple-sequence aligned (MSA) input, support .gz or .bz2 compressed file\n"
+		"TREE-FILE  FILE                  : phylogenetic-tree file build on the MSA sequences (.tree / .tre)\n"
+		"Options:    --no-hmm FLAG        : required: the Hmm profile is built by 3rd party programs, i.e. HMMER3, and supplied as <NAME>.hmm\n"
+		"            -sm  FILE            : trained DNA Substitution Model, required\n"
+		"            -n  STR              : database name (prefix), use 'MSA-FILE' by default\n"
+		"            --fmt  STR           : MSA format, supported format: 'fasta'\n"
+		"            -a|--anno  FILE      : use tab-delimited taxonamy annotation file for the sequences in the MSA and TREE files\n"
+		"            -r|--root  STR       : root name if the original tree root is not named [cellular_organisms]\n"
+		"            -V|--var FLAG        : enable among-site rate varation evaluation of the tree, using a Discrete Gamma Distribution based model\n"
+		"            -k INT               : number of Discrete Gamma Distribution categories to evaluate the tree, ignored if -V not set [" << DEFAULT_DG_CATEGORY << "]\n"
+		"            --device  INT        : device index [0]\n"
+		"            -f|--symfrac, -dm, -p|--process : accepted and ignored (they belong to the profile training)\n"
+		"            -v  FLAG             : enable verbose information; -vv adds the wall time of every phase\n"
+		"            -h|--help            : print this message and exit\n";
+}
+
+static const auto unused_revcom [[maybe_unused]] = &revcom;     /* hu_reads_io.h is shared with the programs that read primers */
+static bool ends_with(const std::string& s, const char* suf) { const size_t k = strlen(suf); return s.size() >= k && s.compare(s.size() - k, k, suf) == 0; }
+static bool read_file(const std::string& fn, std::string& out) {
+	std::ifstream in(fn, std::ios::binary);
+	if(!in.is_open()) return false;
+	std::ostringstream ss; ss << in.rdbuf(); out = ss.str();
+	return !in.bad();
+}
+
+int main(int argc, char** argv) {
+	std::vector<std::string> pos; std::string dbName, fmt, annoFn, smFn, smType, rootName = "cellular_organisms";
+	bool noHmm = false, isVar = false, haveS = false;
+	int K = DEFAULT_DG_CATEGORY, device = 0, verbose = 0;
+	std::vector<std::string> ignored;
+	if(argc == 1) { usage(argv[0]); return EXIT_SUCCESS; }
+	for(int i = 1; i < argc; ++i) {
+		std::string a = argv[i];
+		auto val = [&]() -> const char* { if(i + 1 >= argc) { std::cerr << "Error: option " << a << " needs a value\n"; exit(EXIT_FAILURE); } return argv[++i]; };
+		if(a == "-h" || a == "--help") { usage(argv[0]); return EXIT_SUCCESS; }
+		else if(a == "--version") { std::cerr << argv[0] << ": v1.5.1\nPackage: HmmUFOtu v1.5.1 (file formats and build semantics; hmmufotu_amd engine for gfx950)" << std::endl; return EXIT_SUCCESS; }
+		else if(a == "-n") dbName = val(); else if(a == "--fmt") fmt = val();
+		else if(a == "-a" || a == "--anno") annoFn = val(); else if(a == "-r" || a == "--root") rootName = val();
+		else if(a == "-s" || a == "--sub-model") { smType = val(); haveS = true; }
+		else if(a == "-sm") smFn = val();
+		else if(a == "--no-hmm") noHmm = true; else if(a == "-V" || a == "--var") isVar = true;
+		else if(a == "-k") K = atoi(val()); else if(a == "--device") device = atoi(val());
+		else if(a == "-f" || a == "--symfrac" || a == "-dm" || a == "-p" || a == "--process") { ignored.push_back(a); val(); }
+		else if(a.size() > 1 && a[0] == '-' && a.find_first_not_of('v', 1) == std::string::npos) verbose += (int) a.size() - 1;
+		else if(a[0] == '-' && a.size() > 1) { std::cerr << "Error: unknown option " << a << std::endl; usage(argv[0]); return EXIT_FAILURE; }
+		else pos.push_back(a);
+	}
+	if(pos.size() != 2) { std::cerr << "Error:" << std::endl; usage(argv[0]); return EXIT_FAILURE; }
+	auto info = [&](const std::string& s) { if(verbose) std::cerr << s << std::endl; };
+	/* -vv: wall time of every phase, for profiles/build_program_rate.py */
+	auto tLap = std::chrono::steady_clock::now();
+	auto lap = [&](const char* phase) {
+		const auto now = std::chrono::steady_clock::now();
+		if(verbose > 1) std::cerr << "[phase] " << phase << ": " << std::chrono::duration<double>(now - tLap).count() << " s" << std::endl;
+		tLap = now;
+	};
+	const std::string seqFn = pos[0], treeFn = pos[1];
+	if(!noHmm) { std::cerr << "profile training is not provided here; pass --no-hmm and supply <NAME>.hmm (HMMER3 or hmmufotu-train-hmm)" << std::endl; return EXIT_FAILURE; }
+	if(smFn.empty()) {
+		if(haveS) std::cerr << "-s|--sub-model " << smType << ": the built-in models are read from the reference's installed data directory, which is not shipped here; pass the trained model with -sm FILE" << std::endl;
+		else std::cerr << "-sm FILE must be specified: the built-in models of the reference's data directory are not shipped here" << std::endl;
+		return EXIT_FAILURE;
+	}
+	/* guess input format (src/hmmufotu-build.cpp:198-208) */
+	if(fmt.empty()) {
+		std::string pre = seqFn;
+		if(ends_with(pre, ".gz")) pre.erase(pre.size() - 3); else if(ends_with(pre, ".bz2")) pre.erase(pre.size() - 4);
+		for(const char* e : {"fasta", "fas", "fa", "fna"}) if(ends_with(pre, e)) fmt = "fasta";
+		if(fmt.empty()) for(const char* e : {"fastq", "fq"}) if(ends_with(pre, e)) fmt = "fastq";
+	}
+	if(fmt != "fasta") { std::cerr << "Unsupported sequence format '" << fmt << "'" << std::endl; return EXIT_FAILURE; }
+	if(!ends_with(treeFn, ".tree") && !ends_with(treeFn, ".tre")) { std::cerr << "Unrecognized TREE-FILE format, must be in Newick format" << std::endl; return EXIT_FAILURE; }
+	if(!(MIN_DG_CATEGORY <= K && K <= MAX_DG_CATEGORY)) { std::cerr << "-k must be an integer between " << MIN_DG_CATEGORY << " and " << MAX_DG_CATEGORY << std::endl; return EXIT_FAILURE; }
+	if(device < 0) { std::cerr << "--device must be non-negative" << std::endl; return EXIT_FAILURE; }
+	for(const std::string& o : ignored) info("Note: " + o + " belongs to the profile training and is ignored under --no-hmm");
+
+	/* open and read the inputs */
+	LineIn seqIn;
+	if(!seqIn.open(seqFn)) { std::cerr << "Unable to open seq file '" << seqFn << "' " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+	std::string smText, treeText, annoText;
+	if(!read_file(smFn, smText)) { std::cerr << "Unable to open '" << smFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+	if(!read_file(treeFn, treeText)) { std::cerr << "Unable to open '" << treeFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+	if(!annoFn.empty() && !read_file(annoFn, annoText)) { std::cerr << "Unable to open '" << annoFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+	if(dbName.empty()) dbName = seqFn.substr(seqFn.find_last_of('/') + 1);      /* StringUtils::basename(seqFn) */
+	const std::string ptuFn = dbName + ".ptu";
+
+	/* the MSA: rows as read (case kept), names = the ids */
+	std::vector<std::string> rowName; std::vector<char> msa; size_t L0 = 0;
+	std::unordered_map<std::string, uint32_t> name2row;
+	{
+		Read r;
+		while(next_read(seqIn, false, r, true)) {
+			if(rowName.empty()) L0 = r.seq.size();
+			else if(r.seq.size() != L0) { std::cerr << "Unable to load MSA from '" << seqFn << "': sequence '" << r.id << "' has " << r.seq.size() << " columns, the first one " << L0 << std::endl; return EXIT_FAILURE; }
+			if(!name2row.insert({r.id, (uint32_t) rowName.size()}).second) { std::cerr << "Non-unique seq name " << r.id << " found in your MSA data " << dbName << std::endl; return EXIT_FAILURE; }
+			rowName.push_back(r.id);
+			msa.insert(msa.end(), r.seq.begin(), r.seq.end());
+		}
+		if(rowName.empty() || L0 == 0) { std::cerr << "Unable to load MSA from '" << seqFn << "'" << std::endl; return EXIT_FAILURE; }
+	}
+	const size_t nSeq = rowName.size();
+	info("MSA loaded");
+	lap("read");
+
+	/* the tree */
+	hu_newick* nw = nullptr;
+	if(hu_newick_parse(treeText.data(), (int64_t) treeText.size(), &nw) != HU_OK) { std::cerr << "Unable to read Newick tree in '" << treeFn << "': " << hu_last_error() << std::endl; return EXIT_FAILURE; }
+	info("Newick Tree read");
+	int32_t n = 0;
+	hu_newick_size(nw, &n);
+	std::vector<int32_t> parent(n), childOff((size_t) n + 1), childIdx((size_t) std::max(n - 1, 1));
+	std::vector<double> blen(n);
+	hu_newick_get(nw, parent.data(), blen.data(), childOff.data(), childIdx.data());
+	std::vector<std::string> nodeName(n);
+	for(int32_t i = 0; i < n; ++i) nodeName[i] = hu_newick_name(nw, i);
+	hu_newick_free(nw);
+	info("Phylogenetic Tree constructed with total " + std::to_string(n) + " nodes");
+	if(n < 2) { std::cerr << "Unable to build a database from a tree of " << n << " node" << std::endl; return EXIT_FAILURE; }
+
+	/* loadMSA (src/PhyloTreeUnrooted.cpp:185-221): every leaf takes the row of its name */
+	std::vector<int32_t> rowOf(n, -1);
+	size_t nLeaves = 0, nRead = 0;
+	for(int32_t i = 0; i < n; ++i) if(childOff[i] == childOff[i + 1]) {
+		++nLeaves;
+		auto it = name2row.find(nodeName[i]);
+		if(it != name2row.end()) { rowOf[i] = (int32_t) it->second; ++nRead; }
+	}
+	if(nRead != nLeaves) { std::cerr << "Unmatched MSA and Tree. Found " << nRead << " leaf sequences from MSA but expecting " << nLeaves << " leaves in the Phylogenetic Tree " << std::endl; return EXIT_FAILURE; }
+	info("MSA loaded into Phylogenetic Tree");
+
+	info("Verifying and fixing branch length");
+	for(int32_t i = 0; i < n; ++i) if(parent[i] >= 0 && childOff[i] == childOff[i + 1] && blen[i] <= 0) blen[i] = 1e-5;     /* fixBranchLength, BRANCH_EPS */
+
+	/* annotation */
+	hu_tree_anno* an = nullptr;
+	{
+		std::vector<const char*> nm(n);
+		for(int32_t i = 0; i < n; ++i) nm[i] = nodeName[i].c_str();
+		if(hu_tree_annotate(n, parent.data(), blen.data(), nm.data(), annoFn.empty() ? nullptr : annoText.data(), (int64_t) annoText.size(), rootName.c_str(), &an) != HU_OK) {
+			std::cerr << "Failed to load taxonomy annotation from '" << annoFn << "': " << hu_last_error() << std::endl; return EXIT_FAILURE;
+		}
+	}
+	if(!annoFn.empty()) info("Taxonomy annotation loaded");
+	info("Taxon names formatted");
+	info("Unnamed tree nodes annotated");
+	lap("join");
+	std::vector<const char*> names(n), annos(n);
+	std::vector<double> annoDist(n);
+	for(int32_t i = 0; i < n; ++i) { names[i] = hu_tree_anno_name(an, i); annos[i] = hu_tree_anno_anno(an, i); }
+	hu_tree_anno_dist(an, annoDist.data());
+
+	/* the model: the type is the word behind "Type:" (src/hmmufotu-build.cpp:393-405) */
+	hu_model_desc model;
+	{
+		std::istringstream in(smText);
+		std::string tag, type, line;
+		while(in >> tag) { if(tag[0] == '#') { std::getline(in, line); continue; } if(tag == "Type:") { in >> type; break; } }
+		const std::string withType = type + "\n" + smText;
+		if(type.empty() || hu_model_parse_text(withType.data(), (int64_t) withType.size(), &model) != HU_OK) {
+			std::cerr << "Unable to load DNA Substitution Model from: '" << smFn << "'" << (type.empty() ? "" : std::string(": ") + hu_last_error()) << std::endl; hu_tree_anno_free(an); return EXIT_FAILURE;
+		}
+	}
+	model.dg_k = 0;
+	info("DNA Substitution Model loaded");
+
+	/* the output, then the device */
+	struct stat stBefore;
+	const bool existed = stat(ptuFn.c_str(), &stBefore) == 0;
+	{ std::ofstream probe(ptuFn, std::ios::binary | std::ios::app); if(!probe.is_open()) { std::cerr << "Unable to write to '" << ptuFn << "': " << strerror(errno) << std::endl; hu_tree_anno_free(an); return EXIT_FAILURE; } }
+	void *dUp = nullptr, *dDown = nullptr;
+	auto fail = [&](const std::string& msg) {
+		std::cerr << msg << std::endl;
+		hu_device_free(device, dUp); hu_device_free(device, dDown); hu_tree_anno_free(an);
+		if(!existed) unlink(ptuFn.c_str());       /* only the probe's empty file */
+		return EXIT_FAILURE;
+	};
+	if(hu_device_count() <= device) return fail("Error: device " + std::to_string(device) + " asked for, " + std::to_string(hu_device_count()) + " gfx950 device(s) visible");
+
+	/* MSA::prune: the columns without a residue go (hu_msa_stats counts them on the device) */
+	std::vector<int8_t> seq;
+	int32_t L = 0;
+	{
+		std::vector<int32_t> res(4 * L0), gap(L0), st(nSeq), en(nSeq), ln(nSeq);
+		std::vector<double> w(nSeq), wres(4 * L0), wgap(L0);
+		if(hu_msa_stats(device, (int64_t) nSeq, (int64_t) L0, msa.data(), res.data(), gap.data(), st.data(), en.data(), ln.data(), w.data(), wres.data(), wgap.data()) != HU_OK)
+			return fail(std::string("Error: ") + hu_last_error());
+		std::vector<uint32_t> keep;
+		for(size_t j = 0; j < L0; ++j) if(res[j] + res[L0 + j] + res[2 * L0 + j] + res[3 * L0 + j] > 0) keep.push_back((uint32_t) j);
+		L = (int32_t) keep.size();
+		info("MSA pruned");
+		info("MSA database created for " + std::to_string(nSeq) + " X " + std::to_string(L) + " aligned sequences");
+		if(L < 1) return fail("Unable to build a database: the MSA has no column with a residue");
+		if(L > 65535) return fail("Unable to build a database: " + std::to_string(L) + " columns after pruning, the .ptu readers take at most 65535");
+		int8_t enc[256];
+		hu_msa_encode_table(enc);
+		seq.assign((size_t) n * L, (int8_t) 0);
+		for(int32_t i = 0; i < n; ++i) if(rowOf[i] >= 0) {
+			const char* src = msa.data() + (size_t) rowOf[i] * L0; int8_t* dst = seq.data() + (size_t) i * L;
+			for(int32_t j = 0; j < L; ++j) dst[j] = enc[(unsigned char) src[keep[j]]];
+		}
+	}
+	std::vector<char>().swap(msa);
+	lap("stats");
+
+	/* device memory: both message sets, and the largest of the later steps' scratch: the sweep's node rows and tables, the mutation count's
+	 * states, the writer's staging buffers */
+	{
+		int64_t freeB = 0, totB = 0;
+		if(hu_device_mem_info(device, &freeB, &totB) != HU_OK) return fail(std::string("Error: ") + hu_last_error());
+		const int64_t msgs = 2ll * n * L * 32, sweep = (int64_t) n * L + (int64_t) n * 28 + 64, mut = isVar ? (int64_t) n * L + (int64_t) n * 4 + (int64_t) L * 4 : 0;
+		const int64_t stage = 2 * std::min<int64_t>((int64_t) 256 << 20, (2ll * n - 1) * L * 32) + 8ll * n;     /* hu_ptu_write_stream's two staging buffers */
+		const int64_t need = msgs + std::max(std::max(sweep, mut), stage) + (int64_t) L * 8;
+		if(need > freeB) {
+			char buf[256];
+			snprintf(buf, sizeof(buf), "Unable to build the database on device %d: %d nodes x %d columns need %.3f GB of device memory, %.3f GB are free (column-windowed builds are not provided)", device, n, L, need / 1e9, freeB / 1e9);
+			return fail(buf);
+		}
+		if(hu_device_malloc(device, msgs / 2, &dUp) != HU_OK || hu_device_malloc(device, msgs / 2, &dDown) != HU_OK) return fail(std::string("Error: ") + hu_last_error());
+	}
+	std::vector<double> height(n);
+	info(std::string("Evaluating Phylogenetic Tree at root id: 0") + (isVar ? " with fixed rate model first" : ""));
+	if(hu_tree_evaluate(n, L, parent.data(), blen.data(), seq.data(), &model, device, 0, 0, (double*) dUp, (double*) dDown, height.data()) != HU_OK) return fail(std::string("Error: ") + hu_last_error());
+	info("Node height calculated");
+	lap("first sweep");
+	double alpha = 0;
+	std::vector<double> breaks;
+	if(isVar) { /* src/hmmufotu-build.cpp:431-447 */
+		info("Estimating the shape parameter of the Discrete Gamma Distributin based among-site variation ...");
+		std::vector<int32_t> cnt(L);
+		if(hu_tree_count_mutations(device, n, L, parent.data(), (const double*) dUp, cnt.data()) != HU_OK) return fail(std::string("Error: ") + hu_last_error());
+		std::vector<double> numMut(cnt.begin(), cnt.end());
+		alpha = hu_dg_estimate_shape(L, numMut.data());
+		lap("mutation count");
+		if(alpha == std::numeric_limits<double>::infinity()) std::cerr << "Unable to estimate the shape parameter with less than 2 alignment sites" << std::endl;
+		else if(!(alpha > 0)) std::cerr << "Unable to estimate the shape parameter with near invariant rates, reducing to fixed rate model" << std::endl;
+		else {
+			if(verbose) std::cerr << "Estimated alpha = " << alpha << std::endl;
+			breaks.resize((size_t) K + 1);
+			if(hu_dg_model(K, alpha, breaks.data(), model.dg_rate) != HU_OK) return fail(std::string("Error: ") + hu_last_error());
+			model.dg_k = K;
+		}
+	}
+	if(model.dg_k == 0) info("Evaluating Phylogenetic Tree at all other " + std::to_string(n - 1) + " nodes");     /* the sweep above left every directed edge's message */
+	else {
+		info("Re-evaluating Phylogenetic Tree at all " + std::to_string(n) + " nodes");
+		for(int32_t i = 0; i < n; ++i) if(rowOf[i] < 0) memset(seq.data() + (size_t) i * L, 0, (size_t) L);
+		if(hu_tree_evaluate(n, L, parent.data(), blen.data(), seq.data(), &model, device, 0, 0, (double*) dUp, (double*) dDown, height.data()) != HU_OK) return fail(std::string("Error: ") + hu_last_error());
+	}
+	lap("second sweep");
+	double loglik = 0;
+	if(hu_tree_loglik(device, n, L, 0, &model, (const double*) dUp, nullptr, &loglik) != HU_OK) return fail(std::string("Error: ") + hu_last_error());
+	if(verbose) std::cerr << "Final Tree log-liklihood: " << loglik << std::endl;
+	info("Ancestor sequence of all intermediate nodes inferred");
+	lap("log-likelihood");
+
+	info("Saving database files ...");
+	hu_tree_desc td;
+	memset(&td, 0, sizeof(td));
+	td.n_nodes = n; td.cs_len = L; td.parent = parent.data(); td.blen = blen.data(); td.seq = seq.data(); td.up = (const double*) dUp; td.down = (const double*) dDown;
+	td.height = height.data(); td.anno_dist = annoDist.data(); td.msgs_on_device = 1;
+	if(hu_ptu_write_stream(ptuFn.c_str(), &td, names.data(), annos.data(), &model, smText.c_str(), alpha, model.dg_k ? breaks.data() : nullptr,
+			childOff.data(), childIdx.data(), rowOf.data(), 0) != HU_OK) {
+		std::cerr << "Unable to save Phylogenetic Tree index: " << hu_last_error() << std::endl;
+		hu_device_free(device, dUp); hu_device_free(device, dDown); hu_tree_anno_free(an);
+		unlink(ptuFn.c_str());
+		return EXIT_FAILURE;
+	}
+	info("Phylogenetic Tree index saved");
+	lap("write");
+	hu_device_free(device, dUp); hu_device_free(device, dDown); hu_tree_anno_free(an);
+	return EXIT_SUCCESS;
+}

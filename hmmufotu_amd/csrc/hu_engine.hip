@@ -501,16 +501,47 @@ static std::string model_text_of(const hu_model_desc& m) {
 	else if(m.type == HU_K80) o += "kappa: " + num(m.par[0]) + "\n";
 	return o;
 }
-extern "C" int hu_ptu_write(const char* path, const hu_tree_desc* t, const char* const* names, const char* const* annos, const hu_model_desc* model,
-		const char* model_text, double dg_alpha, const double* dg_breaks) try {
-	if(!path || !t || !model || t->n_nodes < 2 || t->cs_len < 1 || !t->parent || !t->blen || !t->seq || !t->up || !t->down || !t->height) { hu_set_error("hu_ptu_write: bad argument"); return HU_ERR_ARG; }
-	if(model->type < 0 || model->type > HU_JC69 || model->dg_k < 0 || model->dg_k > HU_MAX_DGK) { hu_set_error("hu_ptu_write: bad model"); return HU_ERR_ARG; }
-	if(t->win_len > 0 && t->win_len != t->cs_len) { hu_set_error("hu_ptu_write: the file format holds whole messages, not a column window"); return HU_ERR_ARG; }
+/* One writer behind hu_ptu_write and hu_ptu_write_stream.  fn: the entry's name for messages.  childOff / childIdx / rowOf NULL: children in id
+ * order, MSA index = k-th leaf in node order (hu_ptu_write).  pipelined: device messages go through k_ptu_gather and two staging buffers on two
+ * streams instead of one blocking copy per edge. */
+static int ptu_write_impl(const char* fn, const char* path, const hu_tree_desc* t, const char* const* names, const char* const* annos, const hu_model_desc* model,
+		const char* model_text, double dg_alpha, const double* dg_breaks, const int32_t* childOff, const int32_t* childIdx, const int32_t* rowOf,
+		int64_t stagingBytes, bool pipelined) {
+	if(!path || !t || !model || t->n_nodes < 2 || t->cs_len < 1 || !t->parent || !t->blen || !t->seq || !t->up || !t->down || !t->height) { hu_set_error("%s: bad argument", fn); return HU_ERR_ARG; }
+	if(model->type < 0 || model->type > HU_JC69 || model->dg_k < 0 || model->dg_k > HU_MAX_DGK) { hu_set_error("%s: bad model", fn); return HU_ERR_ARG; }
+	if(t->win_len > 0 && t->win_len != t->cs_len) { hu_set_error("%s: the file format holds whole messages, not a column window", fn); return HU_ERR_ARG; }
+	if((childOff == nullptr) != (childIdx == nullptr) || stagingBytes < 0) { hu_set_error("%s: bad argument", fn); return HU_ERR_ARG; }
 	const int n = t->n_nodes, L = t->cs_len;
 	std::vector<std::vector<int32_t>> children(n);
 	int root = -1;
-	for(int i = 0; i < n; ++i) { if(t->parent[i] < 0) root = i; else if(t->parent[i] < n) children[t->parent[i]].push_back(i); else { hu_set_error("hu_ptu_write: parent out of range"); return HU_ERR_ARG; } }
-	if(root < 0) { hu_set_error("hu_ptu_write: tree has no root"); return HU_ERR_ARG; }
+	for(int i = 0; i < n; ++i) { if(t->parent[i] < 0) root = i; else if(t->parent[i] < n) children[t->parent[i]].push_back(i); else { hu_set_error("%s: parent out of range", fn); return HU_ERR_ARG; } }
+	if(root < 0) { hu_set_error("%s: tree has no root", fn); return HU_ERR_ARG; }
+	if(childOff) { /* the caller's order: a permutation of every node's children */
+		if(childOff[0] != 0 || childOff[n] != n - 1) { hu_set_error("%s: child order does not list %d children", fn, n - 1); return HU_ERR_ARG; }
+		std::vector<uint8_t> seen(n, 0);
+		for(int u = 0; u < n; ++u) {
+			if(childOff[u + 1] - childOff[u] != (int32_t) children[u].size()) { hu_set_error("%s: child order names %d children of node %d, the tree has %zu", fn, childOff[u + 1] - childOff[u], u, children[u].size()); return HU_ERR_ARG; }
+			for(int32_t c = childOff[u]; c < childOff[u + 1]; ++c) {
+				const int32_t v = childIdx[c];
+				if(v < 0 || v >= n || t->parent[v] != u || seen[v]) { hu_set_error("%s: child order entry %d is not a child of node %d, or is listed twice", fn, c, u); return HU_ERR_ARG; }
+				seen[v] = 1;
+			}
+			children[u].assign(childIdx + childOff[u], childIdx + childOff[u + 1]);
+		}
+	}
+	std::vector<std::pair<uint32_t, int64_t>> msaIdx;     /* (MSA row, node id) */
+	if(rowOf) {
+		for(int i = 0; i < n; ++i) {
+			if(children[i].empty() != (rowOf[i] >= 0)) { hu_set_error("%s: node %d is %s and has MSA row %d", fn, i, children[i].empty() ? "a leaf" : "no leaf", rowOf[i]); return HU_ERR_ARG; }
+			if(rowOf[i] >= 0) msaIdx.push_back({(uint32_t) rowOf[i], (int64_t) i});
+		}
+		std::sort(msaIdx.begin(), msaIdx.end());
+		for(size_t k = 1; k < msaIdx.size(); ++k) if(msaIdx[k].first == msaIdx[k - 1].first) { hu_set_error("%s: MSA row %u belongs to two leaves", fn, msaIdx[k].first); return HU_ERR_ARG; }
+	}
+	else for(int i = 0; i < n; ++i) if(children[i].empty()) msaIdx.push_back({(uint32_t) msaIdx.size(), (int64_t) i});
+	const size_t row = (size_t) L * 4;
+	const bool stream = pipelined && t->msgs_on_device;
+	if(stream && ((((uintptr_t) t->up) | ((uintptr_t) t->down)) & 15)) { hu_set_error("%s: the device message buffers must be 16-byte aligned", fn); return HU_ERR_ARG; }
 	std::ofstream f(path, std::ios::binary);
 	if(!f) { hu_set_error("cannot write PTU file '%s'", path); return HU_ERR_IO; }
 	auto put = [&](const void* p, size_t k) { f.write((const char*) p, (std::streamsize) k); };
@@ -530,47 +561,109 @@ extern "C" int hu_ptu_write(const char* path, const hu_tree_desc* t, const char*
 		const double ad = t->anno_dist ? t->anno_dist[i] : 0.0; put(&ad, 8);
 	}
 	const uint64_t nEdges = 2ull * (n - 1); put(&nEdges, 8);
-	const size_t row = (size_t) L * 4;
-	double* stage = nullptr;
-	std::vector<double> hostRow;
-	if(t->msgs_on_device) { if(hipHostMalloc((void**) &stage, row * 8, hipHostMallocDefault) != hipSuccess) { (void) hipGetLastError(); hostRow.resize(row); stage = hostRow.data(); } }
-	auto msg = [&](const double* base, int node) -> const double* {
-		const double* p = base + (size_t) node * row;
-		if(!t->msgs_on_device) return p;
-		if(hipMemcpy(stage, p, row * 8, hipMemcpyDeviceToHost) != hipSuccess) return nullptr;
-		return stage;
+	/* both directions of every edge, grouped by their first node: parent first, then the children; the root row ends the list */
+	auto edgeHeader = [&](int u, int v) {
+		const bool uIsParent = t->parent[u] < 0 || v != t->parent[u];
+		const int child = uIsParent ? v : u;
+		const int64_t a = u, b2 = v; put(&a, 8); put(&b2, 8);
+		const uint8_t fl = uIsParent ? 1 : 0; put(&fl, 1);
+		const double len = t->blen[child]; put(&len, 8);
+		const uint64_t N = row; put(&N, 8);
 	};
 	bool ok = true;
-	for(int u = 0; u < n && ok; ++u) { /* both directions of every edge, grouped by their first node: parent first, then the children */
-		std::vector<int32_t> nb;
-		if(t->parent[u] >= 0) nb.push_back(t->parent[u]);
-		nb.insert(nb.end(), children[u].begin(), children[u].end());
-		for(int32_t v : nb) {
-			const bool uIsParent = t->parent[u] < 0 || v != t->parent[u];
-			const int child = uIsParent ? v : u;
-			const int64_t a = u, b2 = v; put(&a, 8); put(&b2, 8);
-			const uint8_t fl = uIsParent ? 1 : 0; put(&fl, 1);
-			const double len = t->blen[child]; put(&len, 8);
-			const uint64_t N = row; put(&N, 8);
-			const double* m = msg(uIsParent ? t->down : t->up, child);
-			if(!m) { ok = false; break; }
-			put(m, row * 8);
+	if(!stream) {
+		double* stage = nullptr;
+		std::vector<double> hostRow;
+		if(t->msgs_on_device) { if(hipHostMalloc((void**) &stage, row * 8, hipHostMallocDefault) != hipSuccess) { (void) hipGetLastError(); hostRow.resize(row); stage = hostRow.data(); } }
+		auto msg = [&](const double* base, int node) -> const double* {
+			const double* p = base + (size_t) node * row;
+			if(!t->msgs_on_device) return p;
+			if(hipMemcpy(stage, p, row * 8, hipMemcpyDeviceToHost) != hipSuccess) return nullptr;
+			return stage;
+		};
+		for(int u = 0; u < n && ok; ++u) {
+			std::vector<int32_t> nb;
+			if(t->parent[u] >= 0) nb.push_back(t->parent[u]);
+			nb.insert(nb.end(), children[u].begin(), children[u].end());
+			for(int32_t v : nb) {
+				const bool uIsParent = t->parent[u] < 0 || v != t->parent[u];
+				edgeHeader(u, v);
+				const double* m = msg(uIsParent ? t->down : t->up, uIsParent ? v : u);
+				if(!m) { ok = false; break; }
+				put(m, row * 8);
+			}
+			if(pipelined && !f) { hu_set_error("writing PTU file '%s' failed", path); return HU_ERR_IO; }
 		}
+		if(ok) {
+			const int64_t rid = root; put(&rid, 8);
+			const double* m = msg(t->up, root);
+			if(m) put(m, row * 8); else ok = false;
+		}
+		if(stage && hostRow.empty()) (void) hipHostFree(stage);
+		if(!ok) { hu_set_error("%s: copying a message from the device failed", fn); return HU_ERR_DEVICE; }
 	}
-	if(ok) {
-		const int64_t rid = root; put(&rid, 8);
-		const double* m = msg(t->up, root);
-		if(m) put(m, row * 8); else ok = false;
+	else {
+		/* items in file order: (u, v) for the edges, (root, -1) for the root row; code = node << 1 | from down[] */
+		const size_t nItems = (size_t) nEdges + 1;
+		std::vector<int32_t> itU(nItems), itV(nItems);
+		std::vector<uint32_t> code(nItems);
+		{
+			size_t k = 0;
+			for(int u = 0; u < n; ++u) {
+				if(t->parent[u] >= 0) { itU[k] = u; itV[k] = t->parent[u]; code[k++] = (uint32_t) u << 1; }
+				for(int32_t v : children[u]) { itU[k] = u; itV[k] = v; code[k++] = (uint32_t) v << 1 | 1u; }
+			}
+			itU[k] = root; itV[k] = -1; code[k++] = (uint32_t) root << 1;
+			if(k != nItems) { hu_set_error("%s: tree is not connected", fn); return HU_ERR_ARG; }
+		}
+		const size_t rowBytes = row * 8;
+		const size_t want = stagingBytes > 0 ? (size_t) stagingBytes : (size_t) 256 << 20;
+		const size_t per = std::min(nItems, std::max<size_t>(1, want / rowBytes));     /* a run never splits a message */
+		const int64_t pieces = (int64_t)(rowBytes / 16);
+		uint32_t* dCode = nullptr; uint4* dStage[2] = {nullptr, nullptr}; char* hStage[2] = {nullptr, nullptr}; hipStream_t st[2] = {nullptr, nullptr};
+		HuScope guard([&] {
+			for(int i = 0; i < 2; ++i) { if(st[i]) { (void) hipStreamSynchronize(st[i]); (void) hipStreamDestroy(st[i]); } if(dStage[i]) (void) hipFree(dStage[i]); if(hStage[i]) (void) hipHostFree(hStage[i]); }
+			if(dCode) (void) hipFree(dCode);
+		});
+		#define WCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { hu_set_error("%s: %s failed: %s", fn, #call, hipGetErrorString(e_)); return HU_ERR_DEVICE; } } while(0)
+		WCHK(hipMalloc((void**) &dCode, nItems * 4));
+		WCHK(hipMemcpy(dCode, code.data(), nItems * 4, hipMemcpyHostToDevice));
+		for(int i = 0; i < 2; ++i) {
+			WCHK(hipStreamCreate(&st[i]));
+			WCHK(hipMalloc((void**) &dStage[i], per * rowBytes));
+			WCHK(hipHostMalloc((void**) &hStage[i], per * rowBytes, hipHostMallocDefault));
+		}
+		(void) hipGetLastError();
+		const size_t nRuns = (nItems + per - 1) / per;
+		auto enqueue = [&](size_t c) -> hipError_t {
+			const size_t a = c * per, m = std::min(per, nItems - a);
+			const int b = (int)(c & 1);
+			k_ptu_gather<<<dim3((unsigned)((pieces + 255) / 256), (unsigned) std::min<size_t>(m, 65535)), 256, 0, st[b]>>>(
+				reinterpret_cast<const uint4*>(t->up), reinterpret_cast<const uint4*>(t->down), dCode + a, (int64_t) m, pieces, dStage[b]);
+			hipError_t e = hipGetLastError();
+			if(e != hipSuccess) return e;
+			return hipMemcpyAsync(hStage[b], dStage[b], m * rowBytes, hipMemcpyDeviceToHost, st[b]);
+		};
+		WCHK(enqueue(0));
+		for(size_t c = 0; c < nRuns; ++c) {
+			if(c + 1 < nRuns) WCHK(enqueue(c + 1));       /* gathered and copied while run c is written */
+			const int b = (int)(c & 1);
+			WCHK(hu_wait(st[b]));
+			const size_t a = c * per, m = std::min(per, nItems - a);
+			for(size_t k = 0; k < m; ++k) {
+				if(itV[a + k] >= 0) edgeHeader(itU[a + k], itV[a + k]);
+				else { const int64_t rid = root; put(&rid, 8); }
+				put(hStage[b] + k * rowBytes, rowBytes);
+			}
+			if(!f) { hu_set_error("writing PTU file '%s' failed", path); return HU_ERR_IO; }
+		}
+		#undef WCHK
 	}
-	if(stage && hostRow.empty()) (void) hipHostFree(stage);
-	if(!ok) { hu_set_error("hu_ptu_write: copying a message from the device failed"); return HU_ERR_DEVICE; }
 	for(int i = 0; i < n; ++i) { const int64_t id = i; put(&id, 8); put(&t->height[i], 8); }
-	{ /* MSA index: the leaves in node order */
-		uint32_t nl = 0;
-		for(int i = 0; i < n; ++i) nl += children[i].empty();
+	{ /* MSA index */
+		const uint32_t nl = (uint32_t) msaIdx.size();
 		put(&nl, 4);
-		uint32_t k = 0;
-		for(int i = 0; i < n; ++i) if(children[i].empty()) { put(&k, 4); const int64_t id = i; put(&id, 8); ++k; }
+		for(const auto& e : msaIdx) { put(&e.first, 4); put(&e.second, 8); }
 	}
 	{
 		static const char* mnames[] = {"GTR", "TN93", "HKY85", "F81", "K80", "JC69"};
@@ -587,7 +680,16 @@ extern "C" int hu_ptu_write(const char* path, const hu_tree_desc* t, const char*
 	f.flush();
 	if(!f) { hu_set_error("writing PTU file '%s' failed", path); return HU_ERR_IO; }
 	return HU_OK;
+}
+extern "C" int hu_ptu_write(const char* path, const hu_tree_desc* t, const char* const* names, const char* const* annos, const hu_model_desc* model,
+		const char* model_text, double dg_alpha, const double* dg_breaks) try {
+	return ptu_write_impl("hu_ptu_write", path, t, names, annos, model, model_text, dg_alpha, dg_breaks, nullptr, nullptr, nullptr, 0, false);
 } catch(...) { return hu_catch_all("hu_ptu_write"); }
+extern "C" int hu_ptu_write_stream(const char* path, const hu_tree_desc* t, const char* const* names, const char* const* annos, const hu_model_desc* model,
+		const char* model_text, double dg_alpha, const double* dg_breaks, const int32_t* child_off, const int32_t* child_idx, const int32_t* msa_row_of_leaf,
+		int64_t staging_bytes) try {
+	return ptu_write_impl("hu_ptu_write_stream", path, t, names, annos, model, model_text, dg_alpha, dg_breaks, child_off, child_idx, msa_row_of_leaf, staging_bytes, true);
+} catch(...) { return hu_catch_all("hu_ptu_write_stream"); }
 
 /* the reference's own text forms, parsed from memory: what operator<<(ostream&, const BandedHMMP7&) and DNASubModel::write emit */
 extern "C" int hu_profile_parse_text(const char* text, int64_t len, int32_t* K, int32_t* L, double* EM, double* EI, double* T, int32_t* p2cs) try {
@@ -881,6 +983,52 @@ extern "C" int hu_tree_count_mutations(int device, int32_t n_nodes, int32_t cs_l
 	#undef MCHK
 	return HU_OK;
 } catch(...) { return hu_catch_all("hu_tree_count_mutations"); }
+
+extern "C" int hu_device_mem_info(int device, int64_t* free_bytes, int64_t* total_bytes) try {
+	if(hu_device_count() <= 0) { hu_set_error("no gfx950 device visible: the engine has no CPU path"); return HU_ERR_DEVICE; }
+	HIPCHK(hipSetDevice(device));
+	size_t f = 0, t = 0;
+	HIPCHK(hipMemGetInfo(&f, &t));
+	if(free_bytes) *free_bytes = (int64_t) f; if(total_bytes) *total_bytes = (int64_t) t;
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_device_mem_info"); }
+extern "C" int hu_device_malloc(int device, int64_t bytes, void** out) try {
+	if(!out || bytes < 1) { hu_set_error("hu_device_malloc: bad argument"); return HU_ERR_ARG; }
+	*out = nullptr;
+	if(hu_device_count() <= 0) { hu_set_error("no gfx950 device visible: the engine has no CPU path"); return HU_ERR_DEVICE; }
+	HIPCHK(hipSetDevice(device));
+	const hipError_t e = hipMalloc(out, (size_t) bytes);
+	if(e != hipSuccess) { (void) hipGetLastError(); *out = nullptr; hu_set_error("hipMalloc(%lld bytes) failed: %s", (long long) bytes, hipGetErrorString(e)); return HU_ERR_NOMEM; }
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_device_malloc"); }
+extern "C" void hu_device_free(int device, void* p) try {
+	if(!p) return;
+	if(hipSetDevice(device) == hipSuccess) (void) hipFree(p);
+} catch(...) { (void) hu_catch_all("hu_device_free"); }
+
+extern "C" int hu_tree_loglik(int device, int32_t n_nodes, int32_t cs_len, int32_t root, const hu_model_desc* model, const double* up_dev,
+		double* per_col, double* sum) try {
+	if(n_nodes < 1 || cs_len < 1 || root < 0 || root >= n_nodes || !model || !up_dev || !sum) { hu_set_error("hu_tree_loglik: bad argument"); return HU_ERR_ARG; }
+	if(((uintptr_t) up_dev) & 15) { hu_set_error("hu_tree_loglik: the message buffer must be 16-byte aligned"); return HU_ERR_ARG; }
+	if(hu_device_count() <= 0) { hu_set_error("no gfx950 device visible: the engine has no CPU path"); return HU_ERR_DEVICE; }
+	HuModelDev mdl;
+	int rc = hu_model_prepare(model, &mdl);
+	if(rc != HU_OK) return rc;
+	HIPCHK(hipSetDevice(device));
+	const int64_t L = cs_len;
+	DBuf<double> dOut;
+	if((rc = dOut.ensure((size_t) L)) != HU_OK) return rc;
+	(void) hipGetLastError();
+	k_tree_loglik<<<(unsigned)((L + 255) / 256), 256>>>(up_dev + (size_t) root * L * 4, L, mdl.pi[0], mdl.pi[1], mdl.pi[2], mdl.pi[3], dOut.p);
+	HIPCHK(hipGetLastError());
+	std::vector<double> own;
+	if(!per_col) { own.resize((size_t) L); per_col = own.data(); }
+	HIPCHK(hipMemcpy(per_col, dOut.p, (size_t) L * 8, hipMemcpyDeviceToHost));
+	double s = 0;
+	for(int64_t j = 0; j < L; ++j) s += per_col[j];       /* serial j order, src/PhyloTreeUnrooted.cpp:707-712 */
+	*sum = s;
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_tree_loglik"); }
 
 /* ------------------------------------------------------------------------------ batch */
 

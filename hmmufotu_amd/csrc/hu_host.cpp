@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <strings.h>
 #include <fstream>
 #include <functional>
 #include <limits>
@@ -705,3 +706,196 @@ extern "C" int64_t hu_otucs_description(const char* db_name, const char* taxonom
 	if(cap > 0) { const size_t k = std::min<size_t>(d.size(), (size_t) cap - 1); memcpy(out, d.data(), k); out[k] = 0; }
 	return (int64_t) d.size();
 } catch(...) { return hu_catch_all("hu_otucs_description"); }
+
+/* ---- Newick reader (src/NewickTree.h:186-215, src/NewickTree.cpp:37-59) and the node numbering of PTUnrooted(const NewickTree&)
+ * (src/PhyloTreeUnrooted.cpp:131-182).  Iterative: a ladder-shaped tree of 200,000 leaves nests as deep as it is long. */
+struct hu_newick {
+	std::vector<int32_t> parent, childOff, childIdx;
+	std::vector<double> blen;
+	std::vector<std::string> names;
+};
+namespace {
+struct NwNode { std::string name; double len = 0; std::vector<int32_t> kids; };
+inline bool nw_space(unsigned char c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
+inline bool nw_unquoted(unsigned char c) { return c > 0x20 && c < 0x7f && !strchr("()[]':;,", c); }
+}
+extern "C" int hu_newick_parse(const char* text, int64_t len, hu_newick** out) try {
+	if(!text || len < 0 || !out) { hu_set_error("hu_newick_parse: bad argument"); return HU_ERR_ARG; }
+	*out = nullptr;
+	const std::string s(text, (size_t) len);           /* NUL-terminated for strtod */
+	size_t pos = 0;
+	auto skip = [&] { while(pos < s.size() && nw_space((unsigned char) s[pos])) ++pos; };
+	auto fail = [&](const char* what) { hu_set_error("Newick: %s at byte %zu", what, pos); return HU_ERR_IO; };
+	skip();
+	if(pos == s.size()) return fail("empty tree");
+	std::vector<NwNode> nd(1);
+	std::vector<int32_t> open;                         /* nodes whose descendant list is being read */
+	int32_t cur = 0;
+	bool starting = true;                               /* cur may still open a descendant list */
+	for(;;) {
+		skip();
+		if(starting && pos < s.size() && s[pos] == '(') {
+			++pos; open.push_back(cur);
+			nd[cur].kids.push_back((int32_t) nd.size()); cur = (int32_t) nd.size(); nd.emplace_back();
+			continue;
+		}
+		/* label, then branch length, both optional */
+		if(pos < s.size() && nw_unquoted((unsigned char) s[pos])) {
+			const size_t a = pos;
+			while(pos < s.size() && nw_unquoted((unsigned char) s[pos])) ++pos;
+			nd[cur].name = s.substr(a, pos - a);
+		}
+		else if(pos < s.size() && s[pos] == '\'') {
+			const size_t a = ++pos;
+			while(pos < s.size() && s[pos] != '\'' && (unsigned char) s[pos] >= 0x20 && (unsigned char) s[pos] < 0x7f) ++pos;
+			if(pos == a) return fail("empty quoted label");
+			if(pos == s.size() || s[pos] != '\'') return fail("unterminated quoted label");
+			nd[cur].name = s.substr(a, pos - a);
+			++pos;
+		}
+		skip();
+		if(pos < s.size() && s[pos] == ':') {
+			++pos; skip();
+			size_t q = pos;
+			if(q < s.size() && (s[q] == '+' || s[q] == '-')) ++q;
+			const bool numeric = q < s.size() && (isdigit((unsigned char) s[q]) || (s[q] == '.' && q + 1 < s.size() && isdigit((unsigned char) s[q + 1])));
+			const bool word = q < s.size() && (!strncasecmp(s.c_str() + q, "inf", 3) || !strncasecmp(s.c_str() + q, "nan", 3));
+			if(!numeric && !word) return fail("branch length expected");
+			if(numeric && s[q] == '0' && q + 1 < s.size() && (s[q + 1] == 'x' || s[q + 1] == 'X')) { nd[cur].len = 0; pos = q + 1; }   /* no hexadecimal: the 0 is the number */
+			else if(word) {
+				const bool isInf = !strncasecmp(s.c_str() + q, "inf", 3), neg = s[pos] == '-';
+				pos = q + (isInf && !strncasecmp(s.c_str() + q, "infinity", 8) ? 8 : 3);
+				const double v = isInf ? std::numeric_limits<double>::infinity() : std::numeric_limits<double>::quiet_NaN();
+				nd[cur].len = neg ? -v : v;
+			}
+			else { char* e = nullptr; nd[cur].len = strtod(s.c_str() + pos, &e); pos = (size_t)(e - s.c_str()); }
+			skip();
+		}
+		/* the subtree of cur is complete */
+		if(open.empty()) break;
+		if(pos < s.size() && s[pos] == ',') {
+			++pos;
+			nd[open.back()].kids.push_back((int32_t) nd.size()); cur = (int32_t) nd.size(); nd.emplace_back();
+			starting = true;
+			continue;
+		}
+		if(pos < s.size() && s[pos] == ')') { ++pos; cur = open.back(); open.pop_back(); starting = false; continue; }
+		return fail(pos == s.size() || s[pos] == ';' ? "unbalanced brackets: ')' expected" : "',' or ')' expected");
+	}
+	if(pos == s.size() || s[pos] != ';') return fail(pos < s.size() && s[pos] == ')' ? "unbalanced brackets: ')' without '('" : "';' expected");
+	++pos; skip();
+	if(pos != s.size()) return fail("text after the closing ';'");
+	if(nd.size() >= (size_t) 1 << 24) { hu_set_error("Newick: %zu nodes, at most %d are supported", nd.size(), (1 << 24) - 1); return HU_ERR_ARG; }
+	/* ids: depth-first with an explicit stack, children pushed in file order */
+	std::unique_ptr<hu_newick> t(new hu_newick);
+	const size_t n = nd.size();
+	std::vector<int32_t> idOf(n, -1), st{0}, parOf(n, -1);
+	for(size_t i = 0; i < n; ++i) for(int32_t k : nd[i].kids) parOf[k] = (int32_t) i;
+	t->parent.resize(n); t->blen.resize(n); t->names.resize(n);
+	int32_t id = 0;
+	while(!st.empty()) {
+		const int32_t v = st.back(); st.pop_back();
+		idOf[v] = id;
+		t->parent[id] = parOf[v] < 0 ? -1 : idOf[parOf[v]];
+		t->blen[id] = parOf[v] < 0 ? 0.0 : nd[v].len;
+		t->names[id].swap(nd[v].name);
+		++id;
+		for(int32_t k : nd[v].kids) st.push_back(k);
+	}
+	t->childOff.assign(n + 1, 0);
+	for(size_t v = 0; v < n; ++v) t->childOff[idOf[v] + 1] = (int32_t) nd[v].kids.size();
+	for(size_t i = 0; i < n; ++i) t->childOff[i + 1] += t->childOff[i];
+	t->childIdx.resize(n - 1);
+	for(size_t v = 0; v < n; ++v) { int32_t o = t->childOff[idOf[v]]; for(int32_t k : nd[v].kids) t->childIdx[o++] = idOf[k]; }
+	*out = t.release();
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_newick_parse"); }
+extern "C" void hu_newick_free(hu_newick* t) { delete t; }
+extern "C" int hu_newick_size(const hu_newick* t, int32_t* n_nodes) { if(!t || !n_nodes) return HU_ERR_ARG; *n_nodes = (int32_t) t->parent.size(); return HU_OK; }
+extern "C" int hu_newick_get(const hu_newick* t, int32_t* parent, double* blen, int32_t* child_off, int32_t* child_idx) {
+	if(!t) return HU_ERR_ARG;
+	if(parent) memcpy(parent, t->parent.data(), t->parent.size() * 4);
+	if(blen) memcpy(blen, t->blen.data(), t->blen.size() * 8);
+	if(child_off) memcpy(child_off, t->childOff.data(), t->childOff.size() * 4);
+	if(child_idx && !t->childIdx.empty()) memcpy(child_idx, t->childIdx.data(), t->childIdx.size() * 4);
+	return HU_OK;
+}
+extern "C" const char* hu_newick_name(const hu_newick* t, int32_t node) { return t && node >= 0 && node < (int32_t) t->names.size() ? t->names[node].c_str() : ""; }
+
+/* ---- loadAnnotation, formatName, annotate (src/PhyloTreeUnrooted.cpp:223-240, :956-1006; src/PhyloTreeUnrooted.h:1531-1578) ---- */
+struct hu_tree_anno { std::vector<std::string> names, annos; std::vector<double> dist; };
+namespace {
+/* boost::split(fields, s, is_any_of(";: "), token_compress_on): a run of separators ends a field; a separator at either end leaves an empty field there */
+std::vector<std::string> taxon_fields(const std::string& s) {
+	std::vector<std::string> f(1);
+	bool inSep = false;
+	for(char c : s) {
+		if(c == ';' || c == ':' || c == ' ') { if(!inSep) f.emplace_back(); inSep = true; }
+		else { f.back() += c; inSep = false; }
+	}
+	return f;
+}
+bool taxon_canonical(const std::string& x) { return x.size() > 3 && x[1] == '_' && x[2] == '_' && strchr("dkpcofgs", x[0]) != nullptr; }
+bool taxon_full(const std::string& s) {
+	static const char level[] = "kpcofgs";
+	const std::vector<std::string> f = taxon_fields(s);
+	for(size_t i = 0; i < f.size(); ++i) if(i < 7 && !(f[i].size() >= 3 && f[i][0] == level[i] && f[i][1] == '_' && f[i][2] == '_')) return false;   /* past Species the prefix is "" */
+	return true;
+}
+bool taxon_partial(const std::string& s) { for(const std::string& x : taxon_fields(s)) if(!taxon_canonical(x)) return false; return true; }
+std::string taxon_format(const std::string& s) {
+	if(s.empty()) return s;
+	std::string o;
+	for(const std::string& x : taxon_fields(s)) if(taxon_canonical(x)) { if(!o.empty()) o += ';'; o += x; }
+	return o;
+}
+}
+extern "C" int hu_tree_annotate(int32_t n, const int32_t* parent, const double* blen, const char* const* names, const char* anno_text,
+		int64_t anno_len, const char* root_name, hu_tree_anno** out) try {
+	if(n < 1 || !parent || !blen || !names || !out || (anno_text && anno_len < 0)) { hu_set_error("hu_tree_annotate: bad argument"); return HU_ERR_ARG; }
+	*out = nullptr;
+	for(int32_t i = 0; i < n; ++i) if(parent[i] >= n || parent[i] == i) { hu_set_error("hu_tree_annotate: parent of node %d out of range", i); return HU_ERR_ARG; }
+	std::unique_ptr<hu_tree_anno> a(new hu_tree_anno);
+	a->names.resize(n); a->annos.resize(n); a->dist.assign(n, 0.0);
+	for(int32_t i = 0; i < n; ++i) a->names[i] = names[i] ? names[i] : "";
+	if(anno_text) {
+		std::map<std::string, std::string> name2anno;
+		std::string anno;                                   /* kept from line to line: see the header */
+		const char* p = anno_text; const char* end = anno_text + anno_len;
+		while(p < end) {
+			const char* e = (const char*) memchr(p, '\n', (size_t)(end - p));
+			const char* le = e ? e : end;
+			const char* tab = (const char*) memchr(p, '\t', (size_t)(le - p));
+			const std::string name(p, tab ? tab : le);
+			if(tab) { const char* t2 = (const char*) memchr(tab + 1, '\t', (size_t)(le - tab - 1)); anno.assign(tab + 1, t2 ? t2 : le); }
+			name2anno[name] = anno;
+			p = le + 1;
+		}
+		for(int32_t i = 0; i < n; ++i) { auto it = name2anno.find(a->names[i]); if(it != name2anno.end()) a->names[i] = it->second; }
+	}
+	for(int32_t i = 0; i < n; ++i) a->names[i] = taxon_format(a->names[i]);
+	std::vector<uint8_t> full(n), partial(n);
+	for(int32_t i = 0; i < n; ++i) { full[i] = taxon_full(a->names[i]); partial[i] = taxon_partial(a->names[i]); }
+	const std::string rootName = root_name ? root_name : "cellular_organisms";
+	std::vector<int32_t> path;
+	for(int32_t i = 0; i < n; ++i) {
+		path.clear();
+		int32_t p = i, steps = 0;
+		while(!full[p] && parent[p] >= 0) {
+			if(++steps > n) { hu_set_error("hu_tree_annotate: the parents of node %d form a cycle", i); return HU_ERR_ARG; }
+			a->dist[i] += blen[p];
+			if(partial[p]) path.push_back(p);
+			p = parent[p];
+		}
+		if(full[p]) path.push_back(p);
+		std::string s;
+		for(size_t k = path.size(); k-- > 0;) { if(!s.empty()) s += ';'; s += a->names[path[k]]; }
+		a->annos[i] = path.empty() ? rootName : s;
+	}
+	*out = a.release();
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_tree_annotate"); }
+extern "C" void hu_tree_anno_free(hu_tree_anno* a) { delete a; }
+extern "C" const char* hu_tree_anno_name(const hu_tree_anno* a, int32_t node) { return a && node >= 0 && node < (int32_t) a->names.size() ? a->names[node].c_str() : ""; }
+extern "C" const char* hu_tree_anno_anno(const hu_tree_anno* a, int32_t node) { return a && node >= 0 && node < (int32_t) a->annos.size() ? a->annos[node].c_str() : ""; }
+extern "C" int hu_tree_anno_dist(const hu_tree_anno* a, double* anno_dist) { if(!a || !anno_dist) return HU_ERR_ARG; memcpy(anno_dist, a->dist.data(), a->dist.size() * 8); return HU_OK; }

@@ -117,3 +117,35 @@ __global__ __launch_bounds__(256) void k_mut_count(const int8_t* __restrict__ st
 	}
 	if(c) atomicAdd(&cnt[j], c);
 }
+
+/* PTUnrooted::treeLoglik(pi, X, j) = dot_product_scaled(pi, X.col(j)) (src/PhyloTreeUnrooted.h:1341-1343, :1505-1510) of the root
+ * message: log(pi . exp(v + s)) - s, s = MIN_LOGLIK_EXP - max(v) when max(v) is finite and below MIN_LOGLIK_EXP, else 0.  One lane
+ * per column, two 16-byte loads; the dot product in Eigen's association for a Vector4d, (p0 e0 + p2 e2) + (p1 e1 + p3 e3).
+ * msg [csLen][4]: up[root] as hu_tree_evaluate leaves it.  The host adds the columns up in serial order. */
+__global__ __launch_bounds__(256) void k_tree_loglik(const double* __restrict__ msg, int64_t csLen, double p0, double p1, double p2, double p3,
+		double* __restrict__ out) {
+	const int64_t j = (int64_t) blockIdx.x * 256 + threadIdx.x;
+	if(j >= csLen) return;
+	const double2* p = reinterpret_cast<const double2*>(msg + j * 4);
+	const double2 a = p[0], b = p[1];
+	const double mx = fmax(fmax(a.x, a.y), fmax(b.x, b.y));
+	const double sc = (mx != -INFINITY && mx < HU_MIN_LOGLIK_EXP) ? HU_MIN_LOGLIK_EXP - mx : 0.0;
+	const double e0 = exp(a.x + sc), e1 = exp(a.y + sc), e2 = exp(b.x + sc), e3 = exp(b.y + sc);
+	out[j] = log((p0 * e0 + p2 * e2) + (p1 * e1 + p3 * e3)) - sc;
+}
+
+/* The payloads of a run of consecutive directed edges of a .ptu, packed in file order (hu_ptu_write_stream): item e of the run is
+ * the message down[c] (code = c << 1 | 1: the edge parent -> c) or up[c] (code = c << 1: the edge c -> parent, and the root row that
+ * ends the file).  A message is `pieces` = 2 csLen pieces of 16 bytes; lane = one piece, one 16-byte load and one 16-byte store.
+ * grid (pieces / 256, min(items, 65535)): a workgroup row walks the items with the grid's stride.
+ * dst [items][pieces].  The host has checked every code against the node count. */
+__global__ __launch_bounds__(256) void k_ptu_gather(const uint4* __restrict__ up, const uint4* __restrict__ down, const uint32_t* __restrict__ code,
+		int64_t items, int64_t pieces, uint4* __restrict__ dst) {
+	const int64_t q = (int64_t) blockIdx.x * 256 + threadIdx.x;
+	if(q >= pieces) return;
+	for(int64_t e = blockIdx.y; e < items; e += gridDim.y) {
+		const uint32_t c = code[e];
+		const uint4* src = (c & 1u) ? down : up;
+		dst[e * pieces + q] = src[(int64_t)(c >> 1) * pieces + q];
+	}
+}

@@ -292,6 +292,110 @@ def write_ptu(path, parent, blen, seq, up, down, height, model: ModelDesc, names
                                      C.c_double(dg_alpha), _p(br, C.c_double) if br is not None else None))
 
 
+def write_ptu_stream(path, parent, blen, seq, up, down, height, model: ModelDesc, names=None, annos=None, anno_dist=None, model_text=None,
+                     dg_alpha=0.0, dg_breaks=None, msgs_on_device=False, child_off=None, child_idx=None, msa_row_of_leaf=None, staging_bytes=0):
+    """hu_ptu_write_stream: write_ptu with a chosen child order (CSR child_off [n + 1], child_idx [n - 1]), the MSA index as (row, node)
+    pairs (msa_row_of_leaf [n], -1 for inner nodes), and device messages packed by k_ptu_gather through two staging buffers of
+    staging_bytes each (0: 256 MB)."""
+    keep = dict(parent=np.ascontiguousarray(parent, np.int32), blen=np.ascontiguousarray(blen, np.float64), seq=np.ascontiguousarray(seq, np.int8),
+                height=np.ascontiguousarray(height, np.float64))
+    td = TreeDesc()
+    td.n_nodes, td.cs_len = keep["seq"].shape
+    td.parent = _p(keep["parent"], C.c_int32); td.blen = _p(keep["blen"], C.c_double); td.seq = _p(keep["seq"], C.c_int8); td.height = _p(keep["height"], C.c_double)
+    if msgs_on_device:
+        td.up = C.c_void_p(int(up)); td.down = C.c_void_p(int(down)); td.msgs_on_device = 1
+    else:
+        keep["up"] = np.ascontiguousarray(up, np.float64); keep["down"] = np.ascontiguousarray(down, np.float64)
+        td.up = keep["up"].ctypes.data_as(C.c_void_p); td.down = keep["down"].ctypes.data_as(C.c_void_p)
+    if anno_dist is not None:
+        keep["ad"] = np.ascontiguousarray(anno_dist, np.float64); td.anno_dist = _p(keep["ad"], C.c_double)
+    arr = lambda xs: (C.c_char_p * len(xs))(*[x.encode() for x in xs]) if xs is not None else None
+    i32 = lambda a: np.ascontiguousarray(a, np.int32) if a is not None else None
+    br = np.ascontiguousarray(dg_breaks, np.float64) if dg_breaks is not None else None
+    co, ci, ro = i32(child_off), i32(child_idx), i32(msa_row_of_leaf)
+    _chk(load_library().hu_ptu_write_stream(path.encode(), C.byref(td), arr(names), arr(annos), C.byref(model), model_text.encode() if model_text else None,
+                                            C.c_double(dg_alpha), _p(br, C.c_double) if br is not None else None,
+                                            _p(co, C.c_int32) if co is not None else None, _p(ci, C.c_int32) if ci is not None else None,
+                                            _p(ro, C.c_int32) if ro is not None else None, C.c_int64(int(staging_bytes))))
+
+
+def tree_info(ptu_path: str) -> dict:
+    """hu_tree_info_*: the tree of a .ptu without its messages (host only): parent, blen, anno_dist, is_leaf, names, annos, and every
+    node's children in the order their parent -> child edges stand in the file"""
+    lib = load_library()
+    h = C.c_void_p()
+    _chk(lib.hu_tree_info_load(ptu_path.encode(), C.byref(h)))
+    try:
+        n = C.c_int32(0); L = C.c_int32(0); root = C.c_int32(0); md = ModelDesc()
+        _chk(lib.hu_tree_info_get(h, C.byref(n), C.byref(L), C.byref(root), C.byref(md)))
+        n = n.value
+        out = dict(n_nodes=n, cs_len=L.value, root=root.value, model=md, parent=np.zeros(n, np.int32), blen=np.zeros(n), anno_dist=np.zeros(n),
+                   is_leaf=np.zeros(n, bool), names=[], annos=[], children=[])
+        for i in range(n):
+            p = C.c_int32(0); b = C.c_double(0); d = C.c_double(0); lf = C.c_int32(0); nm = C.c_char_p(); an = C.c_char_p()
+            _chk(lib.hu_tree_info_node(h, C.c_int32(i), C.byref(p), C.byref(b), C.byref(d), C.byref(lf), C.byref(nm), C.byref(an)))
+            out["parent"][i] = p.value; out["blen"][i] = b.value; out["anno_dist"][i] = d.value; out["is_leaf"][i] = bool(lf.value)
+            out["names"].append(nm.value.decode()); out["annos"].append(an.value.decode())
+            ch = C.POINTER(C.c_int32)()
+            k = int(lib.hu_tree_info_children(h, C.c_int32(i), C.byref(ch)))
+            out["children"].append([int(ch[j]) for j in range(k)])
+        return out
+    finally:
+        lib.hu_tree_info_free(h)
+
+
+def newick_parse(text) -> dict:
+    """hu_newick_parse: parent, blen, names with the reference's node ids, and every node's children in file order (children: list of
+    arrays; child_off / child_idx: the same as a CSR).  Raises EngineError with the byte offset on malformed text."""
+    lib = load_library()
+    lib.hu_newick_name.restype = C.c_char_p
+    b = text.encode() if isinstance(text, str) else bytes(text)
+    h = C.c_void_p()
+    _chk(lib.hu_newick_parse(b, C.c_int64(len(b)), C.byref(h)))
+    try:
+        n = C.c_int32(0)
+        _chk(lib.hu_newick_size(h, C.byref(n)))
+        n = n.value
+        out = dict(parent=np.zeros(n, np.int32), blen=np.zeros(n), child_off=np.zeros(n + 1, np.int32), child_idx=np.zeros(max(n - 1, 0), np.int32))
+        _chk(lib.hu_newick_get(h, _p(out["parent"], C.c_int32), _p(out["blen"], C.c_double), _p(out["child_off"], C.c_int32),
+                               _p(out["child_idx"], C.c_int32) if n > 1 else None))
+        out["names"] = [lib.hu_newick_name(h, C.c_int32(i)).decode() for i in range(n)]
+        out["children"] = [out["child_idx"][out["child_off"][i]:out["child_off"][i + 1]] for i in range(n)]
+        return out
+    finally:
+        lib.hu_newick_free(h)
+
+
+def tree_annotate(parent, blen, names, anno_text=None, root_name=None):
+    """hu_tree_annotate: loadAnnotation (anno_text: the "name<TAB>annotation" lines, or None), formatName and annotate of the build.
+    Returns (names, annotations, anno_dist)."""
+    lib = load_library()
+    lib.hu_tree_anno_name.restype = C.c_char_p; lib.hu_tree_anno_anno.restype = C.c_char_p
+    parent = np.ascontiguousarray(parent, np.int32); blen = np.ascontiguousarray(blen, np.float64)
+    n = len(parent)
+    nm = (C.c_char_p * n)(*[x.encode() for x in names])
+    at = (anno_text.encode() if isinstance(anno_text, str) else bytes(anno_text)) if anno_text is not None else None
+    h = C.c_void_p()
+    _chk(lib.hu_tree_annotate(C.c_int32(n), _p(parent, C.c_int32), _p(blen, C.c_double), nm, at, C.c_int64(len(at) if at is not None else 0),
+                              root_name.encode() if root_name is not None else None, C.byref(h)))
+    try:
+        d = np.zeros(n)
+        _chk(lib.hu_tree_anno_dist(h, _p(d, C.c_double)))
+        return ([lib.hu_tree_anno_name(h, C.c_int32(i)).decode() for i in range(n)],
+                [lib.hu_tree_anno_anno(h, C.c_int32(i)).decode() for i in range(n)], d)
+    finally:
+        lib.hu_tree_anno_free(h)
+
+
+def tree_loglik(n_nodes: int, cs_len: int, root: int, model: ModelDesc, up_ptr: int, device=0):
+    """hu_tree_loglik: (per-column log-likelihoods [cs_len], their serial sum) of the root message at up_ptr[root] (DEVICE buffer
+    [n_nodes][cs_len][4] as tree_evaluate leaves it)"""
+    per = np.zeros(cs_len); s = C.c_double(0)
+    _chk(load_library().hu_tree_loglik(C.c_int(device), C.c_int32(n_nodes), C.c_int32(cs_len), C.c_int32(root), C.byref(model),
+                                       C.c_void_p(int(up_ptr)), _p(per, C.c_double), C.byref(s)))
+    return per, float(s.value)
+
+
 class SeedIndex:
     """Host k-mer index standing in for the CSFM lookup of alignSeq (hu_seed_index_*)."""
 

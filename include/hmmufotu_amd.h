@@ -234,6 +234,74 @@ int hu_dg_model(int32_t K, double alpha, double* breaks, double* rates);
  * n < 2; <= 0 (or NaN) means near-invariant rates, which hmmufotu-build answers with the fixed-rate model (src/hmmufotu-build.cpp:437-446) */
 double hu_dg_estimate_shape(int64_t n, const double* X);
 
+/* ---- the rest of hmmufotu-build --no-hmm (src/hmmufotu-build.cpp:346-503 without the csfm, hmm and msa parts) ----
+ * Newick reader, host only: the grammar of src/NewickTree.h:186-215 as NewickTree::read applies it (src/NewickTree.cpp:37-59:
+ * phrase_parse with a white-space skipper, and the whole text must be consumed).  subtree = [ '(' subtree (',' subtree)* ')' ] [label]
+ * [':' double]; tree = subtree ';'.  An unquoted label is a run of printable characters without blanks and ( ) [ ] ' : ; ,  — a quoted
+ * one is '...' with no quote inside (blanks inside are kept), and its name is the text between the quotes.  Node ids are those of
+ * PTUnrooted(const NewickTree&) (src/PhyloTreeUnrooted.cpp:131-154): depth-first from the root (id 0) with an explicit stack, children
+ * pushed in file order, so the LAST child of a node gets the smallest id among its siblings.
+ * Refused with HU_ERR_IO and a message that names the byte offset: unbalanced brackets, a missing ';', text after the closing ';',
+ * a ':' without a number, an empty tree (no token before the end).
+ * hu_newick_get: parent [n] (-1 for the root), blen [n] (a missing length is 0, and so is the root's: the reference never reads it),
+ * child_off [n + 1] / child_idx [n - 1]: every node's children IN FILE ORDER, the order of addEdge (:170-179) and so of the node's
+ * neighbour list behind its parent in a reference-built .ptu.  Any pointer may be NULL. */
+typedef struct hu_newick hu_newick;
+int hu_newick_parse(const char* text, int64_t len, hu_newick** out);
+void hu_newick_free(hu_newick* t);
+int hu_newick_size(const hu_newick* t, int32_t* n_nodes);
+int hu_newick_get(const hu_newick* t, int32_t* parent, double* blen, int32_t* child_off, int32_t* child_idx);
+const char* hu_newick_name(const hu_newick* t, int32_t node);   /* "" for an unnamed node; lives as long as t */
+
+/* The annotation steps of the build, host only, on a tree whose branch lengths are final (after fixBranchLength):
+ *   loadAnnotation (src/PhyloTreeUnrooted.cpp:223-240) when anno_text is not NULL: lines "name<TAB>annotation"; a node whose NAME is
+ *     a key takes the annotation as its new name (a later line for the same key wins; a line without a TAB keeps the annotation of the
+ *     line before it, as the reference's getline on an exhausted stream does);
+ *   formatName / formatTaxonName (:974-986): the name split at any of ";: " (TAXON_SEP, adjacent separators as one), the fields
+ *     isCanonicalName accepts (longer than 3 bytes and starting with one of d__ k__ p__ c__ o__ f__ g__ s__, src/PhyloTreeUnrooted.h:1564-1574)
+ *     joined with ";";
+ *   annotate (:988-1006): from the node towards the root until a node whose name isFullCanonicalName (field i starts with the prefix of
+ *     level i: k p c o f g s, :956-963) or the root; the branch lengths walked are added to anno_dist in that order, partially canonical
+ *     names (:965-972) on the way are collected, and the annotation is their join with ";" from the root's side, or root_name
+ *     (NULL: "cellular_organisms") when there is none.
+ * Results through the handle: names and annotations per node, anno_dist [n]. */
+typedef struct hu_tree_anno hu_tree_anno;
+int hu_tree_annotate(int32_t n_nodes, const int32_t* parent, const double* blen, const char* const* names, const char* anno_text,
+		int64_t anno_len, const char* root_name, hu_tree_anno** out);
+void hu_tree_anno_free(hu_tree_anno* a);
+const char* hu_tree_anno_name(const hu_tree_anno* a, int32_t node);
+const char* hu_tree_anno_anno(const hu_tree_anno* a, int32_t node);
+int hu_tree_anno_dist(const hu_tree_anno* a, double* anno_dist /* [n] */);
+
+/* PTUnrooted::treeLoglik() (src/PhyloTreeUnrooted.cpp:707-712, src/PhyloTreeUnrooted.h:1341-1343): per column
+ * dot_product_scaled(pi, up[root][:, j]) (:1505-1510) = log(pi . exp(v + s)) - s with s = -510 - max(v) when max(v) is finite and below
+ * -510 (MIN_LOGLIK_EXP), else 0 — on the device, one lane per column, from the root message hu_tree_evaluate leaves at up_dev[root]
+ * (up_dev: DEVICE [n_nodes][cs_len][4], whole columns).  per_col: host [cs_len] (may be NULL); *sum: their sum in serial j order on
+ * the host, so it depends on no reduction tree. */
+int hu_tree_loglik(int device, int32_t n_nodes, int32_t cs_len, int32_t root, const hu_model_desc* model, const double* up_dev,
+		double* per_col, double* sum);
+
+/* Device memory for a caller of hu_tree_evaluate that holds no HIP runtime of its own (hmmufotu-amd-build): free and total bytes of the
+ * device, and a buffer on it.  hu_device_malloc: HU_ERR_NOMEM when the device cannot back it. */
+int hu_device_mem_info(int device, int64_t* free_bytes, int64_t* total_bytes);
+int hu_device_malloc(int device, int64_t bytes, void** out);
+void hu_device_free(int device, void* p);
+
+/* hu_ptu_write for a real build.  The same arguments, and
+ *   child_off [n + 1] / child_idx [n - 1]: every node's children in the order to write them behind its parent (hu_newick_get gives the
+ *     reference's: file order); NULL: ascending id, as hu_ptu_write;
+ *   msa_row_of_leaf [n]: the MSA row of every leaf (other nodes: -1); the MSA index block then holds (row, node id) in ascending row as
+ *     PTUnrooted::saveMSAIndex writes its map (src/PhyloTreeUnrooted.cpp:569-578); NULL: the k-th leaf in node order, as hu_ptu_write;
+ *   staging_bytes: size of each of the two staging buffers (0: 256 MB); rounded down to whole messages, at least one.
+ * With msgs_on_device the payloads of a run of consecutive directed edges (and the root row, last) are packed by k_ptu_gather into a
+ * device staging buffer, copied with ONE hipMemcpyAsync into page-locked memory and written from there, header and payload
+ * alternately, while the next run is gathered and copied on the other stream (hu_ptu_write: one blocking copy per edge).  up / down
+ * must then be 16-byte aligned.  Host-resident messages take the plain loop.  The stream is checked after every run: a short write
+ * ends the call with HU_ERR_IO.  With NULL child order and NULL rows the file is byte for byte hu_ptu_write's. */
+int hu_ptu_write_stream(const char* path, const hu_tree_desc* tree, const char* const* names, const char* const* annos, const hu_model_desc* model,
+		const char* model_text, double dg_alpha, const double* dg_breaks, const int32_t* child_off, const int32_t* child_idx,
+		const int32_t* msa_row_of_leaf, int64_t staging_bytes);
+
 /* ---- the tree of a .ptu without its messages (host only, no device): what the consumers of an assignment file need of the database —
  * hmmufotu-sum the nodes' taxon annotations (src/hmmufotu-sum.cpp:378-383), hmmufotu-jplace the topology, branch lengths and the order of
  * every node's children as PTUnrooted::load leaves it (src/hmmufotu-jplace.cpp:197, src/PhyloTreeUnrooted.cpp:1135-1157).  The 4 x csLen
