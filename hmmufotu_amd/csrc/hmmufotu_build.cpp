@@ -1,12 +1,14 @@
 // hmmufotu-amd-build: a <NAME>.ptu database from a reference MSA and its phylogenetic tree — the --no-hmm mode of hmmufotu-build
-// (src/hmmufotu-build.cpp:307-503 without the csfm, hmm and msa parts).  The host reads and joins the inputs; the wide loops run on
+// (src/hmmufotu-build.cpp:307-503 without the hmm and msa parts), and with --csfm its seed index file <NAME>.csfm (csfm.build(msa), :320-328, and
+// csfm.save, :479-485).  The host reads and joins the inputs; the wide loops run on
 // the device: the MSA column counts behind MSA::prune (hu_msa_stats), the tree evaluated at every root (hu_tree_evaluate), the
 // per-site mutation counts behind -V (hu_tree_count_mutations), the tree log-likelihood (hu_tree_loglik) and the gather of the
-// messages for the file (hu_ptu_write_stream).  Options and inputs are checked, and every input read and joined, before a device
+// messages for the file (hu_ptu_write_stream); with --csfm the suffix array of the concatenated MSA rows, its BWT and samples (hu_csfm_write).  Options and inputs are checked, and every input read and joined, before a device
 // is asked for.
 //   hmmufotu-amd-build <MSA-FILE> <TREE-FILE> --no-hmm -sm FILE [-n NAME] [--fmt fasta] [-a|--anno FILE] [-r|--root STR] [-V|--var]
-//                      [-k INT] [--device N] [-v]
-// Writes <NAME>.ptu only: no .msa and no .csfm (hmmufotu-amd rebuilds its seed index from the .ptu), and no .hmm — the profile comes
+//                      [-k INT] [--csfm] [--device N] [-v]
+// Writes <NAME>.ptu, and <NAME>.csfm when asked (without it hmmufotu-amd rebuilds its seed index from the .ptu on every start; the reference's
+// hmmufotu cannot start without it): no .msa, and no .hmm — the profile comes
 // from a third-party trainer (HMMER3, hmmufotu-train-hmm) and is put beside the .ptu as <NAME>.hmm.
 #include <cerrno>
 #include <chrono>
@@ -39,6 +41,7 @@ static void usage(const char* p) {
 		"            -r|--root  STR       : root name if the original tree root is not named [cellular_organisms]\n"
 		"            -V|--var FLAG        : enable among-site rate varation evaluation of the tree, using a Discrete Gamma Distribution based model\n"
 		"            -k INT               : number of Discrete Gamma Distribution categories to evaluate the tree, ignored if -V not set [" << DEFAULT_DG_CATEGORY << "]\n"
+		"            --csfm FLAG          : also write the seed index file <NAME>.csfm, over all rows of the pruned MSA (the suffix array is built on the device)\n"
 		"            --device  INT        : device index [0]\n"
 		"            -f|--symfrac, -dm, -p|--process : accepted and ignored (they belong to the profile training)\n"
 		"            -v  FLAG             : enable verbose information; -vv adds the wall time of every phase\n"
@@ -56,7 +59,7 @@ static bool read_file(const std::string& fn, std::string& out) {
 
 int main(int argc, char** argv) {
 	std::vector<std::string> pos; std::string dbName, fmt, annoFn, smFn, smType, rootName = "cellular_organisms";
-	bool noHmm = false, isVar = false, haveS = false;
+	bool noHmm = false, isVar = false, haveS = false, withCsfm = false;
 	int K = DEFAULT_DG_CATEGORY, device = 0, verbose = 0;
 	std::vector<std::string> ignored;
 	if(argc == 1) { usage(argv[0]); return EXIT_SUCCESS; }
@@ -69,7 +72,7 @@ int main(int argc, char** argv) {
 		else if(a == "-a" || a == "--anno") annoFn = val(); else if(a == "-r" || a == "--root") rootName = val();
 		else if(a == "-s" || a == "--sub-model") { smType = val(); haveS = true; }
 		else if(a == "-sm") smFn = val();
-		else if(a == "--no-hmm") noHmm = true; else if(a == "-V" || a == "--var") isVar = true;
+		else if(a == "--no-hmm") noHmm = true; else if(a == "--csfm") withCsfm = true; else if(a == "-V" || a == "--var") isVar = true;
 		else if(a == "-k") K = atoi(val()); else if(a == "--device") device = atoi(val());
 		else if(a == "-f" || a == "--symfrac" || a == "-dm" || a == "-p" || a == "--process") { ignored.push_back(a); val(); }
 		else if(a.size() > 1 && a[0] == '-' && a.find_first_not_of('v', 1) == std::string::npos) verbose += (int) a.size() - 1;
@@ -113,7 +116,7 @@ int main(int argc, char** argv) {
 	if(!read_file(treeFn, treeText)) { std::cerr << "Unable to open '" << treeFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
 	if(!annoFn.empty() && !read_file(annoFn, annoText)) { std::cerr << "Unable to open '" << annoFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
 	if(dbName.empty()) dbName = seqFn.substr(seqFn.find_last_of('/') + 1);      /* StringUtils::basename(seqFn) */
-	const std::string ptuFn = dbName + ".ptu";
+	const std::string ptuFn = dbName + ".ptu", csfmFn = dbName + ".csfm";
 
 	/* the MSA: rows as read (case kept), names = the ids */
 	std::vector<std::string> rowName; std::vector<char> msa; size_t L0 = 0;
@@ -198,11 +201,15 @@ int main(int argc, char** argv) {
 	struct stat stBefore;
 	const bool existed = stat(ptuFn.c_str(), &stBefore) == 0;
 	{ std::ofstream probe(ptuFn, std::ios::binary | std::ios::app); if(!probe.is_open()) { std::cerr << "Unable to write to '" << ptuFn << "': " << strerror(errno) << std::endl; hu_tree_anno_free(an); return EXIT_FAILURE; } }
+	struct stat stCsfm;
+	const bool csfmExisted = withCsfm && stat(csfmFn.c_str(), &stCsfm) == 0;
+	if(withCsfm) { std::ofstream probe(csfmFn, std::ios::binary | std::ios::app); if(!probe.is_open()) { std::cerr << "Unable to write to '" << csfmFn << "': " << strerror(errno) << std::endl; hu_tree_anno_free(an); if(!existed) unlink(ptuFn.c_str()); return EXIT_FAILURE; } }
 	void *dUp = nullptr, *dDown = nullptr;
 	auto fail = [&](const std::string& msg) {
 		std::cerr << msg << std::endl;
 		hu_device_free(device, dUp); hu_device_free(device, dDown); hu_tree_anno_free(an);
 		if(!existed) unlink(ptuFn.c_str());       /* only the probe's empty file */
+		if(withCsfm && !csfmExisted) unlink(csfmFn.c_str());
 		return EXIT_FAILURE;
 	};
 	if(hu_device_count() <= device) return fail("Error: device " + std::to_string(device) + " asked for, " + std::to_string(hu_device_count()) + " gfx950 device(s) visible");
@@ -228,6 +235,24 @@ int main(int argc, char** argv) {
 		for(int32_t i = 0; i < n; ++i) if(rowOf[i] >= 0) {
 			const char* src = msa.data() + (size_t) rowOf[i] * L0; int8_t* dst = seq.data() + (size_t) i * L;
 			for(int32_t j = 0; j < L; ++j) dst[j] = enc[(unsigned char) src[keep[j]]];
+		}
+		if(withCsfm) { /* csfm.build(msa) over ALL rows of the pruned MSA in file order, csSeq from the weighted counts (MSA::calculateCS, src/MSA.cpp:211-226),
+		                * csIdentity from the raw ones (identityAt, :59-61) */
+			std::vector<char> rows(nSeq * (size_t) L);
+			for(size_t i = 0; i < nSeq; ++i) { const char* src = msa.data() + i * L0; char* dst = rows.data() + i * (size_t) L; for(int32_t j = 0; j < L; ++j) dst[j] = src[keep[j]]; }
+			std::string cs((size_t) L, '-');
+			std::vector<double> ident((size_t) L);
+			for(int32_t j = 0; j < L; ++j) {
+				const size_t c = keep[j];
+				int best = 0, rawMax = res[c];
+				for(int b = 1; b < 4; ++b) { if(wres[b * L0 + c] > wres[best * L0 + c]) best = b; rawMax = std::max(rawMax, res[b * L0 + c]); }
+				if(wres[best * L0 + c] >= wgap[c]) cs[j] = "ACGT"[best];
+				ident[j] = rawMax / static_cast<double>(nSeq);
+			}
+			if(hu_csfm_write(csfmFn.c_str(), (int64_t) nSeq, L, rows.data(), cs.c_str(), ident.data(), device) != HU_OK) return fail(std::string("Unable to build CSFM index: ") + hu_last_error());
+			info("CSFM index built");
+			info("CSFM saved");                     /* the reference saves it with the other files at the end; here it is written while the device is still free */
+			lap("csfm");
 		}
 	}
 	std::vector<char>().swap(msa);
@@ -294,6 +319,7 @@ int main(int argc, char** argv) {
 		std::cerr << "Unable to save Phylogenetic Tree index: " << hu_last_error() << std::endl;
 		hu_device_free(device, dUp); hu_device_free(device, dDown); hu_tree_anno_free(an);
 		unlink(ptuFn.c_str());
+		if(withCsfm && !csfmExisted) unlink(csfmFn.c_str());
 		return EXIT_FAILURE;
 	}
 	info("Phylogenetic Tree index saved");

@@ -5,6 +5,7 @@
 #include <string>
 #include <functional>
 #include <istream>
+#include <ostream>
 #include <vector>
 #include <exception>
 #include <mutex>
@@ -188,5 +189,10 @@ template<class F> void hu_run_threads(unsigned nt, F work) {
 	hu_helpers_release(got);
 	if(first) std::rethrow_exception(first);
 }
+/* saveProgInfo (src/util/ProgEnv.cpp:24-29): the 20-byte head of a .ptu and of a .csfm — the program name and the version 1.5.1 */
+inline void hu_write_prog_info(std::ostream& f) { const int32_t ver[3] = {1, 5, 1}; f.write("HmmUFOtu", 8); f.write((const char*) ver, 12); }
+/* the device steps of hu_csfm_write (hu_engine.hip): the suffix array of text[0, n), then bwt [n], marks [(n + 63) / 64] (row i at bit i & 63 of word
+ * i / 64) and sampled [(n + 3) / 4], all host.  rounds: doubling rounds taken; sa_seconds: device time of the suffix array alone. */
+int hu_csfm_device_pass(int device, const uint8_t* text, int64_t n, uint8_t* bwt, uint64_t* marks, uint32_t* sampled, int32_t* rounds, double* sa_seconds);
 /* runs f when the scope is left, by return or by exception */
 template<class F> struct HuScope { F f; explicit HuScope(F f) : f(f) {} ~HuScope() { f(); } HuScope(const HuScope&) = delete; HuScope& operator=(const HuScope&) = delete; };

@@ -28,6 +28,7 @@
 #include "hu_kern_anneal.h"
 #include "hu_kern_build.h"
 #include "hu_kern_otucs.h"
+#include "hu_kern_csfm.h"
 
 #define HIPCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { \
 	hu_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return HU_ERR_DEVICE; } } while(0)
@@ -546,7 +547,7 @@ static int ptu_write_impl(const char* fn, const char* path, const hu_tree_desc* 
 	if(!f) { hu_set_error("cannot write PTU file '%s'", path); return HU_ERR_IO; }
 	auto put = [&](const void* p, size_t k) { f.write((const char*) p, (std::streamsize) k); };
 	auto str = [&](const char* s_, size_t k) { const uint64_t len = k; put(&len, 8); if(k) put(s_, k); };
-	put("HmmUFOtu", 8); { const int32_t ver[3] = {1, 5, 1}; put(ver, 12); }
+	hu_write_prog_info(f);
 	{ const uint64_t nn = (uint64_t) n; put(&nn, 8); const int32_t l = L; put(&l, 4); }
 	char tmp[32];
 	for(int i = 0; i < n; ++i) {
@@ -1005,6 +1006,110 @@ extern "C" void hu_device_free(int device, void* p) try {
 	if(!p) return;
 	if(hipSetDevice(device) == hipSuccess) (void) hipFree(p);
 } catch(...) { (void) hu_catch_all("hu_device_free"); }
+
+/* ------------------------------------------------------------------------------ the .csfm writer's device steps */
+namespace {
+struct HuSaDev {
+	uint8_t* text = nullptr; uint64_t* key[2] = {nullptr, nullptr}; uint32_t* pos[2] = {nullptr, nullptr};
+	uint32_t *rank = nullptr, *hist = nullptr, *tileSum = nullptr;
+	int cur = 0;                                               /* pos[cur] holds the suffix array when sa_build returns HU_OK */
+	void dropKeys() { (void) hipFree(key[0]); (void) hipFree(key[1]); key[0] = key[1] = nullptr; }
+	~HuSaDev() { dropKeys(); (void) hipFree(text); (void) hipFree(pos[0]); (void) hipFree(pos[1]); (void) hipFree(rank); (void) hipFree(hist); (void) hipFree(tileSum); }
+};
+inline uint32_t sa_bits(uint64_t v) { uint32_t b = 0; while(v) { ++b; v >>= 1; } return b; }
+}
+#define SCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { hu_set_error("%s: %s failed: %s", fn, #call, hipGetErrorString(e_)); return HU_ERR_DEVICE; } } while(0)
+/* the suffix array of text[0, n) on the device, left in d.pos[d.cur]; the arguments are checked before a device is asked for */
+static int sa_build(const char* fn, int device, const uint8_t* text, int64_t n64, int64_t extraBytes, HuSaDev& d, int32_t* rounds, double* seconds) {
+	if(!text || n64 < 1 || n64 >= (1ll << 31)) { hu_set_error("%s: the text must hold 1 .. 2^31 - 1 symbols, got %lld", fn, (long long) n64); return HU_ERR_ARG; }
+	const size_t n = (size_t) n64;
+	for(size_t i = 0; i < n; ++i) if(text[i] > 4) { hu_set_error("%s: symbol %d at text position %zu (0 = separator, 1..4 = bases)", fn, (int) text[i], i); return HU_ERR_ARG; }
+	if(hu_device_count() <= 0) { hu_set_error("no gfx950 device visible: the engine has no CPU path"); return HU_ERR_DEVICE; }
+	SCHK(hipSetDevice(device));
+	const uint32_t nTiles = (uint32_t)((n + HU_SA_TILE - 1) / HU_SA_TILE);
+	const size_t m = (size_t) nTiles * 256, nScanN = (n + 1023) / 1024, nScanM = (m + 1023) / 1024;
+	{
+		size_t freeB = 0, totB = 0;
+		SCHK(hipMemGetInfo(&freeB, &totB));
+		const size_t need = n + 2 * 8 * n + 2 * 4 * n + 4 * n + 4 * m + 4 * (std::max(nScanN, nScanM) + 1) + (size_t) std::max<int64_t>(extraBytes, 0) + 4096;
+		if(need > freeB) { hu_set_error("%s: a text of %zu symbols needs %.3f GB of device memory, %.3f GB are free", fn, n, need / 1e9, freeB / 1e9); return HU_ERR_NOMEM; }
+	}
+	SCHK(hipMalloc((void**) &d.text, n)); SCHK(hipMalloc((void**) &d.key[0], 8 * n)); SCHK(hipMalloc((void**) &d.key[1], 8 * n));
+	SCHK(hipMalloc((void**) &d.pos[0], 4 * n)); SCHK(hipMalloc((void**) &d.pos[1], 4 * n)); SCHK(hipMalloc((void**) &d.rank, 4 * n));
+	SCHK(hipMalloc((void**) &d.hist, 4 * m)); SCHK(hipMalloc((void**) &d.tileSum, 4 * (std::max(nScanN, nScanM) + 1)));
+	SCHK(hipMemcpy(d.text, text, n, hipMemcpyHostToDevice));
+	(void) hipGetLastError();
+	const auto t0 = std::chrono::steady_clock::now();
+	const unsigned gN = (unsigned)((n + 255) / 256), gT = (nTiles + 3) / 4;
+	auto pass = [&](int shift) {                                     /* one stable pass on the 8-bit digit at `shift` */
+		k_sa_hist<<<gT, 256>>>(d.key[d.cur], n, shift, nTiles, d.hist);
+		k_sa_scan_sums<<<(unsigned) nScanM, 1024>>>(m, d.hist, d.tileSum);
+		k_sa_scan_tiles<<<1, 1024>>>(nScanM, d.tileSum);
+		k_sa_scan_apply<<<(unsigned) nScanM, 1024>>>(m, d.hist, d.tileSum);
+		k_sa_scatter<<<gT, 256>>>(d.key[d.cur], d.pos[d.cur], n, shift, nTiles, d.hist, d.key[d.cur ^ 1], d.pos[d.cur ^ 1]);
+		d.cur ^= 1;
+	};
+	uint32_t groups = 0;
+	auto rank = [&]() -> int {                                       /* ranks of the sorted keys; groups = number of distinct keys */
+		k_sa_head_sums<<<(unsigned) nScanN, 1024>>>(d.key[d.cur], n, d.tileSum);
+		k_sa_scan_tiles<<<1, 1024>>>(nScanN, d.tileSum);
+		k_sa_rank<<<(unsigned) nScanN, 1024>>>(d.key[d.cur], d.pos[d.cur], n, d.tileSum, d.rank);
+		SCHK(hipGetLastError());
+		SCHK(hipMemcpy(&groups, d.tileSum + nScanN, 4, hipMemcpyDeviceToHost));
+		return HU_OK;
+	};
+	k_sa_key0<<<gN, 256>>>(d.text, n, d.key[d.cur], d.pos[d.cur]);
+	for(int shift = 0; shift < 3 * HU_SA_H0; shift += 8) pass(shift);
+	int rc = rank();
+	if(rc != HU_OK) return rc;
+	int32_t r = 0;
+	const int32_t maxRounds = (int32_t) sa_bits(n - 1) + 2;           /* ceil(log2 n) + 2 */
+	for(size_t h = HU_SA_H0; groups < n; h *= 2) {
+		if(++r > maxRounds || groups == 0) { hu_set_error("%s: internal: %u of %zu suffixes told apart after %d doubling rounds", fn, groups, n, (int) r - 1); return HU_ERR_STATE; }
+		k_sa_key<<<gN, 256>>>(d.rank, n, h, d.key[d.cur], d.pos[d.cur]);
+		/* the low word is at most `groups`, the high word below it: the digits above are zero in every key and are skipped */
+		for(int shift = 0; shift < (int) sa_bits(groups); shift += 8) pass(shift);
+		for(int shift = 0; shift < (int) sa_bits(groups - 1); shift += 8) pass(32 + shift);
+		if((rc = rank()) != HU_OK) return rc;
+	}
+	SCHK(hipDeviceSynchronize());
+	if(rounds) *rounds = r;
+	if(seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+	return HU_OK;
+}
+extern "C" int32_t hu_suffix_array_tile(void) { return HU_SA_TILE; }
+extern "C" int hu_suffix_array(int device, const uint8_t* text, int64_t n, int32_t* sa, int32_t* rounds, double* device_seconds) try {
+	const char* fn = "hu_suffix_array";
+	if(!sa) { hu_set_error("%s: bad argument", fn); return HU_ERR_ARG; }
+	HuSaDev d;
+	const int rc = sa_build(fn, device, text, n, 0, d, rounds, device_seconds);
+	if(rc != HU_OK) return rc;
+	SCHK(hipMemcpy(sa, d.pos[d.cur], 4 * (size_t) n, hipMemcpyDeviceToHost));
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_suffix_array"); }
+/* the suffix array, then the BWT, the sample marks and the sampled values read off it (hu_csfm_write, hu_csfm_write.cpp) */
+int hu_csfm_device_pass(int device, const uint8_t* text, int64_t n64, uint8_t* bwt, uint64_t* marks, uint32_t* sampled, int32_t* rounds, double* sa_seconds) {
+	const char* fn = "hu_csfm_write";
+	HuSaDev d;
+	const int rc = sa_build(fn, device, text, n64, 0, d, rounds, sa_seconds);      /* the outputs below take the place of the key buffers */
+	if(rc != HU_OK) return rc;
+	const size_t n = (size_t) n64, nScan = (n + 1023) / 1024, nWords = (n + 63) / 64, nSamp = (n + 3) / 4;
+	d.dropKeys();
+	uint8_t* dBwt = nullptr; unsigned long long* dMarks = nullptr; uint32_t* dSamp = nullptr;
+	HuScope guard([&] { (void) hipFree(dBwt); (void) hipFree(dMarks); (void) hipFree(dSamp); });
+	SCHK(hipMalloc((void**) &dBwt, n)); SCHK(hipMalloc((void**) &dMarks, 8 * nWords)); SCHK(hipMalloc((void**) &dSamp, 4 * nSamp));
+	k_csfm_bwt<<<(unsigned) nScan, 1024>>>(d.text, d.pos[d.cur], n, dBwt, dMarks, d.tileSum);
+	k_sa_scan_tiles<<<1, 1024>>>(nScan, d.tileSum);
+	k_csfm_samples<<<(unsigned) nScan, 1024>>>(d.pos[d.cur], n, d.tileSum, nSamp, dSamp);
+	SCHK(hipGetLastError());
+	uint32_t got = 0;
+	SCHK(hipMemcpy(&got, d.tileSum + nScan, 4, hipMemcpyDeviceToHost));
+	if(got != nSamp) { hu_set_error("%s: internal: %u sampled rows, expected %zu: the sort did not return a permutation", fn, got, nSamp); return HU_ERR_STATE; }
+	SCHK(hipMemcpy(bwt, dBwt, n, hipMemcpyDeviceToHost)); SCHK(hipMemcpy(marks, dMarks, 8 * nWords, hipMemcpyDeviceToHost));
+	SCHK(hipMemcpy(sampled, dSamp, 4 * nSamp, hipMemcpyDeviceToHost));
+	return HU_OK;
+}
+#undef SCHK
 
 extern "C" int hu_tree_loglik(int device, int32_t n_nodes, int32_t cs_len, int32_t root, const hu_model_desc* model, const double* up_dev,
 		double* per_col, double* sum) try {

@@ -139,7 +139,7 @@ extern "C" int hu_seed_index_create(int32_t n_nodes, int32_t cs_len, const int32
 } catch(...) { return hu_catch_all("hu_seed_index_create"); }
 /* ------------------------------------------------------------------------------------------
  * Reading the reference's own index file, <DB>.csfm (CSFMIndex::save / load, src/CSFMIndex.cpp:176-230):
- *     string alphabet name (size_t length + bytes) | char gapCh | uint16 csLen | int32 concatLen | int32 C[256] |
+ *     [the 20 bytes of saveProgInfo, when hmmufotu-build wrote the file] | string alphabet name (size_t length + bytes) | char gapCh | uint16 csLen | int32 concatLen | int32 C[256] |
  *     string csSeq | double csIdentity[csLen + 1] | uint16 concat2CS[concatLen + 1] | uint32 saSampled[concatLen / 4] |
  *     saIdx: a libcds BitSequenceRRR | bwt: a libcds WaveletTreeNoptrs over BitSequenceRRR levels with a MapperNone
  * libcds (vendored by the reference under src/libcds, v1.0.x) serialises
@@ -240,6 +240,11 @@ extern "C" int hu_seed_index_load_csfm(const char* path, int32_t K, const int32_
 	Reader R(f);
 	auto fail = [&](const char* what) { fclose(f); hu_set_error("%s: %s", path, what); return HU_ERR_IO; };
 	std::string abc, csSeq;
+	{ /* a file of hmmufotu-build starts with saveProgInfo's 20 bytes (src/hmmufotu-build.cpp:479-480); a bare CSFMIndex::save with the size_t 3 of "DNA" */
+		char head[8];
+		if(R.left >= 20 && fread(head, 1, 8, f) == 8 && memcmp(head, "HmmUFOtu", 8) == 0) { if(fseek(f, 20, SEEK_SET) != 0) return fail("no alphabet name"); R.left -= 20; }
+		else rewind(f);
+	}
 	if(!R.str(abc)) return fail("no alphabet name");
 	if(abc != "DNA") return fail("not a DNA index");
 	(void) R.val<char>();

@@ -245,6 +245,68 @@ def msa_stats(rows, device=0) -> dict:
     return out
 
 
+def _msa_rows(rows, what) -> np.ndarray:
+    """an alignment (list of equal-length str/bytes rows, or a uint8 [n][L] array) as a contiguous uint8 [n][L] array"""
+    if isinstance(rows, np.ndarray):
+        a = np.ascontiguousarray(rows, np.uint8)
+        if a.ndim != 2 or a.size == 0:
+            raise EngineError("%s: rows must be a non-empty [n][L] array" % what)
+        return a
+    b = [r.encode() if isinstance(r, str) else bytes(r) for r in rows]
+    if not b or any(len(r) != len(b[0]) for r in b):
+        raise EngineError("%s: rows must be non-empty and of equal length" % what)
+    return np.frombuffer(b"".join(b), np.uint8).reshape(len(b), len(b[0]))
+
+
+def suffix_array_tile() -> int:
+    """hu_suffix_array_tile: the pairs one wave sorts per radix pass"""
+    return int(load_library().hu_suffix_array_tile())
+
+
+def suffix_array(text, device=0, info=False):
+    """hu_suffix_array: the suffix array (int32 [n]) of a text of symbols 0..4 (bytes or a uint8 array), built on the device;
+    info=True: (sa, doubling rounds, device seconds)"""
+    t = np.ascontiguousarray(np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else text, np.uint8).ravel()
+    sa = np.zeros(len(t), np.int32)
+    rounds = C.c_int32(0); sec = C.c_double(0)
+    _chk(load_library().hu_suffix_array(C.c_int(device), _p(t, C.c_uint8), C.c_int64(len(t)), _p(sa, C.c_int32), C.byref(rounds), C.byref(sec)))
+    return (sa, int(rounds.value), float(sec.value)) if info else sa
+
+
+def _csfm_args(what, rows, cs_seq, cs_identity):
+    a = _msa_rows(rows, what)
+    n, L = a.shape
+    cs = cs_seq.encode() if isinstance(cs_seq, str) else bytes(cs_seq)
+    ident = np.ascontiguousarray(cs_identity, np.float64).ravel()
+    if len(cs) != L or len(ident) != L or b"\0" in cs:
+        raise EngineError("%s: cs_seq has %d characters and cs_identity %d values, the rows %d columns" % (what, len(cs), len(ident), L))
+    return a, n, L, cs, ident
+
+
+def csfm_encode(path, rows, cs_seq, cs_identity, sa):
+    """hu_csfm_encode (host only): the reference's <DB>.csfm of an alignment from a GIVEN suffix array of its concatenated text.
+    rows as msa_stats takes them; cs_seq [L] characters; cs_identity [L]"""
+    a, n, L, cs, ident = _csfm_args("csfm_encode", rows, cs_seq, cs_identity)
+    sa = np.ascontiguousarray(sa, np.int32).ravel()
+    need = int((msa_encode_table()[a] >= 0).sum()) + n + 1
+    if len(sa) != need:
+        raise EngineError("csfm_encode: the suffix array has %d entries, the concatenated text %d symbols" % (len(sa), need))
+    _chk(load_library().hu_csfm_encode(str(path).encode(), C.c_int64(n), C.c_int64(L), a.ctypes.data_as(C.c_char_p), cs, _p(ident, C.c_double), _p(sa, C.c_int32)))
+
+
+def csfm_write(path, rows, cs_seq, cs_identity, device=0):
+    """hu_csfm_write: the same file, the suffix array, the BWT and the samples built on the device"""
+    a, n, L, cs, ident = _csfm_args("csfm_write", rows, cs_seq, cs_identity)
+    _chk(load_library().hu_csfm_write(str(path).encode(), C.c_int64(n), C.c_int64(L), a.ctypes.data_as(C.c_char_p), cs, _p(ident, C.c_double), C.c_int(device)))
+
+
+def csfm_write_timing() -> dict:
+    """hu_csfm_write_timing: the phases of this thread's last csfm_write, in seconds, and its doubling rounds"""
+    s = np.zeros(4); r = C.c_int32(0)
+    _chk(load_library().hu_csfm_write_timing(_p(s, C.c_double), C.byref(r)))
+    return dict(text=s[0], device=s[1], encode_write=s[2], suffix_array=s[3], rounds=int(r.value))
+
+
 def tree_count_mutations(parent, cs_len: int, up_ptr: int, device=0) -> np.ndarray:
     """hu_tree_count_mutations: per column, the non-root nodes whose inferred state differs from their parent's, from the DEVICE
     fixed-rate up buffer at up_ptr ([n][cs_len][4] float64, as tree_evaluate leaves it with win_len 0)"""

@@ -589,6 +589,30 @@ int64_t hu_otucs_description(const char* db_name, const char* taxonomy, double a
 /* the annotation distance of a node (PTUNode::getAnnoDist), beside hu_db_get_annotation */
 int hu_db_get_anno_dist(const hu_db* db, int32_t node, double* out);
 
+/* ---- the seed index file <DB>.csfm (hmmufotu-build's csfm.build(msa) + csfm.save) -------------------------------
+ * hu_suffix_array: what divsufsort(concatSeq, SA, N) returns in CSFMIndex::buildBWT (src/CSFMIndex.cpp:327-335), built on the device by
+ * prefix doubling over a radix sort.  text: n bytes of 0 (separator, terminator) and 1..4 (bases), 1 <= n < 2^31; sa [n]: the start
+ * positions of the suffixes in ascending order, a suffix that is a proper prefix of another first.  rounds (may be NULL): doubling rounds
+ * taken; device_seconds (may be NULL): time on the device without the copies.  HU_ERR_ARG for n out of range (before the text is read)
+ * or a symbol above 4, both before a device is asked for; HU_ERR_NOMEM with the bytes needed and the bytes free when the device cannot
+ * hold the sort (about 29.3 bytes per symbol).  hu_suffix_array_tile: the pairs one wave sorts per pass, for tests of the tile edges. */
+int hu_suffix_array(int device, const uint8_t* text, int64_t n, int32_t* sa, int32_t* rounds, double* device_seconds);
+int32_t hu_suffix_array_tile(void);
+/* CSFMIndex::save (src/CSFMIndex.cpp:176-198) of the index CSFMIndex::build makes (buildBasic, buildConcatSeq, buildBWT, :275-368), behind
+ * the 20-byte head saveProgInfo puts in front of it (src/hmmufotu-build.cpp:479-480).  rows: n_seq rows of cs_len bytes, row-major, as read
+ * (case kept): the pruned alignment, ALL its rows in file order.  A byte is a gap or a residue by hu_msa_encode_table, a residue's symbol is
+ * encode(toupper(c)) + 1; any other byte is refused with its row and column (HU_ERR_ARG; the reference refuses such an alignment when it
+ * loads it).  cs_seq: the cs_len characters of MSA::calculateCS, zero-terminated (the file's leading blank is added here); cs_identity
+ * [cs_len]: MSA::identityAt of every column (the file's leading 0 is added here).
+ * hu_csfm_encode: host only, from a GIVEN suffix array sa [N] of the concatenated text, N = residues + n_seq + 1 (HU_ERR_ARG when it is no
+ * permutation of 0 .. N - 1; its order is not checked).  hu_csfm_write: the suffix array, the BWT, the marks of the sampled rows and the
+ * sampled values come from the device (hu_suffix_array's construction); the file is encoded and written on up to 16 host threads.
+ * Both refuse cs_len > 65535 and N >= 2^31 before anything is allocated.  hu_csfm_write_timing: of this thread's last hu_csfm_write,
+ * seconds [4] = text, device (with copies), encode + write, suffix array alone; rounds = doubling rounds. */
+int hu_csfm_encode(const char* path, int64_t n_seq, int64_t cs_len, const char* rows, const char* cs_seq, const double* cs_identity, const int32_t* sa);
+int hu_csfm_write(const char* path, int64_t n_seq, int64_t cs_len, const char* rows, const char* cs_seq, const double* cs_identity, int device);
+int hu_csfm_write_timing(double* seconds /* [4] */, int32_t* rounds);
+
 #ifdef __cplusplus
 }
 #endif
