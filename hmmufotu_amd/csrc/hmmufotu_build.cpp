@@ -10,20 +10,13 @@
 // Writes <NAME>.ptu, and <NAME>.csfm when asked (without it hmmufotu-amd rebuilds its seed index from the .ptu on every start; the reference's
 // hmmufotu cannot start without it): no .msa, and no .hmm — the profile comes
 // from a third-party trainer (HMMER3, hmmufotu-train-hmm) and is put beside the .ptu as <NAME>.hmm.
-#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <iostream>
 #include <limits>
-#include <sstream>
-#include <unordered_map>
 #include <sys/stat.h>
 #include <unistd.h>
-#include "hu_reads_io.h"
-#include "../../include/hmmufotu_amd.h"
+#include "hu_build_inputs.h"     /* the reading, joining and pruning shared with hmmufotu-amd-train-sm */
 
 /* src/hmmufotu-build.cpp:59-61 */
 static const int DEFAULT_DG_CATEGORY = 4, MIN_DG_CATEGORY = 2, MAX_DG_CATEGORY = 8;
@@ -46,15 +39,6 @@ static void usage(const char* p) {
 		"            -f|--symfrac, -dm, -p|--process : accepted and ignored (they belong to the profile training)\n"
 		"            -v  FLAG             : enable verbose information; -vv adds the wall time of every phase\n"
 		"            -h|--help            : print this message and exit\n";
-}
-
-static const auto unused_revcom [[maybe_unused]] = &revcom;     /* hu_reads_io.h is shared with the programs that read primers */
-static bool ends_with(const std::string& s, const char* suf) { const size_t k = strlen(suf); return s.size() >= k && s.compare(s.size() - k, k, suf) == 0; }
-static bool read_file(const std::string& fn, std::string& out) {
-	std::ifstream in(fn, std::ios::binary);
-	if(!in.is_open()) return false;
-	std::ostringstream ss; ss << in.rdbuf(); out = ss.str();
-	return !in.bad();
 }
 
 int main(int argc, char** argv) {
@@ -96,14 +80,9 @@ int main(int argc, char** argv) {
 		return EXIT_FAILURE;
 	}
 	/* guess input format (src/hmmufotu-build.cpp:198-208) */
-	if(fmt.empty()) {
-		std::string pre = seqFn;
-		if(ends_with(pre, ".gz")) pre.erase(pre.size() - 3); else if(ends_with(pre, ".bz2")) pre.erase(pre.size() - 4);
-		for(const char* e : {"fasta", "fas", "fa", "fna"}) if(ends_with(pre, e)) fmt = "fasta";
-		if(fmt.empty()) for(const char* e : {"fastq", "fq"}) if(ends_with(pre, e)) fmt = "fastq";
-	}
+	hu_guess_seq_format(seqFn, fmt);
 	if(fmt != "fasta") { std::cerr << "Unsupported sequence format '" << fmt << "'" << std::endl; return EXIT_FAILURE; }
-	if(!ends_with(treeFn, ".tree") && !ends_with(treeFn, ".tre")) { std::cerr << "Unrecognized TREE-FILE format, must be in Newick format" << std::endl; return EXIT_FAILURE; }
+	if(!hu_is_newick_name(treeFn)) { std::cerr << "Unrecognized TREE-FILE format, must be in Newick format" << std::endl; return EXIT_FAILURE; }
 	if(!(MIN_DG_CATEGORY <= K && K <= MAX_DG_CATEGORY)) { std::cerr << "-k must be an integer between " << MIN_DG_CATEGORY << " and " << MAX_DG_CATEGORY << std::endl; return EXIT_FAILURE; }
 	if(device < 0) { std::cerr << "--device must be non-negative" << std::endl; return EXIT_FAILURE; }
 	for(const std::string& o : ignored) info("Note: " + o + " belongs to the profile training and is ignored under --no-hmm");
@@ -118,49 +97,19 @@ int main(int argc, char** argv) {
 	if(dbName.empty()) dbName = seqFn.substr(seqFn.find_last_of('/') + 1);      /* StringUtils::basename(seqFn) */
 	const std::string ptuFn = dbName + ".ptu", csfmFn = dbName + ".csfm";
 
-	/* the MSA: rows as read (case kept), names = the ids */
-	std::vector<std::string> rowName; std::vector<char> msa; size_t L0 = 0;
-	std::unordered_map<std::string, uint32_t> name2row;
-	{
-		Read r;
-		while(next_read(seqIn, false, r, true)) {
-			if(rowName.empty()) L0 = r.seq.size();
-			else if(r.seq.size() != L0) { std::cerr << "Unable to load MSA from '" << seqFn << "': sequence '" << r.id << "' has " << r.seq.size() << " columns, the first one " << L0 << std::endl; return EXIT_FAILURE; }
-			if(!name2row.insert({r.id, (uint32_t) rowName.size()}).second) { std::cerr << "Non-unique seq name " << r.id << " found in your MSA data " << dbName << std::endl; return EXIT_FAILURE; }
-			rowName.push_back(r.id);
-			msa.insert(msa.end(), r.seq.begin(), r.seq.end());
-		}
-		if(rowName.empty() || L0 == 0) { std::cerr << "Unable to load MSA from '" << seqFn << "'" << std::endl; return EXIT_FAILURE; }
-	}
-	const size_t nSeq = rowName.size();
-	info("MSA loaded");
+	/* the MSA, the tree, and loadMSA: every leaf takes the row of its name */
+	HuBuildInputs inp;
+	if(!hu_load_msa(seqIn, seqFn, dbName, inp, info)) return EXIT_FAILURE;
+	const size_t nSeq = inp.nSeq, L0 = inp.L0;
+	std::vector<char>& msa = inp.msa;
 	lap("read");
-
-	/* the tree */
-	hu_newick* nw = nullptr;
-	if(hu_newick_parse(treeText.data(), (int64_t) treeText.size(), &nw) != HU_OK) { std::cerr << "Unable to read Newick tree in '" << treeFn << "': " << hu_last_error() << std::endl; return EXIT_FAILURE; }
-	info("Newick Tree read");
-	int32_t n = 0;
-	hu_newick_size(nw, &n);
-	std::vector<int32_t> parent(n), childOff((size_t) n + 1), childIdx((size_t) std::max(n - 1, 1));
-	std::vector<double> blen(n);
-	hu_newick_get(nw, parent.data(), blen.data(), childOff.data(), childIdx.data());
-	std::vector<std::string> nodeName(n);
-	for(int32_t i = 0; i < n; ++i) nodeName[i] = hu_newick_name(nw, i);
-	hu_newick_free(nw);
-	info("Phylogenetic Tree constructed with total " + std::to_string(n) + " nodes");
+	if(!hu_load_tree(treeText, treeFn, inp, info)) return EXIT_FAILURE;
+	const int32_t n = inp.n;
+	std::vector<int32_t> &parent = inp.parent, &childOff = inp.childOff, &childIdx = inp.childIdx, &rowOf = inp.rowOf;
+	std::vector<double>& blen = inp.blen;
+	std::vector<std::string>& nodeName = inp.nodeName;
 	if(n < 2) { std::cerr << "Unable to build a database from a tree of " << n << " node" << std::endl; return EXIT_FAILURE; }
-
-	/* loadMSA (src/PhyloTreeUnrooted.cpp:185-221): every leaf takes the row of its name */
-	std::vector<int32_t> rowOf(n, -1);
-	size_t nLeaves = 0, nRead = 0;
-	for(int32_t i = 0; i < n; ++i) if(childOff[i] == childOff[i + 1]) {
-		++nLeaves;
-		auto it = name2row.find(nodeName[i]);
-		if(it != name2row.end()) { rowOf[i] = (int32_t) it->second; ++nRead; }
-	}
-	if(nRead != nLeaves) { std::cerr << "Unmatched MSA and Tree. Found " << nRead << " leaf sequences from MSA but expecting " << nLeaves << " leaves in the Phylogenetic Tree " << std::endl; return EXIT_FAILURE; }
-	info("MSA loaded into Phylogenetic Tree");
+	if(!hu_join_msa_tree(inp, info)) return EXIT_FAILURE;
 
 	info("Verifying and fixing branch length");
 	for(int32_t i = 0; i < n; ++i) if(parent[i] >= 0 && childOff[i] == childOff[i + 1] && blen[i] <= 0) blen[i] = 1e-5;     /* fixBranchLength, BRANCH_EPS */
@@ -218,24 +167,16 @@ int main(int argc, char** argv) {
 	std::vector<int8_t> seq;
 	int32_t L = 0;
 	{
-		std::vector<int32_t> res(4 * L0), gap(L0), st(nSeq), en(nSeq), ln(nSeq);
-		std::vector<double> w(nSeq), wres(4 * L0), wgap(L0);
-		if(hu_msa_stats(device, (int64_t) nSeq, (int64_t) L0, msa.data(), res.data(), gap.data(), st.data(), en.data(), ln.data(), w.data(), wres.data(), wgap.data()) != HU_OK)
-			return fail(std::string("Error: ") + hu_last_error());
-		std::vector<uint32_t> keep;
-		for(size_t j = 0; j < L0; ++j) if(res[j] + res[L0 + j] + res[2 * L0 + j] + res[3 * L0 + j] > 0) keep.push_back((uint32_t) j);
-		L = (int32_t) keep.size();
-		info("MSA pruned");
-		info("MSA database created for " + std::to_string(nSeq) + " X " + std::to_string(L) + " aligned sequences");
+		std::string err;
+		if(!hu_prune_msa(device, inp, info, err)) return fail("Error: " + err);
+		const std::vector<int32_t>& res = inp.res; const std::vector<double> &wres = inp.wres, &wgap = inp.wgap; const std::vector<uint32_t>& keep = inp.keep;
+		L = inp.L;
 		if(L < 1) return fail("Unable to build a database: the MSA has no column with a residue");
 		if(L > 65535) return fail("Unable to build a database: " + std::to_string(L) + " columns after pruning, the .ptu readers take at most 65535");
 		int8_t enc[256];
 		hu_msa_encode_table(enc);
 		seq.assign((size_t) n * L, (int8_t) 0);
-		for(int32_t i = 0; i < n; ++i) if(rowOf[i] >= 0) {
-			const char* src = msa.data() + (size_t) rowOf[i] * L0; int8_t* dst = seq.data() + (size_t) i * L;
-			for(int32_t j = 0; j < L; ++j) dst[j] = enc[(unsigned char) src[keep[j]]];
-		}
+		for(int32_t i = 0; i < n; ++i) if(rowOf[i] >= 0) hu_encode_row(inp, enc, (size_t) rowOf[i], seq.data() + (size_t) i * L);
 		if(withCsfm) { /* csfm.build(msa) over ALL rows of the pruned MSA in file order, csSeq from the weighted counts (MSA::calculateCS, src/MSA.cpp:211-226),
 		                * csIdentity from the raw ones (identityAt, :59-61) */
 			std::vector<char> rows(nSeq * (size_t) L);

@@ -29,6 +29,7 @@
 #include "hu_kern_build.h"
 #include "hu_kern_otucs.h"
 #include "hu_kern_csfm.h"
+#include "hu_kern_sm.h"
 
 #define HIPCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { \
 	hu_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return HU_ERR_DEVICE; } } while(0)
@@ -984,6 +985,63 @@ extern "C" int hu_tree_count_mutations(int device, int32_t n_nodes, int32_t cs_l
 	#undef MCHK
 	return HU_OK;
 } catch(...) { return hu_catch_all("hu_tree_count_mutations"); }
+
+/* ------------------------------------------------------------------------------ substitution-model training (hmmufotu-train-sm) */
+static thread_local double g_smTiming[3] = {0, 0, 0};
+extern "C" int hu_sm_counts(int device, int64_t n_rows, int64_t cs_len, const int8_t* rows, int64_t n_items, const int32_t* items,
+		int32_t* counts, int32_t* dn, int32_t* base) try {
+	const char* fn = "hu_sm_counts";
+	if(n_rows < 1 || cs_len < 1 || n_rows > INT32_MAX || cs_len > INT32_MAX / 4 || !rows || n_items < 0 || n_items + n_rows > INT32_MAX || !base ||
+			(n_items > 0 && (!items || !counts || !dn))) { hu_set_error("%s: bad argument", fn); return HU_ERR_ARG; }
+	for(int64_t i = 0; i < n_items; ++i) { /* every row the kernel will read, before a device is asked for */
+		const int32_t r0 = items[3 * i], r1 = items[3 * i + 1], r2 = items[3 * i + 2];
+		if(r0 < -1 || r0 >= n_rows || r1 < 0 || r1 >= n_rows || r2 < 0 || r2 >= n_rows) { hu_set_error("%s: item %lld names rows %d, %d, %d of %lld (row0 may be -1 for a pair)", fn, (long long) i, r0, r1, r2, (long long) n_rows); return HU_ERR_ARG; }
+	}
+	if(hu_device_count() <= 0) { hu_set_error("no gfx950 device visible: the engine has no CPU path"); return HU_ERR_DEVICE; }
+	HIPCHK(hipSetDevice(device));
+	const int64_t stride = (cs_len + 15) / 16 * 16;     /* the device rows are padded to whole 16-byte pieces with the gap code */
+	const size_t rowBytes = (size_t) n_rows * stride, itemBytes = (size_t) n_items * 12, outBytes = (size_t) n_items * HU_SM_VALUES * 4, baseBytes = (size_t) n_rows * 16;
+	uint4* dRows = nullptr; int32_t *dItems = nullptr, *dOut = nullptr, *dBase = nullptr;
+	HuScope guard([&] { (void) hipFree(dRows); (void) hipFree(dItems); (void) hipFree(dOut); (void) hipFree(dBase); });
+	#define SCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { hu_set_error("%s: %s failed: %s", fn, #call, hipGetErrorString(e_)); return HU_ERR_DEVICE; } } while(0)
+	{
+		size_t freeB = 0, totB = 0;
+		SCHK(hipMemGetInfo(&freeB, &totB));
+		const size_t need = rowBytes + itemBytes + outBytes + baseBytes + 1024;
+		if(need > freeB) { hu_set_error("%s: %lld rows x %lld columns and %lld items need %.3f GB of device memory, %.3f GB are free", fn, (long long) n_rows, (long long) cs_len, (long long) n_items, need / 1e9, freeB / 1e9); return HU_ERR_NOMEM; }
+	}
+	auto t0 = std::chrono::steady_clock::now();
+	auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
+	SCHK(hipMalloc((void**) &dRows, rowBytes)); SCHK(hipMalloc((void**) &dBase, baseBytes));
+	if(n_items > 0) { SCHK(hipMalloc((void**) &dItems, itemBytes)); SCHK(hipMalloc((void**) &dOut, outBytes)); }
+	if(stride != cs_len) {
+		SCHK(hipMemset(dRows, 0xFE, rowBytes));     /* -2, the gap code */
+		SCHK(hipMemcpy2D(dRows, (size_t) stride, rows, (size_t) cs_len, (size_t) cs_len, (size_t) n_rows, hipMemcpyHostToDevice));
+	}
+	else SCHK(hipMemcpy(dRows, rows, rowBytes, hipMemcpyHostToDevice));
+	if(n_items > 0) SCHK(hipMemcpy(dItems, items, itemBytes, hipMemcpyHostToDevice));
+	SCHK(hipDeviceSynchronize());
+	g_smTiming[0] = since();
+	(void) hipGetLastError();
+	k_sm_counts<<<(unsigned)(n_items + n_rows), HU_SM_BLOCK>>>(dRows, n_rows, stride / 16, dItems, n_items, dOut, dBase);
+	SCHK(hipGetLastError());
+	SCHK(hipDeviceSynchronize());
+	g_smTiming[1] = since() - g_smTiming[0];
+	SCHK(hipMemcpy(base, dBase, baseBytes, hipMemcpyDeviceToHost));
+	if(n_items > 0) {
+		std::vector<int32_t> out((size_t) n_items * HU_SM_VALUES);
+		SCHK(hipMemcpy(out.data(), dOut, outBytes, hipMemcpyDeviceToHost));
+		for(int64_t i = 0; i < n_items; ++i) { memcpy(counts + 16 * i, out.data() + HU_SM_VALUES * i, 64); memcpy(dn + 4 * i, out.data() + HU_SM_VALUES * i + 16, 16); }
+	}
+	g_smTiming[2] = since() - g_smTiming[0] - g_smTiming[1];
+	#undef SCHK
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_sm_counts"); }
+extern "C" int hu_sm_counts_timing(double* seconds) {
+	if(!seconds) return HU_ERR_ARG;
+	memcpy(seconds, g_smTiming, sizeof(g_smTiming));
+	return HU_OK;
+}
 
 extern "C" int hu_device_mem_info(int device, int64_t* free_bytes, int64_t* total_bytes) try {
 	if(hu_device_count() <= 0) { hu_set_error("no gfx950 device visible: the engine has no CPU path"); return HU_ERR_DEVICE; }

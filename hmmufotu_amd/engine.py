@@ -307,6 +307,89 @@ def csfm_write_timing() -> dict:
     return dict(text=s[0], device=s[1], encode_write=s[2], suffix_array=s[3], rounds=int(r.value))
 
 
+SM_TYPES = ["GTR", "TN93", "HKY85", "F81", "K80", "JC69"]
+SM_METHODS = {"gojobori": 0, "goldman": 1}
+
+
+def sm_training_set(parent, child_off, child_idx, row_of, method="Gojobori") -> np.ndarray:
+    """hu_sm_training_set (host only): the items [k][3] = (row0, row1, row2) of the reference's Gojobori (triples) or Goldman (pairs,
+    row0 = -1) training set, on the arrays of newick_parse and row_of [n] (the MSA row of every leaf, -1 elsewhere).  Gojobori draws
+    from the C library's rand() as the reference does; this call never seeds it."""
+    parent = np.ascontiguousarray(parent, np.int32); co = np.ascontiguousarray(child_off, np.int32)
+    ci = np.ascontiguousarray(child_idx, np.int32); ro = np.ascontiguousarray(row_of, np.int32)
+    n = len(parent)
+    if str(method).lower() not in SM_METHODS:
+        raise EngineError("sm_training_set: unknown training method '%s'" % method)
+    if len(co) != n + 1 or len(ci) < n - 1 or len(ro) != n:
+        raise EngineError("sm_training_set: the arrays do not describe one tree of %d nodes" % n)
+    if len(ci) == 0:
+        ci = np.zeros(1, np.int32)
+    items = np.zeros((n, 3), np.int32); k = C.c_int64(0)
+    _chk(load_library().hu_sm_training_set(C.c_int32(n), _p(parent, C.c_int32), _p(co, C.c_int32), _p(ci, C.c_int32), _p(ro, C.c_int32),
+                                           C.c_int(SM_METHODS[str(method).lower()]), _p(items, C.c_int32), C.byref(k)))
+    return items[:k.value].copy()
+
+
+def sm_counts(rows, items, device=0) -> dict:
+    """hu_sm_counts: for int8 rows [n_rows][cs_len] (codes of msa_encode_table) and items [k][3], on the device: counts [k][4][4]
+    (from, to), dn [k][4] = d, N of (row0, row1) and of (row0, row2) — for a pair (row0 = -1) of (row1, row1) and (row1, row2) —,
+    base [n_rows][4]; pass [k]: the reference's distance test on dn (hu_sm_item_pass)."""
+    rows = np.ascontiguousarray(rows, np.int8)
+    items = np.ascontiguousarray(items, np.int32).reshape(-1, 3)
+    if rows.ndim != 2 or rows.size == 0:
+        raise EngineError("sm_counts: rows must be a non-empty [n_rows][cs_len] array")
+    n, L = rows.shape; k = len(items)
+    out = dict(counts=np.zeros((k, 4, 4), np.int32), dn=np.zeros((k, 4), np.int32), base=np.zeros((n, 4), np.int32))
+    lib = load_library()
+    _chk(lib.hu_sm_counts(C.c_int(device), C.c_int64(n), C.c_int64(L), _p(rows, C.c_int8), C.c_int64(k), _p(items, C.c_int32),
+                          _p(out["counts"], C.c_int32), _p(out["dn"], C.c_int32), _p(out["base"], C.c_int32)))
+    out["pass"] = sm_item_pass(items, out["dn"])
+    return out
+
+
+def sm_counts_timing() -> dict:
+    """hu_sm_counts_timing: the phases of this thread's last sm_counts, in seconds"""
+    s = np.zeros(3)
+    _chk(load_library().hu_sm_counts_timing(_p(s, C.c_double)))
+    return dict(to_device=s[0], kernel=s[1], to_host=s[2])
+
+
+def sm_item_pass(items, dn) -> np.ndarray:
+    """hu_sm_item_pass: per item whether its p-distances are within DNASubModel::MAX_PDIST (NaN fails)"""
+    items = np.ascontiguousarray(items, np.int32).reshape(-1, 3); dn = np.ascontiguousarray(dn, np.int32).reshape(-1, 4)
+    if len(items) != len(dn):
+        raise EngineError("sm_item_pass: %d items, %d distance rows" % (len(items), len(dn)))
+    ok = np.zeros(len(items), np.int32)
+    _chk(load_library().hu_sm_item_pass(C.c_int64(len(items)), _p(items, C.c_int32), _p(dn, C.c_int32), _p(ok, C.c_int32)))
+    return ok.astype(bool)
+
+
+def sm_train(model_type, mats, passed, base, info=False):
+    """hu_sm_train (host only): the ModelDesc of type model_type ("GTR" .. "JC69" or its index) trained on mats [k][4][4] in item order,
+    of which passed [k] marks the ones the reference's vector holds, and the four base counts.  info=True: (model, matrices used)"""
+    t = SM_TYPES.index(model_type) if isinstance(model_type, str) else int(model_type)
+    mats = np.ascontiguousarray(mats, np.float64).reshape(-1, 16)
+    ok = np.ascontiguousarray(np.asarray(passed).astype(bool), np.int32).ravel()
+    f = np.ascontiguousarray(base, np.int64).ravel()
+    if len(ok) != len(mats) or len(f) != 4:
+        raise EngineError("sm_train: %d matrices, %d decisions, %d base counts" % (len(mats), len(ok), len(f)))
+    md = ModelDesc(); used = C.c_int64(0)
+    _chk(load_library().hu_sm_train(C.c_int(t), C.c_int64(len(mats)), _p(mats, C.c_double), _p(ok, C.c_int32), _p(f, C.c_int64), C.byref(md), C.byref(used)))
+    return (md, int(used.value)) if info else md
+
+
+def sm_write_text(model: ModelDesc) -> str:
+    """hu_sm_write_text: the model file of a ModelDesc as DNASubModel::write lays it out, every number as %.17g"""
+    lib = load_library()
+    lib.hu_sm_write_text.restype = C.c_int64
+    n = int(lib.hu_sm_write_text(C.byref(model), None, C.c_int64(0)))
+    if n < 0:
+        _chk(n)
+    buf = C.create_string_buffer(n + 1)
+    lib.hu_sm_write_text(C.byref(model), buf, C.c_int64(n + 1))
+    return buf.value.decode()
+
+
 def tree_count_mutations(parent, cs_len: int, up_ptr: int, device=0) -> np.ndarray:
     """hu_tree_count_mutations: per column, the non-root nodes whose inferred state differs from their parent's, from the DEVICE
     fixed-rate up buffer at up_ptr ([n][cs_len][4] float64, as tree_evaluate leaves it with win_len 0)"""

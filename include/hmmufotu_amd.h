@@ -613,6 +613,57 @@ int hu_csfm_encode(const char* path, int64_t n_seq, int64_t cs_len, const char* 
 int hu_csfm_write(const char* path, int64_t n_seq, int64_t cs_len, const char* rows, const char* cs_seq, const double* cs_identity, int device);
 int hu_csfm_write_timing(double* seconds /* [4] */, int32_t* rounds);
 
+/* ---- training a substitution model (hmmufotu-train-sm) -------------------------------------------------------
+ * model->trainParams(tree.getModelTransitionSet(method), tree.getModelFreqEst()) of src/hmmufotu-train-sm.cpp:232-233 in four steps:
+ * which rows are compared (host), the counts over their columns (device), the closed-form trainers (host), the model file (host).
+ *
+ * hu_sm_training_set: PTUnrooted::getModelTraningSetGojobori / getModelTraningSetGoldman (src/PhyloTreeUnrooted.cpp:449-486) up to the
+ * point where sequences are read, on the arrays of hu_newick_get; row_of [n]: the MSA row of every leaf, -1 for the other nodes.  A
+ * node's neighbour list is "parent, then children in file order"; isLeaf / isTip / firstChild / lastChild are those of
+ * src/PhyloTreeUnrooted.h:199-267 (a leaf has ONE neighbour, so a root with a single child is one).  Nodes are visited in id order.
+ *   HU_SM_GOJOBORI: a node with exactly two children, one of them a tip, gives (row0, row1, row2) = (randomLeaf(the other child), the
+ *     tip's first child, its last child).  randomLeaf (src/PhyloTreeUnrooted.h:1480-1486) steps to children[rand() % size] until a
+ *     leaf: rand() is the C library's and is never seeded here, so an unseeded process draws what the reference's program draws.
+ *   HU_SM_GOLDMAN: a tip with more than two neighbours gives (-1, first child's row, last child's row).
+ * Every candidate is returned; whether it is used is decided from the distances hu_sm_counts measures (hu_sm_item_pass).
+ * items: [n_nodes][3] int32 of room; *n_items: how many were written.  No counting, no device. */
+enum { HU_SM_GOJOBORI = 0, HU_SM_GOLDMAN = 1 };
+int hu_sm_training_set(int32_t n_nodes, const int32_t* parent, const int32_t* child_off, const int32_t* child_idx, const int32_t* row_of,
+		int method, int32_t* items, int64_t* n_items);
+/* The column loops, on the device (k_sm_counts, one workgroup per item and per row).  rows [n_rows][cs_len]: codes as hu_msa_encode_table
+ * gives them (0..3 residue, negative: gap or invalid).  items [n_items][3] as above, rows checked against n_rows before a device is
+ * asked for.  Outputs, all host, all integer and therefore exact:
+ *   counts [n_items][16], row-major from, to.  A triple is DNASubModel::calcTransFreq3Seq(row0, row1, row2) (src/DNASubModel.cpp:75-104):
+ *     per column with three residues the ancestor is b0 if b0 == b1 or b0 == b2, else b1 if b1 == b2, else the column is skipped; one
+ *     is added to (anc, b0), (anc, b1), (anc, b2).  A pair is calcTransFreq2Seq(row1, row2) (:52-62).
+ *   dn [n_items][4]: d, N of SeqUtils::pDist (src/SeqUtils.cpp:37-54; N = columns where both are residues, d = those that differ) for
+ *     (row0, row1) and (row0, row2); for a pair for (row1, row1) — the reference's Goldman test compares the row with itself — and
+ *     (row1, row2).
+ *   base [n_rows][4]: DNASubModel::calcBaseFreq of every row (:106-112).
+ * n_items may be 0.  HU_ERR_NOMEM with the bytes needed and the bytes free when the device cannot hold the rows (each padded to a
+ * multiple of 16 bytes) and the outputs.  hu_sm_counts_timing: of this thread's last call, seconds [3] = allocation and copies to
+ * the device, the kernel, the copies back. */
+int hu_sm_counts(int device, int64_t n_rows, int64_t cs_len, const int8_t* rows, int64_t n_items, const int32_t* items,
+		int32_t* counts, int32_t* dn, int32_t* base);
+int hu_sm_counts_timing(double* seconds /* [3] */);
+/* pass [n_items]: SeqUtils::pDist(...) <= DNASubModel::MAX_PDIST (0.15, src/DNASubModel.cpp:39) as the two training-set loops apply
+ * it: (double) d / N, both distances of a triple, the first of a pair; N == 0 gives NaN, which fails. */
+int hu_sm_item_pass(int64_t n_items, const int32_t* items, const int32_t* dn, int32_t* pass);
+/* trainParams of the six models (src/GTR.cpp:92-122, src/TN93.cpp:88-102, src/HKY85.cpp:86-98, src/F81.cpp:84-89, src/K80.cpp:81-89,
+ * src/JC69.h:79-80).  mats [n_items][16] row-major in item order, of which those with pass != 0 are the reference's vector; base [4]:
+ * getModelFreqEst (src/PhyloTreeUnrooted.cpp:488-494), the base counts summed over the leaf rows.  Fills type, pi and par of *out
+ * (dg_k = 0).  GTR: constrainedQfromP (src/DNASubModel.cpp:147-164) of every matrix, those that pass isValidRate
+ * (src/DNASubModel.h:200-206) scaled by minus their TRACE (scale's default pi = Ones, src/DNASubModel.cpp:123-126) and averaged, then
+ * R(i, j) = Q(i, j) / pi(j), symmetrised.  n_used (may be NULL): the matrices that entered — for GTR the valid ones.
+ * Where the reference would print NaN this entry refuses with HU_ERR_ARG and says so: no valid matrix (GTR), Tv == 0 (TN93, HKY85,
+ * K80), base counts that sum to 0 (every model with a pi). */
+int hu_sm_train(int type, int64_t n_items, const double* mats, const int32_t* pass, const int64_t* base, hu_model_desc* out, int64_t* n_used);
+/* DNASubModel::write of the model (src/GTR.cpp:83-90 and friends): the lines of the model block hu_ptu_write generates, every number as
+ * %.17g, so hu_model_parse_text returns pi and par bit for bit; GTR's "Q:" lines hold setQfromParams' matrix scaled by minus its
+ * trace, as the reference computes it (both readers skip them).  Returns the length without the terminator and writes at most cap
+ * bytes, terminator included; negative on a bad argument. */
+int64_t hu_sm_write_text(const hu_model_desc* model, char* buf, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif
