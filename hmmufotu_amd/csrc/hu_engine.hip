@@ -30,6 +30,7 @@
 #include "hu_kern_otucs.h"
 #include "hu_kern_csfm.h"
 #include "hu_kern_sm.h"
+#include "hu_kern_sim.h"
 
 #define HIPCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { \
 	hu_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return HU_ERR_DEVICE; } } while(0)
@@ -1042,6 +1043,112 @@ extern "C" int hu_sm_counts_timing(double* seconds) {
 	memcpy(seconds, g_smTiming, sizeof(g_smTiming));
 	return HU_OK;
 }
+
+/* ------------------------------------------------------------------------------ simulated reads (hmmufotu-sim) */
+static thread_local double g_simTiming[3] = {0, 0, 0};
+extern "C" int hu_sim_reads(const hu_db* db, int64_t n, const int32_t* node, const double* rc, const int32_t* start, const int32_t* end,
+		const double* gap_frac, uint64_t seed, uint64_t read0, int want_mate, char* aligned, char* seq, char* mate, int32_t* seq_len) try {
+	const char* fn = "hu_sim_reads";
+	if(!db || n < 0 || n > INT32_MAX || !gap_frac || (n > 0 && (!node || !rc || !start || !end || !aligned || !seq || !seq_len || (want_mate && !mate)))) { hu_set_error("%s: bad argument", fn); return HU_ERR_ARG; }
+	const HuDbDev& d = db->dev;
+	if(d.winStart != 0 || d.winLen != d.csLen) { hu_set_error("%s: the database holds a column window; the simulation needs the whole database", fn); return HU_ERR_ARG; }
+	/* every index the kernel forms, before anything reaches the device */
+	std::vector<int64_t> off((size_t) n);
+	int64_t total = 0;
+	for(int64_t r = 0; r < n; ++r) {
+		if(node[r] < 0 || node[r] >= d.nNodes || node[r] == d.root) { hu_set_error("%s: read %lld: node %d is %s", fn, (long long) r, node[r], node[r] == d.root ? "the root, which has no branch above it" : "not a node of the database"); return HU_ERR_ARG; }
+		if(!(start[r] >= 0 && start[r] <= end[r] && end[r] < d.csLen)) { hu_set_error("%s: read %lld: columns %d .. %d of a database of %d", fn, (long long) r, start[r], end[r], d.csLen); return HU_ERR_ARG; }
+		if(!(rc[r] >= 0 && rc[r] <= 1)) { hu_set_error("%s: read %lld: branch point %g outside [0, 1]", fn, (long long) r, rc[r]); return HU_ERR_ARG; }
+		off[(size_t) r] = total;
+		total += (int64_t) end[r] - start[r] + 1;
+	}
+	if(n == 0) { g_simTiming[0] = g_simTiming[1] = g_simTiming[2] = 0; return HU_OK; }
+	HIPCHK(hipSetDevice(db->device));
+	const size_t L = (size_t) d.csLen, R = (size_t) n, T = (size_t) total;
+	const size_t planBytes = R * (4 + 8 + 4 + 4 + 8 + 4);
+	const int nOut = want_mate ? 3 : 2;
+	char* dOut = nullptr; double *dGap = nullptr, *dRc = nullptr; int64_t* dOff = nullptr; int32_t* dI = nullptr;     /* dI: node, start, end, seqLen */
+	HuScope guard([&] { (void) hipFree(dOut); (void) hipFree(dGap); (void) hipFree(dRc); (void) hipFree(dOff); (void) hipFree(dI); });
+	#define SCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { hu_set_error("%s: %s failed: %s", fn, #call, hipGetErrorString(e_)); return HU_ERR_DEVICE; } } while(0)
+	{
+		size_t freeB = 0, totB = 0;
+		SCHK(hipMemGetInfo(&freeB, &totB));
+		const size_t need = T * nOut + L * 8 + planBytes + 4096;
+		if(need > freeB) { hu_set_error("%s: %lld reads of %lld columns need %.3f GB of device memory, %.3f GB are free", fn, (long long) n, (long long) total, need / 1e9, freeB / 1e9); return HU_ERR_NOMEM; }
+	}
+	auto t0 = std::chrono::steady_clock::now();
+	auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
+	SCHK(hipMalloc((void**) &dOut, T * nOut)); SCHK(hipMalloc((void**) &dGap, L * 8)); SCHK(hipMalloc((void**) &dRc, R * 8));
+	SCHK(hipMalloc((void**) &dOff, R * 8)); SCHK(hipMalloc((void**) &dI, R * 16));
+	SCHK(hipMemcpy(dGap, gap_frac, L * 8, hipMemcpyHostToDevice)); SCHK(hipMemcpy(dRc, rc, R * 8, hipMemcpyHostToDevice));
+	SCHK(hipMemcpy(dOff, off.data(), R * 8, hipMemcpyHostToDevice));
+	SCHK(hipMemcpy(dI, node, R * 4, hipMemcpyHostToDevice)); SCHK(hipMemcpy(dI + R, start, R * 4, hipMemcpyHostToDevice)); SCHK(hipMemcpy(dI + 2 * R, end, R * 4, hipMemcpyHostToDevice));
+	SCHK(hipDeviceSynchronize());
+	g_simTiming[0] = since();
+	HuSimArgs a;
+	a.up = d.up; a.down = d.down; a.blen = d.blen; a.csLen = d.csLen; a.gapFrac = dGap;
+	a.node = dI; a.start = dI + R; a.end = dI + 2 * R; a.rc = dRc; a.off = dOff;
+	a.key0 = (uint32_t)(seed & 0xffffffffu); a.key1 = (uint32_t)(seed >> 32); a.read0 = read0;
+	a.aligned = dOut; a.seq = dOut + T; a.mate = want_mate ? dOut + 2 * T : nullptr; a.seqLen = dI + 3 * R;
+	(void) hipGetLastError();
+	k_sim_reads<<<(unsigned) n, HU_SIM_BLOCK>>>(db->mdl, a);
+	SCHK(hipGetLastError());
+	SCHK(hipDeviceSynchronize());
+	g_simTiming[1] = since() - g_simTiming[0];
+	/* into buffers of the library first: the caller's stay untouched unless every copy succeeds */
+	std::vector<char> hOut(T * nOut); std::vector<int32_t> hLen(R);
+	SCHK(hipMemcpy(hOut.data(), dOut, T * nOut, hipMemcpyDeviceToHost)); SCHK(hipMemcpy(hLen.data(), dI + 3 * R, R * 4, hipMemcpyDeviceToHost));
+	memcpy(aligned, hOut.data(), T); memcpy(seq_len, hLen.data(), R * 4);
+	/* the ungapped outputs hold seq_len[r] bytes at the read's offset; the rest of its room is cleared, not left as the device had it */
+	memset(seq, 0, T); if(want_mate) memset(mate, 0, T);
+	for(size_t r = 0; r < R; ++r) {
+		memcpy(seq + off[r], hOut.data() + T + off[r], (size_t) hLen[r]);
+		if(want_mate) memcpy(mate + off[r], hOut.data() + 2 * T + off[r], (size_t) hLen[r]);
+	}
+	g_simTiming[2] = since() - g_simTiming[0] - g_simTiming[1];
+	#undef SCHK
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_sim_reads"); }
+extern "C" int hu_sim_timing(double* seconds) {
+	if(!seconds) return HU_ERR_ARG;
+	memcpy(seconds, g_simTiming, sizeof(g_simTiming));
+	return HU_OK;
+}
+extern "C" int hu_sim_gap_frac(const hu_db* db, int64_t n_seq, int64_t msa_len, const char* msa, double* gap_frac) try {
+	const char* fn = "hu_sim_gap_frac";
+	if(!db || !gap_frac || (msa && (n_seq < 1 || msa_len < 1))) { hu_set_error("%s: bad argument", fn); return HU_ERR_ARG; }
+	const int64_t L = db->dev.csLen, n = db->dev.nNodes;
+	std::vector<char> own;
+	if(!msa) { /* the leaf rows of the database in node-id order, as text: a residue code as its letter, every other code as a gap */
+		std::vector<int32_t> nb((size_t) n, 0);
+		for(int64_t i = 0; i < n; ++i) if(db->parent[i] >= 0) { ++nb[i]; ++nb[db->parent[i]]; }
+		n_seq = 0;
+		for(int64_t i = 0; i < n; ++i) n_seq += nb[i] == 1;     /* PTUNode::isLeaf: one neighbour */
+		if(n_seq < 1) { hu_set_error("%s: the tree has no leaf", fn); return HU_ERR_ARG; }
+		own.resize((size_t) n_seq * L);
+		size_t k = 0;
+		for(int64_t i = 0; i < n; ++i) if(nb[i] == 1) { const int8_t* s = &db->seq[(size_t) i * L]; for(int64_t j = 0; j < L; ++j) { const int8_t b = s[j]; own[k++] = b >= 0 && b < 4 ? "ACGT"[b] : '-'; } }
+		msa = own.data(); msa_len = L;
+	}
+	const size_t M = (size_t) msa_len, N = (size_t) n_seq;
+	std::vector<int32_t> res(4 * M), gap(M), st(N), en(N), ln(N);
+	std::vector<double> sw(N), wres(4 * M), wgap(M);
+	const int rc = hu_msa_stats(db->device, n_seq, msa_len, msa, res.data(), gap.data(), st.data(), en.data(), ln.data(), sw.data(), wres.data(), wgap.data());
+	if(rc != HU_OK) return rc;
+	/* a given alignment is pruned as MSA::prune does; the database's own rows are its columns as they are (one written from arrays
+	 * may keep columns without a residue: all weight is gap weight there, the fraction is 1) */
+	const bool prune = own.empty();
+	int64_t kept = 0;
+	for(size_t j = 0; j < M; ++j) kept += !prune || (res[j] | res[M + j] | res[2 * M + j] | res[3 * M + j]) != 0;
+	if(kept != L) { hu_set_error("%s: %lld columns of the alignment hold a residue, the database has %lld columns", fn, (long long) kept, (long long) L); return HU_ERR_ARG; }
+	size_t k = 0;
+	for(size_t j = 0; j < M; ++j) {
+		if(prune && !(res[j] | res[M + j] | res[2 * M + j] | res[3 * M + j])) continue;     /* a column MSA::prune drops */
+		const double numRes = (wres[j] + wres[2 * M + j]) + (wres[M + j] + wres[3 * M + j]);     /* resWCount.col(j).sum(): Eigen's two-lane reduction */
+		gap_frac[k++] = wgap[j] / (numRes + wgap[j]);
+	}
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_sim_gap_frac"); }
 
 extern "C" int hu_device_mem_info(int device, int64_t* free_bytes, int64_t* total_bytes) try {
 	if(hu_device_count() <= 0) { hu_set_error("no gfx950 device visible: the engine has no CPU path"); return HU_ERR_DEVICE; }

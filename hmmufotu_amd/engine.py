@@ -390,6 +390,64 @@ def sm_write_text(model: ModelDesc) -> str:
     return buf.value.decode()
 
 
+class SimOpts(C.Structure):
+    _fields_ = [("max_dist", C.c_double), ("mean_size", C.c_double), ("sd_size", C.c_double), ("min_size", C.c_double), ("max_size", C.c_double),
+                ("n_regions", C.c_int64), ("regions", C.POINTER(C.c_int32))]
+
+
+def sim_philox(counter, key) -> np.ndarray:
+    """hu_sim_philox (host only): the four words of Philox4x32-10 for a counter [4] and a key [2], the generator of the simulated reads"""
+    c = np.ascontiguousarray(counter, np.uint32).ravel(); k = np.ascontiguousarray(key, np.uint32).ravel()
+    if len(c) != 4 or len(k) != 2:
+        raise EngineError("sim_philox: a counter of 4 words and a key of 2")
+    out = np.zeros(4, np.uint32)
+    _chk(load_library().hu_sim_philox(_p(c, C.c_uint32), _p(k, C.c_uint32), _p(out, C.c_uint32)))
+    return out
+
+
+def sim_plan(parent, blen, height, cs_len: int, n: int, seed: int, max_dist=np.inf, mean_size=500.0, sd_size=30.0, min_size=0.0, max_size=0.0,
+             regions=None, attempt=0, info=False) -> dict:
+    """hu_sim_plan (host only): node, rc, start, end of n reads by the rejection loop of hmmufotu-sim on a tree's arrays.  regions: the
+    (start, end) pairs of a BED file; those outside the consensus are dropped.  attempt: the first attempt number, for a plan made in
+    pieces; info=True adds the next one as "attempt"."""
+    parent = np.ascontiguousarray(parent, np.int32); blen = np.ascontiguousarray(blen, np.float64); height = np.ascontiguousarray(height, np.float64)
+    nn = len(parent)
+    if len(blen) != nn or len(height) != nn:
+        raise EngineError("sim_plan: parent, blen and height must have one entry per node")
+    o = SimOpts(float(max_dist), float(mean_size), float(sd_size), float(min_size), float(max_size), 0, None)
+    reg = np.ascontiguousarray(regions if regions is not None else [], np.int32).reshape(-1, 2)
+    if len(reg):
+        o.n_regions = len(reg); o.regions = _p(reg, C.c_int32)
+    out = dict(node=np.zeros(n, np.int32), rc=np.zeros(n), start=np.zeros(n, np.int32), end=np.zeros(n, np.int32))
+    att = C.c_int64(int(attempt))
+    _chk(load_library().hu_sim_plan(C.c_int32(nn), C.c_int32(int(cs_len)), _p(parent, C.c_int32), _p(blen, C.c_double), _p(height, C.c_double), C.byref(o),
+                                    C.c_uint64(int(seed) & (2 ** 64 - 1)), C.byref(att), C.c_int64(n), _p(out["node"], C.c_int32), _p(out["rc"], C.c_double),
+                                    _p(out["start"], C.c_int32), _p(out["end"], C.c_int32)))
+    if info:
+        out["attempt"] = int(att.value)
+    return out
+
+
+def sim_description(c: int, p: int, taxon_c: str, taxon_p: str, rc: float, start: int, end: int, seq_len: int) -> str:
+    """hu_sim_description (host only): the description of a simulated read's FASTA record as hmmufotu-sim writes it"""
+    lib = load_library()
+    lib.hu_sim_description.restype = C.c_int64
+    args = (C.c_int32(c), C.c_int32(p), taxon_c.encode(), taxon_p.encode(), C.c_double(rc), C.c_int32(start), C.c_int32(end), C.c_int64(seq_len))
+    n = int(lib.hu_sim_description(*args, None, C.c_int64(0)))
+    if n < 0:
+        _chk(n)
+    buf = C.create_string_buffer(n + 1)
+    lib.hu_sim_description(*args, buf, C.c_int64(n + 1))
+    return buf.value.decode()
+
+
+def sim_timing() -> dict:
+    """hu_sim_timing: the phases of this thread's last Database.sim_reads, in seconds"""
+    s = np.zeros(3)
+    _chk(load_library().hu_sim_timing(_p(s, C.c_double)))
+    return dict(to_device=s[0], kernel=s[1], to_host=s[2])
+
+
 def tree_count_mutations(parent, cs_len: int, up_ptr: int, device=0) -> np.ndarray:
     """hu_tree_count_mutations: per column, the non-root nodes whose inferred state differs from their parent's, from the DEVICE
     fixed-rate up buffer at up_ptr ([n][cs_len][4] float64, as tree_evaluate leaves it with win_len 0)"""
@@ -732,6 +790,52 @@ class Database:
                 s0, s1 = int(recs[r]["cs_start"]), int(recs[r]["cs_end"])
                 out.append(dict(strand=strands[i], cs_start=s0, cs_end=s1, alignment=rows[r][s0 - 1:s1], n_nodes=self.n_nodes,
                                 n_leaves=n_leaves, hit_nodes=int(hn[i]), hit_leaves=int(hl[i])))
+        return out
+
+    def tree(self) -> dict:
+        """hu_db_get_tree: parent, blen, height of every node and the node rows seq [n][cs_len]"""
+        out = dict(parent=np.zeros(self.n_nodes, np.int32), blen=np.zeros(self.n_nodes), height=np.zeros(self.n_nodes),
+                   seq=np.zeros((self.n_nodes, self.cs_len), np.int8))
+        _chk(load_library().hu_db_get_tree(self.h, _p(out["parent"], C.c_int32), _p(out["blen"], C.c_double), _p(out["seq"], C.c_int8), _p(out["height"], C.c_double)))
+        return out
+
+    def sim_plan(self, n: int, seed: int, **kw) -> dict:
+        """sim_plan on this database's tree (hmmufotu-sim's choice of branch, branch point and columns for n reads)"""
+        t = self.tree()
+        return sim_plan(t["parent"], t["blen"], t["height"], self.cs_len, n, seed, **kw)
+
+    def sim_gap_frac(self, msa=None) -> np.ndarray:
+        """hu_sim_gap_frac: MSA::gapWFrac of every column, from the alignment msa (rows as for msa_stats; its columns with a residue must
+        be this database's) or, without one, from the database's own leaf rows in node-id order"""
+        out = np.zeros(self.cs_len)
+        if msa is None:
+            _chk(load_library().hu_sim_gap_frac(self.h, C.c_int64(0), C.c_int64(0), None, _p(out, C.c_double)))
+        else:
+            a = _msa_rows(msa, "sim_gap_frac")
+            _chk(load_library().hu_sim_gap_frac(self.h, C.c_int64(a.shape[0]), C.c_int64(a.shape[1]), a.ctypes.data_as(C.c_char_p), _p(out, C.c_double)))
+        return out
+
+    def sim_reads(self, plan, gap_frac, seed: int, read0=0, mate=False) -> dict:
+        """hu_sim_reads: the reads of a plan (node, rc, start, end as sim_plan returns them), read r being global read read0 + r of the
+        seed.  aligned: per read its columns as a str of ACGT-; seq: the same without '-'; mate (mate=True): the reverse complement of
+        seq; seq_len [n]."""
+        node = np.ascontiguousarray(plan["node"], np.int32); rc = np.ascontiguousarray(plan["rc"], np.float64)
+        st = np.ascontiguousarray(plan["start"], np.int32); en = np.ascontiguousarray(plan["end"], np.int32)
+        gf = np.ascontiguousarray(gap_frac, np.float64)
+        n = len(node)
+        if len(rc) != n or len(st) != n or len(en) != n or len(gf) != self.cs_len:
+            raise EngineError("sim_reads: a plan of %d reads needs %d entries per array, and gap_frac one per column" % (n, n))
+        cols = np.maximum(en.astype(np.int64) - st + 1, 0)
+        off = np.concatenate([[0], np.cumsum(cols)]).astype(np.int64)
+        total = max(int(off[-1]), 1)
+        al = np.zeros(total, np.uint8); sq = np.zeros(total, np.uint8); mt = np.zeros(total if mate else 1, np.uint8); ln = np.zeros(max(n, 1), np.int32)
+        _chk(load_library().hu_sim_reads(self.h, C.c_int64(n), _p(node, C.c_int32), _p(rc, C.c_double), _p(st, C.c_int32), _p(en, C.c_int32), _p(gf, C.c_double),
+                                         C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(read0)), C.c_int(int(mate)), al.ctypes.data_as(C.c_char_p),
+                                         sq.ctypes.data_as(C.c_char_p), mt.ctypes.data_as(C.c_char_p), _p(ln, C.c_int32)))
+        ab, sb, mb = al.tobytes(), sq.tobytes(), mt.tobytes()
+        out = dict(aligned=[ab[off[r]:off[r + 1]].decode() for r in range(n)], seq=[sb[off[r]:off[r] + ln[r]].decode() for r in range(n)], seq_len=ln[:n].copy())
+        if mate:
+            out["mate"] = [mb[off[r]:off[r] + ln[r]].decode() for r in range(n)]
         return out
 
     def otu_consensus(self):

@@ -664,6 +664,76 @@ int hu_sm_train(int type, int64_t n_items, const double* mats, const int32_t* pa
  * bytes, terminator included; negative on a bad argument. */
 int64_t hu_sm_write_text(const hu_model_desc* model, char* buf, int64_t cap);
 
+/* ---- simulated reads with a known answer (hmmufotu-sim) --------------------------------------------------------
+ * The loop of src/hmmufotu-sim.cpp:351-424 in three steps: which branch, branch point and columns every read takes (host), the
+ * sites of all reads (device), the description of a record (host).  Random numbers are Philox4x32-10 words keyed by the seed,
+ * key = (seed & 0xffffffff, seed >> 32); a uniform of [0, 1) is ((hi >> 5) * 2^26 + (lo >> 6)) * 2^-53 of two words.  The reference
+ * draws from Boost's mt11213b: the distributions are the reference's, the streams are not.
+ *
+ * hu_sim_philox: out [4] = Philox4x32-10(counter [4], key [2]), the code host and device share; for known-answer tests. */
+int hu_sim_philox(const uint32_t* counter, const uint32_t* key, uint32_t* out);
+/* The options of the rejection loop: -d, -m, -s, -l, -u and the (start, end) pairs of the -R BED file as read (columns 2 and 3). */
+typedef struct {
+	double max_dist;            /* a read's point is at most this far above a leaf; +inf: anywhere */
+	double mean_size, sd_size;  /* amplicon size ~ normal(mean, sd) */
+	double min_size, max_size;  /* clamps; max_size 0: none */
+	int64_t n_regions;          /* 0: reads start anywhere on the consensus */
+	const int32_t* regions;     /* [n_regions][2] */
+} hu_sim_opts;
+void hu_sim_default_opts(hu_sim_opts* o);     /* src/hmmufotu-sim.cpp:56-60: inf, 500, 30, 0, 0; no regions */
+/* whether a BED line (s, e) gives a region: 0 <= s < e < cs_len.  The reference (:303) also takes e == cs_len and then reads one
+ * column past the alignment; here that line is dropped like the others outside the consensus. */
+int hu_sim_region_ok(int32_t s, int32_t e, int32_t cs_len);
+/* The rejection loop of src/hmmufotu-sim.cpp:351-380 for n reads, on the arrays of hu_db_get_tree (or of any tree: no device).
+ * A node is drawn uniformly among those with height <= max_dist (node_dist, :337-344) and the branch point rc uniformly in [0, 1);
+ * the attempt is dropped when the node is the root, when height[c] + blen[c] * rc > max_dist, or when end >= cs_len.  Without
+ * regions start is uniform on [0, cs_len - 1], len = (int) normal(mean, sd) (Box-Muller), raised to (int) min_size, cut to
+ * (int) max_size when that is above 0, and end = start + len: len + 1 columns, as the reference's inclusive loop walks them.  With
+ * regions a uniformly chosen accepted line (s, e) gives start = s + 1, end = e (the reference's own off-by-one), and when no line is
+ * accepted the reads start anywhere, as in the reference.  One deviation: a negative len (end < start, an empty record in the
+ * reference) is dropped too.
+ * Attempt number a draws from the counters (b, a & 0xffffffff, a >> 32, 1): block b = 0 gives the node (words 0, 1) and rc (2, 3),
+ * b = 1 the start or the region (0, 1), b = 2 the two uniforms of the normal.  *attempt: in, the first attempt number (0 for a new
+ * plan); out, the next one: a plan made in pieces is the plan made at once, so it depends on (seed, options) alone.
+ * HU_ERR_ARG: sizes the reference's option checks refuse, no node below the root within max_dist, min_size >= cs_len without
+ * regions, or ten million attempts in a row without a read. */
+int hu_sim_plan(int32_t n_nodes, int32_t cs_len, const int32_t* parent, const double* blen, const double* height, const hu_sim_opts* o,
+		uint64_t seed, int64_t* attempt, int64_t n, int32_t* node, double* rc, int32_t* start, int32_t* end);
+/* MSA::gapWFrac(j) = gapWCount(j) / (resWCount.col(j).sum() + gapWCount(j)) (src/MSA.cpp:71-75) of every column, from hu_msa_stats on
+ * the database's device; the four weighted residue counts are summed as (A + G) + (C + T).  gap_frac: [cs_len].
+ * msa: n_seq rows of msa_len bytes as read, restricted to the columns MSA::prune keeps (at least one residue); their number must be
+ * the database's cs_len (HU_ERR_ARG otherwise).  msa == NULL: the database's own leaf rows (nodes with one neighbour) in node-id
+ * order, rewritten as text (a residue as its letter, any other code as '-'), every column kept: a column without a residue, which
+ * only a database made from arrays can have, gets the fraction 1.  A .ptu keeps the leaf rows of the .msa it was built
+ * with, so the second form differs from the reference's <DB>.msa only in the order of the rows, i.e. in the order the weighted
+ * counts are summed. */
+int hu_sim_gap_frac(const hu_db* db, int64_t n_seq, int64_t msa_len, const char* msa, double* gap_frac);
+/* The per-site loop of src/hmmufotu-sim.cpp:393-409 for n reads at once (k_sim_reads, one workgroup per read).  Read r lies on the
+ * branch above node[r], blen * rc[r] above the node, and covers the columns start[r] .. end[r].  At column j
+ *   w = Philox(counter (j, g & 0xffffffff, g >> 32, 0)), g = read0 + r;   u_gap from words 0, 1;   u_base from words 2, 3;
+ *   a gap when u_gap <= gap_frac[j] (:394); else q = exp(rLoglik - max) of :401-405, computed from the packed messages as
+ *   q_i = max((Pr(v rc) msg(c -> p))_i (Pr(v (1 - rc)) msg(p -> c))_i, 0) with the plain model's Pr (no discrete-Gamma rates, as in
+ *   the reference), S = q0 + q1 + q2 + q3 summed in that order, t = u_base * S, and the base is the first i with
+ *   t < q0 + ... + q_i, else 3.
+ * Outputs (host).  off[r] = the columns of the reads before r.  aligned: at off[r] the end - start + 1 characters "ACGT-" of the
+ * read; seq: at off[r] the same without '-', seq_len[r] of them, the rest of the read's room zeroed; mate (want_mate != 0, else
+ * ignored): likewise the reverse complement of seq.  Each needs the sum of all reads' columns in bytes.
+ * The same (seed, read0 + r) gives the same read in any call.  hu_sim_timing: of this thread's last call, seconds [3] = allocation
+ * and copies to the device, the kernel, the copies back.
+ * HU_ERR_ARG, with the outputs untouched and before anything reaches the device: a node outside [0, n_nodes) or the root, columns
+ * that are not 0 <= start <= end < cs_len, an rc outside [0, 1], a database that keeps a column window (hu_db_load_window). */
+int hu_sim_reads(const hu_db* db, int64_t n, const int32_t* node, const double* rc, const int32_t* start, const int32_t* end,
+		const double* gap_frac, uint64_t seed, uint64_t read0, int want_mate, char* aligned, char* seq, char* mate, int32_t* seq_len);
+int hu_sim_timing(double* seconds /* [3] */);
+/* host only: the description of a read's FASTA record (src/hmmufotu-sim.cpp:384-386, 413-416),
+ *   branchID=<c>-><p>;taxonID=<id>;taxonName="<name>";branchPoint=<rc>;csStart=<start>;csEnd=<end>;seqLen=<seq_len>;
+ * id and name are those of c when rc <= 0.5, else of p; taxon_c / taxon_p: PTUNode::getTaxon() of the two nodes, which is
+ * hu_db_get_annotation (with ";Other" appended when hu_db_get_anno_dist is NaN: getTaxon's maxDist is inf).  rc as
+ * boost::lexical_cast<string>(double) writes it, %.17g.  seq_len: the length of the record's sequence before -r cuts it.  Returns the
+ * length (without the terminator) and writes at most cap bytes, terminator included; HU_ERR_ARG (negative) on a null argument. */
+int64_t hu_sim_description(int32_t c, int32_t p, const char* taxon_c, const char* taxon_p, double rc, int32_t start, int32_t end, int64_t seq_len,
+		char* out, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif
