@@ -1,4 +1,5 @@
-// The inputs of the programs that start from a reference MSA and its tree (hmmufotu-amd-build, hmmufotu-amd-train-sm): what
+// The inputs of the programs that start from a reference MSA and its tree (hmmufotu-amd-build, hmmufotu-amd-train-sm; hmmufotu-amd-train-hmm
+// takes the MSA alone): what
 // src/hmmufotu-build.cpp:198-208, :346-392 and src/hmmufotu-train-sm.cpp:133-229 do before the model is used.  The FASTA reader
 // (.gz / .bz2), hu_newick_parse with the reference's node ids and file-order children, the join of leaves and rows by name with the
 // reference's messages (PTUnrooted::loadMSA, src/PhyloTreeUnrooted.cpp:185-221), and MSA::prune (src/MSA.cpp:87-138) behind
@@ -40,6 +41,8 @@ struct HuBuildInputs {
 	/* the prune: the columns kept, and the counts of hu_msa_stats over the columns as read */
 	std::vector<uint32_t> keep; int32_t L = 0;
 	std::vector<int32_t> res, gap; std::vector<double> wres, wgap;
+	/* per row, from the same call: first / last residue column as read (-1: none) and the normalised sequence weight */
+	std::vector<int32_t> start, end; std::vector<double> weight;
 };
 
 /* guess input format (src/hmmufotu-build.cpp:198-208) */
@@ -103,9 +106,9 @@ static bool hu_join_msa_tree(HuBuildInputs& in, const HuInfo& info) {
 static bool hu_prune_msa(int device, HuBuildInputs& in, const HuInfo& info, std::string& err) {
 	const size_t L0 = in.L0, nSeq = in.nSeq;
 	in.res.resize(4 * L0); in.gap.resize(L0); in.wres.resize(4 * L0); in.wgap.resize(L0);
-	std::vector<int32_t> st(nSeq), en(nSeq), ln(nSeq);
-	std::vector<double> w(nSeq);
-	if(hu_msa_stats(device, (int64_t) nSeq, (int64_t) L0, in.msa.data(), in.res.data(), in.gap.data(), st.data(), en.data(), ln.data(), w.data(), in.wres.data(), in.wgap.data()) != HU_OK) {
+	std::vector<int32_t> ln(nSeq);
+	in.start.resize(nSeq); in.end.resize(nSeq); in.weight.resize(nSeq);
+	if(hu_msa_stats(device, (int64_t) nSeq, (int64_t) L0, in.msa.data(), in.res.data(), in.gap.data(), in.start.data(), in.end.data(), ln.data(), in.weight.data(), in.wres.data(), in.wgap.data()) != HU_OK) {
 		err = hu_last_error(); return false;
 	}
 	in.keep.clear();

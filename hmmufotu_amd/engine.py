@@ -390,6 +390,94 @@ def sm_write_text(model: ModelDesc) -> str:
     return buf.value.decode()
 
 
+HMM_MAX_MIX = 32
+
+
+class HmmPrior(C.Structure):
+    """hu_hmm_prior: the five Dirichlet models of a .dm file"""
+    _fields_ = [("me_L", C.c_int32), ("pad0", C.c_int32), ("me_q", C.c_double * HMM_MAX_MIX), ("me_alpha", (C.c_double * HMM_MAX_MIX) * 4),
+                ("ie_alpha", C.c_double * 4), ("mt_alpha", C.c_double * 3), ("it_alpha", C.c_double * 2), ("dt_alpha", C.c_double * 2)]
+
+    def as_dict(self) -> dict:
+        L = int(self.me_L)
+        return dict(me_q=np.array(self.me_q[:L]), me_alpha=np.array([list(r[:L]) for r in self.me_alpha]), ie_alpha=np.array(self.ie_alpha[:]),
+                    mt_alpha=np.array(self.mt_alpha[:]), it_alpha=np.array(self.it_alpha[:]), dt_alpha=np.array(self.dt_alpha[:]))
+
+
+def hmm_prior_read(path: str) -> HmmPrior:
+    """hu_hmm_prior_read (host only): the prior file (.dm) of hmmufotu-train-hmm — a Dirichlet mixture for the match emissions and four
+    Dirichlet densities for the insert emissions and the M, I and D transitions.  A damaged file raises EngineError."""
+    p = HmmPrior()
+    _chk(load_library().hu_hmm_prior_read(os.fsencode(str(path)), C.byref(p)))
+    return p
+
+
+def hmm_match_columns(res_wcount, gap_wcount, n_seq: int, symfrac=0.5) -> dict:
+    """hu_hmm_match_columns (host only): from the weighted counts of msa_stats over the pruned columns (res_wcount [4][L], gap_wcount [L])
+    the match columns of a profile: mask [L], K, and per profile position map (1-based column), cons (str) and identity"""
+    rw = np.ascontiguousarray(res_wcount, np.float64); gw = np.ascontiguousarray(gap_wcount, np.float64).ravel()
+    if rw.ndim != 2 or rw.shape[0] != 4 or rw.shape[1] != len(gw) or len(gw) == 0:
+        raise EngineError("hmm_match_columns: res_wcount must be [4][L] and gap_wcount [L]")
+    L = len(gw)
+    mask = np.zeros(L, np.uint8); mp = np.zeros(L, np.int32); cons = C.create_string_buffer(L); ident = np.zeros(L); K = C.c_int32(0)
+    _chk(load_library().hu_hmm_match_columns(C.c_int64(L), C.c_int64(int(n_seq)), _p(rw, C.c_double), _p(gw, C.c_double), C.c_double(symfrac),
+                                             _p(mask, C.c_uint8), C.byref(K), _p(mp, C.c_int32), cons, _p(ident, C.c_double)))
+    k = int(K.value)
+    return dict(mask=mask.astype(bool), K=k, map=mp[:k].copy(), cons=cons.raw[:k].decode(), identity=ident[:k].copy())
+
+
+def hmm_counts(rows, weight, start, end, mask, device=0) -> dict:
+    """hu_hmm_counts, on the device: the raw weighted counts of BandedHMMP7::build over the pruned alignment rows (list of equal-length
+    str/bytes, or a uint8 [n][L] array) with the weights, starts and ends of msa_stats and the mask of hmm_match_columns:
+    e_m [K+1][4] (row 0: COMPO), e_i [K+1][4], t [K+1][3][3] indexed (from, to) with M, I, D = 0, 1, 2"""
+    a = _msa_rows(rows, "hmm_counts")
+    n, L = a.shape
+    w = np.ascontiguousarray(weight, np.float64).ravel(); st = np.ascontiguousarray(start, np.int32).ravel(); en = np.ascontiguousarray(end, np.int32).ravel()
+    m = np.ascontiguousarray(np.asarray(mask).astype(bool), np.uint8).ravel()
+    if len(w) != n or len(st) != n or len(en) != n or len(m) != L:
+        raise EngineError("hmm_counts: %d rows x %d columns, %d weights, %d starts, %d ends, a mask of %d" % (n, L, len(w), len(st), len(en), len(m)))
+    K = int(m.sum())
+    out = dict(e_m=np.zeros((K + 1, 4)), e_i=np.zeros((K + 1, 4)), t=np.zeros((K + 1, 3, 3)))
+    _chk(load_library().hu_hmm_counts(C.c_int(device), C.c_int64(n), C.c_int64(L), a.ctypes.data_as(C.c_char_p), _p(w, C.c_double), _p(st, C.c_int32),
+                                      _p(en, C.c_int32), _p(m, C.c_uint8), C.c_int32(K), _p(out["e_m"], C.c_double), _p(out["e_i"], C.c_double),
+                                      _p(out["t"], C.c_double)))
+    return out
+
+
+def hmm_counts_timing() -> dict:
+    """hu_hmm_counts_timing: the phases of this thread's last hmm_counts, in seconds, and the device memory it held"""
+    s = np.zeros(4); peak = C.c_int64(0)
+    _chk(load_library().hu_hmm_counts_timing(_p(s, C.c_double), C.byref(peak)))
+    return dict(to_device=s[0], states_kernel=s[1], counts_kernel=s[2], to_host=s[3], peak_bytes=int(peak.value))
+
+
+def hmm_estimate(e_m, e_i, t, n_seq: int, prior: HmmPrior) -> dict:
+    """hu_hmm_estimate (host only): the effective sequence number by bisection on the mean relative entropy and the probabilities of the
+    profile, priors applied: p_m, p_i [K+1][4], p_t [K+1][3][3], eff_n, passes"""
+    em = np.ascontiguousarray(e_m, np.float64); ei = np.ascontiguousarray(e_i, np.float64); tt = np.ascontiguousarray(t, np.float64)
+    if em.ndim != 2 or em.shape[1] != 4 or em.shape[0] < 2 or ei.shape != em.shape or tt.shape != (em.shape[0], 3, 3):
+        raise EngineError("hmm_estimate: counts must be e_m [K+1][4], e_i [K+1][4], t [K+1][3][3] with K >= 1")
+    K = em.shape[0] - 1
+    out = dict(p_m=np.zeros_like(em), p_i=np.zeros_like(ei), p_t=np.zeros_like(tt))
+    eff = C.c_double(0); passes = C.c_int32(0)
+    _chk(load_library().hu_hmm_estimate(C.c_int32(K), _p(em, C.c_double), _p(ei, C.c_double), _p(tt, C.c_double), C.c_int64(int(n_seq)), C.byref(prior),
+                                        _p(out["p_m"], C.c_double), _p(out["p_i"], C.c_double), _p(out["p_t"], C.c_double), C.byref(eff), C.byref(passes)))
+    out["eff_n"] = float(eff.value); out["passes"] = int(passes.value)
+    return out
+
+
+def hmm_write(path, p_m, p_i, p_t, map, cons, cs_len: int, n_seq: int, eff_n: float, name="unnamed", version="hmmufotu_amd", date=""):
+    """hu_hmm_write (host only): the profile as the text of the reference's operator<<, costs at 6 significant digits"""
+    pm = np.ascontiguousarray(p_m, np.float64); pi = np.ascontiguousarray(p_i, np.float64); pt = np.ascontiguousarray(p_t, np.float64)
+    mp = np.ascontiguousarray(map, np.int32).ravel(); cs = cons.encode() if isinstance(cons, str) else bytes(cons)
+    K = pm.shape[0] - 1
+    if pm.ndim != 2 or pm.shape[1] != 4 or pi.shape != pm.shape or pt.shape != (K + 1, 3, 3) or len(mp) != K or len(cs) != K:
+        raise EngineError("hmm_write: p_m, p_i [K+1][4], p_t [K+1][3][3], map and cons of K entries")
+    _chk(load_library().hu_hmm_write(os.fsencode(str(path)), str(version).encode(), str(name).encode(), C.c_int32(K), C.c_int32(int(cs_len)),
+                                     _p(pm, C.c_double), _p(pi, C.c_double), _p(pt, C.c_double), _p(mp, C.c_int32), cs, C.c_int64(int(n_seq)),
+                                     C.c_double(eff_n), str(date).encode()))
+
+
 class SimOpts(C.Structure):
     _fields_ = [("max_dist", C.c_double), ("mean_size", C.c_double), ("sd_size", C.c_double), ("min_size", C.c_double), ("max_size", C.c_double),
                 ("n_regions", C.c_int64), ("regions", C.POINTER(C.c_int32))]

@@ -734,6 +734,74 @@ int hu_sim_timing(double* seconds /* [3] */);
 int64_t hu_sim_description(int32_t c, int32_t p, const char* taxon_c, const char* taxon_p, double rc, int32_t start, int32_t end, int64_t seq_len,
 		char* out, int64_t cap);
 
+/* ---- training the profile HMM (hmmufotu-train-hmm) --------------------------------------------------------------
+ * BandedHMMP7::build (src/BandedHMMP7.cpp:386-541) in five steps: the prior file (host), which columns are match columns (host),
+ * the weighted counts over all cells (device), the effective sequence number and the probabilities (host), the file (host).
+ * All arrays are row-major; E_M / E_I are [K + 1][4] (row 0 of E_M: COMPO), T is [K + 1][3][3] indexed (from, to) with M = 0, I = 1,
+ * D = 2 (p7_state, src/BandedHMMP7.h:157).
+ *
+ * hu_hmm_prior_read: operator>> of BandedHMMP7Prior (src/BandedHMMP7Prior.cpp:39-62) with DirichletMixture::read
+ * (src/math/DirichletMixture.cpp:254-285) and DirichletDensity::read (src/math/DirichletDensity.cpp:135-162): five blocks, each a
+ * head line ("Match emission:", "Insert emission:", "Match transition:", "Insert transition:", "Delete transition:") followed by a
+ * model.  Stricter than the reference, which reads whatever sscanf and operator>> leave: every label line must be there, every
+ * number must parse and be finite, alpha > 0, q >= 0, the five blocks must all be present with dimensions 4 (L components, 1 <= L <=
+ * HU_HMM_MAX_MIX) / 4 / 3 / 2 / 2.  HU_ERR_IO with the block and the reason otherwise. */
+#define HU_HMM_MAX_MIX 32
+typedef struct {
+	int32_t me_L, pad0;                        /* components of the match-emission mixture */
+	double me_q[HU_HMM_MAX_MIX];               /* mixture coefficients */
+	double me_alpha[4][HU_HMM_MAX_MIX];        /* alpha(i, j): residue i, component j, as the file lays it out */
+	double ie_alpha[4], mt_alpha[3], it_alpha[2], dt_alpha[2];
+} hu_hmm_prior;
+int hu_hmm_prior_read(const char* path, hu_hmm_prior* out);
+/* The match columns (src/BandedHMMP7.cpp:405-411, :517-530), host only, from the weighted counts of hu_msa_stats restricted to the
+ * pruned columns: res_wcount [4][cs_len], gap_wcount [cs_len].  Column j is a match column when MSA::symWFrac(j) >= symfrac
+ * (src/MSA.cpp:77-81), numRes / (numRes + gapWCount) with numRes = (A + G) + (C + T); a column without weight (NaN) is none.
+ * Outputs: mask [cs_len] (1 = match); *K; for k = 1 .. K at index k - 1: map (the 1-based column, the MAP tag), cons (MSA::CSBaseAt,
+ * the first maximum of the weighted counts, lower-case when wIdentityAt < CONS_THRESHOLD = 0.9) and identity (MSA::wIdentityAt,
+ * :65-67, the maximum / n_seq); each has cs_len entries of room.  HU_ERR_ARG: symfrac outside the open interval (0, 1) as build()
+ * throws (:390-391), more than 65,535 columns (kMaxCS, src/BandedHMMP7.h:279: the reference's index arrays end there), or K = 0. */
+int hu_hmm_match_columns(int64_t cs_len, int64_t n_seq, const double* res_wcount, const double* gap_wcount, double symfrac,
+		uint8_t* mask, int32_t* K, int32_t* map, char* cons, double* identity);
+/* The counting loops of src/BandedHMMP7.cpp:424-477 on the device (k_hmm_states, k_hmm_counts: hu_kern_hmm.h).  msa: n_seq rows of
+ * cs_len bytes, the pruned text as read; weight / start / end [n_seq]: seq_weight, start and end of hu_msa_stats, the columns
+ * renumbered after the prune; mask [cs_len] and K of hu_hmm_match_columns.  Outputs, host, raw weighted counts: e_m, e_i [K + 1][4],
+ * t [K + 1][9].  Per cell (i, j) with state sm (determineMatchingState, src/BandedHMMP7.h:713-716; a byte is a residue when
+ * hu_msa_encode_table gives >= 0) and k = the match columns at or before j: M adds w to e_m(k, b) and to COMPO, I to e_i(k, b), and
+ * t(k)(sm, smN) gets w where smN is the state of the nearest non-P cell right of j on the row, if there is one and the pair is
+ * neither I->D nor D->I (the reference reads an unassigned variable there).  Then every row adds w to
+ * t(0)(M, state at start) and to t(K)(state at end, M); a row with start < 0 (no residue) adds nothing anywhere.
+ * Every column has its own sums in ascending i; the host adds the columns of one k up in ascending j.  Needs 2 n_seq cs_len bytes of
+ * device memory: HU_ERR_NOMEM with the bytes needed and the bytes free.  HU_ERR_ARG, before a device is asked for: cs_len above
+ * 65,535, a mask that does not hold K match columns, a weight that is negative or not finite, a start / end outside the row or on a
+ * byte that is no residue.  hu_hmm_counts_timing: of this thread's last call, seconds [4] = allocation and copies to the device,
+ * k_hmm_states, k_hmm_counts, the copy back and the host's sums; *peak_bytes: device memory in use during the call beyond what was
+ * in use before it, by hipMemGetInfo. */
+int hu_hmm_counts(int device, int64_t n_seq, int64_t cs_len, const char* msa, const double* weight, const int32_t* start, const int32_t* end,
+		const uint8_t* mask, int32_t K, double* e_m, double* e_i, double* t);
+int hu_hmm_counts_timing(double* seconds /* [4] */, int64_t* peak_bytes);
+/* effN and the probabilities (src/BandedHMMP7.cpp:479-494), host only.  e_m, e_i, t: the counts above; n_seq: the rows of the MSA.
+ * effN is RootFinder::rootBisection (src/math/RootFinder.cpp:22-76; absEps = relEps = 1e-10, resEps = 0, no iteration limit) on
+ * [0, n_seq] of RelativeEntropyTargetFunc (src/BandedHMMP7.cpp:1122-1135): the counts scaled by x / n_seq (scale, :248-257),
+ * estimateParams (:280-315) with DirichletMixture::meanPostP (src/math/DirichletMixture.cpp:45-61) on the match emissions and
+ * DirichletDensity::meanPostP (src/math/DirichletDensity.cpp:25-27) on the rest, then meanRelativeEntropy (:317-322) in bits
+ * (src/math/LinearAlgebraBasic.h:90-98) against the uniform background, minus DEFAULT_ERE = 1.  The function is pure, so the two
+ * evaluations at the bracket's ends that the reference repeats on every pass are not repeated.  No sign change: effN = n_seq.
+ * Then the counts are scaled by effN / n_seq and estimated once more, specials included (T[0](D,M) = 1, T[0](D,D) = 0, T[K](M,D) = 0,
+ * T[K](D,M) = 1, T[K](D,D) = 0; T[K].row(M) is not renormalised).  Outputs: probabilities in the layout of the inputs (which they
+ * may not alias), *eff_n, *passes = the bisection passes taken (0 without a sign change).  Sums of 4 are (x0 + x2) + (x1 + x3), of
+ * 3 (x0 + x1) + x2. */
+int hu_hmm_estimate(int32_t K, const double* e_m, const double* e_i, const double* t, int64_t n_seq, const hu_hmm_prior* prior,
+		double* p_m, double* p_i, double* p_t, double* eff_n, int32_t* passes);
+/* operator<< of BandedHMMP7 (src/BandedHMMP7.cpp:324-378) for a trained profile: HMMER3/f <version>, NAME, LENG, ALPH DNA, the tags
+ * MAXL RF MM CONS CS MAP NSEQ EFFN DATE in the order build() sets them (:497-538; EFFN as %g, date: the DATE value, written as
+ * given), the HMM header, then per k the match line (k = 0: COMPO) with MAP, CONS and "-" for RF, MM and CS, the insert line and the
+ * transition line m->m m->i m->d i->m i->i d->m d->d.  Every number is the cost -log p at 6 significant digits (%g, the stream's
+ * default); infinity is "*" on the insert and transition lines and "inf" on the match line, as Eigen prints it.  map, cons: as
+ * hu_hmm_match_columns returns them.  path "-": the standard output.  Returns HU_ERR_IO when the file cannot be written. */
+int hu_hmm_write(const char* path, const char* version, const char* name, int32_t K, int32_t cs_len, const double* p_m, const double* p_i,
+		const double* p_t, const int32_t* map, const char* cons, int64_t n_seq, double eff_n, const char* date);
+
 #ifdef __cplusplus
 }
 #endif
