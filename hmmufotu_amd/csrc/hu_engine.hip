@@ -2514,6 +2514,18 @@ extern "C" int hu_estimate_batch(hu_batch* b, const hu_opts* o) try {
 				else if(spt <= 8) k_estimate_blk<8, 256><<<eg, 256, 0, b->stream>>>(EST_ARGS);
 				else k_estimate_blk<12, 256><<<eg, 256, 0, b->stream>>>(EST_ARGS);
 			}
+			else if(var == 98 && spt > 4 && spt <= 6) { /* diagnostic: the shipped 6-site instance with s_memtime stamps, averaged over the slots that ran, to stderr */
+				DBuf<long long> ddb;
+				if((rc = ddb.ensure((size_t) egl * 4)) != HU_OK) return rc;
+				HIPCHK(hipMemsetAsync(ddb.p, 0, (size_t) egl * 4 * sizeof(long long), b->stream));
+				k_estimate_prod<6, 4, 4, true><<<egl, 256, 0, b->stream>>>(EST_ARGS, order, xm, ddb.p);
+				std::vector<long long> hd((size_t) egl * 4);
+				HIPCHK(hipMemcpyAsync(hd.data(), ddb.p, hd.size() * sizeof(long long), hipMemcpyDeviceToHost, b->stream));
+				HIPCHK(hu_wait(b->stream));
+				double acc[4] = {0}; size_t ran = 0;
+				for(size_t c = 0; c < (size_t) egl; ++c) if(hd[c * 4 + 3]) { ++ran; for(int i = 0; i < 4; ++i) acc[i] += (double) hd[c * 4 + i]; }
+				if(ran) fprintf(stderr, "[est dbg] per slot (s_memtime ticks, %zu slots): prologue %.0f load %.0f rest %.0f total %.0f\n", ran, acc[0] / ran, acc[1] / ran, acc[2] / ran, acc[3] / ran);
+			}
 			else if(var == 1 && spt <= 6) k_estimate_prod<12, 2><<<egl, 128, 0, b->stream>>>(EST_ARGS, order, xm);
 			else if(var == 3 && spt <= 6) k_estimate_prod<6, 4, 1><<<egl, 256, 0, b->stream>>>(EST_ARGS, order, xm);
 			else if(spt <= 2) k_estimate_prod<2, 4><<<egl, 256, 0, b->stream>>>(EST_ARGS, order, xm);
@@ -2714,14 +2726,23 @@ extern "C" int hu_place_batch(hu_batch* b, const hu_opts* o) try {
 					if((rc = ddb.ensure(nc * 12)) != HU_OK) return rc;
 					long long* dd = ddb.p;
 					HIPCHK(hipMemsetAsync(dd, 0, nc * 12 * sizeof(long long), b->stream));
+					/* place_var = 98 stamps the instance that the batch would take, in its launch order: the split form (GS = 10, sites through the
+					 * site list) where every read fits its slots, the column-order form (GS = 0) otherwise or with place_nosplit */
+					const bool split98 = var == 98 && !pass && !b->knob.place_nosplit && spt2 > 8 && b->maxGapSites <= 10 * 128 && b->maxBaseSites <= 2 * 128;
 					if(var == 99) k_place_blk<6, 4, 3, 0, 1, true><<<grid, 256, 0, b->stream>>>(PL_ARGS, dd);
-					else k_place_blk<12, 2, 3, 0, 2, true, 1><<<grid, 128, 0, b->stream>>>(PL_ARGS, dd);
+					else if(split98) {
+						if((rc = b->dPerm.ensure((size_t) b->n * 12 * 128)) != HU_OK) return rc;
+						k_site_perm<<<b->n, 64, 0, b->stream>>>(dev, b->n, b->dCodes.p, b->dStart.p, b->dEnd.p, 10 * 128, 2 * 128, b->dPerm.p);
+						k_place_blk<12, 2, 3, 0, 2, true, 1, 10><<<grid, 128, 0, b->stream>>>(PL_ARGS, dd, order, b->dPerm.p, b->dPermCnt.p, xm);
+					}
+					else k_place_blk<12, 2, 3, 0, 2, true, 1><<<grid, 128, 0, b->stream>>>(PL_ARGS, dd, order, nullptr, nullptr, xm);
 					std::vector<long long> hd(nc * 12);
 					HIPCHK(hipMemcpyAsync(hd.data(), dd, nc * 12 * sizeof(long long), hipMemcpyDeviceToHost, b->stream));
 					HIPCHK(hu_wait(b->stream));
 					double acc[8] = {0}, ae[4] = {0};
 					for(size_t c = 0; c < nc; ++c) { for(int i = 0; i < 8; ++i) acc[i] += (double) hd[c * 8 + i]; for(int i = 0; i < 4; ++i) ae[i] += (double) hd[nc * 8 + c * 4 + i]; }
-					fprintf(stderr, "[place dbg] per candidate (s_memtime ticks): load %.0f tables %.0f sweeps %.0f em %.0f total %.0f | outer %.2f em steps %.2f\n",
+					fprintf(stderr, "[place dbg] %s, per candidate (s_memtime ticks): load %.0f tables %.0f sweeps %.0f em %.0f total %.0f | outer %.2f em steps %.2f\n",
+							var == 99 ? "4 waves x 6 sites" : split98 ? "2 waves x 12 sites, gap/base split slots" : "2 waves x 12 sites, column order",
 							acc[0] / nc, acc[1] / nc, acc[2] / nc, acc[3] / nc, acc[4] / nc, acc[5] / nc, acc[6] / nc);
 					fprintf(stderr, "[place dbg] inside the EM steps, per step: arithmetic %.0f wave reduction %.0f exchange between the waves %.0f tail %.0f\n",
 							ae[0] / acc[6], ae[1] / acc[6], ae[2] / acc[6], ae[3] / acc[6]);
@@ -2740,6 +2761,8 @@ extern "C" int hu_place_batch(hu_batch* b, const hu_opts* o) try {
 					if(b->knob.trace) fprintf(stderr, "[hu] place: %zu candidates, max region %d, %d sites per thread, %s, %s\n", nc, maxR, S, split ? "gap/base split slots" : "column order", "EM across both waves");
 					if(split) {
 						if((rc = b->dPerm.ensure((size_t) b->n * S * 128)) != HU_OK) return rc;
+						/* not cleared: k_site_perm writes the entries below a read's counts, and k_place_blk discards what an invalid slot reads (entry 0 of its half,
+						 * unwritten for a read without gap sites or without base sites): the address is inside the read's row, the value is never used */
 						k_site_perm<<<b->n, 64, 0, b->stream>>>(dev, b->n, b->dCodes.p, b->dStart.p, b->dEnd.p, G * 128, (S - G) * 128, b->dPerm.p);
 						/* regions of <= 1,024 sites (150-base reads): the whole v message in LDS (VL = 3, 24 KB per workgroup), 168 VGPRs, three waves per
 						 * SIMD: FIVE workgroups per CU instead of four (the LDS holds five) — the kernel's time goes with the resident candidates

@@ -178,12 +178,24 @@ __device__ inline uint32_t hu_xcd_pos(uint32_t b, uint32_t nb, int xmap) {
 	return b < per * 8 ? (b & 7u) * per + (b >> 3) : b;
 }
 
-template<int SPT, int NW, int OCC = 1>
-__global__ __launch_bounds__(64 * NW, OCC) void k_estimate_prod(HuDbDev db, HuModelDev mdl, const int8_t* __restrict__ codes,
+/* waves per SIMD that the register allocation must leave room for: with every load of a thread in flight at once the unbounded allocation
+ * takes a few registers more than the slot-by-slot form did and would drop a wave (130 / 170 VGPRs at 6 / 8 sites); bounded, each instance
+ * keeps the occupancy it had, without scratch */
+__host__ __device__ constexpr int hu_est_waves(int spt, int occ) {
+	const int w = spt <= 2 ? 8 : spt <= 4 ? 5 : spt <= 6 ? 4 : spt <= 8 ? 3 : 2;
+	return occ > w ? occ : w;
+}
+/* DBG: diagnostic build (est_var = 98), s_memtime stamps into dbg[block][4]: the prologue up to the first vector load (the chain of scalar
+ * loads and the per-wave exp), the load phase (first load issued .. last one returned), the rest, the workgroup's life */
+template<int SPT, int NW, int OCC = 1, bool DBG = false>
+__global__ __launch_bounds__(64 * NW, hu_est_waves(SPT, OCC)) void k_estimate_prod(HuDbDev db, HuModelDev mdl, const int8_t* __restrict__ codes,
 		const int32_t* __restrict__ rstart, const int32_t* __restrict__ rend, const uint32_t* __restrict__ parDN,
 		const int32_t* __restrict__ seedCnt, const int32_t* __restrict__ seedId, const uint32_t* __restrict__ seedDN,
-		int weighted, HuEstOut* __restrict__ out, const uint32_t* __restrict__ order, int xmap = 0) {
+		int weighted, HuEstOut* __restrict__ out, const uint32_t* __restrict__ order, int xmap = 0, long long* __restrict__ dbg = nullptr) {
 	constexpr int THREADS = 64 * NW;
+	long long tk[4] = {0, 0, 0, 0}, t0 = 0, tl = 0;
+	auto stamp = [&](int i) { if(DBG) { const long long t = (long long) __builtin_amdgcn_s_memtime(); tk[i] += t - tl; tl = t; } };
+	if(DBG) { t0 = tl = (long long) __builtin_amdgcn_s_memtime(); }
 	__shared__ double redd[2 * NW];
 	__shared__ int redi[2 * NW];
 	__shared__ __attribute__((aligned(16))) double Qtab[NW][24];   /* [wave][0..3] = exp(lam_m wnr), [4 + b * 4 + i] = Q^b_i */
@@ -219,19 +231,44 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_estimate_prod(HuDbDev db, HuMo
 	const int8_t* __restrict__ cd = codes + (size_t) read * db.csLen + start;
 	const int64_t sOff = (int64_t) un * db.winLen + (start - db.winStart);
 	const int piMax = argmax4d(mdl.logpi);
-	/* one pass over HBM: z_i = (P(wur) e^U)_i (P(wvr) e^V)_i of the thread's sites stays in registers */
+	/* one pass over HBM: z_i = (P(wur) e^U)_i (P(wvr) e^V)_i of the thread's sites stays in registers.
+	 * ONE round trip for the whole load phase: every load of the thread is issued before anything waits for one.  The exponents k of the
+	 * packed messages are loaded like the messages, at the clamped index and without a condition, and go first: loads return in order, so
+	 * their sums free their registers before z is built.  (Added under `j < n` inside the loop, they made each slot a block of its own
+	 * that ended in a wait for everything outstanding: six dependent round trips per workgroup at six sites per thread.) */
 	double z[SPT][4]; unsigned long long bop = 0; int ksum = 0;
+	double aU[SPT][4], aV[SPT][4];
+	/* uniform bases and a 32-bit site index: one offset register per load instead of an address pair, SPT slots of them are live at once */
+	const double* __restrict__ Ub = db.up + sOff * 4; const double* __restrict__ Vb = db.down + sOff * 4;
+	const int32_t* __restrict__ upKb = db.upK + sOff; const int32_t* __restrict__ downKb = db.downK + sOff;
+	/* slot t holds a site of the region: tid + THREADS t < n, written so that no per-slot site number stays in a register */
+	auto inr = [&](int t) { return tid < n - THREADS * t; };
+	stamp(0);
 	{
-		double aU[SPT][4], aV[SPT][4];
+		int kU[SPT], kV[SPT];
 #pragma unroll
 		for(int t = 0; t < SPT; ++t) {
-			const int j = tid + THREADS * t;
-			const int jj = j < n ? j : 0;
-			load4(db.up + (sOff + jj) * 4, aU[t]); load4(db.down + (sOff + jj) * 4, aV[t]);
+			const int jj = inr(t) ? tid + THREADS * t : 0;
+			kU[t] = upKb[(size_t) jj]; kV[t] = downKb[(size_t) jj];
+		}
+		__builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+		for(int t = 0; t < SPT; ++t) {
+			const int jj = inr(t) ? tid + THREADS * t : 0;
+			load4(Ub + (size_t) jj * 4, aU[t]); load4(Vb + (size_t) jj * 4, aV[t]);
 			const int b = cd[jj];
 			bop |= (unsigned long long)(b >= 0 ? b : 4) << (3 * t);
-			if(j < n) ksum += db.upK[sOff + jj] + db.downK[sOff + jj];
 		}
+		__builtin_amdgcn_sched_barrier(0);   /* nothing that waits for a load moves up among the loads */
+#pragma unroll
+		for(int t = 0; t < SPT; ++t) {
+			asm volatile("" : "+v"(kU[t]), "+v"(kV[t]));   /* the loads stay where they are: unconditional, ahead of the messages */
+			ksum += inr(t) ? kU[t] + kV[t] : 0;
+		}
+	}
+	if(DBG) { double x = 0; for(int t = 0; t < SPT; ++t) x += aU[t][0] + aV[t][0]; if(x == 1.2345e-300 || bop == ~0ull) tk[2] = 1; } /* wait for the loads */
+	stamp(1);
+	{
 #pragma unroll
 		for(int t = 0; t < SPT; ++t) {
 			const double su1 = Eu[0] * aU[t][1], su2 = Eu[1] * aU[t][2], su3 = Eu[2] * aU[t][3];
@@ -253,7 +290,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_estimate_prod(HuDbDev db, HuMo
 		for(int t = 0; t < SPT; ++t) {
 			const int bi = (int)((bop >> (3 * t)) & 7u);
 			const int b1 = argmax4_tied_lin(z[t]), b2 = bi < 4 ? bi : piMax;
-			nd += __popcll(__ballot(tid + THREADS * t < n && b1 != b2));
+			nd += __popcll(__ballot(inr(t) && b1 != b2));
 		}
 		if(lane == 0) redi[wave] = nd;
 		lds_barrier();
@@ -268,7 +305,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_estimate_prod(HuDbDev db, HuMo
 		double dsum = 0, nsum = 0;
 #pragma unroll
 		for(int t = 0; t < SPT; ++t) {
-			if(tid + THREADS * t >= n) continue;
+			if(!inr(t)) continue;
 			const int bi = (int)((bop >> (3 * t)) & 7u);
 			const int b1 = argmax4_tied_lin(z[t]), b2 = bi < 4 ? bi : piMax;
 			const double w1 = sel4(z[t], b1) / ((z[t][0] + z[t][2]) + (z[t][1] + z[t][3]));
@@ -318,7 +355,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_estimate_prod(HuDbDev db, HuMo
 	for(int t = 0; t < SPT; ++t) {
 		const double* q = Q + 4 + ((bop >> (3 * t)) & 7u) * 4;
 		double x = fmax(fma(q[3], z[t][3], fma(q[2], z[t][2], fma(q[1], z[t][1], q[0] * z[t][0]))), 0.0);
-		if(tid + THREADS * t >= n) x = 1.0;
+		if(!inr(t)) x = 1.0;
 		mant *= __builtin_amdgcn_frexp_mant(x);
 		esum += x == 0.0 ? 0 : __builtin_amdgcn_frexp_exp(x);
 	}
@@ -333,6 +370,10 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_estimate_prod(HuDbDev db, HuMo
 		for(int w = 1; w < NW; ++w) { m *= redd[w]; e += redi[NW + w]; }
 		HuEstOut o; o.ratio = ratio; o.wnr = wnr; o.loglik = log(m) + (double) e * HU_LN2;
 		out[(size_t) read * HU_MAX_SEEDS + s] = o;
+	}
+	if(DBG) {
+		stamp(2);
+		if(tid == 0) { tk[3] = tl - t0; for(int i = 0; i < 4; ++i) dbg[(size_t) blockIdx.x * 4 + i] = tk[i]; }
 	}
 }
 
@@ -558,20 +599,29 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_place_blk(HuDbDev db, HuModelD
 	double u[SPT][3], v[SPT][3]; unsigned long long bop = 0, bop2 = 0;   /* base / gap code of slot t: 3 bits, slots 21.. in bop2 */
 	{
 		double aU[SPT][4], aV[SPT][4];
+		/* two round trips for the whole load phase: all the site list entries of the thread, then all its messages and codes.  (Taken slot
+		 * by slot, each entry was waited for with everything outstanding, the previous slot's messages included: SPT dependent round trips.)
+		 * An invalid slot reads entry 0 of its half of the list (inside the read's row, possibly unwritten) and takes site 0. */
+		int js[SPT];
 #pragma unroll
 		for(int t = 0; t < SPT; ++t) {
-			int jj;
 			if(GS > 0) { /* slot t of the site list: [0, GS x THREADS) gap sites, then the base sites */
 				const int i = t < GS ? tid + THREADS * t : tid + THREADS * (t - GS);
 				const bool val = i < (t < GS ? nGap : nBase);
-				jj = val ? (int) perm[(size_t) read * (SPT * THREADS) + (t < GS ? 0 : GS * THREADS) + i] : 0;
+				const int e = (int) perm[(size_t) read * (SPT * THREADS) + (t < GS ? 0 : GS * THREADS) + (val ? i : 0)];
+				js[t] = val ? e : 0;
 			}
-			else { const int j = tid + THREADS * t; jj = j < n ? j : 0; }
+			else { const int j = tid + THREADS * t; js[t] = j < n ? j : 0; }
+		}
+#pragma unroll
+		for(int t = 0; t < SPT; ++t) {
+			const int jj = js[t];
 			load4(Ub + (size_t) jj * 4, aU[t]); load4(Vb + (size_t) jj * 4, aV[t]);
 			const int b = cdr[jj];
 			if(t < 21) bop |= (unsigned long long)(b >= 0 ? b : 4) << (3 * t);
 			else bop2 |= (unsigned long long)(b >= 0 ? b : 4) << (3 * (t - 21));
 		}
+		__builtin_amdgcn_sched_barrier(0);   /* the normalisation below waits for the loads: none of it moves up among them */
 #pragma unroll
 		for(int t = 0; t < SPT; ++t) {
 			const double iu = 1.0 / aU[t][0], iv = 1.0 / aV[t][0];
