@@ -1,5 +1,6 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY.  C ABI over the CPU restatement (ctypes-friendly).
-// See oracle_models.h for the scope note.  PARITY UNPINNED for everything floating-point; the integer rows a8
+// See oracle_models.h for the scope note.  The floating-point rows of models and placement are held to a 50-digit derivation (tests/test_hiprec_oracle.py), the profile chain
+// and Viterbi to invariants only; the integer rows a8
 // (DigitalSeq encoding) and a9 (SeqUtils::pDist) are checked against the reference's own code where it compiles without Eigen3 /
 // Boost (oracle/_ref/libref_seq.so, tests/test_ref_seq.py), row f2's file format against its vendored libcds (oracle/csfm_ref.cpp).
 #include <cstdio>
@@ -124,12 +125,21 @@ void orc_estimate(void* tr, const int8_t* seq, int start, int end, long id, doub
 	nodes[0] = p.cNode; nodes[1] = p.pNode; nodes[2] = p.aNode;
 }
 /* out: loglik, wnr, ratio, height; returns outer iteration count */
+void orc_place_full(void* tr, const int8_t* seq, int start, int end, int cNode, double ratio0, double wnr0, double maxHeight, int fixRoot,
+		double* out, int* aNode, int* iters);
 int orc_place(void* tr, const int8_t* seq, int start, int end, int cNode, double ratio0, double wnr0, double maxHeight, double* out, int* aNode) {
+	int iters[2];
+	orc_place_full(tr, seq, start, end, cNode, ratio0, wnr0, maxHeight, 0, out, aNode, iters);
+	return iters[0];
+}
+/* placeSeq of one candidate, with --fix-root-loglik on request, and both iteration counts: iters[0] outer, iters[1] passes of the 2-node EM */
+void orc_place_full(void* tr, const int8_t* seq, int start, int end, int cNode, double ratio0, double wnr0, double maxHeight, int fixRoot,
+		double* out, int* aNode, int* iters) {
 	Tree* t = (Tree*) tr;
 	Placement p; p.start = start; p.end = end; p.cNode = cNode; p.pNode = t->parent[cNode]; p.ratio = ratio0; p.wnr = wnr0; p.wuv = t->blen[cNode];
-	placeSeq(*t, seq, p, maxHeight);
+	placeSeq(*t, seq, p, maxHeight, fixRoot != 0);
 	out[0] = p.loglik; out[1] = p.wnr; out[2] = p.ratio; out[3] = p.height; *aNode = p.aNode;
-	return p.iters;
+	iters[0] = p.iters; iters[1] = p.emIters;
 }
 
 struct OrcOpts { double maxDiff, maxHeight, maxError; int maxNSeed, weighted, onlyML, prior, tieMode, fixRootLoglik; double tieTol; };

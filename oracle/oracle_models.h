@@ -4,11 +4,15 @@
 // Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may use
 // anything under oracle/.  The product (hmmufotu_amd/) never links this code.
 //
-// PARITY UNPINNED: the reference cannot be compiled here (Eigen3/Boost absent)
-// and its own tests hold no numeric vectors for this path.  The
-// only reference-produced numbers available are the trained model files under
-// data/*.sm (Q matrix of the GTR model, beta of TN93/HKY85/F81); the oracle is
-// pinned against those plus mathematical invariants (tests/test_oracle_*.py).
+// PARITY: the reference cannot be compiled here (Eigen3/Boost absent) and its own
+// tests hold no numeric vectors for this path.  What pins this code:
+//  * the trained model files under data/*.sm (Q matrix of the GTR model, beta of
+//    TN93/HKY85/F81) plus mathematical invariants (tests/test_oracle_*.py);
+//  * a second derivation of the formulas with independent arithmetic (50 digits,
+//    linear space, P = expm(Q t) with Q built from each model's definition;
+//    tests/golden/make_hiprec_golden.py -> tests/golden/hiprec.npz), to which
+//    tests/test_hiprec_oracle.py holds P(t) of the six models (P = expm(Q t), 1e-13).
+// The profile chain and Viterbi (oracle_hmm.h) have no such second derivation.
 //
 // This header: DNA substitution models  P(t)  and the discrete-Gamma rates.
 //   GTR   : src/GTR.h:116-121, src/GTR.cpp:124-145, src/DNASubModel.cpp:123-126

@@ -1,4 +1,9 @@
-// ORACLE — TEST INFRASTRUCTURE ONLY (see oracle_models.h header).  PARITY UNPINNED.
+// ORACLE — TEST INFRASTRUCTURE ONLY (see oracle_models.h header).
+// PARITY: pinned by a second derivation of the formulas with independent 50-digit arithmetic (tests/golden/make_hiprec_golden.py, tests/test_hiprec_oracle.py): the tree
+// messages and root logliks (1e-11 / 1e-12), estimateSeq (integer quotients bit for bit, logliks 1e-12), the joint EM of placeSeq (outer
+// and EM iteration counts equal, lengths 1e-9), the intended root loglik, filterPlacements' set and calcQValues under both priors — six
+// models, with and without dGamma, regions of 1 to 190 columns.  Not covered there: the seed ORDER (tests/test_seed_order.py holds it to
+// the literal libstdc++ sort), max_height, the chimera check, and components that tie in exact arithmetic outside K80 / JC69.
 //
 // Seed-Estimate-Place phylogenetic placement on a pre-evaluated unrooted tree.  Follows
 //   src/SeqUtils.cpp:37-54 (pDist), src/HmmUFOtu_main.cpp:127-216 (getSeed, estimateSeq,

@@ -163,12 +163,14 @@ class Tree:
                            C.c_int(int(weighted)), _p(out, C.c_double), _p(nodes, C.c_int))
         return dict(ratio=out[0], wnr=out[1], loglik=out[2], wuv=out[3], cNode=int(nodes[0]), pNode=int(nodes[1]), aNode=int(nodes[2]))
 
-    def place(self, seq, start, end, c_node, ratio0, wnr0, max_height=float("inf")):
+    def place(self, seq, start, end, c_node, ratio0, wnr0, max_height=float("inf"), fix_root=False):
+        """placeSeq of one candidate; iters: outer iterations, em_iters: passes of the 2-node EM summed over both branches;
+        fix_root: loglik is the intended root loglik (--fix-root-loglik) instead of the reference's constant"""
         seq = np.ascontiguousarray(seq, np.int8)
-        out = np.zeros(4); a = C.c_int(0)
-        it = lib().orc_place(self.h, _p(seq, C.c_int8), C.c_int(start), C.c_int(end), C.c_int(int(c_node)), C.c_double(ratio0),
-                             C.c_double(wnr0), C.c_double(max_height), _p(out, C.c_double), C.byref(a))
-        return dict(loglik=out[0], wnr=out[1], ratio=out[2], height=out[3], aNode=a.value, iters=it)
+        out = np.zeros(4); a = C.c_int(0); it = np.zeros(2, np.int32)
+        lib().orc_place_full(self.h, _p(seq, C.c_int8), C.c_int(start), C.c_int(end), C.c_int(int(c_node)), C.c_double(ratio0),
+                             C.c_double(wnr0), C.c_double(max_height), C.c_int(int(fix_root)), _p(out, C.c_double), C.byref(a), _p(it, C.c_int))
+        return dict(loglik=out[0], wnr=out[1], ratio=out[2], height=out[3], aNode=a.value, iters=int(it[0]), em_iters=int(it[1]))
 
     def assign(self, seq, start, end, opts=None):
         opts = opts or default_opts()

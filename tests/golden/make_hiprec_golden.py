@@ -1,0 +1,561 @@
+"""Regenerates tests/golden/hiprec.npz: the floating-point stages of the per-read task in 50-digit arithmetic.
+
+    python tests/golden/make_hiprec_golden.py [--out PATH] [--workers N]
+
+A second derivation, independent of oracle/ and of the engine: it is written from the reference's source (cited as file:line below)
+and the mathematics, imports neither, and works in LINEAR space with mpmath (mp.dps = 50) where both of them work in log space with
+the reference's -510 scaling rule (src/PhyloTreeUnrooted.h:1495-1510) — at 50 digits with an unbounded exponent that rule is a no-op.
+hmmufotu_amd.synth supplies DATA only: the tree (parent, blen), the leaf rows, the model parameters and the discrete-Gamma rates.
+Every float64 input is taken as the exact number it is; every stored value is the float64 rounding of the 50-digit result.
+
+Contents, per database CASE (key prefix "<model><dg_k>_"):
+  a. P(t) = expm(Q t) of the model's rate matrix Q at t in TS, each also multiplied by the database's dGamma rates.
+  c. the messages of every directed edge at MSG_COLS columns — the fewest, a median number and the most leaf gaps; all 200 would not
+     fit the size cap of a golden file (no file there is larger than 170 KB, this one is to stay below) —, the root
+     log-likelihood of EVERY column and its serial sum.
+  d. seven aligned reads (make_reads: codes, start, end) and the seed list (every non-root node).
+  e. per read and non-root node: estimateSeq unweighted / weighted, placeSeq (joint EM from the unweighted estimate), the F4 constant,
+     the intended root loglik; filterPlacements membership at maxError = 20; for the reads of Q_READS the exact complements 1 - p of
+     calcQValues' posteriors (q = min(250, -10 log10(1 - p)) is left to the reader: float64(1 - p) keeps every digit where p -> 1)
+     for prior UNIFORM / HEIGHT with and without the fixed root loglik.
+  f. decision margins: per candidate the smallest relative distance of a convergence quantity from BRANCH_EPS, the same distance
+     of the EM quantities in units of what double precision leaves of them (class Margin), and the smallest gap between the two best
+     inferred-state components; per read the smallest distance of a filter gap from 20.
+The run fails if more than 5 % of a database's candidates are knife-edge (margin < 1e-6, conditioned margin < 1 or state gap < 1e-9)
+or a filter gap lies within 1e-6 of 20: change READ_SEED then, not the caps.
+
+The archive is written with fixed zip timestamps, so a rerun reproduces it byte for byte.
+"""
+from __future__ import annotations
+
+import argparse
+import io
+import multiprocessing
+import os
+import sys
+import zipfile
+
+import numpy as np
+from mpmath import mp, mpf, matrix, expm, eigsy
+
+mp.dps = 50
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+CASES = [("GTR", 4), ("TN93", 3), ("HKY85", 4), ("F81", 0), ("K80", 2), ("JC69", 0)]
+DB_ARGS = dict(n_leaves=16, cs_len=200, n_match=120)           # synth.make_db(16, 200, model, dg_k, n_match=120), default seed
+TS = [0.0, 1e-5, 1e-3, 0.05, 1.0, 10.0]
+MSG_COLS = 3                                                     # message columns stored per database (chosen in db_state)
+READ_SEED = 2029
+Q_READS = (2, 4, 5, 6)                                           # reads whose q-value posteriors are stored (the size cap again)
+GAP = -2
+BRANCH_EPS = mpf(1e-5)                                           # src/PhyloTreeUnrooted.cpp:71 (the double 1e-5)
+MAX_ITER = 100                                                   # src/PhyloTreeUnrooted.h:1381
+MAX_ERROR = 20.0
+KNIFE_MARGIN, KNIFE_GAP, KNIFE_CAP, FILTER_MARGIN = 1e-6, 1e-9, 0.05, 1e-6
+A, C, G, T = 0, 1, 2, 3
+
+
+def case_name(model, dg_k):
+    return "%s%d" % (model, dg_k)
+
+
+# ----------------------------------------------------------------------------- a. models
+def build_Q(name, pi, par):
+    """rate matrix of each model from its definition; pi / par as floats (exact)"""
+    pi = [mpf(float(x)) for x in pi]
+    par = [mpf(float(x)) for x in par]
+    Q = [[mpf(0)] * 4 for _ in range(4)]
+    if name == "GTR":
+        # src/GTR.cpp:124-131: Q.col(j) = R.col(j) * pi(j); diagonal = -rowsum; Q = scale(Q) with the DEFAULT pi = Ones()
+        # (src/DNASubModel.h:154, src/DNASubModel.cpp:123-126): beta = sum_i Q_ii, Q / -beta
+        for i in range(4):
+            for j in range(4):
+                if i != j:
+                    Q[i][j] = par[4 * i + j] * pi[j]
+    elif name in ("TN93", "HKY85"):
+        # src/TN93.h:99-110,113-154 / src/HKY85.h:111-153: exchange rate beta between any two bases, times kr on A<->G and ky on C<->T
+        # (HKY85: kr = ky = kappa); beta is the stored parameter
+        if name == "TN93":
+            kr, ky, beta = par[0], par[1], par[2]
+        else:
+            kr = ky = par[0]; beta = par[1]
+        for i in range(4):
+            for j in range(4):
+                if i != j:
+                    k = kr if {i, j} == {A, G} else ky if {i, j} == {C, T} else mpf(1)
+                    Q[i][j] = beta * k * pi[j]
+    elif name == "F81":
+        for i in range(4):                                       # src/F81.h:110-118
+            for j in range(4):
+                if i != j:
+                    Q[i][j] = par[0] * pi[j]
+    elif name == "K80":
+        kappa = par[0]; beta = 1 / (2 * kappa)                   # src/K80.h:98-100,113-118; transversions beta, transitions kappa beta
+        for i in range(4):
+            for j in range(4):
+                if i != j:
+                    Q[i][j] = kappa * beta if {i, j} in ({A, G}, {C, T}) else beta
+    elif name == "JC69":
+        for i in range(4):                                       # src/JC69.h:97-101
+            for j in range(4):
+                if i != j:
+                    Q[i][j] = mpf(1) / 3
+    else:
+        raise ValueError(name)
+    for i in range(4):
+        Q[i][i] = -sum(Q[i][j] for j in range(4) if j != i)
+    if name == "GTR":
+        s = -sum(Q[i][i] for i in range(4))
+        Q = [[x / s for x in row] for row in Q]
+    return Q
+
+
+class ModelP:
+    """P(t) of a reversible model.  The tables of the archive come from mpmath.expm(Q t); the thousands of P(t) inside the
+    branch-length loops come from the spectral form of the same Q, which __init__ holds to expm at every t of TS."""
+
+    def __init__(self, name, pi, par):
+        self.pi = [mpf(0.25)] * 4 if name in ("K80", "JC69") else [mpf(float(x)) for x in pi]
+        self.Q = build_Q(name, self.pi, par)
+        sq = [mp.sqrt(p) for p in self.pi]
+        S = matrix(4, 4)
+        for i in range(4):
+            for j in range(4):
+                S[i, j] = (sq[i] * self.Q[i][j] / sq[j] + sq[j] * self.Q[j][i] / sq[i]) / 2      # detailed balance: symmetric
+        lam, V = eigsy(S)
+        self.lam = [lam[k] for k in range(4)]
+        self.L = [[V[i, k] / sq[i] for k in range(4)] for i in range(4)]
+        self.R = [[V[j, k] * sq[j] for j in range(4)] for k in range(4)]
+        for t in TS:
+            for i, row in enumerate(self.expm(mpf(t))):
+                assert abs(sum(row) - 1) < mpf(10) ** -40
+                for j, x in enumerate(row):
+                    assert abs(x - self.P(mpf(t))[i][j]) < mpf(10) ** -40, (name, t)
+
+    def expm(self, t):
+        M = expm(matrix(self.Q) * t)
+        return [[M[i, j] for j in range(4)] for i in range(4)]
+
+    def P(self, t):
+        if t == 0:                                               # exactly I (src/GTR.h:116-121; the closed forms of the others give it too)
+            return [[mpf(int(i == j)) for j in range(4)] for i in range(4)]
+        e = [mp.exp(l * t) for l in self.lam]
+        return [[sum(self.L[i][k] * e[k] * self.R[k][j] for k in range(4)) for j in range(4)] for i in range(4)]
+
+
+# ----------------------------------------------------------------------------- c. messages (linear space)
+def conv(P, m):
+    """sum_k P(i -> k) m_k: what dot_product_scaled(Matrix4d, Vector4d) is the logarithm of (src/PhyloTreeUnrooted.h:1495-1503)"""
+    return [P[i][0] * m[0] + P[i][1] * m[1] + P[i][2] * m[2] + P[i][3] * m[3] for i in range(4)]
+
+
+def join(contribs, dg):
+    """message of an inner node from incoming (P of every rate category, message) pairs (src/PhyloTreeUnrooted.cpp:320-346): the product
+    over the children per category, and with dGamma the plain average over the categories at THIS node (row_mean_exp_scaled,
+    src/PhyloTreeUnrooted.h:1521-1529)"""
+    K = len(contribs[0][0])
+    acc = [mpf(0)] * 4
+    for k in range(K):
+        prod = [mpf(1)] * 4
+        for Pk, m in contribs:
+            c = conv(Pk[k], m)
+            prod = [prod[i] * c[i] for i in range(4)]
+        acc = [acc[i] + prod[i] for i in range(4)]
+    return [a / K for a in acc] if dg else acc
+
+
+def leaf_vec(code, pi):
+    """getLeafLoglik (src/PhyloTreeUnrooted.h:1431-1437): the base's unit vector, pi for a gap"""
+    return [mpf(1) if i == code else mpf(0) for i in range(4)] if code >= 0 else list(pi)
+
+
+TIE = mpf(10) ** -40                                             # components closer than this (relative) are equal in exact arithmetic
+
+
+def argmax4(v):
+    """Eigen's maxCoeff(&idx): the first maximum (of components that tie in exact arithmetic, the first)"""
+    thr = max(v) * (1 - TIE)
+    for i in range(4):
+        if v[i] >= thr:
+            return i
+
+
+def flog(x):
+    return float("-inf") if x == 0 else float(mp.log(x))
+
+
+class DbState:
+    pass
+
+
+def db_state(ci):
+    from hmmufotu_amd import synth
+    name, dg_k = CASES[ci]
+    db = synth.make_db(DB_ARGS["n_leaves"], DB_ARGS["cs_len"], name, dg_k, n_match=DB_ARGS["n_match"])
+    s = DbState()
+    s.ci, s.name, s.dg_k = ci, name, dg_k
+    s.n, s.L = db.n_nodes, db.cs_len
+    s.parent = [int(x) for x in db.parent]
+    s.blen = [mpf(float(x)) for x in db.blen]
+    s.is_leaf = [bool(x) for x in db.is_leaf]
+    s.anno = [int(x) for x in db.anno_id]
+    s.rates = [mpf(float(x)) for x in db.dg_r] if dg_k > 0 else [mpf(1)]
+    s.model = ModelP(name, db.model.pi, db.model.par)
+    pi = s.model.pi
+    n, L = s.n, s.L
+    kids = [[] for _ in range(n)]
+    for i in range(1, n):
+        kids[s.parent[i]].append(i)
+    Pn = [None] + [[s.model.P(s.blen[i] * r) for r in s.rates] for i in range(1, n)]
+    dg = dg_k > 0
+    up = [None] * n; down = [None] * n
+    for u in range(n - 1, -1, -1):                               # parents are numbered before their children
+        if s.is_leaf[u]:
+            up[u] = [leaf_vec(int(db.seq[u, j]), pi) for j in range(L)]
+        else:
+            up[u] = [join([(Pn[c], up[c][j]) for c in kids[u]], dg) for j in range(L)]
+    for u in range(1, n):
+        p = s.parent[u]
+        down[u] = [join(([(Pn[p], down[p][j])] if p != 0 else []) + [(Pn[c], up[c][j]) for c in kids[p] if c != u], dg) for j in range(L)]
+    s.up, s.down = up, down
+    # ancestral rows: per-site argmax of the node -> parent message (src/PhyloTreeUnrooted.cpp:1085-1093); the data's must be these
+    seq = np.array(db.seq, np.int8)
+    for u in range(n):
+        if not s.is_leaf[u]:
+            for j in range(L):                                   # components equal in exact arithmetic (K80 / JC69): any of them
+                assert up[u][j][int(db.seq[u, j])] >= max(up[u][j]) * (1 - TIE), "inner row %d of the database is not the argmax of the 50-digit message" % u
+    s.seq = seq
+    # heights: the smallest distance to a descendant leaf (src/PhyloTreeUnrooted.cpp:274-287)
+    h = [None] * n
+    for u in range(n - 1, -1, -1):
+        h[u] = mpf(0) if s.is_leaf[u] else min(h[c] + s.blen[c] for c in kids[u])
+    s.height = h
+    # treeLoglik of a column: log(pi . root message) (src/PhyloTreeUnrooted.cpp:707-719)
+    s.root_ll = [mp.log(sum(pi[i] * up[0][j][i] for i in range(4))) for j in range(L)]
+    s.root_ll_sum = sum(s.root_ll)
+    ngap = (seq[np.array(s.is_leaf)] < 0).sum(0)
+    s.msg_cols = sorted({int(np.argmin(ngap)), int(np.argmax(ngap)), int(np.argsort(ngap, kind="stable")[L // 2])})
+    assert len(s.msg_cols) == MSG_COLS
+    s.reads = make_reads(s)
+    return s
+
+
+# ----------------------------------------------------------------------------- d. reads
+def make_reads(s):
+    """(codes [L], start, end) x 7: regions of 1, 2, 64 (no gap site), 65 (all gaps but the two ends), 128 (equal to a leaf over its
+    region: d = 0), 129 (30 % diverged from every leaf) and 190 columns (a leaf with 3 % substitutions and its gaps).  Both end columns
+    of every read hold a base, as an aligned read's do."""
+    rng = np.random.default_rng(READ_SEED + s.ci)
+    leaves = np.flatnonzero(s.is_leaf)
+    L = s.L
+
+    def from_leaf(cols, mut, gaps):
+        u = int(leaves[rng.integers(len(leaves))])
+        start = int(rng.integers(2, L - cols - 1)); end = start + cols - 1
+        at = np.arange(start, end + 1)
+        anc = s.seq[s.parent[u], at]
+        b = np.where(s.seq[u, at] >= 0, s.seq[u, at], anc).astype(np.int8)
+        m = rng.random(cols) < mut
+        b[m] = (b[m] + rng.integers(1, 4, size=int(m.sum()))) % 4
+        if gaps == "leaf":
+            g = s.seq[u, at] < 0
+            g[0] = g[-1] = False
+            b[g] = GAP
+        elif gaps == "all":
+            b[1:-1] = GAP
+        codes = np.full(L, GAP, np.int8)
+        codes[at] = b
+        return codes, start, end, u
+
+    reads = [from_leaf(1, 0.03, None), from_leaf(2, 0.03, None), from_leaf(64, 0.03, None), from_leaf(65, 0.03, "all")]
+    while True:                                                  # equal to a leaf wherever both hold a base
+        cd, st, en, u = from_leaf(128, 0.0, "leaf")
+        if ((cd[st:en + 1] >= 0) & (s.seq[u, st:en + 1] >= 0)).sum() >= 40:
+            both = (cd >= 0) & (s.seq[u] >= 0)
+            assert (cd[both] == s.seq[u][both]).all()
+            reads.append((cd, st, en, u))
+            break
+    while True:                                                  # 30 % diverged: no leaf closer than 0.25 over the compared sites
+        cd, st, en, u = from_leaf(129, 0.30, "leaf")
+        far = True
+        for l in leaves:
+            both = (cd[st:en + 1] >= 0) & (s.seq[l, st:en + 1] >= 0)
+            if both.sum() and (cd[st:en + 1][both] != s.seq[l, st:en + 1][both]).mean() < 0.25:
+                far = False
+        if far:
+            reads.append((cd, st, en, u))
+            break
+    reads.append(from_leaf(190, 0.03, "leaf"))
+    return [(r[0], r[1], r[2]) for r in reads]
+
+
+# ----------------------------------------------------------------------------- e. one candidate
+def pdist_counts(a, b, start, end):
+    """SeqUtils::pDist (src/SeqUtils.cpp:37-54): sites where both hold a base, and those of them that differ"""
+    both = (a[start:end + 1] >= 0) & (b[start:end + 1] >= 0)
+    return int((a[start:end + 1][both] != b[start:end + 1][both]).sum()), int(both.sum())
+
+
+class Margin:
+    """m: the smallest relative distance of a convergence quantity from BRANCH_EPS.  cond: the smallest distance of an EM quantity
+    |log q - log q0| from BRANCH_EPS in units of what a relative error of P_ERR in p does to it through q = 1 - p, P_ERR (1/q + 1/q0):
+    an EM that does not converge halves q pass after pass until 1 - p has no digits left, and from there on the pass count is the
+    arithmetic's (q sticks at 2^-53 and the test reads 0, or q reaches 0 and it reads NaN), not the formula's."""
+    P_ERR = mpf("1e-14")                                         # ~100 ulp: a reciprocal refined by one Newton step from 2^-23
+
+    def __init__(self):
+        self.m = mpf(1)
+        self.cond = mp.inf
+
+    def see(self, x, q=None, q0=None):
+        self.m = min(self.m, abs(x - BRANCH_EPS) / BRANCH_EPS)
+        if q is not None:
+            self.cond = min(self.cond, abs(x - BRANCH_EPS) / (self.P_ERR * (1 / q + 1 / q0)))
+
+
+def em2(pi, Um, Vm, w0, max_l, mg):
+    """the 2-node EM of src/PhyloTreeUnrooted.cpp:749-798 on linear messages: A = pi . (U o V), B = (pi . U)(pi . V) per site.  A site is
+    skipped there when logA or logB is NaN; with messages that are not all zero neither can be (asserted).  Returns (w, passes)."""
+    q0 = mp.exp(-w0); p0 = 1 - q0
+    AB = []
+    for a, b in zip(Um, Vm):
+        Aj = sum(pi[i] * a[i] * b[i] for i in range(4))
+        Bj = sum(pi[i] * a[i] for i in range(4)) * sum(pi[i] * b[i] for i in range(4))
+        assert Bj > 0
+        AB.append((Aj, Bj))
+    n = len(AB)
+    p, q, steps = p0, q0, 0
+    it = 0
+    while it < MAX_ITER and 0 <= p <= 1:
+        steps += 1
+        p = sum(Bj * p0 / (Aj * q0 + Bj * p0) for Aj, Bj in AB) / n
+        q = 1 - p
+        assert q > 0, "a branch length ran to infinity: choose other reads"
+        x = abs(mp.log(q) - mp.log(q0))
+        mg.see(x, q, q0)
+        if x < BRANCH_EPS:
+            break
+        p0, q0 = p, q
+        it += 1
+    w = -mp.log(q)
+    return (max_l if w > max_l else w), steps
+
+
+def candidate(s, ri, u):
+    """everything the archive holds for read ri on the branch above node u, as a dict of floats / ints"""
+    codes, start, end = s.reads[ri]
+    v = s.parent[u]
+    pi, M = s.model.pi, s.model
+    n = end - start + 1
+    cols = range(start, end + 1)
+    U = [s.up[u][j] for j in cols]; V = [s.down[u][j] for j in cols]
+    N = [leaf_vec(int(codes[j]), pi) for j in cols]
+    out = {}
+    # ---- estimateSeq (src/PhyloTreeUnrooted.cpp:849-877)
+    dc, Nc = pdist_counts(s.seq[u], codes, start, end)
+    dp, Np = pdist_counts(s.seq[v], codes, start, end)
+    out["dN"] = (dc, Nc, dp, Np)
+    if Nc == 0 or Np == 0 or dc * Np + dp * Nc == 0:
+        ratio = mpf(1) / 2                                       # cDist / (cDist + pDist) is NaN
+    else:
+        ratio = (mpf(dc) / Nc) / (mpf(dc) / Nc + mpf(dp) / Np)
+    w0 = s.blen[u]
+    wur = w0 * ratio; wvr = w0 - wur
+    Pu, Pv = M.P(wur), M.P(wvr)                                  # model->Pr(wur): no rate categories here
+    R = [[a * b for a, b in zip(conv(Pu, U[j]), conv(Pv, V[j]))] for j in range(n)]
+    d = 0; dw = mpf(0); Nw = mpf(0); gap = mp.inf
+    for j in range(n):                                           # src/PhyloTreeUnrooted.cpp:1018-1052
+        b1, b2 = argmax4(R[j]), argmax4(N[j])
+        srt = sorted(R[j], reverse=True)
+        if srt[3] < srt[0] * (1 - TIE):                          # four equal components: the first wins on any arithmetic
+            gap = min(gap, mp.log(srt[0]) - mp.log(srt[1]) if srt[1] > 0 else mp.inf)
+        w = (R[j][b1] / sum(R[j])) * (N[j][b2] / sum(N[j]))
+        if b1 != b2:
+            d += 1; dw += w
+        Nw += w
+    out["est_d"] = d
+    wnr_u = mpf(d) / n; wnr_w = dw / Nw
+
+    def est_ll(wnr):
+        Pn = M.P(wnr)
+        tot = mpf(0); neg_inf = False
+        for j in range(n):
+            x = sum(pi[i] * R[j][i] * c for i, c in enumerate(conv(Pn, N[j])))
+            if x == 0:
+                neg_inf = True
+            else:
+                tot += mp.log(x)
+        return mpf("-inf") if neg_inf else tot
+    ll_u, ll_w = est_ll(wnr_u), est_ll(wnr_w)
+    out.update(est_ratio=float(ratio), est_wnr_w=float(wnr_w), est_ll=float(ll_u), est_ll_w=float(ll_w),
+               state_gap=float(gap) if gap != mp.inf else np.inf)
+    # ---- placeSeq: copySubTree, the new root r on the branch, the joint EM (src/PhyloTreeUnrooted.cpp:879-954, 800-847)
+    dg = s.dg_k > 0
+    catP = lambda t: [M.P(t * r) for r in s.rates]               # loglikConv(child, j, dG->rate(k)) (src/PhyloTreeUnrooted.cpp:315-318)
+    lenUR = w0 * ratio; lenVR = w0 * (1 - ratio); lenNR = wnr_u
+    w0j = lenUR + lenVR
+    wur0, wnr0 = lenUR, lenNR
+    wur = lenUR
+    mg = Margin()
+    outer = em = 0
+    it = 0
+    while it < MAX_ITER and 0 <= wur <= w0j:
+        outer += 1
+        PU, PV = catP(lenUR), catP(lenVR)
+        RN = [join([(PU, U[j]), (PV, V[j])], dg) for j in range(n)]
+        wnr, k = em2(pi, RN, N, lenNR, mpf(1), mg); em += k
+        lenNR = wnr
+        PN = catP(lenNR)
+        RU = [join([(PV, V[j]), (PN, N[j])], dg) for j in range(n)]
+        wur, k = em2(pi, RU, U, lenUR, w0j, mg); em += k
+        lenUR = wur
+        lenVR = w0j - wur
+        a, b = abs(wur - wur0), abs(wnr - wnr0)
+        mg.see(a); mg.see(b)
+        if a < BRANCH_EPS and b < BRANCH_EPS:
+            break
+        wur0, wnr0 = wur, wnr
+        it += 1
+    pl_ratio = lenUR / w0
+    height = s.height[u] + lenUR
+    a_node = u if pl_ratio <= mpf(1) / 2 else v                  # max_height = inf (src/PhyloTreeUnrooted.cpp:949-952)
+    # the value placeSeq returns: the root message is left at INVALID_LOGLIK = 1 (src/PhyloTreeUnrooted.cpp:918-922), so
+    # treeLoglik sums log(sum_i pi_i e^1) over the region
+    const_ll = n * mp.log(sum(pi) * mp.e)
+    # --fix-root-loglik: loglik(r, j) from the three children at the optimised lengths (src/PhyloTreeUnrooted.cpp:320-346)
+    PU, PV, PN = catP(lenUR), catP(w0j - lenUR), catP(lenNR)
+    root_ll = sum(mp.log(sum(pi[i] * x for i, x in enumerate(join([(PU, U[j]), (PV, V[j]), (PN, N[j])], dg)))) for j in range(n))
+    anno_dist = (w0 * pl_ratio + lenNR) if a_node == u else ((1 - pl_ratio) * w0 + lenNR)       # src/PhyloTreeUnrooted.h:464-467
+    log_prior_height = -(anno_dist - lenNR + height)             # src/PhyloTreeUnrooted.cpp:1166-1177
+    out.update(pl_ratio=float(pl_ratio), pl_wnr=float(lenNR), pl_outer=outer, pl_em=em, pl_a_node=a_node, pl_root_ll=float(root_ll),
+               pl_const_ll=float(const_ll), margin=float(mg.m), margin_cond=float(min(mg.cond, mpf(10) ** 30)))
+    out["_q"] = (ll_u, const_ll, root_ll, log_prior_height, s.anno[a_node])
+    return out
+
+
+def q_complements(cands):
+    """calcQValues (src/HmmUFOtu_main.cpp:182-216) over one read's candidates: 1 - p of every placement and of its taxon, for
+    (prior, fixed root) in (U,0) (H,0) (U,1) (H,1) -> [n][4][2]"""
+    out = np.zeros((len(cands), 4, 2))
+    for vi, (prior, fix) in enumerate(((0, 0), (1, 0), (0, 1), (1, 1))):
+        lp = [(c["_q"][2] if fix else c["_q"][1]) + (c["_q"][3] if prior else 0) for c in cands]
+        mx = max(lp)
+        e = [mp.exp(x - mx) for x in lp]
+        tot = sum(e)
+        for i, c in enumerate(cands):
+            out[i, vi, 0] = float(sum(x for k, x in enumerate(e) if k != i) / tot)
+            out[i, vi, 1] = float(sum(x for k, x in enumerate(e) if cands[k]["_q"][4] != c["_q"][4]) / tot)
+    return out
+
+
+# ----------------------------------------------------------------------------- driver
+_STATES = {}
+
+
+def _task(t):
+    ci, ri, u = t
+    return t, candidate(_STATES[ci], ri, u)
+
+
+def assemble(states, results):
+    """{key: array} of the whole archive"""
+    arc = {"ts": np.array(TS), "max_error": np.array(MAX_ERROR), "dps": np.array(mp.dps), "read_seed": np.array(READ_SEED),
+           "q_reads": np.array(Q_READS, np.int32), "db_args": np.array([DB_ARGS["n_leaves"], DB_ARGS["cs_len"], DB_ARGS["n_match"]], np.int32),
+           "cases": np.array([case_name(*c) for c in CASES])}
+    over = []
+    for s in states:
+        px = case_name(s.name, s.dg_k) + "_"
+        nr, nodes = len(s.reads), list(range(1, s.n))
+        mult = [mpf(1)] + (s.rates if s.dg_k > 0 else [])
+        arc[px + "P"] = np.array([[[[float(x) for x in row] for row in s.model.expm(mpf(t) * m)] for m in mult] for t in TS])
+        arc[px + "parent"] = np.array(s.parent, np.int32)
+        arc[px + "blen"] = np.array([float(x) for x in s.blen])
+        arc[px + "seq"] = s.seq
+        arc[px + "height"] = np.array([float(x) for x in s.height])
+        arc[px + "msg_cols"] = np.array(s.msg_cols, np.int32)
+        arc[px + "up"] = np.array([[[flog(x) for x in s.up[u][j]] for j in s.msg_cols] for u in range(s.n)])
+        arc[px + "down"] = np.array([[[flog(x) for x in s.down[u][j]] if u else [0.0] * 4 for j in s.msg_cols] for u in range(s.n)])
+        arc[px + "root_ll"] = np.array([float(x) for x in s.root_ll])
+        arc[px + "root_ll_sum"] = np.array(float(s.root_ll_sum))
+        arc[px + "codes"] = np.stack([r[0] for r in s.reads])
+        arc[px + "start"] = np.array([r[1] for r in s.reads], np.int32)
+        arc[px + "end"] = np.array([r[2] for r in s.reads], np.int32)
+        arc[px + "seeds"] = np.array(nodes, np.int32)
+        cand = [[results[(s.ci, ri, u)] for u in nodes] for ri in range(nr)]
+        f = lambda key, dt=np.float64: np.array([[c[key] for c in row] for row in cand], dt)
+        arc[px + "dN"] = f("dN", np.int16)
+        arc[px + "est_d"] = f("est_d", np.int16)
+        for key in ("est_ratio", "est_wnr_w", "est_ll", "est_ll_w", "pl_ratio", "pl_wnr", "pl_root_ll"):
+            arc[px + key] = f(key)
+        arc[px + "pl_const_ll"] = np.array([row[0]["pl_const_ll"] for row in cand])
+        arc[px + "pl_outer"] = f("pl_outer", np.uint8)
+        arc[px + "pl_em"] = f("pl_em", np.uint16)
+        arc[px + "pl_a_node"] = f("pl_a_node", np.uint8)
+        arc[px + "margin"] = f("margin", np.float32)
+        arc[px + "state_gap"] = f("state_gap", np.float32)
+        arc[px + "margin_cond"] = f("margin_cond", np.float32)
+        ll = f("est_ll")
+        gapf = ll.max(1, keepdims=True) - ll                     # filterPlacements (src/HmmUFOtu_main.cpp:162-173)
+        arc[px + "filter_in"] = ~(gapf > MAX_ERROR)
+        exact = [[max(c["_q"][0] for c in row) - c["_q"][0] for c in row] for row in cand]
+        fm = np.array([min(float(abs(x - mpf(MAX_ERROR))) for x in row) for row in exact])
+        arc[px + "filter_margin"] = fm.astype(np.float32)
+        assert (arc[px + "filter_in"] == np.array([[not (x > mpf(MAX_ERROR)) for x in row] for row in exact])).all()
+        assert fm.min() > FILTER_MARGIN, "a filter gap within %g of %g (%s): change READ_SEED" % (FILTER_MARGIN, MAX_ERROR, px)
+        knife = (arc[px + "margin"] < KNIFE_MARGIN) | (arc[px + "state_gap"] < KNIFE_GAP) | (arc[px + "margin_cond"] < 1)
+        if knife.mean() > KNIFE_CAP:
+            over.append("%s: %d knife-edge candidates of %d" % (px[:-1], knife.sum(), knife.size))
+        arc[px + "omp"] = np.stack([q_complements(cand[ri]) for ri in Q_READS])
+        print("%-7s knife-edge %d/%d, smallest margin %.3g, conditioned %.3g, state gap %.3g, filter margin %.3g" %
+              (px[:-1], knife.sum(), knife.size, arc[px + "margin"].min(), arc[px + "margin_cond"].min(), arc[px + "state_gap"].min(), fm.min()), flush=True)
+    assert not over, "more than %g of a database's candidates are knife-edge: change READ_SEED (%s)" % (KNIFE_CAP, "; ".join(over))
+    return arc
+
+
+def write_archive(path, arc):
+    """an .npz (deflated) with fixed member timestamps: the same arrays give the same bytes"""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for k in sorted(arc):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(arc[k]), allow_pickle=False)
+            zi = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            zi.external_attr = 0o644 << 16
+            z.writestr(zi, buf.getvalue(), compresslevel=9)
+
+
+def one_candidate(case, ri, u):
+    """a single candidate regenerated (tests/test_hiprec_oracle.py proves with it that the archive is this file's output)"""
+    ci = [case_name(*c) for c in CASES].index(case)
+    if ci not in _STATES:
+        _STATES[ci] = db_state(ci)
+    c = candidate(_STATES[ci], ri, u)
+    c.pop("_q")
+    return c
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(HERE, "hiprec.npz"))
+    ap.add_argument("--workers", type=int, default=min(16, os.cpu_count() or 1))
+    a = ap.parse_args()
+    workers = max(1, min(16, a.workers))
+    ctx = multiprocessing.get_context("fork")
+    with ctx.Pool(min(workers, len(CASES))) as pool:
+        states = pool.map(db_state, range(len(CASES)))
+    for s in states:
+        _STATES[s.ci] = s
+    tasks = [(s.ci, ri, u) for s in states for ri in range(len(s.reads)) for u in range(1, s.n)]
+    tasks.sort(key=lambda t: -(states[t[0]].reads[t[1]][2] - states[t[0]].reads[t[1]][1]) * (1 + max(states[t[0]].dg_k, 1)))
+    with ctx.Pool(workers) as pool:                              # forked after _STATES is filled: the workers inherit it
+        results = dict(pool.imap_unordered(_task, tasks, chunksize=4))
+    write_archive(a.out, assemble(states, results))
+    print("wrote %s: %d bytes" % (a.out, os.path.getsize(a.out)))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,84 @@
+"""Shared by tests/test_hiprec_oracle.py and tests/test_hiprec_gpu.py: tests/golden/hiprec.npz (the floating-point stages in 50-digit
+arithmetic, written by tests/golden/make_hiprec_golden.py) and the rules both files read it by."""
+import os
+
+import numpy as np
+
+from conftest import get_db
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hiprec.npz")
+CASES = ["GTR4", "TN933", "HKY854", "F810", "K802", "JC690"]
+KNIFE_MARGIN, KNIFE_GAP = 1e-6, 1e-9
+VARIANTS = {(0, 0): 0, (1, 0): 1, (0, 1): 2, (1, 1): 3}        # (prior, fix_root_loglik) -> index into omp
+MAX_Q = 250.0
+
+_ARC = {}
+
+
+class Case:
+    """one database of the archive: its arrays as attributes, and the synthetic database they were computed on"""
+
+    def __init__(self, name):
+        if not _ARC:
+            with np.load(GOLD) as z:
+                _ARC.update({k: z[k] for k in z.files})
+        self.name = name
+        for k, v in _ARC.items():
+            if k.startswith(name + "_"):
+                setattr(self, k[len(name) + 1:], v)
+        self.ts, self.max_error, self.q_reads = _ARC["ts"], float(_ARC["max_error"].ravel()[0]), [int(x) for x in _ARC["q_reads"]]
+        self.root_ll_sum = float(self.root_ll_sum.ravel()[0])
+        n_leaves, cs_len, n_match = (int(x) for x in _ARC["db_args"])
+        model, dg_k = name[:-1], int(name[-1])
+        self.db = get_db(n_leaves, cs_len, model, dg_k=dg_k, seed=97, n_match=n_match)
+        # the same case: tree, rows and rates are the ones the 50-digit run was given
+        assert np.array_equal(self.db.parent, self.parent) and np.array_equal(self.db.blen, self.blen) and np.array_equal(self.db.seq, self.seq)
+        self.rates = np.concatenate([[1.0], self.db.dg_r]) if dg_k else np.ones(1)
+        self.n_reads = len(self.start)
+        # f. knife-edge candidates: the counts and the unweighted wnr are not compared, the lengths only to REL
+        # (margin_cond < 1: an EM quantity closer to 1e-5 than a relative error of 1e-14 in p moves it through q = 1 - p — an EM that does
+        # not converge halves q until 1 - p has no digits left, and the pass count from there on is the arithmetic's, not the formula's)
+        self.knife = (self.margin < KNIFE_MARGIN) | (self.state_gap < KNIFE_GAP) | (self.margin_cond < 1)
+
+    def times(self):
+        """the branch lengths of P: [len(ts)][1 + dg_k]"""
+        return self.ts[:, None] * self.rates[None, :]
+
+    def dist(self, ri, k):
+        """cDist of candidate k of read ri as getSeed computes it: d / N in double (NaN for no compared site)"""
+        d, N = int(self.dN[ri, k, 0]), int(self.dN[ri, k, 1])
+        return float("nan") if N == 0 else float(d) / N
+
+    def ratio_double(self, ri, k):
+        """estimateSeq's ratio from the stored counts with the reference's own three double operations (src/PhyloTreeUnrooted.cpp:853-858)"""
+        dc, Nc, dp, Np = (int(x) for x in self.dN[ri, k])
+        with np.errstate(all="ignore"):
+            c = np.float64(dc) / np.float64(Nc); p = np.float64(dp) / np.float64(Np)
+            r = c / (c + p)
+        return 0.5 if np.isnan(r) else float(r)
+
+    def wnr_unweighted(self, ri, k):
+        return float(self.est_d[ri, k]) / float(self.end[ri] - self.start[ri] + 1)
+
+    def placed_height(self, ri, k):
+        u = int(self.seeds[k])
+        return float(self.height[u] + self.pl_ratio[ri, k] * self.blen[u])
+
+    def q_exact(self, ri, prior, fix):
+        """(q_place, q_taxon, 1 - p_place, 1 - p_taxon) [n_cand] of read ri (one of q_reads) from the exact complements"""
+        omp = self.omp[self.q_reads.index(ri), :, VARIANTS[(prior, fix)], :]
+        with np.errstate(divide="ignore"):
+            q = np.minimum(MAX_Q, -10.0 * np.log10(omp))
+        return q[:, 0], q[:, 1], omp[:, 0], omp[:, 1]
+
+
+def q_ok(q, q_exact, omp, eps):
+    """the conditioned q bound: |dq| <= (10 / ln 10) eps / (1 - p) + 1e-12 q; where p > 1 - 1e-6 only that both sides give q >= 59.9"""
+    if omp < 1e-6:
+        return q >= 59.9 and q_exact >= 59.9
+    return abs(q - q_exact) <= (10.0 / np.log(10.0)) * eps / omp + 1e-12 * q_exact
+
+
+def ratio_half(case, ri):
+    """a placed ratio within 1e-6 of 0.5 switches the taxon node: the taxon sums of that read are not comparable"""
+    return bool((np.abs(case.pl_ratio[ri] - 0.5) < 1e-6).any())

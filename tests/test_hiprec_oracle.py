@@ -1,0 +1,195 @@
+"""The CPU oracle against an independent 50-digit derivation of the same formulas (tests/golden/hiprec.npz, written from the reference's
+source by tests/golden/make_hiprec_golden.py, which imports neither oracle/ nor the engine).
+
+Bounds (none of them comes from what the oracle gives):
+  Model.P                 absolute 1e-13
+  tree messages           1e-11 relative to max(|x|, 1); -inf components are -inf on both sides
+  estimateSeq             ratio: the reference's three double operations on the stored integer counts, bit for bit, and within 4 ulp of the
+                          exact quotient; unweighted wnr = count / n bit for bit; weighted wnr absolute 1e-12 (a quotient of two sums of at
+                          most 190 products of weights in [0, 1]: some hundred roundings of 1.1e-16); loglik relative 1e-12
+  placeSeq                outer and EM iteration counts equal; ratio, wnr, height absolute 1e-9; the constant loglik and the intended
+                          root loglik relative 1e-12
+  filterPlacements        the same set
+  q-values                |dq| <= (10 / ln 10) 1e-9 / (1 - p) + 1e-12 q with the exact posterior p; where p > 1 - 1e-6, both sides >= 59.9
+A knife-edge candidate (a convergence quantity within 1e-6 relative of 1e-5, an EM quantity that double precision cannot tell from 1e-5
+— hiprec_cases.Case.knife —, or two inferred-state components within 1e-9) is compared neither in its counts nor in its unweighted wnr,
+and in its lengths to 1e-6 only.  The generator allows 5 % of a database's candidates to be; the archive holds 10 of 1,260, all of the
+third kind and all on JC69's two-column read (10 of that database's 210: 4.8 %).
+Measured: P(t) 1.0e-15, the oracle's messages 9.1e-13 (synth's 4.2e-12), logliks 5.0e-15, placed lengths 5.3e-14, all counts equal.
+"""
+import glob
+import importlib.util
+import os
+import re
+
+import numpy as np
+import pytest
+
+from hiprec_cases import CASES, Case, q_ok, ratio_half
+
+REL = 1e-6
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def _oracle(c):
+    from oracle import oracle_py as O
+    db = c.db
+    m = O.Model(db.model.type_id, db.model.pi, db.model.par)
+    T = O.Tree(db.parent, db.blen, db.seq, db.up, db.down, db.height, m, db.dg_r if db.dg_k > 0 else None, db.anno_id)
+    return O, m, T
+
+
+def _rel(a, b):
+    return abs(a - b) / max(abs(a), abs(b), 1e-300)
+
+
+def worse(worst, key, x):
+    """worst[key] = max(worst[key], x) for a distance that is a number (Python's max(0.0, nan) is 0.0)"""
+    x = float(x)
+    assert np.isfinite(x), (key, x)
+    worst[key] = max(worst[key], x)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_model_P(name):
+    c = Case(name)
+    _, m, _ = _oracle(c)
+    worst = 0.0
+    for i, row in enumerate(c.times()):
+        for k, t in enumerate(row):
+            d = np.abs(m.P(float(t)) - c.P[i, k]).max()
+            assert np.isfinite(d)
+            worst = max(worst, d)
+    print("hiprec oracle P", name, worst)
+    assert worst < 1e-13
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_messages(name):
+    """the oracle's two-pass pruning and the database's own messages (the ones every other test feeds to oracle and engine)"""
+    c = Case(name)
+    O, m, _ = _oracle(c)
+    db = c.db
+    leaf_only = np.where(db.is_leaf[:, None], db.seq, 0).astype(np.int8)
+    up, down, seq, h = O.tree_evaluate(db.parent, db.blen, leaf_only, m, db.dg_r if db.dg_k else None)
+    assert np.array_equal(seq, db.seq)
+    assert np.abs(h - c.height).max() < 1e-14
+    for who, (u_, d_) in dict(oracle=(up, down), synth=(db.up, db.down)).items():
+        for got, want in ((u_[:, c.msg_cols], c.up), (d_[1:, c.msg_cols], c.down[1:])):
+            inf = np.isneginf(want)
+            assert np.array_equal(np.isneginf(got), inf), who
+            err = np.abs(got[~inf] - want[~inf]) / np.maximum(np.abs(want[~inf]), 1.0)
+            print("hiprec oracle messages", name, who, err.max())
+            assert np.isfinite(err).all() and err.max() < 1e-11, who
+        root = u_[0]                                             # treeLoglik of a column: log(pi . exp(root message))
+        mx = root.max(1)
+        ll = mx + np.log((np.asarray(m.pi)[None, :] * np.exp(root - mx[:, None])).sum(1))
+        assert (np.abs(ll - c.root_ll) <= 1e-12 * np.abs(c.root_ll)).all(), who
+        assert _rel(ll.sum(), c.root_ll_sum) < 1e-12, who
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_estimate(name):
+    c = Case(name)
+    _, _, T = _oracle(c)
+    worst = dict(ll=0.0, ll_w=0.0, wnr_w=0.0)
+    for ri in range(c.n_reads):
+        st, en = int(c.start[ri]), int(c.end[ri])
+        for k, u in enumerate(c.seeds):
+            e0 = T.estimate(c.codes[ri], st, en, u, c.dist(ri, k), weighted=False)
+            e1 = T.estimate(c.codes[ri], st, en, u, c.dist(ri, k), weighted=True)
+            assert e0["ratio"] == c.ratio_double(ri, k) == e1["ratio"]
+            assert abs(e0["ratio"] - c.est_ratio[ri, k]) <= 4 * np.spacing(c.est_ratio[ri, k])
+            if not c.knife[ri, k]:
+                assert e0["wnr"] == c.wnr_unweighted(ri, k), (ri, u)
+            assert np.isfinite([e0["loglik"], e1["loglik"], c.est_ll[ri, k], c.est_ll_w[ri, k]]).all(), (ri, u)
+            worse(worst, "wnr_w", abs(e1["wnr"] - c.est_wnr_w[ri, k]))
+            worse(worst, "ll", _rel(e0["loglik"], c.est_ll[ri, k]))
+            worse(worst, "ll_w", _rel(e1["loglik"], c.est_ll_w[ri, k]))
+    print("hiprec oracle estimate", name, worst)
+    assert worst["ll"] < 1e-12 and worst["ll_w"] < 1e-12 and worst["wnr_w"] < 1e-12, worst
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_place(name):
+    c = Case(name)
+    _, _, T = _oracle(c)
+    worst = dict(ratio=0.0, wnr=0.0, height=0.0, const=0.0, root=0.0)
+    for ri in range(c.n_reads):
+        st, en = int(c.start[ri]), int(c.end[ri])
+        for k, u in enumerate(c.seeds):
+            p = T.place(c.codes[ri], st, en, u, c.ratio_double(ri, k), c.wnr_unweighted(ri, k))
+            pf = T.place(c.codes[ri], st, en, u, c.ratio_double(ri, k), c.wnr_unweighted(ri, k), fix_root=True)
+            assert (pf["ratio"], pf["wnr"], pf["iters"], pf["em_iters"]) == (p["ratio"], p["wnr"], p["iters"], p["em_iters"])
+            errs = (abs(p["ratio"] - c.pl_ratio[ri, k]), abs(p["wnr"] - c.pl_wnr[ri, k]), abs(p["height"] - c.placed_height(ri, k)))
+            assert np.isfinite(errs).all() and np.isfinite([p["loglik"], pf["loglik"]]).all(), (ri, u, p, pf)
+            if c.knife[ri, k]:                                   # counts not compared, lengths to REL; everything else as for any candidate
+                assert max(errs) <= REL, (ri, u, errs)
+            else:
+                assert (p["iters"], p["em_iters"]) == (int(c.pl_outer[ri, k]), int(c.pl_em[ri, k])), (ri, u)
+                for key, e in zip(("ratio", "wnr", "height"), errs):
+                    worse(worst, key, e)
+            if abs(c.pl_ratio[ri, k] - 0.5) > 1e-6:
+                assert p["aNode"] == int(c.pl_a_node[ri, k])
+            worse(worst, "const", _rel(p["loglik"], c.pl_const_ll[ri]))
+            worse(worst, "root", _rel(pf["loglik"], c.pl_root_ll[ri, k]))
+    print("hiprec oracle place", name, worst)
+    assert worst["ratio"] < 1e-9 and worst["wnr"] < 1e-9 and worst["height"] < 1e-9, worst
+    assert worst["const"] < 1e-12, worst
+    assert worst["root"] < 1e-12, worst                          # the intended root loglik (--fix-root-loglik): the project's figure for logliks
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_assign_filter_set_and_q_values(name):
+    from oracle import oracle_py as O
+    c = Case(name)
+    _, _, T = _oracle(c)
+    n_cand = len(c.seeds)
+    for ri in range(c.n_reads):
+        st, en = int(c.start[ri]), int(c.end[ri])
+        res = T.assign(c.codes[ri], st, en, O.default_opts(maxError=c.max_error))
+        assert sorted(int(x) for x in res["seed_ids"]) == sorted(int(x) for x in c.seeds)
+        assert sorted(int(x) for x in res["filt_order"]) == sorted(int(u) for u, keep in zip(c.seeds, c.filter_in[ri]) if keep), ri
+        if ri not in c.q_reads:
+            continue
+        for prior in (0, 1):
+            for fix in (0, 1):
+                res = T.assign(c.codes[ri], st, en, O.default_opts(maxError=1e9, prior=prior, fixRootLoglik=fix))
+                assert res["n"] == n_cand
+                qp, qt, op, ot = c.q_exact(ri, prior, fix)
+                for nodes, vals in zip(res["nodes"], res["vals"]):
+                    k = int(nodes[0]) - 1                        # seeds are the nodes 1 .. n - 1 in order
+                    assert int(c.seeds[k]) == int(nodes[0])
+                    assert q_ok(vals[4], qp[k], op[k], 1e-9), (ri, prior, fix, k, vals[4], qp[k])
+                    if not ratio_half(c, ri):
+                        assert q_ok(vals[5], qt[k], ot[k], 1e-9), (ri, prior, fix, k, vals[5], qt[k])
+
+
+def test_the_archive_is_the_generators_output():
+    """one candidate regenerated in 50-digit arithmetic gives the stored bits"""
+    pytest.importorskip("mpmath")
+    spec = importlib.util.spec_from_file_location("make_hiprec_golden", os.path.join(HERE, "golden", "make_hiprec_golden.py"))
+    gen = importlib.util.module_from_spec(spec); spec.loader.exec_module(gen)
+    c = Case("JC690")
+    ri, k = 2, 4
+    got = gen.one_candidate("JC690", ri, int(c.seeds[k]))
+    assert tuple(got["dN"]) == tuple(int(x) for x in c.dN[ri, k]) and got["est_d"] == int(c.est_d[ri, k])
+    for key in ("est_ratio", "est_wnr_w", "est_ll", "est_ll_w", "pl_ratio", "pl_wnr", "pl_root_ll"):
+        assert got[key] == getattr(c, key)[ri, k], key
+    assert (got["pl_outer"], got["pl_em"], got["pl_a_node"]) == (int(c.pl_outer[ri, k]), int(c.pl_em[ri, k]), int(c.pl_a_node[ri, k]))
+    assert np.float32(got["margin"]) == c.margin[ri, k] and np.float32(got["state_gap"]) == c.state_gap[ri, k]
+    assert np.float32(got["margin_cond"]) == c.margin_cond[ri, k]
+    # and a knife-edge one: the conditioned margin that exempts it is the generator's too
+    ri, k = (int(x) for x in np.argwhere(c.knife)[0])
+    got = gen.one_candidate("JC690", ri, int(c.seeds[k]))
+    assert np.float32(got["margin_cond"]) == c.margin_cond[ri, k] < 1 and got["pl_em"] == int(c.pl_em[ri, k])
+    assert (got["pl_ratio"], got["pl_wnr"]) == (c.pl_ratio[ri, k], c.pl_wnr[ri, k])
+    assert got["pl_const_ll"] == c.pl_const_ll[ri]
+
+
+def test_only_the_generator_imports_mpmath():
+    pat = re.compile(r"^\s*(import|from)\s+mpmath", re.M)
+    root = os.path.dirname(HERE)
+    hits = [p for d in ("tests", "oracle", "hmmufotu_amd") for p in glob.glob(os.path.join(root, d, "**", "*.py"), recursive=True)
+            if pat.search(open(p).read())]
+    assert [os.path.relpath(p, root) for p in hits] == [os.path.join("tests", "golden", "make_hiprec_golden.py")]
