@@ -478,6 +478,144 @@ def hmm_write(path, p_m, p_i, p_t, map, cons, cs_len: int, n_seq: int, eff_n: fl
                                      C.c_double(eff_n), str(date).encode()))
 
 
+DM_STATUS = {1: "converged", 2: "max-it", 3: "nan-overfit", 4: "nan-unused", 5: "not-finite"}
+
+
+class DmProblem(C.Structure):
+    _fields_ = [("K", C.c_int32), ("L", C.c_int32), ("M", C.c_int64), ("data", C.POINTER(C.c_double)), ("alpha0", C.POINTER(C.c_double)),
+                ("q0", C.POINTER(C.c_double))]
+
+
+class DmOpts(C.Structure):
+    _fields_ = [("eta", C.c_double), ("abs_eps_cost", C.c_double), ("rel_eps_cost", C.c_double), ("abs_eps_params", C.c_double),
+                ("rel_eps_params", C.c_double), ("max_iter", C.c_int64), ("chunk", C.c_int32), ("pad0", C.c_int32)]
+
+
+class DmResult(C.Structure):
+    _fields_ = [("alpha", (C.c_double * 10) * 4), ("q", C.c_double * 10), ("cost", C.c_double), ("iterations", C.c_int64), ("status", C.c_int32),
+                ("pad0", C.c_int32)]
+
+
+def dm_training_data(rows, weight, pri_rate=0.05, symfrac=0.5, device=0) -> dict:
+    """hu_dm_training_data, on the device: the five training sets of hmmufotu-train-dm from the pruned alignment rows and the sequence
+    weights of msa_stats, scaled by (1 / pri_rate) / n here: mask [L], and me, ie [4][.], mt [3][.], it, dt [2][.] as the reference's
+    matrices, one data column per column of the array"""
+    a = _msa_rows(rows, "dm_training_data")
+    n, L = a.shape
+    w = np.ascontiguousarray(weight, np.float64).ravel()
+    if len(w) != n:
+        raise EngineError("dm_training_data: %d rows, %d weights" % (n, len(w)))
+    mask = np.zeros(L, np.uint8); cnt = np.zeros(5, np.int64)
+    sets = [np.zeros((L, k)) for k in (4, 4, 3, 2, 2)]
+    _chk(load_library().hu_dm_training_data(C.c_int(device), C.c_int64(n), C.c_int64(L), a.ctypes.data_as(C.c_char_p), _p(w, C.c_double), C.c_double(pri_rate),
+                                            C.c_double(symfrac), _p(mask, C.c_uint8), *[_p(s, C.c_double) for s in sets], _p(cnt, C.c_int64)))
+    out = {k: np.ascontiguousarray(s[:int(c)].T) for k, s, c in zip(("me", "ie", "mt", "it", "dt"), sets, cnt)}
+    out["mask"] = mask.astype(bool)
+    return out
+
+
+def dm_training_data_timing() -> dict:
+    """hu_dm_training_data_timing: the phases of this thread's last dm_training_data, in seconds, and the device memory it held"""
+    s = np.zeros(4); peak = C.c_int64(0)
+    _chk(load_library().hu_dm_training_data_timing(_p(s, C.c_double), C.byref(peak)))
+    return dict(to_device=s[0], wcounts_and_mask=s[1], states_kernels=s[2], counts_kernel=s[3], peak_bytes=int(peak.value))
+
+
+def dm_shuffle(M: int, seed=None) -> np.ndarray:
+    """hu_dm_shuffle (host only): std::random_shuffle of 0 .. M - 1 on the C library's rand(); seed given: srand(seed) first, else the
+    stream goes on"""
+    idx = np.zeros(max(int(M), 1), np.int32)
+    sd = C.c_uint32(int(seed) & 0xFFFFFFFF) if seed is not None else None
+    _chk(load_library().hu_dm_shuffle(C.c_int64(int(M)), C.byref(sd) if sd is not None else None, _p(idx, C.c_int32)))
+    return idx[:int(M)].copy()
+
+
+def _dm_data(data, what):
+    d = np.asarray(data, np.float64)
+    if d.ndim != 2 or not 2 <= d.shape[0] <= 4:
+        raise EngineError("%s: data must be [K][M] with K 2 .. 4" % what)
+    return np.ascontiguousarray(d.T)                                                    # [M][K]: a data column's values together
+
+
+def dm_moment_init(data, L=1, idx=None) -> np.ndarray:
+    """hu_dm_moment_init (host only): where the training of a density (L = 1) or of a mixture of L components (idx: the order of
+    dm_shuffle) starts, alpha [K][L]; 1 where the reference leaves the model as it is"""
+    d = _dm_data(data, "dm_moment_init")
+    M, K = d.shape
+    ix = np.ascontiguousarray(idx, np.int32).ravel() if idx is not None else None
+    if L > 1 and M > 0 and (ix is None or len(ix) != M):
+        raise EngineError("dm_moment_init: a mixture needs idx [M]")
+    alpha = np.zeros((K, int(L)))
+    _chk(load_library().hu_dm_moment_init(C.c_int32(K), C.c_int32(int(L)), C.c_int64(M), _p(d, C.c_double), _p(ix, C.c_int32) if ix is not None else None,
+                                          _p(alpha, C.c_double)))
+    return alpha
+
+
+def dm_train(problems, eta=0.001, abs_eps_cost=0.0, rel_eps_cost=1e-6, abs_eps_params=0.0, rel_eps_params=1e-4, max_iter=0, chunk=None, device=0,
+             progress=None) -> list:
+    """hu_dm_train, on the device: gradient ascent of a batch of independent problems, one workgroup each.  problems: dicts with data
+    [K][M], alpha0 [K][L] (a density: [K] or [K][1]) and optionally q0 [L].  Per problem a dict of alpha [K][L], q [L], cost, iterations
+    and status (a name of DM_STATUS).  progress(iterations, running) is called after every launch of `chunk` iterations."""
+    lib = load_library()
+    o = DmOpts()
+    lib.hu_dm_default_opts(C.byref(o))
+    o.eta, o.abs_eps_cost, o.rel_eps_cost, o.abs_eps_params, o.rel_eps_params, o.max_iter = eta, abs_eps_cost, rel_eps_cost, abs_eps_params, rel_eps_params, int(max_iter)
+    if chunk is not None:
+        o.chunk = int(chunk)
+    n = len(problems)
+    P = (DmProblem * max(n, 1))(); R = (DmResult * max(n, 1))()
+    keep = []
+    for i, pr in enumerate(problems):
+        d = _dm_data(pr["data"], "dm_train")
+        a0 = np.ascontiguousarray(np.asarray(pr["alpha0"], np.float64).reshape(d.shape[1], -1))
+        q0 = np.ascontiguousarray(pr["q0"], np.float64).ravel() if pr.get("q0") is not None else None
+        if q0 is not None and len(q0) != a0.shape[1]:
+            raise EngineError("dm_train: problem %d: q0 of %d entries, alpha0 of %d components" % (i, len(q0), a0.shape[1]))
+        keep.append((d, a0, q0))
+        P[i] = DmProblem(d.shape[1], a0.shape[1], d.shape[0], _p(d, C.c_double), _p(a0, C.c_double), _p(q0, C.c_double) if q0 is not None else None)
+    CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int64, C.c_int32)
+    cb = CB((lambda user, it, running: progress(int(it), int(running))) if progress else 0)
+    _chk(lib.hu_dm_train(C.c_int(device), C.c_int32(n), P, C.byref(o), R, cb, None))
+    out = []
+    for i, (d, a0, q0) in enumerate(keep):
+        K, L = a0.shape
+        out.append(dict(alpha=np.array([list(R[i].alpha[r][:L]) for r in range(K)]), q=np.array(R[i].q[:L]), cost=float(R[i].cost),
+                        iterations=int(R[i].iterations), status=DM_STATUS.get(int(R[i].status), str(int(R[i].status)))))
+    return out
+
+
+def dm_special(x, device=0):
+    """hu_dm_special (test probe): the training kernel's lgamma and digamma at the points x > 0"""
+    xs = np.ascontiguousarray(x, np.float64).ravel()
+    lg = np.zeros_like(xs); dg = np.zeros_like(xs)
+    _chk(load_library().hu_dm_special(C.c_int(device), C.c_int64(len(xs)), _p(xs, C.c_double), _p(lg, C.c_double), _p(dg, C.c_double)))
+    return lg, dg
+
+
+def dm_write(path, me_q, me_alpha, ie_alpha, mt_alpha, it_alpha, dt_alpha, cost):
+    """hu_dm_write (host only): a prior file (.dm) as the reference's operator<< writes it; cost: the five training costs ME IE MT IT DT"""
+    p = HmmPrior()
+    q = np.asarray(me_q, np.float64).ravel(); a = np.asarray(me_alpha, np.float64)
+    L = len(q)
+    if a.shape != (4, L) or not 1 <= L <= HMM_MAX_MIX:
+        raise EngineError("dm_write: me_q [L] and me_alpha [4][L]")
+    p.me_L = L
+    for j in range(L):
+        p.me_q[j] = q[j]
+        for i in range(4):
+            p.me_alpha[i][j] = a[i, j]
+    for name, v, k in (("ie_alpha", ie_alpha, 4), ("mt_alpha", mt_alpha, 3), ("it_alpha", it_alpha, 2), ("dt_alpha", dt_alpha, 2)):
+        v = np.asarray(v, np.float64).ravel()
+        if len(v) != k:
+            raise EngineError("dm_write: %s of %d entries" % (name, k))
+        for i in range(k):
+            getattr(p, name)[i] = v[i]
+    c = np.ascontiguousarray(cost, np.float64).ravel()
+    if len(c) != 5:
+        raise EngineError("dm_write: five costs")
+    _chk(load_library().hu_dm_write(os.fsencode(str(path)), C.byref(p), _p(c, C.c_double)))
+
+
 class SimOpts(C.Structure):
     _fields_ = [("max_dist", C.c_double), ("mean_size", C.c_double), ("sd_size", C.c_double), ("min_size", C.c_double), ("max_size", C.c_double),
                 ("n_regions", C.c_int64), ("regions", C.POINTER(C.c_int32))]

@@ -802,6 +802,64 @@ int hu_hmm_estimate(int32_t K, const double* e_m, const double* e_i, const doubl
 int hu_hmm_write(const char* path, const char* version, const char* name, int32_t K, int32_t cs_len, const double* p_m, const double* p_i,
 		const double* p_t, const int32_t* map, const char* cons, int64_t n_seq, double eff_n, const char* date);
 
+/* ---- training the prior file (hmmufotu-train-dm) ----------------------------------------------------------------
+ * src/hmmufotu-train-dm.cpp:236-373 in five steps: the training sets (device), the shuffle and the moment fit that start a model
+ * (host), the gradient ascent of a batch of models (device), the file (host).  A training set is [M][K]: the K values of a data
+ * column lie together.  A model's alpha is [K][L], residue or transition i, component j; a density is a model with L = 1.
+ *
+ * hu_dm_training_data: the double loop of src/hmmufotu-train-dm.cpp:253-333 on the pruned alignment (msa, n_seq rows of cs_len bytes,
+ * and weight [n_seq] as hu_msa_stats returns it).  The weights are scaled by (1 / pri_rate) / n_seq (MSA::sclaleWeight, :236-237), the
+ * weighted counts are summed again from the scaled weights (MSA::updateWeightedCounts, src/MSA.cpp:280-293), a column is a match
+ * column where symWFrac(j) >= symfrac (src/MSA.cpp:81-85; symfrac in [0, 1]), and the states are determineMatchingState's as in
+ * hu_hmm_counts (k_hmm_states), I->D and D->I not counted.  As in the reference, the search for the next cell steps past the cell it
+ * found before it tests for the end (:287-294), so a transition into the last column is dropped like one into nothing.  Outputs: mask
+ * [cs_len]; data_me, data_ie [.][4] (weighted base counts of the match / other columns), data_mt [.][3] (M->M M->I M->D), data_it
+ * [.][2] (I->M I->I), data_dt [.][2] (D->M D->D), each with room for cs_len columns and holding, in ascending j, the columns
+ * j < cs_len - 1 with a non-zero entry (the emissions: every column); n_cols [5] their numbers of columns.  Every value is a serial
+ * sum over the rows in ascending order: the reference's bit for bit.  hu_dm_training_data_timing: of this thread's last call, seconds
+ * [4] = allocation and copies to the device, the weighted counts and the mask, k_hmm_states and k_dm_drop, k_dm_counts; *peak_bytes
+ * as hu_hmm_counts_timing. */
+int hu_dm_training_data(int device, int64_t n_seq, int64_t cs_len, const char* msa, const double* weight, double pri_rate, double symfrac,
+		uint8_t* mask, double* data_me, double* data_ie, double* data_mt, double* data_it, double* data_dt, int64_t* n_cols /* [5] */);
+int hu_dm_training_data_timing(double* seconds /* [4] */, int64_t* peak_bytes);
+/* host only: std::random_shuffle of 0 .. M - 1 as DirichletMixture::momentInit calls it (src/math/DirichletMixture.cpp:215-218):
+ * libstdc++'s loop, for i = 1 .. M - 1 swap(idx[i], idx[rand() % (i + 1)]), on the C library's rand().  seed non-NULL: srand(*seed)
+ * first (src/hmmufotu-train-dm.cpp:184); NULL: the stream goes on, which is what a further seed of -n does. */
+int hu_dm_shuffle(int64_t M, const uint32_t* seed, int32_t* idx);
+/* host only: momentInit of a density (L = 1; src/math/DirichletDensity.cpp:105-133; idx unused) or of a mixture (L >= 2;
+ * src/math/DirichletMixture.cpp:208-252; idx [M]: the order hu_dm_shuffle gave).  alpha [K][L] comes back as 1 where the reference
+ * leaves the model untouched: M < 2 (density) or M < 2 L (mixture), and a density or a block of M / L columns in which no i gives
+ * alphaNorm > 0. */
+int hu_dm_moment_init(int32_t K, int32_t L, int64_t M, const double* data, const int32_t* idx, double* alpha);
+/* trainML of src/math/DirichletDensity.cpp:46-77 and src/math/DirichletMixture.cpp:92-146 without their momentInit, for n independent
+ * problems on the device: k_dm_train, one workgroup per problem, at most `chunk` iterations per launch; the host launches until no
+ * problem is running and calls progress(user, iterations of the furthest problem, problems still running) after every launch.  What
+ * a problem carries between launches is complete: the result is the same bit for bit for every chunk and for every batch the problem
+ * is part of.  K 2 .. 4; L 1 (density) or 2 .. 10 (mixture); alpha0 [K][L] > 0 (w starts as its logarithm); q0 [L], NULL: 1 / L.
+ * status: HU_DM_CONVERGED the reference's stop test (isApprox on alpha at abs_eps_params + rel_eps_params |alpha_old|, and
+ * 0 <= deltaC < abs_eps_cost + rel_eps_cost cOld); HU_DM_MAXIT max_iter iterations done (0: no limit); HU_DM_NAN_OVERFIT an alpha
+ * became 0 and HU_DM_NAN_UNUSED a mixture coefficient fell below 1 / M, the reference's two NaN returns (cost: NaN);
+ * HU_DM_NOT_FINITE the cost is NaN or infinite, where the reference would not end.  M = 0: nothing is trained, alpha0 comes back with
+ * cost 0 and HU_DM_CONVERGED after 0 iterations. */
+#define HU_DM_CONVERGED 1
+#define HU_DM_MAXIT 2
+#define HU_DM_NAN_OVERFIT 3
+#define HU_DM_NAN_UNUSED 4
+#define HU_DM_NOT_FINITE 5
+typedef struct { int32_t K, L; int64_t M; const double* data; const double* alpha0; const double* q0; } hu_dm_problem;
+typedef struct { double eta, abs_eps_cost, rel_eps_cost, abs_eps_params, rel_eps_params; int64_t max_iter; int32_t chunk, pad0; } hu_dm_opts;
+typedef struct { double alpha[4][10]; double q[10]; double cost; int64_t iterations; int32_t status, pad0; } hu_dm_result;
+typedef void (*hu_dm_progress)(void* user, int64_t iterations, int32_t running);
+void hu_dm_default_opts(hu_dm_opts* o);     /* eta 0.001 (src/math/DirichletModel.cpp:15); epsilons 0, 1e-6, 0, 1e-4 (src/BandedHMMP7Prior.cpp:32-35); max_iter 0; chunk 64 */
+int hu_dm_train(int device, int32_t n, const hu_dm_problem* prob, const hu_dm_opts* opts, hu_dm_result* out, hu_dm_progress progress, void* user);
+/* test probe: the kernels' lgamma (the device library's) and digamma (hu_kern_dm.h) at n points x > 0 */
+int hu_dm_special(int device, int64_t n, const double* x, double* lgamma_out, double* digamma_out);
+/* host only: operator<< of BandedHMMP7Prior (src/BandedHMMP7Prior.cpp:62-69) with DirichletMixture::print
+ * (src/math/DirichletMixture.cpp:197-206) and DirichletDensity::print (src/math/DirichletDensity.cpp:96-103): the training costs cost
+ * [5] (ME IE MT IT DT) at the stream's 6 digits, q and alpha under Eigen's FullPrecision format, 16 significant digits, every entry
+ * right-aligned to the widest of its matrix.  path "-": the standard output. */
+int hu_dm_write(const char* path, const hu_hmm_prior* prior, const double* cost /* [5] */);
+
 #ifdef __cplusplus
 }
 #endif
