@@ -4,19 +4,18 @@
 //   hmmufotu-amd-sum <HmmUFOtu-DB> <INFILE [INFILE2 ...]> -o OTU-OUT [-r FILE] [-l FILE] [--use-dbname] [-q DBL] [--aln-iden DBL]
 //                    [--hmm-iden DBL] [-n INT] [-s INT] [-v]
 //                    [-t OTU-TREE]
-// -t: the OTU tree (PTUnrooted::convertToNewickTree(getAncestors(otuSeen), prefix), src/PhyloTreeUnrooted.cpp:426-447, 1127-1133; NewickTree::write,
-// src/NewickTree.cpp:61-77): the tree cut down to the paths from the OTUs to the root — a node's children are written, all of them, when one
-// of them lies on such a path.
+// -t: the OTU tree, the tree cut down to the paths from the OTUs to the root (hu_otu_tree.h, shared with hmmufotu-amd-merge).
 // Not here: -c (consensus sequences of the OTUs: Dirichlet-density inference, training-side code of the reference) and --pseudo-tree (its new
 // node ids follow the iteration order of a hash set of pointers: not reproducible); asking for them is an error, not a silent skip.
 // Host only: the tree's annotations come from <DB>.ptu through hu_tree_info_* (messages read past), the profile map from <DB>.hmm.
 #include <algorithm>
 #include <fstream>
-#include <functional>
 #include <iostream>
 #include <map>
 #include <sstream>
 #include "hu_tsv_reader.h"
+#include "hu_num_format.h"
+#include "hu_otu_tree.h"
 #include "../../include/hmmufotu_amd.h"
 
 static void usage(const char* p) {
@@ -36,9 +35,6 @@ static void usage(const char* p) {
 		"            -v  FLAG           : verbose\n"
 		"            (-c and --pseudo-tree of hmmufotu-sum are not provided)\n";
 }
-
-/* a count as Eigen's IOFormat(FullPrecision) prints a double holding an integer (src/OTUTable.cpp:26, 161) */
-static std::string num(double v) { std::ostringstream o; o.precision(15); o << v; return o.str(); }
 
 int main(int argc, char** argv) {
 	std::vector<std::string> pos; std::string otuFn, readFn, listFn, treeFn;
@@ -136,7 +132,7 @@ int main(int argc, char** argv) {
 		const char* anno = "";
 		hu_tree_info_node(ti, u, nullptr, nullptr, nullptr, nullptr, nullptr, &anno);
 		otuOut << prefix << u;
-		for(long c : count[u]) otuOut << "\t" << num((double) c);
+		for(long c : count[u]) otuOut << "\t" << hu_num((double) c);
 		otuOut << "\t" << anno << std::endl;                             /* PTUNode::getTaxon(maxDist = inf) == the annotation */
 	}
 	if(readOut.is_open()) { /* src/hmmufotu-sum.cpp:433-440; the info string starts without a blank there, too */
@@ -146,21 +142,7 @@ int main(int argc, char** argv) {
 	if(!treeFn.empty()) { /* src/hmmufotu-sum.cpp:462-466 */
 		std::ofstream treeOut(treeFn);
 		if(!treeOut) { std::cerr << "Unable to write to '" << treeFn << "'" << std::endl; return EXIT_FAILURE; }
-		int32_t root = 0;
-		hu_tree_info_get(ti, nullptr, nullptr, &root, nullptr);
-		std::vector<char> onPath((size_t) N, 0);                          /* getAncestors(otuSeen): the OTUs and everything above them */
-		for(int32_t u : kept) for(int32_t v = u; v >= 0 && !onPath[v]; ) { onPath[v] = 1; int32_t par = -1; hu_tree_info_node(ti, v, &par, nullptr, nullptr, nullptr, nullptr, nullptr); v = par; }
-		std::function<void(int32_t)> write = [&](int32_t u) {
-			const int32_t* ch = nullptr; const int nc = hu_tree_info_children(ti, u, &ch);
-			bool flag = false;
-			for(int i = 0; i < nc; ++i) flag |= onPath[ch[i]] != 0;
-			if(flag) { treeOut << '('; for(int i = 0; i < nc; ++i) { if(i) treeOut << ","; write(ch[i]); } treeOut << ')'; }
-			int32_t par = -1; double len = 0;
-			hu_tree_info_node(ti, u, &par, &len, nullptr, nullptr, nullptr, nullptr);
-			treeOut << prefix << u << ':' << (par < 0 ? 0.0 : len);         /* NewickTree::write: the length whenever it is >= 0, at ostream's default precision */
-		};
-		write(root);
-		treeOut << ';';
+		hu_otu_tree_write(treeOut, ti, kept, prefix);
 	}
 	if(verbose) std::cerr << kept.size() << " OTUs over " << S << " sample(s)" << std::endl;
 	hu_tree_info_free(ti);

@@ -674,6 +674,133 @@ def sim_timing() -> dict:
     return dict(to_device=s[0], kernel=s[1], to_host=s[2])
 
 
+class OtuOpts(C.Structure):
+    _fields_ = [("chunk", C.c_int32), ("key_bits", C.c_int32)]
+
+
+OTU_METHODS = {"uniform": 0, "multinomial": 1}
+
+
+def _otu_dict(h) -> dict:
+    """the content of a hu_otu_table as Python values"""
+    lib = load_library()
+    for f in (lib.hu_otu_table_otu, lib.hu_otu_table_taxon, lib.hu_otu_table_sample):
+        f.restype = C.c_char_p
+    lib.hu_otu_table_counts.restype = C.POINTER(C.c_double)
+    m = C.c_int64(); n = C.c_int64()
+    _chk(lib.hu_otu_table_dims(h, C.byref(m), C.byref(n)))
+    M, S = int(m.value), int(n.value)
+    counts = np.ctypeslib.as_array(lib.hu_otu_table_counts(h), shape=(M, S)).copy() if M * S else np.zeros((M, S))
+    return dict(otus=[lib.hu_otu_table_otu(h, C.c_int64(i)).decode() for i in range(M)], taxa=[lib.hu_otu_table_taxon(h, C.c_int64(i)).decode() for i in range(M)],
+                samples=[lib.hu_otu_table_sample(h, C.c_int64(j)).decode() for j in range(S)], counts=counts)
+
+
+def _otu_handle(table):
+    """a hu_otu_table from dict(otus, taxa, samples, counts [otus][samples]); the caller frees it"""
+    otus = [str(x).encode() for x in table["otus"]]; taxa = [str(x).encode() for x in table["taxa"]]; samples = [str(x).encode() for x in table["samples"]]
+    M, S = len(otus), len(samples)
+    counts = np.ascontiguousarray(table["counts"], np.float64).reshape(M, S) if M * S else np.zeros((M, S))
+    if len(taxa) != M:
+        raise EngineError("otu table: one taxonomy per OTU")
+    h = C.c_void_p()
+    _chk(load_library().hu_otu_table_new(C.c_int64(M), C.c_int64(S), (C.c_char_p * max(M, 1))(*otus), (C.c_char_p * max(M, 1))(*taxa), (C.c_char_p * max(S, 1))(*samples),
+                                         _p(counts, C.c_double), C.byref(h)))
+    return h
+
+
+def otu_table_read(path) -> dict:
+    """hu_otu_table_read (host only): an OTU table in the reference's "table" format as dict(otus, taxa, samples, counts [otus][samples])"""
+    lib = load_library()
+    h = C.c_void_p()
+    _chk(lib.hu_otu_table_read(os.fsencode(str(path)), C.byref(h)))
+    try:
+        return _otu_dict(h)
+    finally:
+        lib.hu_otu_table_free(h)
+
+
+def otu_table_write(path, table, info=""):
+    """hu_otu_table_write (host only): "# HmmUFOtu v1.5.1" + info, the header, one row per OTU, numbers as hmmufotu-amd-sum prints them"""
+    lib = load_library()
+    h = _otu_handle(table)
+    try:
+        _chk(lib.hu_otu_table_write(h, os.fsencode(str(path)), info.encode()))
+    finally:
+        lib.hu_otu_table_free(h)
+
+
+def otu_table_merge(tables) -> dict:
+    """hu_otu_table_merge (host only): the tables added up in the order given, as OTUTable::operator+= adds them"""
+    lib = load_library()
+    acc = _otu_handle(dict(otus=[], taxa=[], samples=[], counts=[]))
+    try:
+        for t in tables:
+            h = _otu_handle(t)
+            try:
+                _chk(lib.hu_otu_table_merge(acc, h))
+            finally:
+                lib.hu_otu_table_free(h)
+        return _otu_dict(acc)
+    finally:
+        lib.hu_otu_table_free(acc)
+
+
+def otu_table_normalize(table, Z=0.0) -> dict:
+    """hu_otu_table_normalize (host only): every cell / (column sum / Z), Z 0 = the largest column sum; "zero_columns": the samples without
+    reads, which stay 0"""
+    lib = load_library()
+    h = _otu_handle(table)
+    try:
+        z = C.c_int64()
+        _chk(lib.hu_otu_table_normalize(h, C.c_double(float(Z)), C.byref(z)))
+        out = _otu_dict(h)
+        out["zero_columns"] = int(z.value)
+        return out
+    finally:
+        lib.hu_otu_table_free(h)
+
+
+def otu_table_prune(table, min_sample=0, otus=True) -> dict:
+    """hu_otu_table_prune_samples, then hu_otu_table_prune_otus (host only): the samples whose total is below min_sample go (0: none), then
+    the OTUs without reads"""
+    lib = load_library()
+    h = _otu_handle(table)
+    try:
+        _chk(lib.hu_otu_table_prune_samples(h, C.c_uint64(int(min_sample))))
+        if otus:
+            _chk(lib.hu_otu_table_prune_otus(h))
+        return _otu_dict(h)
+    finally:
+        lib.hu_otu_table_free(h)
+
+
+def otu_subset(counts, size, method="uniform", seed=0, device=0, chunk=None, key_bits=64) -> np.ndarray:
+    """hu_otu_subset: every sample (column) of counts [otus][samples] rarefied to `size` reads, without ("uniform") or with ("multinomial")
+    replacement; samples of at most `size` reads come back untouched.  device < 0: the library's host path, which gives the same integers."""
+    c = np.ascontiguousarray(counts, np.float64)
+    if c.ndim != 2:
+        raise EngineError("otu_subset: counts [otus][samples]")
+    if method not in OTU_METHODS:
+        raise EngineError("otu_subset: method 'uniform' or 'multinomial', not %r" % (method,))
+    lib = load_library()
+    o = OtuOpts()
+    lib.hu_otu_default_opts(C.byref(o))
+    if chunk is not None:
+        o.chunk = int(chunk)
+    o.key_bits = int(key_bits)
+    out = np.zeros_like(c)
+    _chk(lib.hu_otu_subset(C.c_int(int(device)), C.c_int64(c.shape[0]), C.c_int64(c.shape[1]), _p(c, C.c_double), C.c_uint64(int(size) if int(size) > 0 else 0),
+                           C.c_int(OTU_METHODS[method]), C.c_uint64(int(seed) & (2 ** 64 - 1)), C.byref(o), _p(out, C.c_double)))
+    return out
+
+
+def otu_subset_timing() -> dict:
+    """hu_otu_subset_timing: the phases of this thread's last otu_subset on a device, in seconds"""
+    s = np.zeros(3)
+    _chk(load_library().hu_otu_subset_timing(_p(s, C.c_double)))
+    return dict(to_device=s[0], kernels=s[1], to_host=s[2])
+
+
 def tree_count_mutations(parent, cs_len: int, up_ptr: int, device=0) -> np.ndarray:
     """hu_tree_count_mutations: per column, the non-root nodes whose inferred state differs from their parent's, from the DEVICE
     fixed-rate up buffer at up_ptr ([n][cs_len][4] float64, as tree_evaluate leaves it with win_len 0)"""

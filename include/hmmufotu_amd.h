@@ -860,6 +860,66 @@ int hu_dm_special(int device, int64_t n, const double* x, double* lgamma_out, do
  * right-aligned to the widest of its matrix.  path "-": the standard output. */
 int hu_dm_write(const char* path, const hu_hmm_prior* prior, const double* cost /* [5] */);
 
+/* ---- OTU tables: hmmufotu-merge, hmmufotu-subset, hmmufotu-norm ----
+ * The reference's "table" format (OTUTable::loadTable / saveTable, src/OTUTable.cpp:123-164, behind readProgInfo / writeProgInfo,
+ * src/util/ProgEnv.cpp:101-135): a first line "# HmmUFOtu <version> <info>", a header "otuID <TAB> sample ... <TAB> taxonomy", then per
+ * OTU its id, one number per sample and the rest of the line as taxonomy.  All of hu_otu_table_* is host code.
+ * hu_otu_table_read: HU_ERR_IO with the reference's message when the first line does not scan as "# <name> <version>", names another
+ * program, or carries a version above v1.5.1; a second row with an id already seen is dropped (addOTU returns the first).  Refused
+ * here and not by the reference: a value line before the header (it would add a row of no columns), a second header, a row that has
+ * fewer numbers than the header has samples.  Blank lines are passed over.
+ * hu_otu_table_new: a table from arrays, counts [n_otu][n_sample] row-major; a repeated id is dropped as the reader drops it.
+ * hu_otu_table_write: "# HmmUFOtu v1.5.1<info>", the header, one row per OTU; numbers at ostream's precision 15 as hmmufotu-amd-sum
+ * writes them.  path "-": the standard output.
+ * hu_otu_table_merge: dst += src (src/OTUTable.cpp:211-240): new samples, then new OTUs with src's taxonomy, appended in first-seen
+ * order; counts of a sample name both have are added; an empty dst becomes a copy of src.
+ * hu_otu_table_prune_samples: drops the columns whose sum is < min (min 0: none); hu_otu_table_prune_otus: the rows whose sum is 0.
+ * hu_otu_table_normalize (normalizeConst, :110-121): Z 0 = the largest column sum; every cell becomes cell / (colsum / Z), column sums
+ * taken in ascending row order; an empty or all-zero table is left alone.  A column whose sum is 0 stays 0 and is counted in
+ * *zero_columns (may be NULL) — the reference divides by 0 there and prints NaN.  HU_ERR_ARG for Z < 0 or NaN.
+ * The pointers the getters return stay valid until the table is changed or freed; hu_otu_table_counts is writable. */
+typedef struct hu_otu_table hu_otu_table;
+int hu_otu_table_read(const char* path, hu_otu_table** out);
+int hu_otu_table_new(int64_t n_otu, int64_t n_sample, const char* const* otu_ids, const char* const* taxa, const char* const* samples, const double* counts,
+		hu_otu_table** out);
+void hu_otu_table_free(hu_otu_table* t);
+int hu_otu_table_dims(const hu_otu_table* t, int64_t* n_otu, int64_t* n_sample);
+const char* hu_otu_table_otu(const hu_otu_table* t, int64_t i);
+const char* hu_otu_table_taxon(const hu_otu_table* t, int64_t i);
+const char* hu_otu_table_sample(const hu_otu_table* t, int64_t j);
+double* hu_otu_table_counts(hu_otu_table* t);     /* [n_otu][n_sample], row-major */
+int hu_otu_table_write(const hu_otu_table* t, const char* path, const char* info);
+int hu_otu_table_merge(hu_otu_table* dst, const hu_otu_table* src);
+int hu_otu_table_prune_samples(hu_otu_table* t, uint64_t min);
+int hu_otu_table_prune_otus(hu_otu_table* t);
+int hu_otu_table_normalize(hu_otu_table* t, double Z, int64_t* zero_columns);
+
+/* hu_otu_subset: every sample (column) of counts [n_otu][n_sample] rarefied to `size` reads into out (same shape; may not alias counts),
+ * OTUTable::subsetUniform / subsetMultinom (src/OTUTable.cpp:166-209).  A sample with T_j <= size reads is returned untouched, as there.
+ * device < 0: the host path; otherwise the kernels of hu_kern_otu.h on that device.  Both give the same integers.
+ * The distributions are the reference's, the streams are not (it draws from Boost's mt11213b): the generator is Philox4x32-10
+ * (hu_sim_philox) under the key (seed & 0xffffffff, seed >> 32), and a result is defined by names, not by the order of execution.
+ * HU_OTU_UNIFORM, without replacement: the reads of sample j are numbered t = 0 .. T_j - 1 in row order, OTU i owns [P_i, P_i+1), P the
+ * exclusive prefix sum of column j.  Read t has the key k = (w0 << 32 | w1) >> (64 - key_bits), w the output of the counter
+ * (t & 0xffffffff, t >> 32, j, 2).  The `size` reads smallest in (key, t) order are kept; an OTU's new count is how many lie in its range.
+ * HU_OTU_MULTINOMIAL, with replacement: draw m = 0 .. size - 1 takes r = w0 << 32 | w1 of the counter (m & 0xffffffff, m >> 32, j, 3)
+ * and counts for the OTU that owns read t = (r * T_j) >> 64 (the high half of the 128-bit product; the bias is below T_j / 2^64).
+ * opts NULL: the defaults.  chunk: reads (draws) per workgroup, > 0, device path only — the result does not depend on it.  key_bits:
+ * 1 .. 64; below 64 it makes keys tie, so that the tie rule can be tested; the programs do not offer it.
+ * HU_ERR_ARG with the reason, before anything reaches a device: a cell that is negative, not finite or not an integer (the reference
+ * truncates fractions silently), a column total of 2^32 or more, size 0, an unknown method, chunk or key_bits out of range.
+ * hu_otu_subset_timing: of this thread's last device call, seconds [3] = copies to the device, kernels, copy back. */
+#define HU_OTU_UNIFORM 0
+#define HU_OTU_MULTINOMIAL 1
+typedef struct {
+	int32_t chunk;        /* 16384 */
+	int32_t key_bits;     /* 64 */
+} hu_otu_opts;
+void hu_otu_default_opts(hu_otu_opts* o);
+int hu_otu_subset(int device, int64_t n_otu, int64_t n_sample, const double* counts, uint64_t size, int method, uint64_t seed, const hu_otu_opts* opts,
+		double* out);
+int hu_otu_subset_timing(double* seconds /* [3] */);
+
 #ifdef __cplusplus
 }
 #endif
