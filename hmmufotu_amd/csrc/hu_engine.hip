@@ -2506,15 +2506,18 @@ extern "C" int hu_estimate_batch(hu_batch* b, const hu_opts* o) try {
 			const int xm = b->knob.xcd_map;
 			const unsigned egl = pass ? eg : order ? std::min<unsigned>(eg, (unsigned) b->n * (unsigned) b->seedCap) : eg;
 			const int var = b->knob.est_var;
-			if(stream || spt > 12) k_estimate<<<eg, 64, 0, b->stream>>>(EST_ARGS);
+			/* which instance takes the launch: the tests of the width classes match this line (tests/test_hiprec_gpu.py) */
+			auto said = [&](const char* k) { if(b->knob.trace) fprintf(stderr, "[hu] estimate: max region %d, %s\n", maxR, k); };
+			if(stream || spt > 12) { said("k_estimate"); k_estimate<<<eg, 64, 0, b->stream>>>(EST_ARGS); }
 			else if(var == 2) { /* the per-site log() form, kept for comparison */
-				if(spt <= 2) k_estimate_blk<2, 256><<<eg, 256, 0, b->stream>>>(EST_ARGS);
-				else if(spt <= 4) k_estimate_blk<4, 256><<<eg, 256, 0, b->stream>>>(EST_ARGS);
-				else if(spt <= 6) k_estimate_blk<6, 256><<<eg, 256, 0, b->stream>>>(EST_ARGS);
-				else if(spt <= 8) k_estimate_blk<8, 256><<<eg, 256, 0, b->stream>>>(EST_ARGS);
-				else k_estimate_blk<12, 256><<<eg, 256, 0, b->stream>>>(EST_ARGS);
+				if(spt <= 2) { said("k_estimate_blk<2,256>"); k_estimate_blk<2, 256><<<eg, 256, 0, b->stream>>>(EST_ARGS); }
+				else if(spt <= 4) { said("k_estimate_blk<4,256>"); k_estimate_blk<4, 256><<<eg, 256, 0, b->stream>>>(EST_ARGS); }
+				else if(spt <= 6) { said("k_estimate_blk<6,256>"); k_estimate_blk<6, 256><<<eg, 256, 0, b->stream>>>(EST_ARGS); }
+				else if(spt <= 8) { said("k_estimate_blk<8,256>"); k_estimate_blk<8, 256><<<eg, 256, 0, b->stream>>>(EST_ARGS); }
+				else { said("k_estimate_blk<12,256>"); k_estimate_blk<12, 256><<<eg, 256, 0, b->stream>>>(EST_ARGS); }
 			}
 			else if(var == 98 && spt > 4 && spt <= 6) { /* diagnostic: the shipped 6-site instance with s_memtime stamps, averaged over the slots that ran, to stderr */
+				said("k_estimate_prod<6,4,4,true>");
 				DBuf<long long> ddb;
 				if((rc = ddb.ensure((size_t) egl * 4)) != HU_OK) return rc;
 				HIPCHK(hipMemsetAsync(ddb.p, 0, (size_t) egl * 4 * sizeof(long long), b->stream));
@@ -2526,18 +2529,18 @@ extern "C" int hu_estimate_batch(hu_batch* b, const hu_opts* o) try {
 				for(size_t c = 0; c < (size_t) egl; ++c) if(hd[c * 4 + 3]) { ++ran; for(int i = 0; i < 4; ++i) acc[i] += (double) hd[c * 4 + i]; }
 				if(ran) fprintf(stderr, "[est dbg] per slot (s_memtime ticks, %zu slots): prologue %.0f load %.0f rest %.0f total %.0f\n", ran, acc[0] / ran, acc[1] / ran, acc[2] / ran, acc[3] / ran);
 			}
-			else if(var == 1 && spt <= 6) k_estimate_prod<12, 2><<<egl, 128, 0, b->stream>>>(EST_ARGS, order, xm);
-			else if(var == 3 && spt <= 6) k_estimate_prod<6, 4, 1><<<egl, 256, 0, b->stream>>>(EST_ARGS, order, xm);
-			else if(spt <= 2) k_estimate_prod<2, 4><<<egl, 256, 0, b->stream>>>(EST_ARGS, order, xm);
-			else if(spt <= 4) k_estimate_prod<4, 4><<<egl, 256, 0, b->stream>>>(EST_ARGS, order, xm);
+			else if(var == 1 && spt <= 6) { said("k_estimate_prod<12,2>"); k_estimate_prod<12, 2><<<egl, 128, 0, b->stream>>>(EST_ARGS, order, xm); }
+			else if(var == 3 && spt <= 6) { said("k_estimate_prod<6,4,1>"); k_estimate_prod<6, 4, 1><<<egl, 256, 0, b->stream>>>(EST_ARGS, order, xm); }
+			else if(spt <= 2) { said("k_estimate_prod<2,4>"); k_estimate_prod<2, 4><<<egl, 256, 0, b->stream>>>(EST_ARGS, order, xm); }
+			else if(spt <= 4) { said("k_estimate_prod<4,4>"); k_estimate_prod<4, 4><<<egl, 256, 0, b->stream>>>(EST_ARGS, order, xm); }
 			/* measured and not kept: <3, 8, 3> (512 threads x 3 sites, 66 VGPRs, three pairs per CU on 24 waves): 5.04 ms against 4.40;
 			 * <6, 4, 5> / <6, 4, 6> (five / six workgroups per CU by launch bounds): 96 / 80 VGPRs with 140 / 204 B of scratch, 9.2 / 11.3 ms against 4.4 */
-			else if(spt <= 6) k_estimate_prod<6, 4, 4><<<egl, 256, (size_t)(b->knob.est_lds_pad > 0 && b->knob.est_lds_pad <= 60 ? b->knob.est_lds_pad : 0) * 1024, b->stream>>>(EST_ARGS, order, xm);   /* 128 VGPRs: four workgroups per CU (7.4 -> 6.7 ms) */
-			else if(spt <= 8) k_estimate_prod<8, 4><<<egl, 256, 0, b->stream>>>(EST_ARGS, order, xm);   /* (512 threads x 4 sites measured slower here: 6.99 against 6.36 ms at R ~ 1,850) */
-			else if(var == 4) k_estimate_prod<12, 4><<<egl, 256, 0, b->stream>>>(EST_ARGS, order, xm);    /* est_var = 4: 256 threads x 12 sites, 231 VGPRs, two workgroups of four waves per CU */
+			else if(spt <= 6) { said("k_estimate_prod<6,4,4>"); k_estimate_prod<6, 4, 4><<<egl, 256, (size_t)(b->knob.est_lds_pad > 0 && b->knob.est_lds_pad <= 60 ? b->knob.est_lds_pad : 0) * 1024, b->stream>>>(EST_ARGS, order, xm); }   /* 128 VGPRs: four workgroups per CU (7.4 -> 6.7 ms) */
+			else if(spt <= 8) { said("k_estimate_prod<8,4>"); k_estimate_prod<8, 4><<<egl, 256, 0, b->stream>>>(EST_ARGS, order, xm); }   /* (512 threads x 4 sites measured slower here: 6.99 against 6.36 ms at R ~ 1,850) */
+			else if(var == 4) { said("k_estimate_prod<12,4>"); k_estimate_prod<12, 4><<<egl, 256, 0, b->stream>>>(EST_ARGS, order, xm); }    /* est_var = 4: 256 threads x 12 sites, 231 VGPRs, two workgroups of four waves per CU */
 			/* regions of 2,049 .. 3,072 columns (merged mate pairs): 512 threads x 6 sites, 120 VGPRs — the same two pairs per CU as with 256 x 12, but sixteen
 			 * waves instead of eight work on them and a pair's life is shorter: 5.67 -> 4.92 ms per 4,096 pairs of 2 x 250 bases, 265.6 k -> 276.6 k pairs/s */
-			else k_estimate_prod<6, 8, 2><<<egl, 512, 0, b->stream>>>(EST_ARGS, order, xm);
+			else { said("k_estimate_prod<6,8,2>"); k_estimate_prod<6, 8, 2><<<egl, 512, 0, b->stream>>>(EST_ARGS, order, xm); }
 			#undef EST_ARGS
 		}
 	}
@@ -2701,10 +2704,22 @@ extern "C" int hu_place_batch(hu_batch* b, const hu_opts* o) try {
 			const int spt2 = (maxR + 127) / 128, spt4 = (maxR + 255) / 256;  /* sites per thread with 2 / 4 waves per candidate */
 			const bool stream = b->knob.streaming_sep != 0 || spt4 > 12;
 			#define PL_ARGS dev, b->db->mdl, b->dCodes.p, b->dStart.p, b->dEnd.p, b->dCands.p, b->dPlaceOut.p
+			/* which instance takes the launch: tests/test_gpu_parity.py and tests/test_loads_batched.py match the sites and the site order,
+			 * the tests of the width classes (tests/test_hiprec_gpu.py) the kernel's name */
+			auto said = [&](int S, int NW, bool split, const char* text) {
+				if(!b->knob.trace) return;
+				char k[96]; size_t kn = 0;   /* the name as PL_RUN spells it from its own template arguments, without the blanks */
+				for(const char* c = text; *c && kn + 1 < sizeof(k); ++c) if(*c != ' ') k[kn++] = *c;
+				k[kn] = 0;
+				if(!S) fprintf(stderr, "[hu] place: %zu candidates, max region %d, sites streamed per sweep, column order, one wave per candidate, %s\n", nc, maxR, k);
+				else fprintf(stderr, "[hu] place: %zu candidates, max region %d, %d sites per thread, %s, %s, %s\n", nc, maxR, S, split ? "gap/base split slots" : "column order",
+						NW == 2 ? "EM across both waves" : "EM across four waves", k);
+			};
 			if(stream) { /* regions of more than 3,072 columns: one wave per candidate, messages re-streamed per sweep */
 				const size_t lds = (size_t)(3 * HU_MAX_DGK * 4 + HU_MAX_DGK * 5 * 4 + maxR) * sizeof(double);
 				if(lds > 160 * 1024) { hu_set_error("alignment region of %d columns does not fit the placement kernel's LDS", maxR); return HU_ERR_ARG; }
 				if(lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*) k_place, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+				said(0, 1, false, "k_place");
 				k_place<<<grid, 64, lds, b->stream>>>(PL_ARGS);
 			}
 			else { /* one workgroup per candidate, messages and per-site ratios register-resident.  Measured on MI355X
@@ -2720,7 +2735,13 @@ extern "C" int hu_place_batch(hu_batch* b, const hu_opts* o) try {
 					if((rc = order_by_key(b, b->dSortK.p, b->dSortV.p, nc, (uint32_t) b->db->dev.nNodes, b->dSortV.p + nc, false)) != HU_OK) return rc;
 					order = b->dSortV.p + nc;
 				}
-				#define PL_GO(S, NW, E, R, O) k_place_blk<S, NW, E, R, O><<<grid, 64 * NW, 0, b->stream>>>(PL_ARGS, nullptr, order, nullptr, nullptr, xm)
+				/* every k_place_blk launch of the chain: the trace names the instance from the template arguments that are launched.
+				 * SPLIT: through the site lists (PERM / PCNT) or in column order; LDS: dynamic bytes; DD: the stamps of a diagnostic build */
+				#define PL_RUN(SPLIT, LDS, DD, PERM, PCNT, S, NW, ...) do { said(S, NW, SPLIT, "k_place_blk<" #S "," #NW "," #__VA_ARGS__ ">"); \
+					k_place_blk<S, NW, __VA_ARGS__><<<grid, 64 * NW, LDS, b->stream>>>(PL_ARGS, DD, order, PERM, PCNT, xm); } while(0)
+				#define PL_GO(S, NW, E, R, O) PL_RUN(false, 0, nullptr, nullptr, nullptr, S, NW, E, R, O)
+				/* the batch takes the 8-site split form: every read with a region fits 6 x 128 gap and 2 x 128 base slots */
+				const bool split8 = spt2 > 4 && spt2 <= 8 && !pass && !b->knob.place_nosplit && b->maxGapSites <= 6 * 128 && b->maxBaseSites <= 2 * 128;
 				if((var == 99 || var == 98) && spt4 <= 6) { /* diagnostic: per-phase s_memtime stamps, averaged over the candidates, to stderr */
 					DBuf<long long> ddb;
 					if((rc = ddb.ensure(nc * 12)) != HU_OK) return rc;
@@ -2729,13 +2750,13 @@ extern "C" int hu_place_batch(hu_batch* b, const hu_opts* o) try {
 					/* place_var = 98 stamps the instance that the batch would take, in its launch order: the split form (GS = 10, sites through the
 					 * site list) where every read fits its slots, the column-order form (GS = 0) otherwise or with place_nosplit */
 					const bool split98 = var == 98 && !pass && !b->knob.place_nosplit && spt2 > 8 && b->maxGapSites <= 10 * 128 && b->maxBaseSites <= 2 * 128;
-					if(var == 99) k_place_blk<6, 4, 3, 0, 1, true><<<grid, 256, 0, b->stream>>>(PL_ARGS, dd);
+					if(var == 99) { said(6, 4, false, "k_place_blk<6,4,3,0,1,true>"); k_place_blk<6, 4, 3, 0, 1, true><<<grid, 256, 0, b->stream>>>(PL_ARGS, dd); }
 					else if(split98) {
 						if((rc = b->dPerm.ensure((size_t) b->n * 12 * 128)) != HU_OK) return rc;
 						k_site_perm<<<b->n, 64, 0, b->stream>>>(dev, b->n, b->dCodes.p, b->dStart.p, b->dEnd.p, 10 * 128, 2 * 128, b->dPerm.p);
-						k_place_blk<12, 2, 3, 0, 2, true, 1, 10><<<grid, 128, 0, b->stream>>>(PL_ARGS, dd, order, b->dPerm.p, b->dPermCnt.p, xm);
+						PL_RUN(true, 0, dd, b->dPerm.p, b->dPermCnt.p, 12, 2, 3, 0, 2, true, 1, 10);
 					}
-					else k_place_blk<12, 2, 3, 0, 2, true, 1><<<grid, 128, 0, b->stream>>>(PL_ARGS, dd, order, nullptr, nullptr, xm);
+					else PL_RUN(false, 0, dd, nullptr, nullptr, 12, 2, 3, 0, 2, true, 1);
 					std::vector<long long> hd(nc * 12);
 					HIPCHK(hipMemcpyAsync(hd.data(), dd, nc * 12 * sizeof(long long), hipMemcpyDeviceToHost, b->stream));
 					HIPCHK(hu_wait(b->stream));
@@ -2749,7 +2770,9 @@ extern "C" int hu_place_batch(hu_batch* b, const hu_opts* o) try {
 				}
 				else if(var == 4 && spt4 <= 6) PL_GO(6, 4, 1, 0, 1);
 				else if(var == 5 && spt4 <= 6) PL_GO(6, 4, 2, 1, 1);
-				else if(var == 6 && spt2 <= 12) PL_GO(12, 2, 1, 0, 2);
+				/* place_var = 6: twelve sites per thread with a reciprocal per site -- except where the batch takes the 8-site split form, whose place_var = 6 instance
+				 * (v in registers) is chosen below.  (This branch used to take those batches too, which left that instance unreachable.) */
+				else if(var == 6 && spt2 <= 12 && !split8) PL_GO(12, 2, 1, 0, 2);
 				else if(spt2 <= 4) PL_GO(4, 2, 3, 0, 2);
 				else if(spt2 <= 12 && !(var == 7)) {
 					/* 8 or 12 sites per thread.  When every read of the batch fits, its gap sites and its base sites go to separate
@@ -2757,8 +2780,7 @@ extern "C" int hu_place_batch(hu_batch* b, const hu_opts* o) try {
 					 * need no per-site table.  The counts come from k_site_count (estimate stage, read back by the filter stage). */
 					const int S = spt2 <= 8 ? 8 : 12, G = S - 2;
 					/* every read with a region fits the slots: the largest counts of the batch come with the candidate count (k_cand_scan) */
-					const bool split = !pass && !b->knob.place_nosplit && b->maxGapSites <= G * 128 && b->maxBaseSites <= (S - G) * 128;
-					if(b->knob.trace) fprintf(stderr, "[hu] place: %zu candidates, max region %d, %d sites per thread, %s, %s\n", nc, maxR, S, split ? "gap/base split slots" : "column order", "EM across both waves");
+					const bool split = S == 8 ? split8 : !pass && !b->knob.place_nosplit && b->maxGapSites <= G * 128 && b->maxBaseSites <= (S - G) * 128;
 					if(split) {
 						if((rc = b->dPerm.ensure((size_t) b->n * S * 128)) != HU_OK) return rc;
 						/* not cleared: k_site_perm writes the entries below a read's counts, and k_place_blk discards what an invalid slot reads (entry 0 of its half,
@@ -2768,12 +2790,12 @@ extern "C" int hu_place_batch(hu_batch* b, const hu_opts* o) try {
 						 * SIMD: FIVE workgroups per CU instead of four (the LDS holds five) — the kernel's time goes with the resident candidates
 						 * (DESIGN.md section 7): 4.18 -> 3.78 ms per 8,192 reads at gg_97 scale, 853 k -> 896 k reads/s.  Same arithmetic (results equal to 1e-12, iteration counts identical).
 						 * Measured and not kept: the model constants read from global memory instead of 1.5 KB of LDS, which lets a sixth workgroup in — 32 B of scratch, 3.97 ms. */
-						if(S == 8 && var != 6) k_place_blk<8, 2, 3, 0, 3, false, 3, 6><<<grid, 128, 3 * 8 * 128 * sizeof(double), b->stream>>>(PL_ARGS, nullptr, order, b->dPerm.p, b->dPermCnt.p, xm);
-						else if(S == 8) k_place_blk<8, 2, 3, 0, 2, false, 0, 6><<<grid, 128, 0, b->stream>>>(PL_ARGS, nullptr, order, b->dPerm.p, b->dPermCnt.p, xm);   /* place_var = 6: v in registers, two waves per SIMD */
-						else k_place_blk<12, 2, 3, 0, 2, false, 1, 10><<<grid, 128, (size_t)(b->knob.place_lds_pad > 0 && b->knob.place_lds_pad <= 44 ? b->knob.place_lds_pad : 0) * 1024, b->stream>>>(PL_ARGS, nullptr, order, b->dPerm.p, b->dPermCnt.p, xm);
+						if(S == 8 && var != 6) PL_RUN(true, 3 * 8 * 128 * sizeof(double), nullptr, b->dPerm.p, b->dPermCnt.p, 8, 2, 3, 0, 3, false, 3, 6);
+						else if(S == 8) PL_RUN(true, 0, nullptr, b->dPerm.p, b->dPermCnt.p, 8, 2, 3, 0, 2, false, 0, 6);   /* place_var = 6: v in registers, two waves per SIMD */
+						else PL_RUN(true, (size_t)(b->knob.place_lds_pad > 0 && b->knob.place_lds_pad <= 44 ? b->knob.place_lds_pad : 0) * 1024, nullptr, b->dPerm.p, b->dPermCnt.p, 12, 2, 3, 0, 2, false, 1, 10);
 					}
 					else if(S == 8) PL_GO(8, 2, 3, 0, 2);
-					else k_place_blk<12, 2, 3, 0, 2, false, 1><<<grid, 128, 0, b->stream>>>(PL_ARGS, nullptr, order, nullptr, nullptr, xm);
+					else PL_RUN(false, 0, nullptr, nullptr, nullptr, 12, 2, 3, 0, 2, false, 1);
 				}
 				else if(var == 7 && spt2 <= 12) PL_GO(12, 2, 3, 0, 2);
 				else if(spt4 <= 8) PL_GO(8, 4, 3, 0, 1);
@@ -2784,8 +2806,9 @@ extern "C" int hu_place_batch(hu_batch* b, const hu_opts* o) try {
 				 * four waves per CU.  One component of v in LDS (VL = 1, 24 KB per workgroup) -> 239 VGPRs, two waves per SIMD, TWO candidates per CU:
 				 * 8.2 -> 4.96 ms per 4,096 pairs of 2 x 250 bases, 277 k -> 309 k pairs/s (the kernel's time goes with the resident candidates) */
 				else if(var == 9) PL_GO(12, 4, 3, 0, 1);     /* place_var = 9: the all-register form */
-				else k_place_blk<12, 4, 3, 0, 2, false, 1><<<grid, 256, 0, b->stream>>>(PL_ARGS, nullptr, order, nullptr, nullptr, xm);
+				else PL_RUN(false, 0, nullptr, nullptr, nullptr, 12, 4, 3, 0, 2, false, 1);
 				#undef PL_GO
+				#undef PL_RUN
 			}
 			#undef PL_ARGS
 		}

@@ -1,6 +1,6 @@
-"""Regenerates tests/golden/hiprec.npz: the floating-point stages of the per-read task in 50-digit arithmetic.
+"""Regenerates tests/golden/hiprec.npz and hiprec_wide.npz: the floating-point stages of the per-read task in 50-digit arithmetic.
 
-    python tests/golden/make_hiprec_golden.py [--out PATH] [--workers N]
+    python tests/golden/make_hiprec_golden.py [--set narrow|wide] [--out PATH] [--workers N]
 
 A second derivation, independent of oracle/ and of the engine: it is written from the reference's source (cited as file:line below)
 and the mathematics, imports neither, and works in LINEAR space with mpmath (mp.dps = 50) where both of them work in log space with
@@ -23,6 +23,12 @@ Contents, per database CASE (key prefix "<model><dg_k>_"):
      inferred-state components; per read the smallest distance of a filter gap from 20.
 The run fails if more than 5 % of a database's candidates are knife-edge (margin < 1e-6, conditioned margin < 1 or state gap < 1e-9)
 or a filter gap lies within 1e-6 of 20: change READ_SEED then, not the caps.
+
+--set wide (hiprec_wide.npz) is the same mathematics on the widths the product runs: two databases of 8 leaves x 3,300 columns (GTR with 4
+rate categories, JC69 without dGamma) and twelve reads each (WIDE_READS: a leaf's row with 3 % substitutions, `bases` base sites in a
+region of `cols` columns, every other site a gap), one per width class of the estimate / placement dispatch; per candidate the same values
+as above, q complements for three reads.  To stay under the size cap it holds the messages and the per-column root log-likelihood at the
+MSG_COLS columns only (and the serial sum over all columns), and no P(t) block.  It costs about 65 CPU-minutes (9 minutes with 8 workers).  The conditions above hold for it with its own read seed.
 
 The archive is written with fixed zip timestamps, so a rerun reproduces it byte for byte.
 """
@@ -56,6 +62,14 @@ BRANCH_EPS = mpf(1e-5)                                           # src/PhyloTree
 MAX_ITER = 100                                                   # src/PhyloTreeUnrooted.h:1381
 MAX_ERROR = 20.0
 KNIFE_MARGIN, KNIFE_GAP, KNIFE_CAP, FILTER_MARGIN = 1e-6, 1e-9, 0.05, 1e-6
+# the case sets: db_state, make_reads and assemble take one of them
+NARROW = dict(name="narrow", out="hiprec.npz", cases=CASES, db_args=DB_ARGS, read_seed=READ_SEED, q_reads=Q_READS)
+# --set wide: regions of 512 to 3,073 columns, one read per width class of the estimate / placement dispatch
+WIDE_READS = [(512, 120), (513, 100), (1024, 256), (1024, 257), (1025, 150), (1536, 256), (1400, 257), (1537, 200), (2048, 300),
+              (2049, 250), (3072, 500), (3073, 300)]                # (columns, base sites) of each read
+WIDE = dict(name="wide", out="hiprec_wide.npz", cases=[("GTR", 4), ("JC69", 0)], db_args=dict(n_leaves=8, cs_len=3300, n_match=None),
+            read_seed=2031, q_reads=(2, 5, 10))                     # q-values for (1024, 256), (1536, 256) and (3072, 500)
+SETS = dict(narrow=NARROW, wide=WIDE)
 A, C, G, T = 0, 1, 2, 3
 
 
@@ -192,10 +206,11 @@ class DbState:
     pass
 
 
-def db_state(ci):
+def db_state(ci, only_read=None, cfg=NARROW):
+    """only_read: messages (and what is computed from them) for the columns of that read alone — one_candidate on a wide database"""
     from hmmufotu_amd import synth
-    name, dg_k = CASES[ci]
-    db = synth.make_db(DB_ARGS["n_leaves"], DB_ARGS["cs_len"], name, dg_k, n_match=DB_ARGS["n_match"])
+    name, dg_k = cfg["cases"][ci]
+    db = synth.make_db(cfg["db_args"]["n_leaves"], cfg["db_args"]["cs_len"], name, dg_k, n_match=cfg["db_args"]["n_match"])
     s = DbState()
     s.ci, s.name, s.dg_k = ci, name, dg_k
     s.n, s.L = db.n_nodes, db.cs_len
@@ -207,6 +222,11 @@ def db_state(ci):
     s.model = ModelP(name, db.model.pi, db.model.par)
     pi = s.model.pi
     n, L = s.n, s.L
+    s.seq = np.array(db.seq, np.int8)
+    s.read_seed = cfg["read_seed"]
+    s.reads = make_reads(s) if cfg["name"] == "narrow" else make_wide_reads(s)
+    at = range(L) if only_read is None else range(s.reads[only_read][1], s.reads[only_read][2] + 1)
+    row = lambda f: [f(j) if j in at else None for j in range(L)]
     kids = [[] for _ in range(n)]
     for i in range(1, n):
         kids[s.parent[i]].append(i)
@@ -215,32 +235,30 @@ def db_state(ci):
     up = [None] * n; down = [None] * n
     for u in range(n - 1, -1, -1):                               # parents are numbered before their children
         if s.is_leaf[u]:
-            up[u] = [leaf_vec(int(db.seq[u, j]), pi) for j in range(L)]
+            up[u] = row(lambda j: leaf_vec(int(db.seq[u, j]), pi))
         else:
-            up[u] = [join([(Pn[c], up[c][j]) for c in kids[u]], dg) for j in range(L)]
+            up[u] = row(lambda j: join([(Pn[c], up[c][j]) for c in kids[u]], dg))
     for u in range(1, n):
         p = s.parent[u]
-        down[u] = [join(([(Pn[p], down[p][j])] if p != 0 else []) + [(Pn[c], up[c][j]) for c in kids[p] if c != u], dg) for j in range(L)]
+        down[u] = row(lambda j: join(([(Pn[p], down[p][j])] if p != 0 else []) + [(Pn[c], up[c][j]) for c in kids[p] if c != u], dg))
     s.up, s.down = up, down
     # ancestral rows: per-site argmax of the node -> parent message (src/PhyloTreeUnrooted.cpp:1085-1093); the data's must be these
-    seq = np.array(db.seq, np.int8)
+    seq = s.seq
     for u in range(n):
         if not s.is_leaf[u]:
-            for j in range(L):                                   # components equal in exact arithmetic (K80 / JC69): any of them
+            for j in at:                                         # components equal in exact arithmetic (K80 / JC69): any of them
                 assert up[u][j][int(db.seq[u, j])] >= max(up[u][j]) * (1 - TIE), "inner row %d of the database is not the argmax of the 50-digit message" % u
-    s.seq = seq
     # heights: the smallest distance to a descendant leaf (src/PhyloTreeUnrooted.cpp:274-287)
     h = [None] * n
     for u in range(n - 1, -1, -1):
         h[u] = mpf(0) if s.is_leaf[u] else min(h[c] + s.blen[c] for c in kids[u])
     s.height = h
     # treeLoglik of a column: log(pi . root message) (src/PhyloTreeUnrooted.cpp:707-719)
-    s.root_ll = [mp.log(sum(pi[i] * up[0][j][i] for i in range(4))) for j in range(L)]
-    s.root_ll_sum = sum(s.root_ll)
+    s.root_ll = row(lambda j: mp.log(sum(pi[i] * up[0][j][i] for i in range(4))))
+    s.root_ll_sum = sum(s.root_ll) if only_read is None else None
     ngap = (seq[np.array(s.is_leaf)] < 0).sum(0)
     s.msg_cols = sorted({int(np.argmin(ngap)), int(np.argmax(ngap)), int(np.argsort(ngap, kind="stable")[L // 2])})
     assert len(s.msg_cols) == MSG_COLS
-    s.reads = make_reads(s)
     return s
 
 
@@ -249,7 +267,7 @@ def make_reads(s):
     """(codes [L], start, end) x 7: regions of 1, 2, 64 (no gap site), 65 (all gaps but the two ends), 128 (equal to a leaf over its
     region: d = 0), 129 (30 % diverged from every leaf) and 190 columns (a leaf with 3 % substitutions and its gaps).  Both end columns
     of every read hold a base, as an aligned read's do."""
-    rng = np.random.default_rng(READ_SEED + s.ci)
+    rng = np.random.default_rng(s.read_seed + s.ci)
     leaves = np.flatnonzero(s.is_leaf)
     L = s.L
 
@@ -291,6 +309,26 @@ def make_reads(s):
             break
     reads.append(from_leaf(190, 0.03, "leaf"))
     return [(r[0], r[1], r[2]) for r in reads]
+
+
+def make_wide_reads(s):
+    """(codes [L], start, end) per entry of WIDE_READS, made as tests/test_loads_batched.py makes its reads: a random leaf's row (its
+    parent's inferred base where the leaf has a gap) with 3 % substitutions, `bases` base sites, the two ends among them, in a region of
+    `cols` columns; every other site a gap"""
+    rng = np.random.default_rng(s.read_seed + s.ci)
+    leaves = np.flatnonzero(s.is_leaf)
+    reads = []
+    for cols, bases in WIDE_READS:
+        u = int(leaves[rng.integers(len(leaves))])
+        start = int(rng.integers(20, s.L - cols - 20)); end = start + cols - 1
+        at = np.concatenate([[start, end], start + 1 + rng.choice(cols - 2, size=bases - 2, replace=False)])
+        b = np.where(s.seq[u, at] >= 0, s.seq[u, at], s.seq[s.parent[u], at]).astype(np.int8)
+        mut = rng.random(len(at)) < 0.03
+        b[mut] = (b[mut] + rng.integers(1, 4, size=int(mut.sum()))) % 4
+        codes = np.full(s.L, GAP, np.int8)
+        codes[at] = b
+        reads.append((codes, start, end))
+    return reads
 
 
 # ----------------------------------------------------------------------------- e. one candidate
@@ -457,21 +495,28 @@ _STATES = {}
 
 
 def _task(t):
-    ci, ri, u = t
-    return t, candidate(_STATES[ci], ri, u)
+    key, ri, u = t
+    return t, candidate(_STATES[key], ri, u)
 
 
-def assemble(states, results):
+def assemble(states, results, cfg=NARROW):
     """{key: array} of the whole archive"""
-    arc = {"ts": np.array(TS), "max_error": np.array(MAX_ERROR), "dps": np.array(mp.dps), "read_seed": np.array(READ_SEED),
-           "q_reads": np.array(Q_READS, np.int32), "db_args": np.array([DB_ARGS["n_leaves"], DB_ARGS["cs_len"], DB_ARGS["n_match"]], np.int32),
-           "cases": np.array([case_name(*c) for c in CASES])}
+    wide = cfg["name"] == "wide"
+    da = cfg["db_args"]
+    arc = {"ts": np.array(TS), "max_error": np.array(MAX_ERROR), "dps": np.array(mp.dps), "read_seed": np.array(cfg["read_seed"]),
+           "q_reads": np.array(cfg["q_reads"], np.int32),
+           "db_args": np.array([da["n_leaves"], da["cs_len"], -1 if da["n_match"] is None else da["n_match"]], np.int32),
+           "cases": np.array([case_name(*c) for c in cfg["cases"]])}
+    if wide:                                                     # P(t) is not repeated; (columns, base sites) of every read instead
+        del arc["ts"]
+        arc["read_shapes"] = np.array(WIDE_READS, np.int32)
     over = []
     for s in states:
         px = case_name(s.name, s.dg_k) + "_"
         nr, nodes = len(s.reads), list(range(1, s.n))
         mult = [mpf(1)] + (s.rates if s.dg_k > 0 else [])
-        arc[px + "P"] = np.array([[[[float(x) for x in row] for row in s.model.expm(mpf(t) * m)] for m in mult] for t in TS])
+        if not wide:
+            arc[px + "P"] = np.array([[[[float(x) for x in row] for row in s.model.expm(mpf(t) * m)] for m in mult] for t in TS])
         arc[px + "parent"] = np.array(s.parent, np.int32)
         arc[px + "blen"] = np.array([float(x) for x in s.blen])
         arc[px + "seq"] = s.seq
@@ -479,13 +524,13 @@ def assemble(states, results):
         arc[px + "msg_cols"] = np.array(s.msg_cols, np.int32)
         arc[px + "up"] = np.array([[[flog(x) for x in s.up[u][j]] for j in s.msg_cols] for u in range(s.n)])
         arc[px + "down"] = np.array([[[flog(x) for x in s.down[u][j]] if u else [0.0] * 4 for j in s.msg_cols] for u in range(s.n)])
-        arc[px + "root_ll"] = np.array([float(x) for x in s.root_ll])
+        arc[px + "root_ll"] = np.array([float(s.root_ll[j]) for j in (s.msg_cols if wide else range(s.L))])      # wide: at msg_cols only
         arc[px + "root_ll_sum"] = np.array(float(s.root_ll_sum))
         arc[px + "codes"] = np.stack([r[0] for r in s.reads])
         arc[px + "start"] = np.array([r[1] for r in s.reads], np.int32)
         arc[px + "end"] = np.array([r[2] for r in s.reads], np.int32)
         arc[px + "seeds"] = np.array(nodes, np.int32)
-        cand = [[results[(s.ci, ri, u)] for u in nodes] for ri in range(nr)]
+        cand = [[results[((cfg["name"], s.ci), ri, u)] for u in nodes] for ri in range(nr)]
         f = lambda key, dt=np.float64: np.array([[c[key] for c in row] for row in cand], dt)
         arc[px + "dN"] = f("dN", np.int16)
         arc[px + "est_d"] = f("est_d", np.int16)
@@ -509,7 +554,7 @@ def assemble(states, results):
         knife = (arc[px + "margin"] < KNIFE_MARGIN) | (arc[px + "state_gap"] < KNIFE_GAP) | (arc[px + "margin_cond"] < 1)
         if knife.mean() > KNIFE_CAP:
             over.append("%s: %d knife-edge candidates of %d" % (px[:-1], knife.sum(), knife.size))
-        arc[px + "omp"] = np.stack([q_complements(cand[ri]) for ri in Q_READS])
+        arc[px + "omp"] = np.stack([q_complements(cand[ri]) for ri in cfg["q_reads"]])
         print("%-7s knife-edge %d/%d, smallest margin %.3g, conditioned %.3g, state gap %.3g, filter margin %.3g" %
               (px[:-1], knife.sum(), knife.size, arc[px + "margin"].min(), arc[px + "margin_cond"].min(), arc[px + "state_gap"].min(), fm.min()), flush=True)
     assert not over, "more than %g of a database's candidates are knife-edge: change READ_SEED (%s)" % (KNIFE_CAP, "; ".join(over))
@@ -528,33 +573,41 @@ def write_archive(path, arc):
             z.writestr(zi, buf.getvalue(), compresslevel=9)
 
 
-def one_candidate(case, ri, u):
-    """a single candidate regenerated (tests/test_hiprec_oracle.py proves with it that the archive is this file's output)"""
-    ci = [case_name(*c) for c in CASES].index(case)
-    if ci not in _STATES:
-        _STATES[ci] = db_state(ci)
-    c = candidate(_STATES[ci], ri, u)
+def one_candidate(case, ri, u, set_name="narrow"):
+    """a single candidate regenerated (tests/test_hiprec_oracle.py proves with it that the archive is this file's output); of the wide
+    set's databases only the read's own columns are evaluated"""
+    cfg = SETS[set_name]
+    ci = [case_name(*c) for c in cfg["cases"]].index(case)
+    key = (set_name, ci) if set_name == "narrow" else (set_name, ci, ri)
+    if key not in _STATES:
+        _STATES[key] = db_state(ci, None if set_name == "narrow" else ri, cfg)
+    s = _STATES[key]
+    c = candidate(s, ri, u)
     c.pop("_q")
     return c
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(HERE, "hiprec.npz"))
+    ap.add_argument("--set", choices=sorted(SETS), default="narrow")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--workers", type=int, default=min(16, os.cpu_count() or 1))
     a = ap.parse_args()
+    cfg = SETS[a.set]
+    out = a.out or os.path.join(HERE, cfg["out"])
     workers = max(1, min(16, a.workers))
     ctx = multiprocessing.get_context("fork")
-    with ctx.Pool(min(workers, len(CASES))) as pool:
-        states = pool.map(db_state, range(len(CASES)))
+    n = len(cfg["cases"])
+    with ctx.Pool(min(workers, n)) as pool:
+        states = pool.starmap(db_state, [(ci, None, cfg) for ci in range(n)])
     for s in states:
-        _STATES[s.ci] = s
-    tasks = [(s.ci, ri, u) for s in states for ri in range(len(s.reads)) for u in range(1, s.n)]
-    tasks.sort(key=lambda t: -(states[t[0]].reads[t[1]][2] - states[t[0]].reads[t[1]][1]) * (1 + max(states[t[0]].dg_k, 1)))
+        _STATES[(a.set, s.ci)] = s
+    tasks = [((a.set, s.ci), ri, u) for s in states for ri in range(len(s.reads)) for u in range(1, s.n)]
+    tasks.sort(key=lambda t: -(states[t[0][1]].reads[t[1]][2] - states[t[0][1]].reads[t[1]][1]) * (1 + max(states[t[0][1]].dg_k, 1)))
     with ctx.Pool(workers) as pool:                              # forked after _STATES is filled: the workers inherit it
         results = dict(pool.imap_unordered(_task, tasks, chunksize=4))
-    write_archive(a.out, assemble(states, results))
-    print("wrote %s: %d bytes" % (a.out, os.path.getsize(a.out)))
+    write_archive(out, assemble(states, results, cfg))
+    print("wrote %s: %d bytes" % (out, os.path.getsize(out)))
 
 
 if __name__ == "__main__":

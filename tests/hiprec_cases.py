@@ -1,36 +1,47 @@
-"""Shared by tests/test_hiprec_oracle.py and tests/test_hiprec_gpu.py: tests/golden/hiprec.npz (the floating-point stages in 50-digit
-arithmetic, written by tests/golden/make_hiprec_golden.py) and the rules both files read it by."""
+"""Shared by tests/test_hiprec_oracle.py and tests/test_hiprec_gpu.py: tests/golden/hiprec.npz and hiprec_wide.npz (the floating-point
+stages in 50-digit arithmetic, written by tests/golden/make_hiprec_golden.py --set narrow / wide) and the rules both files read them by.
+The narrow archive holds six models on regions of 1 to 190 columns; the wide one two models on twelve reads of 512 to 3,073 columns, one
+per width class of the estimate / placement dispatch (WIDE_READS)."""
 import os
 
 import numpy as np
 
 from conftest import get_db
 
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hiprec.npz")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+GOLD = dict(narrow=os.path.join(GOLDEN, "hiprec.npz"), wide=os.path.join(GOLDEN, "hiprec_wide.npz"))
 CASES = ["GTR4", "TN933", "HKY854", "F810", "K802", "JC690"]
+WIDE_CASES = ["GTR4", "JC690"]
+# (columns, base sites) of read ri of every wide case: what the tests parametrize over (the archive's read_shapes must be this)
+WIDE_READS = [(512, 120), (513, 100), (1024, 256), (1024, 257), (1025, 150), (1536, 256), (1400, 257), (1537, 200), (2048, 300),
+              (2049, 250), (3072, 500), (3073, 300)]
 KNIFE_MARGIN, KNIFE_GAP = 1e-6, 1e-9
 VARIANTS = {(0, 0): 0, (1, 0): 1, (0, 1): 2, (1, 1): 3}        # (prior, fix_root_loglik) -> index into omp
 MAX_Q = 250.0
 
-_ARC = {}
+_ARCS = dict(narrow={}, wide={})
 
 
 class Case:
     """one database of the archive: its arrays as attributes, and the synthetic database they were computed on"""
 
-    def __init__(self, name):
+    def __init__(self, name, archive="narrow"):
+        _ARC = _ARCS[archive]
         if not _ARC:
-            with np.load(GOLD) as z:
+            with np.load(GOLD[archive]) as z:
                 _ARC.update({k: z[k] for k in z.files})
-        self.name = name
+        self.name, self.archive = name, archive
         for k, v in _ARC.items():
             if k.startswith(name + "_"):
                 setattr(self, k[len(name) + 1:], v)
-        self.ts, self.max_error, self.q_reads = _ARC["ts"], float(_ARC["max_error"].ravel()[0]), [int(x) for x in _ARC["q_reads"]]
+        self.ts, self.max_error, self.q_reads = _ARC.get("ts"), float(_ARC["max_error"].ravel()[0]), [int(x) for x in _ARC["q_reads"]]
         self.root_ll_sum = float(self.root_ll_sum.ravel()[0])
         n_leaves, cs_len, n_match = (int(x) for x in _ARC["db_args"])
         model, dg_k = name[:-1], int(name[-1])
-        self.db = get_db(n_leaves, cs_len, model, dg_k=dg_k, seed=97, n_match=n_match)
+        self.db = get_db(n_leaves, cs_len, model, dg_k=dg_k, seed=97, **(dict(n_match=n_match) if n_match >= 0 else {}))
+        if archive == "wide":                                    # one read per entry of WIDE_READS, its base sites counted
+            shapes = [(int(e - s + 1), int((cd[s:e + 1] >= 0).sum())) for cd, s, e in zip(self.codes, self.start, self.end)]
+            assert shapes == WIDE_READS == [tuple(int(x) for x in r) for r in _ARC["read_shapes"]]
         # the same case: tree, rows and rates are the ones the 50-digit run was given
         assert np.array_equal(self.db.parent, self.parent) and np.array_equal(self.db.blen, self.blen) and np.array_equal(self.db.seq, self.seq)
         self.rates = np.concatenate([[1.0], self.db.dg_r]) if dg_k else np.ones(1)
@@ -39,6 +50,19 @@ class Case:
         # (margin_cond < 1: an EM quantity closer to 1e-5 than a relative error of 1e-14 in p moves it through q = 1 - p — an EM that does
         # not converge halves q until 1 - p has no digits left, and the pass count from there on is the arithmetic's, not the formula's)
         self.knife = (self.margin < KNIFE_MARGIN) | (self.state_gap < KNIFE_GAP) | (self.margin_cond < 1)
+
+    def one_read(self, ri):
+        """the same case with read ri alone (a batch of one read: the kernel instance then depends on that read only)"""
+        import copy
+        c = copy.copy(self)
+        for k in ("codes", "start", "end", "dN", "est_d", "est_ratio", "est_wnr_w", "est_ll", "est_ll_w", "pl_ratio", "pl_wnr", "pl_root_ll",
+                  "pl_const_ll", "pl_outer", "pl_em", "pl_a_node", "margin", "state_gap", "margin_cond", "filter_in", "filter_margin", "knife"):
+            setattr(c, k, getattr(self, k)[ri:ri + 1])
+        c.n_reads = 1
+        c.q_reads = [0] if ri in self.q_reads else []
+        if ri in self.q_reads:
+            c.omp = self.omp[self.q_reads.index(ri):][:1]
+        return c
 
     def times(self):
         """the branch lengths of P: [len(ts)][1 + dg_k]"""

@@ -26,17 +26,58 @@ bound each test asserts (ten times the worst, capped by the project's own figure
                                                      + 1e-12 q
   seed counts, ratio, unweighted wnr, iteration counts, filter set, taxon node                    exact
 
-Regions of at most 190 columns select the four-sites-per-thread instance of k_place_blk with v in registers; the instance with v in LDS
-(regions of 513 to 1,024 columns) is not run here (wide regions are held to the oracle elsewhere).
+Regions of at most 190 columns select the four-sites-per-thread instance of k_place_blk with v in registers and k_estimate_prod<2, 4>.
+Every other instance of the two dispatch chains runs on the wide set (tests/golden/hiprec_wide.npz: GTR+4 and JC69 on 8 leaves x 3,300
+columns, twelve reads of 512 to 3,073 columns, each in a batch of its own; WIDE_INSTANCES / WIDE_KNOB_FORMS below name the instance per
+read, which the tests assert from the trace lines).  Its bounds do not come from the kernels: per quantity
+min(project's, max(the narrow bound above, 10 x the oracle's worst distance over the wide set)), the oracle measured on the CPU first.
+
+  quantity (wide set)                              oracle    narrow bound  bound     kernels' worst (MI355X, over every instance)
+  estimated loglik, relative                       6.2e-14   2.1e-13       6.2e-13   7.4e-16
+  weighted wnr, relative to max(|x|, 1e-3)         5.4e-14   2.9e-13       5.4e-13   3.2e-15
+  placed ratio, wnr, relative to max(|x|, 1e-3)    7.6e-12   4.5e-10       4.5e-10   1.8e-11
+  placed height, relative to max(|x|, 1e-3)        7.5e-13   1.7e-11       1.7e-11   5.3e-12
+  intended root loglik, relative                   5.7e-14   4.8e-14       5.7e-13   1.1e-15
+  the reference's constant loglik, relative        1.6e-16   1e-12         1e-12     1.6e-16
+  q-values, eps of the conditioned bound           2.1e-10   1.2e-11       2.1e-9    6.4e-12
+
+  per instance (wide set)                          reads (columns)                     est. loglik   weighted wnr
+  k_estimate_prod<2,4>                             512                                 7.4e-16       3.2e-15
+  k_estimate_prod<4,4>                             513, 1,024                          7.4e-16       7.9e-16
+  k_estimate_prod<6,4,4>                           1,025, 1,400, 1,536                 6.7e-16       5.8e-16
+  k_estimate_prod<8,4>                             1,537, 2,048                        7.3e-16       8.0e-16
+  k_estimate_prod<6,8,2>                           2,049, 3,072                        7.3e-16       7.6e-16
+  k_estimate_prod<12,4> (est_var = 4)              2,049, 3,072                        7.3e-16
+  k_estimate_blk<2 .. 12,256> (est_var = 2)        512, 1,024, 1,536, 2,048, 3,072     7.4e-16
+  k_estimate (streaming)                           3,073                               7.3e-16       1.0e-15
+                                                                                       ratio, wnr    height     root loglik
+  k_place_blk<4,2,3,0,2>                           512                                 2.4e-12       7.9e-13    7.5e-16
+  k_place_blk<8,2,3,0,3,false,3,6> (v in LDS)      513, 1,024 (256 bases)              5.6e-12       1.0e-12    7.4e-16
+  k_place_blk<8,2,3,0,2,false,0,6> (place_var 6)   513, 1,024 (256 bases)              5.6e-12       1.0e-12
+  k_place_blk<8,2,3,0,2>                           1,024 (257 bases; place_nosplit)    5.6e-12       1.2e-12    5.5e-16
+  k_place_blk<12,2,3,0,2,false,1,10>               1,025, 1,536                        1.8e-11       6.5e-13    8.6e-16
+  k_place_blk<12,2,3,0,2,false,1>                  1,400 (257 bases; place_nosplit)    1.3e-11       4.7e-12    1.1e-15
+  k_place_blk<12,2,1,0,2> (place_var 6)            1,024 and 1,400 (257 bases)         1.3e-11       4.7e-12
+  k_place_blk<12,2,3,0,2> (place_var 7)            513, 1,536                          4.8e-12       1.0e-12
+  k_place_blk<8,4,3,0,1>                           1,537, 2,048                        9.2e-12       5.3e-12    7.3e-16
+  k_place_blk<12,4,3,0,2,false,1>                  2,049, 3,072                        5.3e-12       1.1e-12    7.3e-16
+  k_place_blk<12,4,3,0,1> (place_var 9)            2,049, 3,072                        5.3e-12       1.1e-12
+  k_place (streaming)                              3,073                               6.7e-12       6.9e-13    4.9e-16
+
+With the Newton step of the reciprocal shared by four sites (EMV = 3) removed, every EMV = 3 instance is 7.9e-7 to 5.7e-6 off in ratio / wnr
+and fails here, while tests/test_gpu_parity.py::test_wide_region_kernels (REL against the oracle) still passes; with the spt2 <= 8
+threshold moved by one, the 1,024-column reads fail on the instance assertion alone.
 The oracle against the same values (tests/test_hiprec_oracle.py): P(t) 1.0e-15, messages 9.1e-13 (synth's numpy messages 4.2e-12),
 logliks 5.0e-15, placed lengths 5.3e-14 absolute.
 A knife-edge candidate (hiprec_cases.Case.knife: 10 of the 1,260, all on JC69's two-column read) is compared neither in its counts nor
 in its unweighted wnr, and in its lengths to REL; everything else of it is compared as for any other candidate.
 """
+import re
+
 import numpy as np
 import pytest
 
-from hiprec_cases import CASES, Case, q_ok, ratio_half
+from hiprec_cases import CASES, WIDE_CASES, WIDE_READS, Case, q_ok, ratio_half
 
 pytestmark = pytest.mark.gpu
 
@@ -50,8 +91,20 @@ FLOOR_OF = dict(model_pr="model_pr", msg="msg", tree_ll="loglik", est_ll="loglik
                 root_ll="loglik", q_eps="q_eps")
 
 
+# the wide set: the oracle's worst distance from the 50-digit values over both databases and all twelve reads, measured on the CPU
+# (tests/test_hiprec_oracle.py, the HIPREC oracle_wide_* lines; est_ll is the larger of the unweighted and the weighted loglik, q_eps the eps
+# that the conditioned q bound needs) -- plain double arithmetic on the same formulas: ten times it is what their conditioning at these
+# widths allows a correct double implementation
+ORACLE_WIDE = dict(est_ll=6.2e-14, est_wnr_w=5.4e-14, length=7.6e-12, height=7.5e-13, root_ll=5.7e-14, q_eps=2.1e-10)
+
+
 def bound(key):
     return min(FLOOR[FLOOR_OF[key]], TEN_X[key])
+
+
+def bound_wide(key):
+    """min(project floor, max(the narrow bound, 10 x the oracle's worst distance over the wide set)): fixed before any kernel ran"""
+    return min(FLOOR[FLOOR_OF[key]], max(TEN_X[key], 10.0 * ORACLE_WIDE[key]))
 
 
 def worse(worst, key, x):
@@ -118,10 +171,13 @@ def test_tree_messages_and_loglik(name):
     assert worst["height"] < 1e-14
 
 
-def _run(c, knobs=None, stop_after=None, **opts_kw):
-    """the read stages on the archive's reads: every non-root node a seed, every seed placed unless max_error says otherwise"""
+def _run(c, knobs=None, stop_after=None, D=None, **opts_kw):
+    """the read stages on the archive's reads: every non-root node a seed, every seed placed unless max_error says otherwise.
+    D: a database uploaded already, which stays open"""
     E = _engine()
-    D = E.Database.from_synth(c.db)
+    own = D is None
+    if own:
+        D = E.Database.from_synth(c.db)
     B = E.Batch(D, c.n_reads)
     for k, v in (knobs or {}).items():
         B.set_knob(k, v)
@@ -140,11 +196,13 @@ def _run(c, knobs=None, stop_after=None, **opts_kw):
         B.filter_placements(opts); B.place_seq(opts); B.calc_q_values(opts)
         out["cand"] = B.candidates()
         out["offs"], out["places"] = B.candidate_places()
-    B.close(); D.close()
+    B.close()
+    if own:
+        D.close()
     return out
 
 
-def _check_estimates(c, name, est, weighted, test):
+def _check_estimates(c, name, est, weighted, test, bound=bound):
     er, ew, el = est
     worst = dict(est_ll=0.0, est_wnr_w=0.0)
     for ri in range(c.n_reads):
@@ -161,7 +219,7 @@ def _check_estimates(c, name, est, weighted, test):
     assert worst["est_ll"] <= bound("est_ll") and worst["est_wnr_w"] <= bound("est_wnr_w"), worst
 
 
-def _check_places(c, name, out, test, prior=0, fix=0):
+def _check_places(c, name, out, test, prior=0, fix=0, bound=bound):
     cand, offs, places = out["cand"], out["offs"], out["places"]
     worst = dict(length=0.0, height=0.0, root_ll=0.0, const_ll=0.0, q_eps=0.0)
     n_cand = len(c.seeds)
@@ -240,7 +298,7 @@ def test_place_var6_instance(name):
     """place_var = 6 on regions of at most 190 columns runs k_place_blk<12, 2, 1, 0, 2>: twelve sites per thread and one Newton-refined
     reciprocal per site (EMV = 1), where the shipped instance for these widths, k_place_blk<4, 2, 3, 0, 2>, has four sites per thread and
     one reciprocal per four sites (EMV = 3).  Both keep the v message in registers; the instance that keeps it in LDS takes regions of
-    513 to 1,024 columns and is tied to the oracle by tests/test_gpu_parity.py and tests/test_loads_batched.py"""
+    513 to 1,024 columns and is held to the same values by the wide set below (test_wide_estimate_place_q)"""
     c = Case(name)
     _check_places(c, name, _run(c, knobs=dict(place_var=6)), "place_var6")
 
@@ -252,3 +310,132 @@ def test_streaming_kernels(name):
     out = _run(c, knobs=dict(streaming_sep=1), fix_root_loglik=1)
     _check_estimates(c, name, out["est"], False, "estimate_streaming")
     _check_places(c, name, out, "place_streaming", 0, 1)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# The wide set (tests/golden/hiprec_wide.npz): one read per width class of the dispatch in hu_estimate_batch / hu_place_batch, each in a
+# batch of its own, so that the widest region and the gap / base site maxima that choose the instance are that read's.  The instance is
+# read from the two trace lines and asserted against the table below: a moved threshold fails until the table is edited on purpose.
+#
+#   read (columns, base sites)   estimate                  placement (default knobs)                       site order
+WIDE_INSTANCES = [
+    ((512, 120),  "k_estimate_prod<2,4>",   "k_place_blk<4,2,3,0,2>",             "column order"),           # top of the 4-site class
+    ((513, 100),  "k_estimate_prod<4,4>",   "k_place_blk<8,2,3,0,3,false,3,6>",   "gap/base split slots"),   # v in LDS, last slots almost empty
+    ((1024, 256), "k_estimate_prod<4,4>",   "k_place_blk<8,2,3,0,3,false,3,6>",   "gap/base split slots"),   # 768 gap + 256 base sites: both lists full
+    ((1024, 257), "k_estimate_prod<4,4>",   "k_place_blk<8,2,3,0,2>",             "column order"),           # one base too many
+    ((1025, 150), "k_estimate_prod<6,4,4>", "k_place_blk<12,2,3,0,2,false,1,10>", "gap/base split slots"),
+    ((1536, 256), "k_estimate_prod<6,4,4>", "k_place_blk<12,2,3,0,2,false,1,10>", "gap/base split slots"),   # 1,280 + 256: both lists full
+    ((1400, 257), "k_estimate_prod<6,4,4>", "k_place_blk<12,2,3,0,2,false,1>",    "column order"),
+    ((1537, 200), "k_estimate_prod<8,4>",   "k_place_blk<8,4,3,0,1>",             "column order"),           # first width of the four-wave forms
+    ((2048, 300), "k_estimate_prod<8,4>",   "k_place_blk<8,4,3,0,1>",             "column order"),
+    ((2049, 250), "k_estimate_prod<6,8,2>", "k_place_blk<12,4,3,0,2,false,1>",    "column order"),
+    ((3072, 500), "k_estimate_prod<6,8,2>", "k_place_blk<12,4,3,0,2,false,1>",    "column order"),
+    ((3073, 300), "k_estimate",             "k_place",                            "column order"),           # streaming kernels by width
+]
+assert [w[0] for w in WIDE_INSTANCES] == WIDE_READS
+READ_OF = {shape: ri for ri, shape in enumerate(WIDE_READS)}
+# the forms that only a knob reaches: (read, knobs, estimate, placement, site order)
+WIDE_KNOB_FORMS = [
+    ((513, 100),  dict(place_var=6), "k_estimate_prod<4,4>",   "k_place_blk<8,2,3,0,2,false,0,6>", "gap/base split slots"),   # v in registers
+    ((1024, 256), dict(place_var=6), "k_estimate_prod<4,4>",   "k_place_blk<8,2,3,0,2,false,0,6>", "gap/base split slots"),
+    ((1024, 257), dict(place_var=6), "k_estimate_prod<4,4>",   "k_place_blk<12,2,1,0,2>",          "column order"),
+    ((1400, 257), dict(place_var=6), "k_estimate_prod<6,4,4>", "k_place_blk<12,2,1,0,2>",          "column order"),
+    ((513, 100),  dict(place_var=7), "k_estimate_prod<4,4>",   "k_place_blk<12,2,3,0,2>",          "column order"),
+    ((1536, 256), dict(place_var=7), "k_estimate_prod<6,4,4>", "k_place_blk<12,2,3,0,2>",          "column order"),
+    ((2049, 250), dict(place_var=9, est_var=4), "k_estimate_prod<12,4>", "k_place_blk<12,4,3,0,1>", "column order"),
+    ((3072, 500), dict(place_var=9, est_var=4), "k_estimate_prod<12,4>", "k_place_blk<12,4,3,0,1>", "column order"),
+    ((1024, 256), dict(place_nosplit=1), "k_estimate_prod<4,4>",   "k_place_blk<8,2,3,0,2>",          "column order"),
+    ((1536, 256), dict(place_nosplit=1), "k_estimate_prod<6,4,4>", "k_place_blk<12,2,3,0,2,false,1>", "column order"),
+    ((512, 120),  dict(est_var=2), "k_estimate_blk<2,256>",  "k_place_blk<4,2,3,0,2>",             "column order"),
+    ((1024, 256), dict(est_var=2), "k_estimate_blk<4,256>",  "k_place_blk<8,2,3,0,3,false,3,6>",   "gap/base split slots"),
+    ((1536, 256), dict(est_var=2), "k_estimate_blk<6,256>",  "k_place_blk<12,2,3,0,2,false,1,10>", "gap/base split slots"),
+    ((2048, 300), dict(est_var=2), "k_estimate_blk<8,256>",  "k_place_blk<8,4,3,0,1>",             "column order"),
+    ((3072, 500), dict(est_var=2), "k_estimate_blk<12,256>", "k_place_blk<12,4,3,0,2,false,1>",    "column order"),
+]
+_shape_id = lambda v: "%dx%d" % v if isinstance(v, tuple) else None
+
+
+@pytest.fixture(scope="module")
+def wide():
+    """(case, uploaded database) of a wide case, shared by the tests of this module: the upload of 15 nodes x 3,300 columns costs more
+    than a batch of one read"""
+    held = {}
+
+    def get(name):
+        if name not in held:
+            c = Case(name, "wide")
+            held[name] = (c, _engine().Database.from_synth(c.db))
+        return held[name]
+    yield get
+    for _, D in held.values():
+        D.close()
+
+
+def _instances(err, width):
+    """(estimate kernel, placement kernel, site order) from the trace of one batch: one line of each stage, both naming the read's width"""
+    est = re.findall(r"^\[hu\] estimate: max region (\d+), (\S+)$", err, re.M)
+    pl = re.findall(r"^\[hu\] place: \d+ candidates, max region (\d+), (?:\d+ sites per thread|sites streamed per sweep), "
+                    r"(gap/base split slots|column order), [^,]+, (\S+)$", err, re.M)
+    assert len(est) == 1 and len(pl) <= 1, err
+    assert int(est[0][0]) == width and all(int(p[0]) == width for p in pl), err
+    return (est[0][1],) + ((pl[0][2], pl[0][1]) if pl else (None, None))
+
+
+def _wide_run(wide, capfd, name, shape, knobs=None, **kw):
+    c, D = wide(name)
+    one = c.one_read(READ_OF[shape])
+    capfd.readouterr()
+    out = _run(one, knobs=dict(knobs or {}, trace=1), D=D, **kw)
+    return one, out, _instances(capfd.readouterr().err, shape[0])
+
+
+@pytest.mark.parametrize("name", WIDE_CASES)
+@pytest.mark.parametrize("shape,est_k,place_k,order", WIDE_INSTANCES, ids=_shape_id)
+def test_wide_estimate_place_q(wide, capfd, name, shape, est_k, place_k, order):
+    """default knobs: the unweighted estimate, the placement with the constant loglik, q-values where the archive holds them"""
+    one, out, ran = _wide_run(wide, capfd, name, shape)
+    tag = "%s:%dx%d" % ((name,) + shape)
+    print("HIPREC wide_instance %s %s %s (%s)" % ((tag,) + ran))
+    _check_estimates(one, "%s:%s" % (tag, ran[0]), out["est"], False, "wide_estimate", bound_wide)
+    _check_places(one, "%s:%s" % (tag, ran[1]), out, "wide_place", bound=bound_wide)
+    assert ran == (est_k, place_k, order)
+
+
+@pytest.mark.parametrize("name", WIDE_CASES)
+@pytest.mark.parametrize("shape,est_k,place_k,order", WIDE_INSTANCES, ids=_shape_id)
+def test_wide_estimate_weighted(wide, capfd, name, shape, est_k, place_k, order):
+    """weighted = 1: every k_estimate_prod instance has a weighted path of its own"""
+    one, out, ran = _wide_run(wide, capfd, name, shape, stop_after="estimate", weighted=1)
+    _check_estimates(one, "%s:%dx%d:%s" % (name, shape[0], shape[1], ran[0]), out["est"], True, "wide_estimate_weighted", bound_wide)
+    assert ran[0] == est_k
+
+
+@pytest.mark.parametrize("name", WIDE_CASES)
+@pytest.mark.parametrize("shape,est_k,place_k,order", WIDE_INSTANCES, ids=_shape_id)
+def test_wide_fixed_root_loglik(wide, capfd, name, shape, est_k, place_k, order):
+    """fix_root_loglik = 1: k_root_loglik over regions of up to 3,073 columns"""
+    one, out, ran = _wide_run(wide, capfd, name, shape, fix_root_loglik=1)
+    _check_places(one, "%s:%dx%d:%s" % (name, shape[0], shape[1], ran[1]), out, "wide_place_fix1", 0, 1, bound_wide)
+    assert ran == (est_k, place_k, order)
+
+
+@pytest.mark.parametrize("name", WIDE_CASES)
+@pytest.mark.parametrize("shape,est_k,place_k,order", WIDE_INSTANCES, ids=_shape_id)
+def test_wide_filter_set_at_the_default_max_error(wide, capfd, name, shape, est_k, place_k, order):
+    one, out, ran = _wide_run(wide, capfd, name, shape, max_error=wide(name)[0].max_error)
+    got = sorted(int(x) for x in out["cand"]["c_node"][int(out["offs"][0]):int(out["offs"][1])])
+    assert got == sorted(int(u) for u, keep in zip(one.seeds, one.filter_in[0]) if keep)
+    assert ran == (est_k, place_k, order)
+
+
+@pytest.mark.parametrize("name", WIDE_CASES)
+@pytest.mark.parametrize("shape,knobs,est_k,place_k,order", WIDE_KNOB_FORMS,
+                         ids=["%dx%d-%s" % (w[0] + ("-".join("%s%d" % kv for kv in sorted(w[1].items())),)) for w in WIDE_KNOB_FORMS])
+def test_wide_knob_forms(wide, capfd, name, shape, knobs, est_k, place_k, order):
+    """the instances that only a comparison knob reaches: pinned like the shipped ones"""
+    one, out, ran = _wide_run(wide, capfd, name, shape, knobs=knobs)
+    tag = "%s:%dx%d" % ((name,) + shape)
+    print("HIPREC wide_instance %s %s %s (%s)" % ((tag,) + ran))
+    _check_estimates(one, "%s:%s" % (tag, ran[0]), out["est"], False, "wide_knob_estimate", bound_wide)
+    _check_places(one, "%s:%s" % (tag, ran[1]), out, "wide_knob_place", bound=bound_wide)
+    assert ran == (est_k, place_k, order)

@@ -16,6 +16,10 @@ A knife-edge candidate (a convergence quantity within 1e-6 relative of 1e-5, an 
 and in its lengths to 1e-6 only.  The generator allows 5 % of a database's candidates to be; the archive holds 10 of 1,260, all of the
 third kind and all on JC69's two-column read (10 of that database's 210: 4.8 %).
 Measured: P(t) 1.0e-15, the oracle's messages 9.1e-13 (synth's 4.2e-12), logliks 5.0e-15, placed lengths 5.3e-14, all counts equal.
+The wide set (tests/golden/hiprec_wide.npz: GTR+4 and JC69, 8 leaves x 3,300 columns, twelve reads of 512 to 3,073 columns, no knife-edge
+candidate) runs under the same rules and the same bounds (test_wide_*); its figures are printed as HIPREC oracle_wide_* lines and anchor
+the kernels' bounds on that set (tests/test_hiprec_gpu.py: ORACLE_WIDE).  Measured: logliks 6.2e-14 (estimate) and 5.7e-14 (root), weighted
+wnr 6.5e-15 absolute, placed ratio 1.2e-13 and wnr 1.9e-13 absolute (7.6e-12 relative to max(|x|, 1e-3)), height 6.6e-15, q eps 2.1e-10.
 """
 import glob
 import importlib.util
@@ -25,7 +29,7 @@ import re
 import numpy as np
 import pytest
 
-from hiprec_cases import CASES, Case, q_ok, ratio_half
+from hiprec_cases import CASES, WIDE_CASES, WIDE_READS, Case, q_ok, ratio_half
 
 REL = 1e-6
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -64,10 +68,19 @@ def test_model_P(name):
     assert worst < 1e-13
 
 
+def report(test, name, **worst):
+    """the figures of the wide set, printed as tests/test_hiprec_gpu.py prints its own (DESIGN.md section 5 quotes them)"""
+    print("HIPREC oracle_%s %s %s" % (test, name, " ".join("%s=%.3e" % kv for kv in sorted(worst.items()))))
+
+
 @pytest.mark.parametrize("name", CASES)
 def test_messages(name):
     """the oracle's two-pass pruning and the database's own messages (the ones every other test feeds to oracle and engine)"""
-    c = Case(name)
+    _messages(Case(name))
+
+
+def _messages(c):
+    name = c.name
     O, m, _ = _oracle(c)
     db = c.db
     leaf_only = np.where(db.is_leaf[:, None], db.seq, 0).astype(np.int8)
@@ -84,15 +97,20 @@ def test_messages(name):
         root = u_[0]                                             # treeLoglik of a column: log(pi . exp(root message))
         mx = root.max(1)
         ll = mx + np.log((np.asarray(m.pi)[None, :] * np.exp(root - mx[:, None])).sum(1))
-        assert (np.abs(ll - c.root_ll) <= 1e-12 * np.abs(c.root_ll)).all(), who
+        stored = ll if len(c.root_ll) == len(ll) else ll[c.msg_cols]                            # the wide archive: at msg_cols only
+        assert (np.abs(stored - c.root_ll) <= 1e-12 * np.abs(c.root_ll)).all(), who
         assert _rel(ll.sum(), c.root_ll_sum) < 1e-12, who
 
 
 @pytest.mark.parametrize("name", CASES)
 def test_estimate(name):
-    c = Case(name)
+    _estimate(Case(name))
+
+
+def _estimate(c):
+    name = c.name
     _, _, T = _oracle(c)
-    worst = dict(ll=0.0, ll_w=0.0, wnr_w=0.0)
+    worst = dict(ll=0.0, ll_w=0.0, wnr_w=0.0, wnr_w_rel=0.0)
     for ri in range(c.n_reads):
         st, en = int(c.start[ri]), int(c.end[ri])
         for k, u in enumerate(c.seeds):
@@ -104,17 +122,23 @@ def test_estimate(name):
                 assert e0["wnr"] == c.wnr_unweighted(ri, k), (ri, u)
             assert np.isfinite([e0["loglik"], e1["loglik"], c.est_ll[ri, k], c.est_ll_w[ri, k]]).all(), (ri, u)
             worse(worst, "wnr_w", abs(e1["wnr"] - c.est_wnr_w[ri, k]))
+            worse(worst, "wnr_w_rel", abs(e1["wnr"] - c.est_wnr_w[ri, k]) / max(abs(c.est_wnr_w[ri, k]), 1e-3))
             worse(worst, "ll", _rel(e0["loglik"], c.est_ll[ri, k]))
             worse(worst, "ll_w", _rel(e1["loglik"], c.est_ll_w[ri, k]))
     print("hiprec oracle estimate", name, worst)
     assert worst["ll"] < 1e-12 and worst["ll_w"] < 1e-12 and worst["wnr_w"] < 1e-12, worst
+    return worst
 
 
 @pytest.mark.parametrize("name", CASES)
 def test_place(name):
-    c = Case(name)
+    _place(Case(name))
+
+
+def _place(c):
+    name = c.name
     _, _, T = _oracle(c)
-    worst = dict(ratio=0.0, wnr=0.0, height=0.0, const=0.0, root=0.0)
+    worst = dict(ratio=0.0, wnr=0.0, height=0.0, const=0.0, root=0.0, length_rel=0.0, height_rel=0.0)
     for ri in range(c.n_reads):
         st, en = int(c.start[ri]), int(c.end[ri])
         for k, u in enumerate(c.seeds):
@@ -129,6 +153,9 @@ def test_place(name):
                 assert (p["iters"], p["em_iters"]) == (int(c.pl_outer[ri, k]), int(c.pl_em[ri, k])), (ri, u)
                 for key, e in zip(("ratio", "wnr", "height"), errs):
                     worse(worst, key, e)
+                # the scale tests/test_hiprec_gpu.py measures the kernels on
+                worse(worst, "length_rel", max(errs[0] / max(abs(c.pl_ratio[ri, k]), 1e-3), errs[1] / max(abs(c.pl_wnr[ri, k]), 1e-3)))
+                worse(worst, "height_rel", errs[2] / max(abs(c.placed_height(ri, k)), 1e-3))
             if abs(c.pl_ratio[ri, k] - 0.5) > 1e-6:
                 assert p["aNode"] == int(c.pl_a_node[ri, k])
             worse(worst, "const", _rel(p["loglik"], c.pl_const_ll[ri]))
@@ -137,14 +164,19 @@ def test_place(name):
     assert worst["ratio"] < 1e-9 and worst["wnr"] < 1e-9 and worst["height"] < 1e-9, worst
     assert worst["const"] < 1e-12, worst
     assert worst["root"] < 1e-12, worst                          # the intended root loglik (--fix-root-loglik): the project's figure for logliks
+    return worst
 
 
 @pytest.mark.parametrize("name", CASES)
 def test_assign_filter_set_and_q_values(name):
+    _assign(Case(name))
+
+
+def _assign(c):
     from oracle import oracle_py as O
-    c = Case(name)
     _, _, T = _oracle(c)
     n_cand = len(c.seeds)
+    worst = dict(q_eps=0.0)
     for ri in range(c.n_reads):
         st, en = int(c.start[ri]), int(c.end[ri])
         res = T.assign(c.codes[ri], st, en, O.default_opts(maxError=c.max_error))
@@ -163,6 +195,33 @@ def test_assign_filter_set_and_q_values(name):
                     assert q_ok(vals[4], qp[k], op[k], 1e-9), (ri, prior, fix, k, vals[4], qp[k])
                     if not ratio_half(c, ri):
                         assert q_ok(vals[5], qt[k], ot[k], 1e-9), (ri, prior, fix, k, vals[5], qt[k])
+                    for q, qe, omp in ((vals[4], qp[k], op[k]),) + (() if ratio_half(c, ri) else ((vals[5], qt[k], ot[k]),)):
+                        if omp >= 1e-6:                          # the eps of the conditioned bound that this q needs
+                            worse(worst, "q_eps", max(0.0, (abs(q - qe) - 1e-12 * qe) * omp * np.log(10.0) / 10.0))
+    return worst
+
+
+# ---- the wide set (tests/golden/hiprec_wide.npz): regions of 512 to 3,073 columns under the same rules and the same fixed bounds
+@pytest.mark.parametrize("name", WIDE_CASES)
+def test_wide_messages(name):
+    _messages(Case(name, "wide"))
+
+
+@pytest.mark.parametrize("name", WIDE_CASES)
+def test_wide_estimate(name):
+    c = Case(name, "wide")
+    assert c.n_reads == len(WIDE_READS) and not c.knife.any()       # wide regions: the EM converges properly
+    report("wide_estimate", name, **_estimate(c))
+
+
+@pytest.mark.parametrize("name", WIDE_CASES)
+def test_wide_place(name):
+    report("wide_place", name, **_place(Case(name, "wide")))
+
+
+@pytest.mark.parametrize("name", WIDE_CASES)
+def test_wide_assign_filter_set_and_q_values(name):
+    report("wide_q", name, **_assign(Case(name, "wide")))
 
 
 def test_the_archive_is_the_generators_output():
@@ -184,6 +243,16 @@ def test_the_archive_is_the_generators_output():
     got = gen.one_candidate("JC690", ri, int(c.seeds[k]))
     assert np.float32(got["margin_cond"]) == c.margin_cond[ri, k] < 1 and got["pl_em"] == int(c.pl_em[ri, k])
     assert (got["pl_ratio"], got["pl_wnr"]) == (c.pl_ratio[ri, k], c.pl_wnr[ri, k])
+    assert got["pl_const_ll"] == c.pl_const_ll[ri]
+    # and one of the wide set: the narrowest read (512 columns) on the cheapest model
+    c = Case("JC690", "wide")
+    ri, k = 0, 6
+    got = gen.one_candidate("JC690", ri, int(c.seeds[k]), "wide")
+    assert tuple(got["dN"]) == tuple(int(x) for x in c.dN[ri, k]) and got["est_d"] == int(c.est_d[ri, k])
+    for key in ("est_ratio", "est_wnr_w", "est_ll", "est_ll_w", "pl_ratio", "pl_wnr", "pl_root_ll"):
+        assert got[key] == getattr(c, key)[ri, k], key
+    assert (got["pl_outer"], got["pl_em"], got["pl_a_node"]) == (int(c.pl_outer[ri, k]), int(c.pl_em[ri, k]), int(c.pl_a_node[ri, k]))
+    assert np.float32(got["margin"]) == c.margin[ri, k] and np.float32(got["margin_cond"]) == c.margin_cond[ri, k]
     assert got["pl_const_ll"] == c.pl_const_ll[ri]
 
 
