@@ -3,10 +3,11 @@
 // csfm.save, :479-485).  The host reads and joins the inputs; the wide loops run on
 // the device: the MSA column counts behind MSA::prune (hu_msa_stats), the tree evaluated at every root (hu_tree_evaluate), the
 // per-site mutation counts behind -V (hu_tree_count_mutations), the tree log-likelihood (hu_tree_loglik) and the gather of the
-// messages for the file (hu_ptu_write_stream); with --csfm the suffix array of the concatenated MSA rows, its BWT and samples (hu_csfm_write).  Options and inputs are checked, and every input read and joined, before a device
+// messages for the file (hu_ptu_write_stream); with --col-window the same a window of columns at a time, for a message set beyond the device's
+// memory (hu_tree_sweep_*, hu_ptu_writer_*); with --csfm the suffix array of the concatenated MSA rows, its BWT and samples (hu_csfm_write).  Options and inputs are checked, and every input read and joined, before a device
 // is asked for.
 //   hmmufotu-amd-build <MSA-FILE> <TREE-FILE> --no-hmm -sm FILE [-n NAME] [--fmt fasta] [-a|--anno FILE] [-r|--root STR] [-V|--var]
-//                      [-k INT] [--csfm] [--device N] [-v]
+//                      [-k INT] [--csfm] [--col-window W|auto] [--mem GB] [--device N] [-v]
 // Writes <NAME>.ptu, and <NAME>.csfm when asked (without it hmmufotu-amd rebuilds its seed index from the .ptu on every start; the reference's
 // hmmufotu cannot start without it): no .msa, and no .hmm — the profile comes
 // from a third-party trainer (HMMER3, hmmufotu-train-hmm) and is put beside the .ptu as <NAME>.hmm.
@@ -35,6 +36,8 @@ static void usage(const char* p) {
 		"            -V|--var FLAG        : enable among-site rate varation evaluation of the tree, using a Discrete Gamma Distribution based model\n"
 		"            -k INT               : number of Discrete Gamma Distribution categories to evaluate the tree, ignored if -V not set [" << DEFAULT_DG_CATEGORY << "]\n"
 		"            --csfm FLAG          : also write the seed index file <NAME>.csfm, over all rows of the pruned MSA (the suffix array is built on the device)\n"
+		"            --col-window  INT|auto : evaluate and write the tree in windows of INT columns, so that only 64 x nodes x INT bytes of messages are on the device at once; 'auto': the widest window that fits, none when everything fits\n"
+		"            --mem  GB            : device memory the build may use, in GB [what the device reports free]\n"
 		"            --device  INT        : device index [0]\n"
 		"            -f|--symfrac, -dm, -p|--process : accepted and ignored (they belong to the profile training)\n"
 		"            -v  FLAG             : enable verbose information; -vv adds the wall time of every phase\n"
@@ -46,6 +49,7 @@ int main(int argc, char** argv) {
 	bool noHmm = false, isVar = false, haveS = false, withCsfm = false;
 	int K = DEFAULT_DG_CATEGORY, device = 0, verbose = 0;
 	std::vector<std::string> ignored;
+	std::string colWinArg, memArg; bool haveColWin = false, haveMem = false;
 	if(argc == 1) { usage(argv[0]); return EXIT_SUCCESS; }
 	for(int i = 1; i < argc; ++i) {
 		std::string a = argv[i];
@@ -58,6 +62,7 @@ int main(int argc, char** argv) {
 		else if(a == "-sm") smFn = val();
 		else if(a == "--no-hmm") noHmm = true; else if(a == "--csfm") withCsfm = true; else if(a == "-V" || a == "--var") isVar = true;
 		else if(a == "-k") K = atoi(val()); else if(a == "--device") device = atoi(val());
+		else if(a == "--col-window") { colWinArg = val(); haveColWin = true; } else if(a == "--mem") { memArg = val(); haveMem = true; }
 		else if(a == "-f" || a == "--symfrac" || a == "-dm" || a == "-p" || a == "--process") { ignored.push_back(a); val(); }
 		else if(a.size() > 1 && a[0] == '-' && a.find_first_not_of('v', 1) == std::string::npos) verbose += (int) a.size() - 1;
 		else if(a[0] == '-' && a.size() > 1) { std::cerr << "Error: unknown option " << a << std::endl; usage(argv[0]); return EXIT_FAILURE; }
@@ -85,6 +90,21 @@ int main(int argc, char** argv) {
 	if(!hu_is_newick_name(treeFn)) { std::cerr << "Unrecognized TREE-FILE format, must be in Newick format" << std::endl; return EXIT_FAILURE; }
 	if(!(MIN_DG_CATEGORY <= K && K <= MAX_DG_CATEGORY)) { std::cerr << "-k must be an integer between " << MIN_DG_CATEGORY << " and " << MAX_DG_CATEGORY << std::endl; return EXIT_FAILURE; }
 	if(device < 0) { std::cerr << "--device must be non-negative" << std::endl; return EXIT_FAILURE; }
+	int64_t colWin = -1, memBytes = 0;            /* colWin: -1 not asked for, 0 auto, else the width */
+	if(haveColWin && colWinArg != "auto") {
+		char* end = nullptr;
+		errno = 0;
+		const long long v = strtoll(colWinArg.c_str(), &end, 10);
+		if(colWinArg.empty() || *end || errno || v < 1) { std::cerr << "--col-window must be 'auto' or an integer >= 1, got '" << colWinArg << "'" << std::endl; return EXIT_FAILURE; }
+		colWin = v;
+	}
+	else if(haveColWin) colWin = 0;
+	if(haveMem) {
+		char* end = nullptr;
+		const double gb = strtod(memArg.c_str(), &end);
+		if(memArg.empty() || *end || !(gb > 0) || !std::isfinite(gb) || gb * 1e9 >= 9e18) { std::cerr << "--mem must be a positive number of GB, got '" << memArg << "'" << std::endl; return EXIT_FAILURE; }
+		memBytes = (int64_t)(gb * 1e9);
+	}
 	for(const std::string& o : ignored) info("Note: " + o + " belongs to the profile training and is ignored under --no-hmm");
 
 	/* open and read the inputs */
@@ -154,8 +174,10 @@ int main(int argc, char** argv) {
 	const bool csfmExisted = withCsfm && stat(csfmFn.c_str(), &stCsfm) == 0;
 	if(withCsfm) { std::ofstream probe(csfmFn, std::ios::binary | std::ios::app); if(!probe.is_open()) { std::cerr << "Unable to write to '" << csfmFn << "': " << strerror(errno) << std::endl; hu_tree_anno_free(an); if(!existed) unlink(ptuFn.c_str()); return EXIT_FAILURE; } }
 	void *dUp = nullptr, *dDown = nullptr;
+	hu_tree_sweep* sweep = nullptr; hu_ptu_writer* writer = nullptr;
 	auto fail = [&](const std::string& msg) {
 		std::cerr << msg << std::endl;
+		hu_ptu_writer_abort(writer); hu_tree_sweep_destroy(sweep);
 		hu_device_free(device, dUp); hu_device_free(device, dDown); hu_tree_anno_free(an);
 		if(!existed) unlink(ptuFn.c_str());       /* only the probe's empty file */
 		if(withCsfm && !csfmExisted) unlink(csfmFn.c_str());
@@ -201,18 +223,105 @@ int main(int argc, char** argv) {
 
 	/* device memory: both message sets, and the largest of the later steps' scratch: the sweep's node rows and tables, the mutation count's
 	 * states, the writer's staging buffers */
+	int32_t W = 0;                                /* the window width of a windowed build; 0: everything resident */
 	{
 		int64_t freeB = 0, totB = 0;
 		if(hu_device_mem_info(device, &freeB, &totB) != HU_OK) return fail(std::string("Error: ") + hu_last_error());
+		if(haveMem) freeB = std::min(freeB, memBytes);
 		const int64_t msgs = 2ll * n * L * 32, sweep = (int64_t) n * L + (int64_t) n * 28 + 64, mut = isVar ? (int64_t) n * L + (int64_t) n * 4 + (int64_t) L * 4 : 0;
 		const int64_t stage = 2 * std::min<int64_t>((int64_t) 256 << 20, (2ll * n - 1) * L * 32) + 8ll * n;     /* hu_ptu_write_stream's two staging buffers */
 		const int64_t need = msgs + std::max(std::max(sweep, mut), stage) + (int64_t) L * 8;
-		if(need > freeB) {
-			char buf[256];
-			snprintf(buf, sizeof(buf), "Unable to build the database on device %d: %d nodes x %d columns need %.3f GB of device memory, %.3f GB are free (column-windowed builds are not provided)", device, n, L, need / 1e9, freeB / 1e9);
+		char buf[320];
+		if(colWin > 0 && colWin < L) {
+			W = (int32_t) colWin;
+			const int64_t needW = hu_build_window_need(n, W, isVar);
+			if(needW > freeB) {
+				snprintf(buf, sizeof(buf), "Unable to build the database on device %d: %d nodes x windows of %d columns need %.3f GB of device memory, %.3f GB are free (--col-window auto chooses a width that fits)", device, n, W, needW / 1e9, freeB / 1e9);
+				return fail(buf);
+			}
+		}
+		else if(colWin == 0 && need > freeB) {
+			int64_t needW = 0;
+			if(hu_build_window_plan(n, L, isVar, freeB, &W, &needW) != HU_OK) {
+				snprintf(buf, sizeof(buf), "Unable to build the database on device %d: one column of %d nodes needs %.6f GB of device memory, %.6f GB are free", device, n, needW / 1e9, freeB / 1e9);
+				return fail(buf);
+			}
+			if(W >= L) W = 0;
+		}
+		else if(need > freeB) {
+			snprintf(buf, sizeof(buf), "Unable to build the database on device %d: %d nodes x %d columns need %.3f GB of device memory, %.3f GB are free (--col-window auto builds it in column windows)", device, n, L, need / 1e9, freeB / 1e9);
 			return fail(buf);
 		}
-		if(hu_device_malloc(device, msgs / 2, &dUp) != HU_OK || hu_device_malloc(device, msgs / 2, &dDown) != HU_OK) return fail(std::string("Error: ") + hu_last_error());
+		if(W == 0 && (hu_device_malloc(device, msgs / 2, &dUp) != HU_OK || hu_device_malloc(device, msgs / 2, &dDown) != HU_OK)) return fail(std::string("Error: ") + hu_last_error());
+	}
+	if(W > 0) { /* the windowed build: the resident one below, a window of columns at a time */
+		const int32_t nWin = (L + W - 1) / W;
+		if(verbose) std::cerr << "Building in " << nWin << " column windows of " << W << " columns" << std::endl;
+		auto err = [&]() { return std::string("Error: ") + hu_last_error(); };
+		std::vector<double> height(n), perCol((size_t) L);
+		if(hu_tree_sweep_create(n, L, parent.data(), blen.data(), device, &sweep) != HU_OK) return fail(err());
+		if(hu_device_malloc(device, (int64_t) n * W * 32, &dUp) != HU_OK) return fail(err());
+		info(std::string("Evaluating Phylogenetic Tree at root id: 0") + (isVar ? " with fixed rate model first" : ""));
+		double alpha = 0;
+		std::vector<double> breaks;
+		if(isVar) { /* pass 1: the post-order levels and the mutation counts of every window, joined in column order */
+			info("Estimating the shape parameter of the Discrete Gamma Distributin based among-site variation ...");
+			std::vector<int32_t> cnt(L);
+			for(int32_t a = 0; a < L; a += W) {
+				const int32_t wl = std::min(W, L - a);
+				if(hu_tree_sweep_window(sweep, &model, seq.data(), a, wl, (double*) dUp, nullptr) != HU_OK) return fail(err());
+				if(hu_tree_count_mutations(device, n, wl, parent.data(), (const double*) dUp, cnt.data() + a) != HU_OK) return fail(err());
+			}
+			std::vector<double> numMut(cnt.begin(), cnt.end());
+			alpha = hu_dg_estimate_shape(L, numMut.data());
+			lap("first sweep and mutation count");
+			if(alpha == std::numeric_limits<double>::infinity()) std::cerr << "Unable to estimate the shape parameter with less than 2 alignment sites" << std::endl;
+			else if(!(alpha > 0)) std::cerr << "Unable to estimate the shape parameter with near invariant rates, reducing to fixed rate model" << std::endl;
+			else {
+				if(verbose) std::cerr << "Estimated alpha = " << alpha << std::endl;
+				breaks.resize((size_t) K + 1);
+				if(hu_dg_model(K, alpha, breaks.data(), model.dg_rate) != HU_OK) return fail(err());
+				model.dg_k = K;
+			}
+			for(int32_t i = 0; i < n; ++i) if(rowOf[i] < 0) memset(seq.data() + (size_t) i * L, 0, (size_t) L);
+		}
+		info(model.dg_k == 0 ? "Evaluating Phylogenetic Tree at all other " + std::to_string(n - 1) + " nodes" : "Re-evaluating Phylogenetic Tree at all " + std::to_string(n) + " nodes");
+		if(hu_device_malloc(device, (int64_t) n * W * 32, &dDown) != HU_OK) return fail(err());
+		hu_tree_desc td;
+		memset(&td, 0, sizeof(td));
+		td.n_nodes = n; td.cs_len = L; td.parent = parent.data(); td.blen = blen.data(); td.anno_dist = annoDist.data();
+		if(hu_ptu_writer_open(ptuFn.c_str(), &td, names.data(), annos.data(), childOff.data(), childIdx.data(), rowOf.data(), 0, &writer) != HU_OK)
+			return fail(std::string("Unable to save Phylogenetic Tree index: ") + hu_last_error());
+		double tSweep = 0, tLik = 0, tWrite = 0;
+		auto since = [](std::chrono::steady_clock::time_point& t0) { const auto now = std::chrono::steady_clock::now(); const double d = std::chrono::duration<double>(now - t0).count(); t0 = now; return d; };
+		for(int32_t a = 0; a < L; a += W) { /* pass 2: the full sweep under the final model, the column log-likelihoods, the window to the file */
+			const int32_t wl = std::min(W, L - a);
+			auto t0 = std::chrono::steady_clock::now();
+			double part = 0;
+			if(hu_tree_sweep_window(sweep, &model, seq.data(), a, wl, (double*) dUp, (double*) dDown) != HU_OK) return fail(err());
+			tSweep += since(t0);
+			if(hu_tree_loglik(device, n, wl, 0, &model, (const double*) dUp, perCol.data() + a, &part) != HU_OK) return fail(err());
+			tLik += since(t0);
+			if(hu_ptu_writer_window(writer, a, wl, (const double*) dUp, (const double*) dDown, 1) != HU_OK) return fail(std::string("Unable to save Phylogenetic Tree index: ") + hu_last_error());
+			tWrite += since(t0);
+		}
+		if(verbose > 1) std::cerr << "[phase] second sweep: " << tSweep << " s\n[phase] log-likelihood: " << tLik << " s\n[phase] write windows: " << tWrite << " s" << std::endl;
+		tLap = std::chrono::steady_clock::now();
+		if(hu_tree_sweep_heights(sweep, height.data()) != HU_OK) return fail(err());
+		info("Node height calculated");
+		double loglik = 0;
+		for(int32_t j = 0; j < L; ++j) loglik += perCol[j];     /* serial column order over all windows: the resident build's sum */
+		if(verbose) std::cerr << "Final Tree log-liklihood: " << loglik << std::endl;
+		info("Ancestor sequence of all intermediate nodes inferred");
+		info("Saving database files ...");
+		hu_ptu_writer* w = writer;
+		writer = nullptr;                            /* close frees the handle whatever happens */
+		if(hu_ptu_writer_close(w, seq.data(), height.data(), &model, smText.c_str(), alpha, model.dg_k ? breaks.data() : nullptr) != HU_OK)
+			return fail(std::string("Unable to save Phylogenetic Tree index: ") + hu_last_error());
+		info("Phylogenetic Tree index saved");
+		lap("write");
+		hu_tree_sweep_destroy(sweep); hu_device_free(device, dUp); hu_device_free(device, dDown); hu_tree_anno_free(an);
+		return EXIT_SUCCESS;
 	}
 	std::vector<double> height(n);
 	info(std::string("Evaluating Phylogenetic Tree at root id: 0") + (isVar ? " with fixed rate model first" : ""));

@@ -18,6 +18,8 @@
 #include <sstream>
 #include <new>
 #include <stdexcept>
+#include <fcntl.h>
+#include <unistd.h>
 #include "hu_common.h"
 #include "hu_kern_sep.h"
 #include "hu_kern_align.h"
@@ -504,6 +506,84 @@ static std::string model_text_of(const hu_model_desc& m) {
 	else if(m.type == HU_K80) o += "kappa: " + num(m.par[0]) + "\n";
 	return o;
 }
+/* The pieces of a .ptu that hu_ptu_write, hu_ptu_write_stream and the windowed writer (hu_ptu_writer_*) share; put(p, k) appends k bytes.
+ * ptu_order: every node's children in the order they are written (childOff / childIdx NULL: id order), the MSA index block (rowOf NULL: the
+ * k-th leaf in node order) and the root, with the checks of the caller's order. */
+static int ptu_order(const char* fn, int n, const int32_t* parent, const int32_t* childOff, const int32_t* childIdx, const int32_t* rowOf,
+		std::vector<std::vector<int32_t>>& children, std::vector<std::pair<uint32_t, int64_t>>& msaIdx, int& root) {
+	children.assign(n, {}); msaIdx.clear();
+	root = -1;
+	for(int i = 0; i < n; ++i) { if(parent[i] < 0) root = i; else if(parent[i] < n) children[parent[i]].push_back(i); else { hu_set_error("%s: parent out of range", fn); return HU_ERR_ARG; } }
+	if(root < 0) { hu_set_error("%s: tree has no root", fn); return HU_ERR_ARG; }
+	if(childOff) { /* the caller's order: a permutation of every node's children */
+		if(childOff[0] != 0 || childOff[n] != n - 1) { hu_set_error("%s: child order does not list %d children", fn, n - 1); return HU_ERR_ARG; }
+		std::vector<uint8_t> seen(n, 0);
+		for(int u = 0; u < n; ++u) {
+			if(childOff[u + 1] - childOff[u] != (int32_t) children[u].size()) { hu_set_error("%s: child order names %d children of node %d, the tree has %zu", fn, childOff[u + 1] - childOff[u], u, children[u].size()); return HU_ERR_ARG; }
+			for(int32_t c = childOff[u]; c < childOff[u + 1]; ++c) {
+				const int32_t v = childIdx[c];
+				if(v < 0 || v >= n || parent[v] != u || seen[v]) { hu_set_error("%s: child order entry %d is not a child of node %d, or is listed twice", fn, c, u); return HU_ERR_ARG; }
+				seen[v] = 1;
+			}
+			children[u].assign(childIdx + childOff[u], childIdx + childOff[u + 1]);
+		}
+	}
+	if(rowOf) {
+		for(int i = 0; i < n; ++i) {
+			if(children[i].empty() != (rowOf[i] >= 0)) { hu_set_error("%s: node %d is %s and has MSA row %d", fn, i, children[i].empty() ? "a leaf" : "no leaf", rowOf[i]); return HU_ERR_ARG; }
+			if(rowOf[i] >= 0) msaIdx.push_back({(uint32_t) rowOf[i], (int64_t) i});
+		}
+		std::sort(msaIdx.begin(), msaIdx.end());
+		for(size_t k = 1; k < msaIdx.size(); ++k) if(msaIdx[k].first == msaIdx[k - 1].first) { hu_set_error("%s: MSA row %u belongs to two leaves", fn, msaIdx[k].first); return HU_ERR_ARG; }
+	}
+	else for(int i = 0; i < n; ++i) if(children[i].empty()) msaIdx.push_back({(uint32_t) msaIdx.size(), (int64_t) i});
+	return HU_OK;
+}
+/* one node record: 49 + 2 |name| + L + |anno| bytes */
+template<class Put> static void ptu_put_node(Put&& put, int i, const char* name, const int8_t* seqRow, int L, const char* anno, double annoDist) {
+	auto str = [&](const char* s_, size_t k) { const uint64_t len = k; put(&len, 8); if(k) put(s_, k); };
+	char tmp[32];
+	const int64_t id = i; put(&id, 8);
+	const char* nm = name ? name : (snprintf(tmp, sizeof(tmp), "n%d", i), tmp);
+	str(nm, strlen(nm));
+	const uint8_t withAbc = 0; put(&withAbc, 1);
+	str(nm, strlen(nm));
+	str((const char*) seqRow, (size_t) L);
+	const char* an = anno ? anno : "";
+	str(an, strlen(an));
+	put(&annoDist, 8);
+}
+/* the 33 header bytes of the directed edge u -> v in front of its 32 L payload bytes */
+template<class Put> static void ptu_put_edge_header(Put&& put, const int32_t* parent, const double* blen, int u, int v, size_t row) {
+	const bool uIsParent = parent[u] < 0 || v != parent[u];
+	const int child = uIsParent ? v : u;
+	const int64_t a = u, b2 = v; put(&a, 8); put(&b2, 8);
+	const uint8_t fl = uIsParent ? 1 : 0; put(&fl, 1);
+	const double len = blen[child]; put(&len, 8);
+	const uint64_t N = row; put(&N, 8);
+}
+/* what follows the root row: heights, MSA index, model text, discrete Gamma block */
+template<class Put> static void ptu_put_tail(Put&& put, int n, const double* height, const std::vector<std::pair<uint32_t, int64_t>>& msaIdx, const hu_model_desc* model,
+		const char* model_text, double dg_alpha, const double* dg_breaks) {
+	for(int i = 0; i < n; ++i) { const int64_t id = i; put(&id, 8); put(&height[i], 8); }
+	{ /* MSA index */
+		const uint32_t nl = (uint32_t) msaIdx.size();
+		put(&nl, 4);
+		for(const auto& e : msaIdx) { put(&e.first, 4); put(&e.second, 8); }
+	}
+	{
+		static const char* mnames[] = {"GTR", "TN93", "HKY85", "F81", "K80", "JC69"};
+		std::string mt = std::string(mnames[model->type]) + "\n" + (model_text ? std::string(model_text) : model_text_of(*model));
+		if(mt.empty() || mt.back() != '\n') mt += '\n';
+		put(mt.data(), mt.size());
+	}
+	const uint8_t hasDG = model->dg_k > 0; put(&hasDG, 1);
+	if(hasDG) {
+		const int32_t K = model->dg_k; put(&K, 4); put(&dg_alpha, 8);
+		for(int i = 0; i <= K; ++i) { const double b0 = dg_breaks ? dg_breaks[i] : 0.0; put(&b0, 8); }
+		put(model->dg_rate, (size_t) K * 8);
+	}
+}
 /* One writer behind hu_ptu_write and hu_ptu_write_stream.  fn: the entry's name for messages.  childOff / childIdx / rowOf NULL: children in id
  * order, MSA index = k-th leaf in node order (hu_ptu_write).  pipelined: device messages go through k_ptu_gather and two staging buffers on two
  * streams instead of one blocking copy per edge. */
@@ -515,64 +595,22 @@ static int ptu_write_impl(const char* fn, const char* path, const hu_tree_desc* 
 	if(t->win_len > 0 && t->win_len != t->cs_len) { hu_set_error("%s: the file format holds whole messages, not a column window", fn); return HU_ERR_ARG; }
 	if((childOff == nullptr) != (childIdx == nullptr) || stagingBytes < 0) { hu_set_error("%s: bad argument", fn); return HU_ERR_ARG; }
 	const int n = t->n_nodes, L = t->cs_len;
-	std::vector<std::vector<int32_t>> children(n);
-	int root = -1;
-	for(int i = 0; i < n; ++i) { if(t->parent[i] < 0) root = i; else if(t->parent[i] < n) children[t->parent[i]].push_back(i); else { hu_set_error("%s: parent out of range", fn); return HU_ERR_ARG; } }
-	if(root < 0) { hu_set_error("%s: tree has no root", fn); return HU_ERR_ARG; }
-	if(childOff) { /* the caller's order: a permutation of every node's children */
-		if(childOff[0] != 0 || childOff[n] != n - 1) { hu_set_error("%s: child order does not list %d children", fn, n - 1); return HU_ERR_ARG; }
-		std::vector<uint8_t> seen(n, 0);
-		for(int u = 0; u < n; ++u) {
-			if(childOff[u + 1] - childOff[u] != (int32_t) children[u].size()) { hu_set_error("%s: child order names %d children of node %d, the tree has %zu", fn, childOff[u + 1] - childOff[u], u, children[u].size()); return HU_ERR_ARG; }
-			for(int32_t c = childOff[u]; c < childOff[u + 1]; ++c) {
-				const int32_t v = childIdx[c];
-				if(v < 0 || v >= n || t->parent[v] != u || seen[v]) { hu_set_error("%s: child order entry %d is not a child of node %d, or is listed twice", fn, c, u); return HU_ERR_ARG; }
-				seen[v] = 1;
-			}
-			children[u].assign(childIdx + childOff[u], childIdx + childOff[u + 1]);
-		}
-	}
+	std::vector<std::vector<int32_t>> children;
 	std::vector<std::pair<uint32_t, int64_t>> msaIdx;     /* (MSA row, node id) */
-	if(rowOf) {
-		for(int i = 0; i < n; ++i) {
-			if(children[i].empty() != (rowOf[i] >= 0)) { hu_set_error("%s: node %d is %s and has MSA row %d", fn, i, children[i].empty() ? "a leaf" : "no leaf", rowOf[i]); return HU_ERR_ARG; }
-			if(rowOf[i] >= 0) msaIdx.push_back({(uint32_t) rowOf[i], (int64_t) i});
-		}
-		std::sort(msaIdx.begin(), msaIdx.end());
-		for(size_t k = 1; k < msaIdx.size(); ++k) if(msaIdx[k].first == msaIdx[k - 1].first) { hu_set_error("%s: MSA row %u belongs to two leaves", fn, msaIdx[k].first); return HU_ERR_ARG; }
-	}
-	else for(int i = 0; i < n; ++i) if(children[i].empty()) msaIdx.push_back({(uint32_t) msaIdx.size(), (int64_t) i});
+	int root = -1;
+	{ const int rc = ptu_order(fn, n, t->parent, childOff, childIdx, rowOf, children, msaIdx, root); if(rc != HU_OK) return rc; }
 	const size_t row = (size_t) L * 4;
 	const bool stream = pipelined && t->msgs_on_device;
 	if(stream && ((((uintptr_t) t->up) | ((uintptr_t) t->down)) & 15)) { hu_set_error("%s: the device message buffers must be 16-byte aligned", fn); return HU_ERR_ARG; }
 	std::ofstream f(path, std::ios::binary);
 	if(!f) { hu_set_error("cannot write PTU file '%s'", path); return HU_ERR_IO; }
 	auto put = [&](const void* p, size_t k) { f.write((const char*) p, (std::streamsize) k); };
-	auto str = [&](const char* s_, size_t k) { const uint64_t len = k; put(&len, 8); if(k) put(s_, k); };
 	hu_write_prog_info(f);
 	{ const uint64_t nn = (uint64_t) n; put(&nn, 8); const int32_t l = L; put(&l, 4); }
-	char tmp[32];
-	for(int i = 0; i < n; ++i) {
-		const int64_t id = i; put(&id, 8);
-		const char* nm = names && names[i] ? names[i] : (snprintf(tmp, sizeof(tmp), "n%d", i), tmp);
-		str(nm, strlen(nm));
-		const uint8_t withAbc = 0; put(&withAbc, 1);
-		str(nm, strlen(nm));
-		str((const char*)(t->seq + (size_t) i * L), (size_t) L);
-		const char* an = annos && annos[i] ? annos[i] : "";
-		str(an, strlen(an));
-		const double ad = t->anno_dist ? t->anno_dist[i] : 0.0; put(&ad, 8);
-	}
+	for(int i = 0; i < n; ++i) ptu_put_node(put, i, names ? names[i] : nullptr, t->seq + (size_t) i * L, L, annos ? annos[i] : nullptr, t->anno_dist ? t->anno_dist[i] : 0.0);
 	const uint64_t nEdges = 2ull * (n - 1); put(&nEdges, 8);
 	/* both directions of every edge, grouped by their first node: parent first, then the children; the root row ends the list */
-	auto edgeHeader = [&](int u, int v) {
-		const bool uIsParent = t->parent[u] < 0 || v != t->parent[u];
-		const int child = uIsParent ? v : u;
-		const int64_t a = u, b2 = v; put(&a, 8); put(&b2, 8);
-		const uint8_t fl = uIsParent ? 1 : 0; put(&fl, 1);
-		const double len = t->blen[child]; put(&len, 8);
-		const uint64_t N = row; put(&N, 8);
-	};
+	auto edgeHeader = [&](int u, int v) { ptu_put_edge_header(put, t->parent, t->blen, u, v, row); };
 	bool ok = true;
 	if(!stream) {
 		double* stage = nullptr;
@@ -662,24 +700,7 @@ static int ptu_write_impl(const char* fn, const char* path, const hu_tree_desc* 
 		}
 		#undef WCHK
 	}
-	for(int i = 0; i < n; ++i) { const int64_t id = i; put(&id, 8); put(&t->height[i], 8); }
-	{ /* MSA index */
-		const uint32_t nl = (uint32_t) msaIdx.size();
-		put(&nl, 4);
-		for(const auto& e : msaIdx) { put(&e.first, 4); put(&e.second, 8); }
-	}
-	{
-		static const char* mnames[] = {"GTR", "TN93", "HKY85", "F81", "K80", "JC69"};
-		std::string mt = std::string(mnames[model->type]) + "\n" + (model_text ? std::string(model_text) : model_text_of(*model));
-		if(mt.empty() || mt.back() != '\n') mt += '\n';
-		put(mt.data(), mt.size());
-	}
-	const uint8_t hasDG = model->dg_k > 0; put(&hasDG, 1);
-	if(hasDG) {
-		const int32_t K = model->dg_k; put(&K, 4); put(&dg_alpha, 8);
-		for(int i = 0; i <= K; ++i) { const double b0 = dg_breaks ? dg_breaks[i] : 0.0; put(&b0, 8); }
-		put(model->dg_rate, (size_t) K * 8);
-	}
+	ptu_put_tail(put, n, t->height, msaIdx, model, model_text, dg_alpha, dg_breaks);
 	f.flush();
 	if(!f) { hu_set_error("writing PTU file '%s' failed", path); return HU_ERR_IO; }
 	return HU_OK;
@@ -693,6 +714,234 @@ extern "C" int hu_ptu_write_stream(const char* path, const hu_tree_desc* t, cons
 		int64_t staging_bytes) try {
 	return ptu_write_impl("hu_ptu_write_stream", path, t, names, annos, model, model_text, dg_alpha, dg_breaks, child_off, child_idx, msa_row_of_leaf, staging_bytes, true);
 } catch(...) { return hu_catch_all("hu_ptu_write_stream"); }
+
+/* ------------------------------------------------------------------------------ the windowed .ptu writer */
+namespace {
+/* positioned, buffered output to a descriptor: put() appends at the running offset, every pwrite is checked */
+struct HuPosOut {
+	int fd; int64_t off; std::vector<char> buf; bool ok = true;
+	HuPosOut(int fd_, int64_t off_) : fd(fd_), off(off_) { buf.reserve((size_t) 4 << 20); }
+	static bool pwrite_all(int fd, const void* p, size_t k, int64_t at) {
+		const char* c = (const char*) p;
+		while(k) {
+			const ssize_t w = pwrite(fd, c, k, (off_t) at);
+			if(w < 0) { if(errno == EINTR) continue; return false; }
+			if(w == 0) return false;
+			c += w; k -= (size_t) w; at += w;
+		}
+		return true;
+	}
+	void flush() { if(ok && !buf.empty()) ok = pwrite_all(fd, buf.data(), buf.size(), off); off += (int64_t) buf.size(); buf.clear(); }
+	void operator()(const void* p, size_t k) { if(buf.size() + k > buf.capacity()) flush(); buf.insert(buf.end(), (const char*) p, (const char*) p + k); }
+};
+}
+struct hu_ptu_writer {
+	std::string path; int fd = -1;
+	int32_t n = 0, L = 0; int root = -1;
+	std::vector<int32_t> parent; std::vector<double> blen, annoDist;
+	std::vector<std::string> names, annos; bool haveNames = false, haveAnnos = false;
+	std::vector<std::pair<uint32_t, int64_t>> msaIdx;
+	std::vector<uint32_t> code;                       /* the items in file order: node << 1 | from down[]; the root row last */
+	int64_t nodeOff = 0, edgeOff = 0, recBytes = 0, tailOff = 0;
+	std::vector<uint8_t> given;                       /* [L]: how often a window has covered the column, saturating at 2 */
+	size_t want = 0;                                  /* bytes of each staging buffer asked for */
+	/* device side, made by the first window whose buffers are on the device */
+	int device = -1; uint32_t* dCode = nullptr; uint4* dStage[2] = {nullptr, nullptr}; char* hStage[2] = {nullptr, nullptr}; hipStream_t st[2] = {nullptr, nullptr};
+	size_t stageCap = 0;
+	int64_t payloadAt(size_t k, int64_t winStart) const { return edgeOff + (int64_t) k * recBytes + (k + 1 == code.size() ? 8 : 33) + 32 * winStart; }
+	void freeStage() { for(int i = 0; i < 2; ++i) { if(dStage[i]) (void) hipFree(dStage[i]); if(hStage[i]) (void) hipHostFree(hStage[i]); dStage[i] = nullptr; hStage[i] = nullptr; } stageCap = 0; }
+	void drop(bool removeFile) {
+		if(device >= 0) {
+			(void) hipSetDevice(device);
+			for(int i = 0; i < 2; ++i) if(st[i]) { (void) hipStreamSynchronize(st[i]); (void) hipStreamDestroy(st[i]); st[i] = nullptr; }
+			freeStage();
+			if(dCode) (void) hipFree(dCode);
+			dCode = nullptr; device = -1;
+		}
+		if(fd >= 0) { (void) close(fd); fd = -1; if(removeFile) (void) unlink(path.c_str()); }
+	}
+	~hu_ptu_writer() { drop(true); }      /* a writer that was not closed leaves no file */
+};
+extern "C" int hu_ptu_writer_open(const char* path, const hu_tree_desc* t, const char* const* names, const char* const* annos, const int32_t* child_off,
+		const int32_t* child_idx, const int32_t* msa_row_of_leaf, int64_t staging_bytes, hu_ptu_writer** out) try {
+	const char* fn = "hu_ptu_writer_open";
+	if(!out) { hu_set_error("%s: bad argument", fn); return HU_ERR_ARG; }
+	*out = nullptr;
+	if(!path || !t || t->n_nodes < 2 || t->cs_len < 1 || !t->parent || !t->blen || (child_off == nullptr) != (child_idx == nullptr) || staging_bytes < 0) { hu_set_error("%s: bad argument", fn); return HU_ERR_ARG; }
+	std::unique_ptr<hu_ptu_writer> w(new hu_ptu_writer);
+	const int n = t->n_nodes, L = t->cs_len;
+	w->path = path; w->n = n; w->L = L; w->parent.assign(t->parent, t->parent + n); w->blen.assign(t->blen, t->blen + n);
+	w->annoDist.assign(n, 0.0);
+	if(t->anno_dist) w->annoDist.assign(t->anno_dist, t->anno_dist + n);
+	std::vector<std::vector<int32_t>> children;
+	int rc = ptu_order(fn, n, t->parent, child_off, child_idx, msa_row_of_leaf, children, w->msaIdx, w->root);
+	if(rc != HU_OK) return rc;
+	/* the layout: the node section's size depends on the names, the annotations and L alone */
+	w->nodeOff = 20 + 8 + 4;
+	int64_t nodeBytes = 0;
+	w->haveNames = names != nullptr; w->haveAnnos = annos != nullptr;
+	if(names) w->names.resize(n); if(annos) w->annos.resize(n);
+	for(int i = 0; i < n; ++i) {
+		char tmp[32];
+		if(names && names[i]) w->names[i] = names[i]; else if(names) { snprintf(tmp, sizeof(tmp), "n%d", i); w->names[i] = tmp; }
+		if(annos && annos[i]) w->annos[i] = annos[i];
+		const size_t nm = names ? w->names[i].size() : (size_t) snprintf(tmp, sizeof(tmp), "n%d", i);
+		nodeBytes += 49 + 2 * (int64_t) nm + L + (int64_t)(annos ? w->annos[i].size() : 0);
+	}
+	w->edgeOff = w->nodeOff + nodeBytes + 8;
+	w->recBytes = 33 + 32ll * L;
+	const size_t nItems = 2 * (size_t)(n - 1) + 1;
+	w->code.reserve(nItems);
+	std::vector<int32_t> itV; itV.reserve(nItems);
+	for(int u = 0; u < n; ++u) {
+		if(t->parent[u] >= 0) { w->code.push_back((uint32_t) u << 1); itV.push_back(t->parent[u]); }
+		for(int32_t v : children[u]) { w->code.push_back((uint32_t) v << 1 | 1u); itV.push_back(v); }
+	}
+	w->code.push_back((uint32_t) w->root << 1); itV.push_back(-1);
+	if(w->code.size() != nItems) { hu_set_error("%s: tree is not connected", fn); return HU_ERR_ARG; }
+	w->tailOff = w->edgeOff + (int64_t)(nItems - 1) * w->recBytes + 8 + 32ll * L;
+	w->given.assign(L, 0);
+	w->want = staging_bytes > 0 ? (size_t) staging_bytes : (size_t) 256 << 20;
+	/* the file at its size up to the tail, and every record's header */
+	w->fd = open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+	if(w->fd < 0) { hu_set_error("cannot write PTU file '%s'", path); return HU_ERR_IO; }
+	bool ok = ftruncate(w->fd, (off_t) w->tailOff) == 0;
+	if(ok) {
+		HuPosOut head(w->fd, 0);
+		{ char info[20]; std::ostringstream o; hu_write_prog_info(o); memcpy(info, o.str().data(), 20); head(info, 20); }
+		{ const uint64_t nn = (uint64_t) n; head(&nn, 8); const int32_t l = L; head(&l, 4); }
+		head.flush();
+		HuPosOut cnt(w->fd, w->edgeOff - 8);
+		const uint64_t nEdges = 2ull * (n - 1); cnt(&nEdges, 8);
+		cnt.flush();
+		ok = head.ok && cnt.ok;
+		size_t k = 0;
+		for(int u = 0; u < n && ok; ++u) {
+			const size_t deg = (t->parent[u] >= 0) + children[u].size();
+			for(size_t d = 0; d < deg && ok; ++d, ++k) {
+				char hdr[33]; size_t o = 0;
+				auto put = [&](const void* p, size_t b) { memcpy(hdr + o, p, b); o += b; };
+				ptu_put_edge_header(put, t->parent, t->blen, u, itV[k], (size_t) L * 4);
+				ok = HuPosOut::pwrite_all(w->fd, hdr, 33, w->edgeOff + (int64_t) k * w->recBytes);
+			}
+		}
+		if(ok) { const int64_t rid = w->root; ok = HuPosOut::pwrite_all(w->fd, &rid, 8, w->edgeOff + (int64_t)(nItems - 1) * w->recBytes); }
+	}
+	if(!ok) { hu_set_error("writing PTU file '%s' failed: %s", path, strerror(errno)); return HU_ERR_IO; }      /* ~hu_ptu_writer removes the file */
+	*out = w.release();
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_ptu_writer_open"); }
+extern "C" void hu_ptu_writer_abort(hu_ptu_writer* w) try { delete w; } catch(...) { (void) hu_catch_all("hu_ptu_writer_abort"); }
+extern "C" int hu_ptu_writer_window(hu_ptu_writer* w, int64_t win_start, int64_t win_len, const double* up, const double* down, int on_device) try {
+	const char* fn = "hu_ptu_writer_window";
+	if(!w || !up || !down) { hu_set_error("%s: bad argument", fn); return HU_ERR_ARG; }
+	if(w->fd < 0) { hu_set_error("%s: the writer has failed or is closed", fn); return HU_ERR_STATE; }
+	if(win_start < 0 || win_len < 1 || win_start + win_len > w->L) { hu_set_error("%s: window [%lld, %lld) outside the %d columns", fn, (long long) win_start, (long long)(win_start + win_len), w->L); return HU_ERR_ARG; }
+	const size_t nItems = w->code.size(), piece = (size_t) win_len * 32;
+	int rc = HU_OK;
+	if(!on_device) {
+		for(size_t k = 0; k < nItems && rc == HU_OK; ++k) {
+			const uint32_t c = w->code[k];
+			const double* src = ((c & 1u) ? down : up) + (size_t)(c >> 1) * (size_t) win_len * 4;
+			if(!HuPosOut::pwrite_all(w->fd, src, piece, w->payloadAt(k, win_start))) { hu_set_error("writing PTU file '%s' failed: %s", w->path.c_str(), strerror(errno)); rc = HU_ERR_IO; }
+		}
+	}
+	else {
+		#define WCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { hu_set_error("%s: %s failed: %s", fn, #call, hipGetErrorString(e_)); return HU_ERR_DEVICE; } } while(0)
+		rc = [&]() -> int {
+			if(((((uintptr_t) up) | ((uintptr_t) down)) & 15)) { hu_set_error("%s: the device message buffers must be 16-byte aligned", fn); return HU_ERR_ARG; }
+			if(hu_device_count() <= 0) { hu_set_error("no gfx950 device visible: the engine has no CPU path"); return HU_ERR_DEVICE; }
+			if(w->device < 0) { /* the device of the caller's buffers: the current one */
+				int dev = 0;
+				WCHK(hipGetDevice(&dev));
+				w->device = dev;
+				WCHK(hipMalloc((void**) &w->dCode, nItems * 4));
+				WCHK(hipMemcpy(w->dCode, w->code.data(), nItems * 4, hipMemcpyHostToDevice));
+				for(int i = 0; i < 2; ++i) WCHK(hipStreamCreate(&w->st[i]));
+			}
+			WCHK(hipSetDevice(w->device));
+			const size_t per = std::min(nItems, std::max<size_t>(1, w->want / piece));     /* a run never splits a piece */
+			if(per * piece > w->stageCap) {
+				w->freeStage();
+				for(int i = 0; i < 2; ++i) { WCHK(hipMalloc((void**) &w->dStage[i], per * piece)); WCHK(hipHostMalloc((void**) &w->hStage[i], per * piece, hipHostMallocDefault)); }
+				w->stageCap = per * piece;
+			}
+			(void) hipGetLastError();
+			const int64_t pieces = 2 * win_len;
+			const size_t nRuns = (nItems + per - 1) / per;
+			auto enqueue = [&](size_t c) -> hipError_t {
+				const size_t a = c * per, m = std::min(per, nItems - a);
+				const int b = (int)(c & 1);
+				k_ptu_gather<<<dim3((unsigned)((pieces + 255) / 256), (unsigned) std::min<size_t>(m, 65535)), 256, 0, w->st[b]>>>(
+					reinterpret_cast<const uint4*>(up), reinterpret_cast<const uint4*>(down), w->dCode + a, (int64_t) m, pieces, w->dStage[b]);
+				hipError_t e = hipGetLastError();
+				if(e != hipSuccess) return e;
+				return hipMemcpyAsync(w->hStage[b], w->dStage[b], m * piece, hipMemcpyDeviceToHost, w->st[b]);
+			};
+			WCHK(enqueue(0));
+			for(size_t c = 0; c < nRuns; ++c) {
+				if(c + 1 < nRuns) WCHK(enqueue(c + 1));       /* gathered and copied while run c is written */
+				const int b = (int)(c & 1);
+				WCHK(hu_wait(w->st[b]));
+				const size_t a = c * per, m = std::min(per, nItems - a);
+				for(size_t k = 0; k < m; ++k)
+					if(!HuPosOut::pwrite_all(w->fd, w->hStage[b] + k * piece, piece, w->payloadAt(a + k, win_start))) { hu_set_error("writing PTU file '%s' failed: %s", w->path.c_str(), strerror(errno)); return HU_ERR_IO; }
+			}
+			return HU_OK;
+		}();
+		#undef WCHK
+	}
+	if(rc != HU_OK && rc != HU_ERR_ARG) { w->drop(true); return rc; }
+	if(rc != HU_OK) return rc;
+	for(int64_t j = win_start; j < win_start + win_len; ++j) if(w->given[j] < 2) ++w->given[j];
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_ptu_writer_window"); }
+extern "C" int hu_ptu_writer_close(hu_ptu_writer* w, const int8_t* seq, const double* height, const hu_model_desc* model, const char* model_text,
+		double dg_alpha, const double* dg_breaks) try {
+	const char* fn = "hu_ptu_writer_close";
+	if(!w) { hu_set_error("%s: bad argument", fn); return HU_ERR_ARG; }
+	std::unique_ptr<hu_ptu_writer> own(w);            /* the handle ends here whatever happens; a failure removes the file */
+	if(w->fd < 0) { hu_set_error("%s: the writer has failed", fn); return HU_ERR_STATE; }
+	if(!seq || !height || !model) { hu_set_error("%s: bad argument", fn); return HU_ERR_ARG; }
+	if(model->type < 0 || model->type > HU_JC69 || model->dg_k < 0 || model->dg_k > HU_MAX_DGK) { hu_set_error("%s: bad model", fn); return HU_ERR_ARG; }
+	for(int32_t j = 0; j < w->L; ++j) if(w->given[j] != 1) {
+		hu_set_error("%s: column %d was %s: the windows must tile the %d columns exactly once", fn, j, w->given[j] ? "given more than once" : "given by no window", w->L);
+		return HU_ERR_STATE;
+	}
+	HuPosOut nodes(w->fd, w->nodeOff);
+	for(int i = 0; i < w->n; ++i) ptu_put_node(nodes, i, w->haveNames ? w->names[i].c_str() : nullptr, seq + (size_t) i * w->L, w->L, w->haveAnnos ? w->annos[i].c_str() : nullptr, w->annoDist[i]);
+	nodes.flush();
+	if(nodes.ok && nodes.off != w->edgeOff - 8) { hu_set_error("%s: the node section took %lld bytes, %lld were laid out", fn, (long long)(nodes.off - w->nodeOff), (long long)(w->edgeOff - 8 - w->nodeOff)); return HU_ERR_IO; }
+	HuPosOut tail(w->fd, w->tailOff);
+	ptu_put_tail(tail, w->n, height, w->msaIdx, model, model_text, dg_alpha, dg_breaks);
+	tail.flush();
+	if(!nodes.ok || !tail.ok) { hu_set_error("writing PTU file '%s' failed: %s", w->path.c_str(), strerror(errno)); return HU_ERR_IO; }
+	const int fd = w->fd;
+	w->fd = -1;                                        /* the file stays */
+	if(close(fd) != 0) { (void) unlink(w->path.c_str()); hu_set_error("writing PTU file '%s' failed: %s", w->path.c_str(), strerror(errno)); return HU_ERR_IO; }
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_ptu_writer_close"); }
+
+/* the device bytes of a windowed build at window width W (hu_build_window_need, documented in include/hmmufotu_amd.h) */
+static int64_t build_window_need(int64_t n, int64_t W, bool withVar) {
+	const int64_t stage = std::max<int64_t>(32 * W, std::min<int64_t>((int64_t) 256 << 20, (2 * n - 1) * 32 * W));
+	return 64 * n * W + n * W + (withVar ? n * W + 4 * W : 0) + 8 * W + 2 * stage + 36 * n + (withVar ? 4 * n : 0) + 64;
+}
+extern "C" int64_t hu_build_window_need(int32_t n_nodes, int32_t win_len, int with_var) { return n_nodes < 1 || win_len < 1 ? 0 : build_window_need(n_nodes, win_len, with_var != 0); }
+extern "C" int hu_build_window_plan(int32_t n_nodes, int32_t cs_len, int with_var, int64_t budget_bytes, int32_t* win_len, int64_t* need_bytes) try {
+	if(n_nodes < 2 || cs_len < 1 || !win_len || !need_bytes) { hu_set_error("hu_build_window_plan: bad argument"); return HU_ERR_ARG; }
+	const bool v = with_var != 0;
+	*win_len = 0; *need_bytes = build_window_need(n_nodes, 1, v);
+	if(*need_bytes > budget_bytes) {
+		hu_set_error("hu_build_window_plan: one column of %d nodes needs %lld bytes of device memory, %lld are given", n_nodes, (long long) *need_bytes, (long long) budget_bytes);
+		return HU_ERR_NOMEM;
+	}
+	int64_t lo = 1, hi = cs_len;                       /* need is increasing in W: the largest W that fits */
+	while(lo < hi) { const int64_t mid = (lo + hi + 1) / 2; if(build_window_need(n_nodes, mid, v) <= budget_bytes) lo = mid; else hi = mid - 1; }
+	if(lo >= 256) lo = lo / 256 * 256;
+	*win_len = (int32_t) lo; *need_bytes = build_window_need(n_nodes, lo, v);
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_build_window_plan"); }
 
 /* the reference's own text forms, parsed from memory: what operator<<(ostream&, const BandedHMMP7&) and DNASubModel::write emit */
 extern "C" int hu_profile_parse_text(const char* text, int64_t len, int32_t* K, int32_t* L, double* EM, double* EI, double* T, int32_t* p2cs) try {
@@ -808,6 +1057,72 @@ extern "C" int hu_db_model_pr(const hu_db* db, int n, const double* t, double* P
 } catch(...) { return hu_catch_all("hu_db_model_pr"); }
 
 /* ------------------------------------------------------------------------------ tree pre-evaluation */
+namespace {
+/* what the level sweeps need of a tree: the CSR children lists (children in node-id order) and the nodes in BFS order from the root, which is
+ * sorted by depth; level d is order[lvOff[d] .. lvOff[d + 1]) */
+struct HuTreeTopo {
+	int32_t n = 0, root = -1, maxD = 0;
+	std::vector<int32_t> childOff, childIdx, order, lvOff;
+	int build(int32_t n_, const int32_t* parent) {
+		n = n_; root = -1;
+		std::vector<int32_t> depth(n, -1);
+		childOff.assign(n + 1, 0);
+		for(int i = 0; i < n; ++i) {
+			if(parent[i] < 0) { if(root >= 0) { hu_set_error("tree has more than one root"); return HU_ERR_ARG; } root = i; }
+			else if(parent[i] >= n) { hu_set_error("parent of node %d out of range", i); return HU_ERR_ARG; }
+			else childOff[parent[i] + 1]++;
+		}
+		if(root < 0) { hu_set_error("tree has no root"); return HU_ERR_ARG; }
+		for(int i = 0; i < n; ++i) childOff[i + 1] += childOff[i];
+		childIdx.assign(std::max(n - 1, 1), 0);
+		std::vector<int32_t> fill(childOff.begin(), childOff.end() - 1);
+		for(int i = 0; i < n; ++i) if(parent[i] >= 0) childIdx[fill[parent[i]]++] = i;   /* children in node-id order */
+		/* depths by BFS from the root (no assumption on node numbering) */
+		order.clear(); order.reserve(n); order.push_back(root); depth[root] = 0;
+		for(size_t h = 0; h < order.size(); ++h) { const int u = order[h]; for(int c = childOff[u]; c < childOff[u + 1]; ++c) { depth[childIdx[c]] = depth[u] + 1; order.push_back(childIdx[c]); } }
+		if((int) order.size() != n) { hu_set_error("tree is not connected"); return HU_ERR_ARG; }
+		maxD = 0;
+		for(int i = 0; i < n; ++i) maxD = std::max(maxD, depth[i]);
+		lvOff.assign(maxD + 2, 0);
+		for(int i = 0; i < n; ++i) lvOff[depth[i] + 1]++;
+		for(int d = 0; d <= maxD; ++d) lvOff[d + 1] += lvOff[d];
+		return HU_OK;
+	}
+	/* calcNodeHeight: distance to the nearest descendant leaf (src/PhyloTreeUnrooted.cpp:274-287) */
+	void heights(const int32_t* parent, const double* blen, double* height) const {
+		for(int i = 0; i < n; ++i) height[i] = childOff[i] == childOff[i + 1] ? 0.0 : kInf;
+		for(int h = n - 1; h > 0; --h) { const int u = order[h], p = parent[u]; height[p] = std::min(height[p], height[u] + blen[u]); }
+	}
+};
+/* the per-node arrays of a tree on the device: 28 n + 4 bytes */
+struct HuTreeTopoDev {
+	int32_t *par = nullptr, *off = nullptr, *idx = nullptr, *ord = nullptr; double* len = nullptr;
+	~HuTreeTopoDev() { (void) hipFree(par); (void) hipFree(off); (void) hipFree(idx); (void) hipFree(ord); (void) hipFree(len); }
+	hipError_t upload(const HuTreeTopo& tp, const int32_t* parent, const double* blen) {
+		const size_t n = (size_t) tp.n;
+		hipError_t e;
+		#define UP(ptr, src, bytes) if((e = hipMalloc((void**) &ptr, bytes)) != hipSuccess || (e = hipMemcpy(ptr, src, bytes, hipMemcpyHostToDevice)) != hipSuccess) return e
+		UP(par, parent, n * 4); UP(off, tp.childOff.data(), (n + 1) * 4); UP(idx, tp.childIdx.data(), tp.childIdx.size() * 4);
+		UP(ord, tp.order.data(), n * 4); UP(len, blen, n * 8);
+		#undef UP
+		return hipSuccess;
+	}
+	void bind(HuTreeDev& t) const { t.parent = par; t.blen = len; t.childOff = off; t.childIdx = idx; }
+};
+/* post-order by levels, then (withDown) pre-order by levels, on the default stream */
+void tree_launch_levels(const HuTreeDev& t, const HuModelDev& mdl, const HuTreeTopo& tp, const int32_t* dOrd, bool withDown) {
+	const unsigned gx = (unsigned)((t.winLen + 255) / 256);
+	for(int d = tp.maxD; d >= 0; --d) {
+		const int m = tp.lvOff[d + 1] - tp.lvOff[d];
+		for(int a = 0; a < m; a += 65535) k_tree_up<<<dim3(gx, std::min(65535, m - a)), 256>>>(t, mdl, dOrd + tp.lvOff[d] + a);
+	}
+	if(withDown) for(int d = 1; d <= tp.maxD; ++d) {
+		const int m = tp.lvOff[d + 1] - tp.lvOff[d];
+		for(int a = 0; a < m; a += 65535) k_tree_down<<<dim3(gx, std::min(65535, m - a)), 256>>>(t, mdl, dOrd + tp.lvOff[d] + a);
+	}
+}
+}
+#define TCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { hu_set_error("%s failed: %s", #call, hipGetErrorString(e_)); return HU_ERR_DEVICE; } } while(0)
 extern "C" int hu_tree_evaluate(int32_t n, int32_t cs_len, const int32_t* parent, const double* blen, int8_t* seq,
 		const hu_model_desc* model, int device, int64_t win_start, int64_t win_len, double* up_dev, double* down_dev, double* height) try {
 	if(n < 2 || cs_len < 1 || !parent || !blen || !seq || !model || !up_dev || !down_dev) { hu_set_error("hu_tree_evaluate: bad argument"); return HU_ERR_ARG; }
@@ -818,58 +1133,89 @@ extern "C" int hu_tree_evaluate(int32_t n, int32_t cs_len, const int32_t* parent
 	HuModelDev mdl;
 	int rc = hu_model_prepare(model, &mdl);
 	if(rc != HU_OK) return rc;
-	int root = -1;
-	std::vector<int32_t> cnt(n + 1, 0), depth(n, -1);
-	for(int i = 0; i < n; ++i) {
-		if(parent[i] < 0) { if(root >= 0) { hu_set_error("tree has more than one root"); return HU_ERR_ARG; } root = i; }
-		else if(parent[i] >= n) { hu_set_error("parent of node %d out of range", i); return HU_ERR_ARG; }
-		else cnt[parent[i] + 1]++;
-	}
-	if(root < 0) { hu_set_error("tree has no root"); return HU_ERR_ARG; }
-	for(int i = 0; i < n; ++i) cnt[i + 1] += cnt[i];
-	std::vector<int32_t> childIdx(std::max(n - 1, 1)), fill(cnt.begin(), cnt.end() - 1);
-	for(int i = 0; i < n; ++i) if(parent[i] >= 0) childIdx[fill[parent[i]]++] = i;   /* children in node-id order */
-	/* depths by BFS from the root (no assumption on node numbering) */
-	std::vector<int32_t> order; order.reserve(n); order.push_back(root); depth[root] = 0;
-	for(size_t h = 0; h < order.size(); ++h) { const int u = order[h]; for(int c = cnt[u]; c < cnt[u + 1]; ++c) { depth[childIdx[c]] = depth[u] + 1; order.push_back(childIdx[c]); } }
-	if((int) order.size() != n) { hu_set_error("tree is not connected"); return HU_ERR_ARG; }
-	int maxD = 0;
-	for(int i = 0; i < n; ++i) maxD = std::max(maxD, depth[i]);
-	std::vector<int32_t> lvOff(maxD + 2, 0);
-	for(int i = 0; i < n; ++i) lvOff[depth[i] + 1]++;
-	for(int d = 0; d <= maxD; ++d) lvOff[d + 1] += lvOff[d];
-	/* BFS order is already sorted by depth */
+	HuTreeTopo tp;
+	if((rc = tp.build(n, parent)) != HU_OK) return rc;
 	HuTreeDev t;
-	t.n = n; t.csLen = cs_len; t.root = root; t.winStart = win_start; t.winLen = win_len; t.up = up_dev; t.down = down_dev;
-	int32_t *dPar = nullptr, *dOff = nullptr, *dIdx = nullptr, *dOrd = nullptr; double* dLen = nullptr; int8_t* dSeq = nullptr;
-	HuScope guard([&] { (void) hipFree(dPar); (void) hipFree(dOff); (void) hipFree(dIdx); (void) hipFree(dOrd); (void) hipFree(dLen); (void) hipFree(dSeq); });
-	#define TCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { hu_set_error("%s failed: %s", #call, hipGetErrorString(e_)); return HU_ERR_DEVICE; } } while(0)
-	TCHK(hipMalloc((void**) &dPar, (size_t) n * 4)); TCHK(hipMalloc((void**) &dOff, (size_t)(n + 1) * 4)); TCHK(hipMalloc((void**) &dIdx, childIdx.size() * 4));
-	TCHK(hipMalloc((void**) &dOrd, (size_t) n * 4)); TCHK(hipMalloc((void**) &dLen, (size_t) n * 8)); TCHK(hipMalloc((void**) &dSeq, (size_t) n * cs_len));
-	TCHK(hipMemcpy(dPar, parent, (size_t) n * 4, hipMemcpyHostToDevice)); TCHK(hipMemcpy(dOff, cnt.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice));
-	TCHK(hipMemcpy(dIdx, childIdx.data(), childIdx.size() * 4, hipMemcpyHostToDevice)); TCHK(hipMemcpy(dOrd, order.data(), (size_t) n * 4, hipMemcpyHostToDevice));
-	TCHK(hipMemcpy(dLen, blen, (size_t) n * 8, hipMemcpyHostToDevice)); TCHK(hipMemcpy(dSeq, seq, (size_t) n * cs_len, hipMemcpyHostToDevice));
-	t.parent = dPar; t.blen = dLen; t.childOff = dOff; t.childIdx = dIdx; t.seq = dSeq;
+	t.n = n; t.csLen = cs_len; t.root = tp.root; t.winStart = win_start; t.winLen = win_len; t.up = up_dev; t.down = down_dev;
+	t.seqStride = cs_len; t.seqOff = win_start;
+	HuTreeTopoDev td; int8_t* dSeq = nullptr;
+	HuScope guard([&] { (void) hipFree(dSeq); });
+	TCHK(td.upload(tp, parent, blen));
+	TCHK(hipMalloc((void**) &dSeq, (size_t) n * cs_len));
+	TCHK(hipMemcpy(dSeq, seq, (size_t) n * cs_len, hipMemcpyHostToDevice));
+	td.bind(t); t.seq = dSeq;
 	(void) hipGetLastError();
-	const unsigned gx = (unsigned)((win_len + 255) / 256);
-	for(int d = maxD; d >= 0; --d) { /* post-order by levels */
-		const int m = lvOff[d + 1] - lvOff[d];
-		for(int a = 0; a < m; a += 65535) k_tree_up<<<dim3(gx, std::min(65535, m - a)), 256>>>(t, mdl, dOrd + lvOff[d] + a);
-	}
-	for(int d = 1; d <= maxD; ++d) { /* pre-order by levels */
-		const int m = lvOff[d + 1] - lvOff[d];
-		for(int a = 0; a < m; a += 65535) k_tree_down<<<dim3(gx, std::min(65535, m - a)), 256>>>(t, mdl, dOrd + lvOff[d] + a);
-	}
+	tree_launch_levels(t, mdl, tp, td.ord, true);
 	TCHK(hipGetLastError());
 	TCHK(hipDeviceSynchronize());
 	TCHK(hipMemcpy(seq, dSeq, (size_t) n * cs_len, hipMemcpyDeviceToHost));
-	#undef TCHK
-	if(height) { /* calcNodeHeight: distance to the nearest descendant leaf (src/PhyloTreeUnrooted.cpp:274-287) */
-		for(int i = 0; i < n; ++i) height[i] = cnt[i] == cnt[i + 1] ? 0.0 : kInf;
-		for(int h = n - 1; h > 0; --h) { const int u = order[h], p = parent[u]; height[p] = std::min(height[p], height[u] + blen[u]); }
-	}
+	if(height) tp.heights(parent, blen, height);
 	return HU_OK;
 } catch(...) { return hu_catch_all("hu_tree_evaluate"); }
+
+/* A sweep held across column windows (hu_tree_sweep_*): the tree's arrays stay on the device, a window moves its own [n][win_len] bytes */
+struct hu_tree_sweep {
+	int device = 0; int32_t n = 0, csLen = 0;
+	std::vector<int32_t> parent; std::vector<double> blen;
+	HuTreeTopo tp; HuTreeTopoDev td;
+	int8_t* dSeq = nullptr; int64_t seqCap = 0;        /* [n][seqCap]: grown to the widest window seen */
+	std::vector<int8_t> win;                           /* the window's bytes on the host, packed [n][win_len] */
+	~hu_tree_sweep() { (void) hipFree(dSeq); }
+};
+extern "C" int hu_tree_sweep_create(int32_t n, int32_t cs_len, const int32_t* parent, const double* blen, int device, hu_tree_sweep** out) try {
+	if(!out) { hu_set_error("hu_tree_sweep_create: bad argument"); return HU_ERR_ARG; }
+	*out = nullptr;
+	if(n < 2 || cs_len < 1 || !parent || !blen) { hu_set_error("hu_tree_sweep_create: bad argument"); return HU_ERR_ARG; }
+	std::unique_ptr<hu_tree_sweep> s(new hu_tree_sweep);
+	s->device = device; s->n = n; s->csLen = cs_len; s->parent.assign(parent, parent + n); s->blen.assign(blen, blen + n);
+	int rc = s->tp.build(n, parent);
+	if(rc != HU_OK) return rc;
+	if(hu_device_count() <= 0) { hu_set_error("no gfx950 device visible: the engine has no CPU path"); return HU_ERR_DEVICE; }
+	HIPCHK(hipSetDevice(device));
+	TCHK(s->td.upload(s->tp, parent, blen));
+	*out = s.release();
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_tree_sweep_create"); }
+extern "C" void hu_tree_sweep_destroy(hu_tree_sweep* s) try {
+	if(!s) return;
+	(void) hipSetDevice(s->device);
+	delete s;
+} catch(...) { (void) hu_catch_all("hu_tree_sweep_destroy"); }
+extern "C" int hu_tree_sweep_heights(const hu_tree_sweep* s, double* height) try {
+	if(!s || !height) { hu_set_error("hu_tree_sweep_heights: bad argument"); return HU_ERR_ARG; }
+	s->tp.heights(s->parent.data(), s->blen.data(), height);
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_tree_sweep_heights"); }
+extern "C" int hu_tree_sweep_window(hu_tree_sweep* s, const hu_model_desc* model, int8_t* seq, int64_t win_start, int64_t win_len,
+		double* up_dev, double* down_dev) try {
+	if(!s || !model || !seq || !up_dev) { hu_set_error("hu_tree_sweep_window: bad argument"); return HU_ERR_ARG; }
+	if(win_start < 0 || win_len < 1 || win_start + win_len > s->csLen) { hu_set_error("hu_tree_sweep_window: window [%lld, %lld) outside the %d columns", (long long) win_start, (long long)(win_start + win_len), s->csLen); return HU_ERR_ARG; }
+	HuModelDev mdl;
+	int rc = hu_model_prepare(model, &mdl);
+	if(rc != HU_OK) return rc;
+	HIPCHK(hipSetDevice(s->device));
+	const size_t n = (size_t) s->n, L = (size_t) s->csLen, W = (size_t) win_len, bytes = n * W;
+	if(win_len > s->seqCap) {
+		(void) hipFree(s->dSeq); s->dSeq = nullptr; s->seqCap = 0;
+		TCHK(hipMalloc((void**) &s->dSeq, bytes));
+		s->seqCap = win_len;
+	}
+	s->win.resize(bytes);
+	for(size_t u = 0; u < n; ++u) memcpy(s->win.data() + u * W, seq + u * L + (size_t) win_start, W);
+	TCHK(hipMemcpy(s->dSeq, s->win.data(), bytes, hipMemcpyHostToDevice));
+	HuTreeDev t;
+	t.n = s->n; t.csLen = s->csLen; t.root = s->tp.root; t.winStart = win_start; t.winLen = win_len; t.up = up_dev; t.down = down_dev;
+	t.seqStride = win_len; t.seqOff = 0; t.seq = s->dSeq;
+	s->td.bind(t);
+	(void) hipGetLastError();
+	tree_launch_levels(t, mdl, s->tp, s->td.ord, down_dev != nullptr);
+	TCHK(hipGetLastError());
+	TCHK(hipDeviceSynchronize());
+	TCHK(hipMemcpy(s->win.data(), s->dSeq, bytes, hipMemcpyDeviceToHost));
+	for(size_t u = 0; u < n; ++u) if(s->tp.childOff[u] != s->tp.childOff[u + 1]) memcpy(seq + u * L + (size_t) win_start, s->win.data() + u * W, W);     /* the inner rows */
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_tree_sweep_window"); }
+#undef TCHK
 
 /* ------------------------------------------------------------------------------ database build (hmmufotu-build) */
 /* encode(toupper(c)) of the MSA's alphabet, IUPACNucl (src/MSA.h:380-381, src/IUPACNucl.cpp:34-50, src/DegenAlphabet.cpp:51-63):

@@ -49,7 +49,11 @@ struct HuTreeDev {
 	int64_t winStart, winLen;
 	const int32_t* parent; const double* blen;
 	const int32_t* childOff; const int32_t* childIdx;   /* CSR children lists */
-	int8_t* seq;                                         /* [n][csLen]; inner rows are written */
+	int8_t* seq;                                         /* rows of seqStride bytes, column j of node u at seq[u * seqStride + seqOff + (j - winStart)];
+	                                                      * inner rows are written.  hu_tree_evaluate: whole rows [n][csLen], seqStride = csLen and
+	                                                      * seqOff = winStart; hu_tree_sweep_window: the window's bytes alone, [n][winLen], seqStride =
+	                                                      * winLen and seqOff = 0 */
+	int64_t seqStride, seqOff;
 	double* up; double* down;                            /* [n][winLen][4] */
 };
 
@@ -58,12 +62,12 @@ __global__ __launch_bounds__(256) void k_tree_up(HuTreeDev t, HuModelDev mdl, co
 	const int u = nodes[blockIdx.y];
 	const int64_t w = (int64_t) blockIdx.x * 256 + threadIdx.x;
 	if(w >= t.winLen) return;
-	const int64_t j = t.winStart + w;
+	const size_t sq = (size_t) u * t.seqStride + t.seqOff + w;
 	const int Kc = mdl.dgK > 0 ? mdl.dgK : 1;
 	double out[4];
 	const int c0 = t.childOff[u], c1 = t.childOff[u + 1];
 	if(c0 == c1) { /* leaf (src/PhyloTreeUnrooted.h:1431-1437) */
-		const int b = t.seq[(size_t) u * t.csLen + j];
+		const int b = t.seq[sq];
 		for(int i = 0; i < 4; ++i) out[i] = b >= 0 ? (i == b ? 0.0 : -INFINITY) : mdl.logpi[i];
 	}
 	else {
@@ -74,7 +78,7 @@ __global__ __launch_bounds__(256) void k_tree_up(HuTreeDev t, HuModelDev mdl, co
 			acc.add(mdl, Kc, t.blen[v], M);
 		}
 		acc.finish(mdl, Kc, out);
-		t.seq[(size_t) u * t.csLen + j] = (int8_t) argmax4_tied(out); /* exact-arithmetic ties -> first index, like maxCoeff */
+		t.seq[sq] = (int8_t) argmax4_tied(out); /* exact-arithmetic ties -> first index, like maxCoeff */
 	}
 	double* dst = t.up + ((size_t) u * t.winLen + w) * 4;
 	*reinterpret_cast<double2*>(dst) = make_double2(out[0], out[1]);

@@ -875,6 +875,113 @@ def write_ptu_stream(path, parent, blen, seq, up, down, height, model: ModelDesc
                                             _p(ro, C.c_int32) if ro is not None else None, C.c_int64(int(staging_bytes))))
 
 
+class TreeSweep:
+    """hu_tree_sweep_*: tree_evaluate held across column windows.  The tree's arrays go to the device once; window() moves the
+    [n][win_len] bytes of its columns and fills the DEVICE buffers at up_ptr / down_ptr ([n][win_len][4] float64).  seq: the int8
+    array [n][cs_len] with the leaf rows, whose inner rows window() fills in place.  down_ptr None: the post-order levels only."""
+
+    def __init__(self, parent, blen, cs_len: int, device=0):
+        self.parent = np.ascontiguousarray(parent, np.int32); self.blen = np.ascontiguousarray(blen, np.float64)
+        self.n, self.cs_len = len(self.parent), int(cs_len)
+        self.h = C.c_void_p()
+        _chk(load_library().hu_tree_sweep_create(C.c_int32(self.n), C.c_int32(self.cs_len), _p(self.parent, C.c_int32), _p(self.blen, C.c_double),
+                                                 C.c_int(device), C.byref(self.h)))
+
+    def window(self, seq, model: ModelDesc, win_start: int, win_len: int, up_ptr: int, down_ptr=None):
+        if seq.dtype != np.int8 or not seq.flags.c_contiguous or seq.shape != (self.n, self.cs_len):
+            raise ValueError("seq must be a contiguous int8 array [n][cs_len]")
+        _chk(load_library().hu_tree_sweep_window(self.h, C.byref(model), _p(seq, C.c_int8), C.c_int64(win_start), C.c_int64(win_len),
+                                                 C.c_void_p(int(up_ptr)), C.c_void_p(int(down_ptr)) if down_ptr is not None else None))
+
+    def heights(self) -> np.ndarray:
+        h = np.zeros(self.n)
+        _chk(load_library().hu_tree_sweep_heights(self.h, _p(h, C.c_double)))
+        return h
+
+    def close(self):
+        if self.h:
+            lib = load_library()
+            lib.hu_tree_sweep_destroy.restype = None
+            lib.hu_tree_sweep_destroy(self.h); self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PtuWriter:
+    """hu_ptu_writer_*: write_ptu_stream fed a column window at a time, in any order; the file is byte for byte write_ptu_stream's.
+    window(): up / down are [n][win_len][4] arrays, or device pointers (ints) with on_device=True.  close() takes the rows and heights,
+    refuses unless the windows tiled [0, cs_len) exactly once, and ends the writer; a refusal, a failed write and abort() leave no file."""
+
+    def __init__(self, path, parent, blen, cs_len: int, names=None, annos=None, anno_dist=None, child_off=None, child_idx=None, msa_row_of_leaf=None,
+                 staging_bytes=0):
+        keep = dict(parent=np.ascontiguousarray(parent, np.int32), blen=np.ascontiguousarray(blen, np.float64))
+        td = TreeDesc()
+        td.n_nodes, td.cs_len = len(keep["parent"]), int(cs_len)
+        td.parent = _p(keep["parent"], C.c_int32); td.blen = _p(keep["blen"], C.c_double)
+        if anno_dist is not None:
+            keep["ad"] = np.ascontiguousarray(anno_dist, np.float64); td.anno_dist = _p(keep["ad"], C.c_double)
+        arr = lambda xs: (C.c_char_p * len(xs))(*[x.encode() for x in xs]) if xs is not None else None
+        i32 = lambda a: np.ascontiguousarray(a, np.int32) if a is not None else None
+        co, ci, ro = i32(child_off), i32(child_idx), i32(msa_row_of_leaf)
+        self.n, self.cs_len = td.n_nodes, td.cs_len
+        self.h = C.c_void_p()
+        _chk(load_library().hu_ptu_writer_open(path.encode(), C.byref(td), arr(names), arr(annos), _p(co, C.c_int32) if co is not None else None,
+                                               _p(ci, C.c_int32) if ci is not None else None, _p(ro, C.c_int32) if ro is not None else None,
+                                               C.c_int64(int(staging_bytes)), C.byref(self.h)))
+
+    def window(self, win_start: int, win_len: int, up, down, on_device=False):
+        if on_device:
+            u, d = C.c_void_p(int(up)), C.c_void_p(int(down))
+            keep = None
+        else:
+            keep = (np.ascontiguousarray(up, np.float64), np.ascontiguousarray(down, np.float64))
+            if keep[0].shape != (self.n, win_len, 4) or keep[1].shape != (self.n, win_len, 4):
+                raise ValueError("up / down must be [n][win_len][4]")
+            u, d = keep[0].ctypes.data_as(C.c_void_p), keep[1].ctypes.data_as(C.c_void_p)
+        _chk(load_library().hu_ptu_writer_window(self.h, C.c_int64(win_start), C.c_int64(win_len), u, d, C.c_int(1 if on_device else 0)))
+
+    def close(self, seq, height, model: ModelDesc, model_text=None, dg_alpha=0.0, dg_breaks=None):
+        seq = np.ascontiguousarray(seq, np.int8); height = np.ascontiguousarray(height, np.float64)
+        if seq.shape != (self.n, self.cs_len) or height.shape != (self.n,):
+            raise ValueError("seq must be [n][cs_len], height [n]")
+        br = np.ascontiguousarray(dg_breaks, np.float64) if dg_breaks is not None else None
+        h, self.h = self.h, C.c_void_p()                  # the handle ends here whatever happens
+        _chk(load_library().hu_ptu_writer_close(h, _p(seq, C.c_int8), _p(height, C.c_double), C.byref(model), model_text.encode() if model_text else None,
+                                                C.c_double(dg_alpha), _p(br, C.c_double) if br is not None else None))
+
+    def abort(self):
+        if self.h:
+            lib = load_library()
+            lib.hu_ptu_writer_abort.restype = None
+            lib.hu_ptu_writer_abort(self.h); self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.abort()
+        except Exception:
+            pass
+
+
+def build_window_need(n_nodes: int, win_len: int, with_var: bool) -> int:
+    """hu_build_window_need: the device bytes of a windowed build at window width win_len"""
+    lib = load_library()
+    lib.hu_build_window_need.restype = C.c_int64
+    return int(lib.hu_build_window_need(C.c_int32(n_nodes), C.c_int32(win_len), C.c_int(int(bool(with_var)))))
+
+
+def build_window_plan(n_nodes: int, cs_len: int, with_var: bool, budget_bytes: int):
+    """hu_build_window_plan: (window width, bytes needed at it) of the widest windowed build within budget_bytes; EngineError -4 when
+    not even one column fits"""
+    W = C.c_int32(0); need = C.c_int64(0)
+    _chk(load_library().hu_build_window_plan(C.c_int32(n_nodes), C.c_int32(cs_len), C.c_int(int(bool(with_var))), C.c_int64(int(budget_bytes)),
+                                             C.byref(W), C.byref(need)))
+    return int(W.value), int(need.value)
+
+
 def tree_info(ptu_path: str) -> dict:
     """hu_tree_info_*: the tree of a .ptu without its messages (host only): parent, blen, anno_dist, is_leaf, names, annos, and every
     node's children in the order their parent -> child edges stand in the file"""

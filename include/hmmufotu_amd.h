@@ -302,6 +302,60 @@ int hu_ptu_write_stream(const char* path, const hu_tree_desc* tree, const char* 
 		const char* model_text, double dg_alpha, const double* dg_breaks, const int32_t* child_off, const int32_t* child_idx,
 		const int32_t* msa_row_of_leaf, int64_t staging_bytes);
 
+/* ---- column-windowed builds: a database whose messages do not fit one device (hmmufotu-amd-build --col-window) ----
+ * Felsenstein's recursion (src/PhyloTreeUnrooted.cpp:315-374) treats every column on its own, so the sweep, the mutation counts
+ * (hu_tree_count_mutations with cs_len = win_len), the log-likelihoods (hu_tree_loglik with cs_len = win_len) and the file's payloads can be
+ * made a window of columns at a time; every value is bit-equal to the whole-width entries' for the same column.
+ *
+ * hu_tree_sweep_*: hu_tree_evaluate held across windows.  create sends the topology, the level order and the branch lengths to the device
+ * once (28 n bytes; the tree is checked before a device is asked for); window sends the [n_nodes][win_len] bytes of seq's columns
+ * [win_start, win_start + win_len), runs the level kernels with the window's stride, and puts the inferred inner rows of these columns back
+ * into seq (host [n_nodes][cs_len], leaf rows on entry, as hu_tree_evaluate).  Nothing on the device is sized by n_nodes x cs_len: beside the
+ * caller's up_dev / down_dev (DEVICE [n_nodes][win_len][4]) the handle keeps n_nodes x (the widest win_len seen) bytes.  down_dev NULL: the
+ * post-order levels only, which is all hu_tree_count_mutations reads (pass 1 of -V, src/hmmufotu-build.cpp:431-447).  heights: calcNodeHeight
+ * (:274-287), host only. */
+typedef struct hu_tree_sweep hu_tree_sweep;
+int hu_tree_sweep_create(int32_t n_nodes, int32_t cs_len, const int32_t* parent, const double* blen, int device, hu_tree_sweep** out);
+int hu_tree_sweep_window(hu_tree_sweep* s, const hu_model_desc* model, int8_t* seq, int64_t win_start, int64_t win_len, double* up_dev, double* down_dev);
+int hu_tree_sweep_heights(const hu_tree_sweep* s, double* height);
+void hu_tree_sweep_destroy(hu_tree_sweep* s);
+
+/* hu_ptu_writer_*: PTUnrooted::save (src/PhyloTreeUnrooted.cpp:537-567) fed a window at a time; the file is byte for byte hu_ptu_write_stream's.
+ * The format keeps every directed edge's [cs_len][4] payload contiguous, so the layout is computed first: 32 header bytes, the node section
+ * (per node 49 + 2 |name| + cs_len + |annotation| bytes: known without the inner rows), 8 bytes of edge count, 2 (n - 1) edge records of
+ * 33 + 32 cs_len bytes in hu_ptu_write_stream's order, the root row of 8 + 32 cs_len bytes, the tail.
+ *   open: tree gives n_nodes, cs_len, parent, blen and anno_dist (its other fields are not read); names, annos, child_off / child_idx,
+ *     msa_row_of_leaf and staging_bytes as hu_ptu_write_stream.  Sizes the file up to the tail and writes every record's header.  Needs no device.
+ *   window: up / down [n_nodes][win_len][4] of the columns [win_start, win_start + win_len), in any order of windows.  on_device = 1: DEVICE
+ *     buffers on the current device, 16-byte aligned; runs of consecutive records' 32 win_len-byte pieces are packed by k_ptu_gather (pieces =
+ *     2 win_len) into one of two staging buffers, copied on one of two streams and placed by the host at record offset + 33 + 32 win_start
+ *     (root row: + 8) with positioned writes, while the next run is gathered.  on_device = 0: host buffers, no device needed.
+ *   close: writes the node section from seq [n_nodes][cs_len] (all inner rows are known now) and the tail (height, model, model_text, dg_alpha,
+ *     dg_breaks as hu_ptu_write).  HU_ERR_STATE unless the windows given tile [0, cs_len) exactly once.  Frees the handle in every case.
+ *   abort: frees the handle and removes the file.
+ * Every write's result is checked; a failed write, a failed close and abort leave no file behind. */
+typedef struct hu_ptu_writer hu_ptu_writer;
+int hu_ptu_writer_open(const char* path, const hu_tree_desc* tree, const char* const* names, const char* const* annos, const int32_t* child_off,
+		const int32_t* child_idx, const int32_t* msa_row_of_leaf, int64_t staging_bytes, hu_ptu_writer** out);
+int hu_ptu_writer_window(hu_ptu_writer* w, int64_t win_start, int64_t win_len, const double* up, const double* down, int on_device);
+int hu_ptu_writer_close(hu_ptu_writer* w, const int8_t* seq, const double* height, const hu_model_desc* model, const char* model_text,
+		double dg_alpha, const double* dg_breaks);
+void hu_ptu_writer_abort(hu_ptu_writer* w);
+
+/* The window width of a build, host only.  hu_build_window_need: the device bytes a windowed build of n nodes holds at width W,
+ *   need(W) = 64 n W                           up and down of the second pass, the wider one (the first holds up alone)
+ *           + n W                              the sweep's sequence bytes
+ *           + (with_var ? n W + 4 W + 4 n : 0)  hu_tree_count_mutations: states, counts, parents
+ *           + 8 W                              hu_tree_loglik's column values
+ *           + 2 stage(W) + 8 n                 the writer's two staging buffers and its record codes,
+ *                                              stage(W) = max(32 W, min(2^28, (2 n - 1) 32 W))
+ *           + 28 n + 64                        the sweep's per-node arrays
+ * which grows with W.  hu_build_window_plan: the largest W <= cs_len with need(W) <= budget_bytes, rounded down to a multiple of 256 when it is
+ * 256 or more (whole workgroups of the level kernels), and need(W) in *need_bytes.  HU_ERR_NOMEM when not even one column fits: *win_len = 0,
+ * *need_bytes = need(1), and the message names both numbers. */
+int64_t hu_build_window_need(int32_t n_nodes, int32_t win_len, int with_var);
+int hu_build_window_plan(int32_t n_nodes, int32_t cs_len, int with_var, int64_t budget_bytes, int32_t* win_len, int64_t* need_bytes);
+
 /* ---- the tree of a .ptu without its messages (host only, no device): what the consumers of an assignment file need of the database —
  * hmmufotu-sum the nodes' taxon annotations (src/hmmufotu-sum.cpp:378-383), hmmufotu-jplace the topology, branch lengths and the order of
  * every node's children as PTUnrooted::load leaves it (src/hmmufotu-jplace.cpp:197, src/PhyloTreeUnrooted.cpp:1135-1157).  The 4 x csLen
