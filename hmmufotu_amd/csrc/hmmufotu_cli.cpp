@@ -3,7 +3,8 @@
 // FASTA/FASTQ reading, the seed scans (hu_seed_index_*), strand auto-detection (:500-542), batching, TSV.
 // -C/--chimera* run the segment check of src/hmmufotu.cpp:653-691 in a second batch (hu_chimera_batch).
 // -a writes the aligned reads as FASTA (60 columns, description + ";csStart=..;csEnd=..;", :709-715); --align-only stops
-// after the alignment.  Inputs may be gzip- or bzip2-compressed (.bz2 by name), outputs are when their name ends in .gz / .bz2 (zlib; libbz2 bound at run time).
+// after the alignment.  --otu-table / --otu-cs summarise the sample from the batches as they finish: the files hmmufotu-amd-sum and
+// hmmufotu-amd-otu-cs would write from this run's assignment file, which --no-tsv then leaves unwritten.  Inputs may be gzip- or bzip2-compressed (.bz2 by name), outputs are when their name ends in .gz / .bz2 (zlib; libbz2 bound at run time).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -24,6 +25,8 @@
 #include <zlib.h>
 #include "../../include/hmmufotu_amd.h"
 #include "hu_reads_io.h"
+#include "hu_otu_write.h"
+#include "hu_sum_rule.h"
 
 /* writer: gzip when the file name ends in .gz, bzip2 when it ends in .bz2 */
 struct LineOut {
@@ -61,6 +64,11 @@ static void usage(const char* p) {
 		"                             --gpu + i mod --gpus) instead of whole replicas: for databases beyond one GPU's memory.  Reads are routed\n"
 		"                             by their seeds and re-routed once by their alignment region.  --win-overlap INT [3200] columns shared by\n"
 		"                             neighbouring windows: at least the widest alignment region to be expected\n"
+		"            --otu-table FILE  the OTU table of this sample, as hmmufotu-amd-sum -o FILE writes it from this run's assignment file\n"
+		"            --otu-cs FILE    the consensus sequences of its OTUs, as hmmufotu-amd-otu-cs -c FILE writes them; --otu-no-gap  --otu-effN DBL [2]\n"
+		"            --sample NAME    the table's column name [the -o file name, else READ-FILE1]  --use-dbname  DBNAME as prefix for OTUs\n"
+		"            --otu-q DBL [0]  --otu-aln-iden DBL [0]  --otu-hmm-iden DBL [0]  --otu-min-reads INT [0]   the -q, --aln-iden, --hmm-iden, -n of hmmufotu-amd-sum\n"
+		"            --no-tsv         neither format nor write the assignment lines (needs --otu-table or --otu-cs)\n"
 		"            -S|--seed INT    a seed hit drawn from all its occurrences (CSFMIndex::locateOne) with this seed; without it the first occurrence\n"
 		"                             (locateFirst).  A run repeats at any thread count.  -p|--process INT is accepted and has no effect\n";
 }
@@ -88,6 +96,8 @@ int main(int argc, char** argv) {
 	uint64_t hitSeed = 0; std::string seedOrder = "reference";
 	std::string alnFn;
 	int numSeg = 2; double chimeraErr = NAN, chimeraLod = 0; std::string chiOutFn;
+	std::string otuFn, otuCsFn, sampleName; bool otuNoGap = false, useDb = false, noTsv = false, otuOpt = false, otuDetail = false, chimeraOutOpt = false;
+	double otuEffN = 2; int otuMinRead = 0; hu_tsv::Accept otuFlt;
 	hu_opts o; hu_default_opts(&o);
 	std::string cmd;
 	for(int i = 0; i < argc; ++i) { cmd += argv[i]; cmd += i + 1 < argc ? " " : ""; }
@@ -117,8 +127,19 @@ int main(int argc, char** argv) {
 		else if(a == "--num-segment") numSeg = (int) atof(val());
 		else if(a == "--chimera-err") chimeraErr = atof(val());
 		else if(a == "--chimera-lod") chimeraLod = atof(val());
-		else if(a == "--chimera-out") chiOutFn = val();
-		else if(a == "--chimera-info") chimeraInfo = true;
+		else if(a == "--chimera-out") { chiOutFn = val(); chimeraOutOpt = true; }
+		else if(a == "--chimera-info") { chimeraInfo = true; chimeraOutOpt = true; }
+		else if(a == "--otu-table") { otuFn = val(); otuOpt = true; }
+		else if(a == "--otu-cs") { otuCsFn = val(); otuOpt = true; }
+		else if(a == "--otu-no-gap") { otuNoGap = true; otuOpt = otuDetail = true; }
+		else if(a == "--otu-effN") { otuEffN = atof(val()); otuOpt = otuDetail = true; }
+		else if(a == "--sample") { sampleName = val(); otuOpt = otuDetail = true; }
+		else if(a == "--use-dbname") { useDb = true; otuOpt = otuDetail = true; }
+		else if(a == "--otu-q") { otuFlt.minQ = atof(val()); otuOpt = otuDetail = true; }
+		else if(a == "--otu-aln-iden") { otuFlt.minAln = atof(val()); otuOpt = otuDetail = true; }
+		else if(a == "--otu-hmm-iden") { otuFlt.minHmm = atof(val()); otuOpt = otuDetail = true; }
+		else if(a == "--otu-min-reads") { otuMinRead = atoi(val()); otuOpt = otuDetail = true; }
+		else if(a == "--no-tsv") { noTsv = true; otuOpt = true; }
 		else if(a == "-a") alnFn = val();
 		else if(a == "--align-only") alignOnly = true;
 		else if(a == "--batch") batch = atoi(val());
@@ -145,6 +166,16 @@ int main(int argc, char** argv) {
 	if(seedOrder != "stable" && seedOrder != "reference") { std::cerr << "--seed-order must be either 'stable' or 'reference'" << std::endl; return EXIT_FAILURE; }
 	o.seed_order = seedOrder == "reference" ? HU_SEED_ORDER_LIBSTDCXX : HU_SEED_ORDER_STABLE;
 	if(prior != "uniform" && prior != "height") { std::cerr << "--prior must be either 'uniform' or 'height'" << std::endl; return EXIT_FAILURE; }
+	/* a run that summarises itself (--otu-table / --otu-cs): what cannot go together, said before a device is asked for */
+	const bool wantSum = !otuFn.empty() || !otuCsFn.empty();
+	if(otuOpt && alignOnly) { std::cerr << "--otu-table, --otu-cs and their options cannot be used with --align-only: nothing is placed" << std::endl; return EXIT_FAILURE; }
+	if(otuOpt && colWindows > 1) { std::cerr << "--otu-table, --otu-cs and their options cannot be used with --col-windows above 1" << std::endl; return EXIT_FAILURE; }
+	if(noTsv && !wantSum) { std::cerr << "--no-tsv needs --otu-table or --otu-cs" << std::endl; return EXIT_FAILURE; }
+	if(otuDetail && !wantSum) { std::cerr << "--sample, --use-dbname and the --otu-* options need --otu-table or --otu-cs" << std::endl; return EXIT_FAILURE; }
+	if(noTsv && (!outFn.empty() || !alnFn.empty() || chimeraOutOpt)) { std::cerr << "--no-tsv cannot be used with -o, -a, --chimera-out or --chimera-info" << std::endl; return EXIT_FAILURE; }
+	if(!(otuEffN >= 0) || std::isinf(otuEffN)) { std::cerr << "--otu-effN must be non-negative" << std::endl; return EXIT_FAILURE; }
+	if(!(otuMinRead >= 0)) { std::cerr << "--otu-min-reads must be non-negative integer" << std::endl; return EXIT_FAILURE; }
+	if(sampleName.empty()) sampleName = !outFn.empty() ? outFn : pos[1];      /* the summary programs name a sample after its assignment file */
 	/* the chimera options only count with -C (src/hmmufotu.cpp:248-260); checks of :325-340 */
 	if(!checkChimera) { chimeraInfo = false; chiOutFn.clear(); numSeg = 2; chimeraErr = NAN; chimeraLod = 0; }
 	if(nGpus < 1 || nGpus > 64 || inflight < 1 || inflight > 16 || batch < 1) { std::cerr << "--gpus must be in [1, 64], --inflight in [1, 16], --batch positive" << std::endl; return EXIT_FAILURE; }
@@ -241,7 +272,7 @@ int main(int argc, char** argv) {
 	auto out = [&](const std::string& t) { if(fout.on) fout.write(t); else std::cout.write(t.data(), (std::streamsize) t.size()); };
 	const char* header = chimeraInfo ? hu_tsv_header_chimera() : hu_tsv_header();
 	const std::string preamble = std::string("# HmmUFOtu v1.5.1 taxonomy assignment generated by ") + argv[0] + "\n# command: " + cmd + "\n" + header + "\n";
-	out(preamble);
+	if(!noTsv) out(preamble);
 	LineOut chiOut;
 	if(!chiOutFn.empty()) {
 		if(!chiOut.open(chiOutFn)) { std::cerr << "Unable to write to '" << chiOutFn << "'" << std::endl; return EXIT_FAILURE; }
@@ -249,6 +280,13 @@ int main(int argc, char** argv) {
 	}
 	LineOut alnOut;
 	if(!alnFn.empty() && !alnOut.open(alnFn)) { std::cerr << "Unable to write to align file '" << alnFn << "'" << std::endl; return EXIT_FAILURE; }
+	std::ofstream otuOut, otuCsOut;
+	if(!otuFn.empty()) { otuOut.open(otuFn); if(!otuOut) { std::cerr << "Unable to write to '" << otuFn << "'" << std::endl; return EXIT_FAILURE; } }
+	if(!otuCsFn.empty()) { otuCsOut.open(otuCsFn); if(!otuCsOut) { std::cerr << "Unable to write to '" << otuCsFn << "'" << std::endl; return EXIT_FAILURE; } }
+	/* the column counts of --otu-cs: one handle per replica, on its device; the workers of a replica take turns on it (hu_otucs allows no concurrent calls) */
+	std::vector<hu_otucs*> otuCs(otuCsFn.empty() ? 0 : (size_t) nGpus, nullptr);
+	std::vector<std::mutex> otuCsMu(otuCs.size());
+	for(size_t g = 0; g < otuCs.size(); ++g) CHK(hu_otucs_create(dbs[g], &otuCs[g]));
 	hu_batch_destroy(gb); gb = nullptr;
 	std::vector<const char*> annos(nNodes);
 	for(int i = 0; i < nNodes; ++i) annos[i] = hu_db_get_annotation(db, i);
@@ -261,7 +299,7 @@ int main(int argc, char** argv) {
 	 *                          formatting of several batches runs side by side)
 	 *   writer                 writes the finished batches in read order
 	 * The reference: one OpenMP task per read, lines in completion order under a critical section (src/hmmufotu.cpp:603-751). */
-	struct Done { std::string mainTxt, chiTxt, alnTxt; long n = 0, placed = 0, flagged = 0; };
+	struct Done { std::string mainTxt, chiTxt, alnTxt; long n = 0, placed = 0, flagged = 0; std::vector<int32_t> taxa; };      /* taxa: the taxon of every read that counts (--otu-table / --otu-cs) */
 	struct Pipe {
 		std::mutex mu; std::condition_variable cv;
 		std::deque<std::pair<long, std::unique_ptr<Slot>>> parsed, seeded;
@@ -272,7 +310,7 @@ int main(int argc, char** argv) {
 	} P;
 	const auto tLoop = std::chrono::steady_clock::now();
 	/* busy seconds per stage (reported with -v): which stage bounds the pipeline */
-	std::atomic<long long> usParse{0}, usSeed{0}, usEngine{0}, usFormat{0}, usWrite{0};
+	std::atomic<long long> usParse{0}, usSeed{0}, usEngine{0}, usFormat{0}, usWrite{0}, usSum{0};
 	auto usSince = [](std::chrono::steady_clock::time_point t) { return (long long) std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t).count(); };
 	/* ordinary mode: worker w drives one batch object on replica w % nGpus.  Column-window mode: worker w is a LANE with one batch object per window
 	 * (batch object w * colWindows + k on window k): it splits a batch of reads by window, runs the parts, re-routes, and puts the lines back in read order */
@@ -306,11 +344,24 @@ int main(int argc, char** argv) {
 		}
 		else if((rc = alignOnly ? hu_align_batch(gb, &o) : hu_assign_batch(gb, &o)) != HU_OK) return rc;
 		usEngine += usSince(tE);
+		const hu_chimera_rec* cp = checkChimera ? chi.data() : nullptr;
+		if(wantSum) { /* the reads whose line hmmufotu-amd-sum would accept, from the batch itself; their rows are counted where they lie */
+			auto tS = std::chrono::steady_clock::now();
+			std::vector<hu_sum_rec> sum((size_t) n); std::vector<uint8_t> acc((size_t) n);
+			if((rc = hu_batch_get_summary(gb, cp, sum.data())) != HU_OK || (rc = hu_sum_accept(sum.data(), n, otuFlt.minQ, otuFlt.minAln, otuFlt.minHmm, acc.data())) != HU_OK) return rc;
+			for(int i = 0; i < n; ++i) { if(acc[i]) dn.taxa.push_back(sum[i].taxon); if(noTsv) dn.placed += sum[i].in_main; }
+			if(!otuCs.empty()) {
+				const size_t g = (size_t)(w % nGpus);
+				std::lock_guard<std::mutex> lk(otuCsMu[g]);
+				if((rc = hu_otucs_add_batch(otuCs[g], gb, acc.data())) != HU_OK) return rc;
+			}
+			usSum += usSince(tS);
+		}
+		if(noTsv) { dn.n = n; return HU_OK; }
 		auto tF = std::chrono::steady_clock::now();
 		const int mainKind = alignOnly ? 2 : 0;
 		std::vector<const char*> pid(n), pdesc(n);
 		for(int i = 0; i < n; ++i) { pid[i] = ids[i].c_str(); pdesc[i] = descs[i].c_str(); }
-		const hu_chimera_rec* cp = checkChimera ? chi.data() : nullptr;
 		const char* txt = nullptr;
 		const int64_t need = hu_batch_format_tsv_ptr(gb, pid.data(), pdesc.data(), annos.data(), cp, chimeraInfo, mainKind, &txt);
 		if(need < 0) return (int) need;
@@ -434,7 +485,8 @@ int main(int argc, char** argv) {
 			P.cv.notify_all();
 		}
 	});
-	long total = 0, placed = 0, flagged = 0;
+	long total = 0, placed = 0, flagged = 0, counted = 0;
+	std::map<int32_t, std::vector<long>> otuCount;      /* node -> reads of the one sample: the writer thread's, read after it has joined */
 	std::thread writer([&] {
 		long nextSeq = 0;
 		for(;;) {
@@ -446,7 +498,9 @@ int main(int argc, char** argv) {
 			  dn = std::move(P.done.begin()->second); P.done.erase(P.done.begin()); }
 			P.cv.notify_all();
 			auto tW = std::chrono::steady_clock::now();
-			out(dn.mainTxt);
+			if(!noTsv) out(dn.mainTxt);
+			for(int32_t u : dn.taxa) { std::vector<long>& c = otuCount[u]; if(c.empty()) c.assign(1, 0); c[0]++; }
+			counted += (long) dn.taxa.size();
 			if(alnOut.on) alnOut.write(dn.alnTxt);
 			if(chiOut.on) chiOut.write(dn.chiTxt);
 			usWrite += usSince(tW);
@@ -486,6 +540,31 @@ int main(int argc, char** argv) {
 	writer.join();
 	for(size_t w = 0; w < wgb.size(); ++w) { if(wwb[w]) hu_batch_destroy(wwb[w]); hu_batch_destroy(wgb[w]); }
 	if(P.err != HU_OK) { std::cerr << "Error: " << P.msg << std::endl; return EXIT_FAILURE; }
+	if(wantSum) { /* the OTUs in node order, as hmmufotu-amd-sum and hmmufotu-amd-otu-cs keep and write them (hu_otu_write.h) */
+		const auto tS = std::chrono::steady_clock::now();
+		const std::string prefix = useDb ? pos[0] + "_" : "";
+		std::vector<long> nRead, nSample;
+		const std::vector<int32_t> kept = hu_otu_kept(otuCount, otuMinRead, 0, &nRead, &nSample);
+		if(otuOut.is_open()) {
+			hu_otu_write_table(otuOut, argv[0], std::vector<std::string>(1, sampleName), otuCount, kept, prefix, [&](int32_t u) { return annos[u] ? annos[u] : ""; });
+			otuOut.flush();
+			if(!otuOut) { std::cerr << "Error: writing '" << otuFn << "' failed" << std::endl; return EXIT_FAILURE; }
+		}
+		if(otuCsOut.is_open()) {
+			/* every replica counted on its own device: the others' counts of the kept OTUs join those of replica 0, integers in any order */
+			std::vector<uint32_t> freq((size_t) 4 * L), gap((size_t) L);
+			for(size_t g = 1; g < otuCs.size(); ++g) for(int32_t u : kept) {
+				CHK(hu_otucs_counts(otuCs[g], u, freq.data(), gap.data()));
+				if((uint64_t) freq[0] + freq[(size_t) L] + freq[(size_t) 2 * L] + freq[(size_t) 3 * L] + gap[0] == 0) continue;      /* no row of this OTU on replica g */
+				CHK(hu_otucs_add_counts(otuCs[0], u, freq.data(), gap.data()));
+			}
+			if(!hu_otucs_write_fasta(otuCsOut, otuCs[0], db, pos[0], prefix, kept, nRead, nSample, otuEffN, otuNoGap)) { std::cerr << "Error: " << hu_last_error() << std::endl; return EXIT_FAILURE; }
+			if(!otuCsOut) { std::cerr << "Error: writing '" << otuCsFn << "' failed" << std::endl; return EXIT_FAILURE; }
+		}
+		usSum += usSince(tS);
+		if(verbose) std::cerr << "summary: " << usSum / 1e6 << " busy seconds (summed over " << nWorkers << " workers, and the writing of the table), " << counted << " reads counted in " << kept.size() << " OTUs" << std::endl;
+	}
+	for(hu_otucs* h : otuCs) hu_otucs_free(h);
 	if(verbose) {
 		const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - tLoop).count();
 		std::cerr << "read loop: " << total << (paired ? " pairs" : " reads") << " in " << sec << " s = " << (sec > 0 ? total / sec : 0) << " per second (parse + seed lookup + engine + TSV, "

@@ -13,6 +13,7 @@
 #include <iostream>
 #include <map>
 #include "hu_tsv_reader.h"
+#include "hu_otu_write.h"
 #include "../../include/hmmufotu_amd.h"
 
 static void usage(const char* p) {
@@ -121,36 +122,10 @@ int main(int argc, char** argv) {
 	}
 	if(!flush()) return fail(std::string("Error: ") + hu_last_error());
 	/* the OTUs of the table, in node order (src/hmmufotu-sum.cpp:405-419), and their records (:437-457) */
-	std::vector<int32_t> kept; std::vector<long> nRead, nSample;
-	for(auto& kv : count) {
-		long tot = 0, ns = 0;
-		for(long c : kv.second) { tot += c; ns += c > 0; }
-		if(tot >= minRead && ns >= minSample) { kept.push_back(kv.first); nRead.push_back(tot); nSample.push_back(ns); }
-	}
+	std::vector<long> nRead, nSample;
+	const std::vector<int32_t> kept = hu_otu_kept(count, minRead, minSample, &nRead, &nSample);
 	if(verbose) std::cerr << "Writing OTU Consensus Sequences" << std::endl;
-	const size_t piece = 1024;
-	std::vector<char> seqs; std::vector<char> desc;
-	for(size_t o0 = 0; o0 < kept.size(); o0 += piece) {
-		const size_t m = std::min(piece, kept.size() - o0);
-		seqs.resize(m * (size_t) L);
-		if(hu_otucs_infer(cs, (int32_t) m, kept.data() + o0, effN, seqs.data()) != HU_OK) return fail(std::string("Error: ") + hu_last_error());
-		for(size_t k = 0; k < m; ++k) {
-			const int32_t u = kept[o0 + k];
-			double annoDist = 0;
-			hu_db_get_anno_dist(db, u, &annoDist);
-			const char* anno = hu_db_get_annotation(db, u);
-			const int64_t need = hu_otucs_description(dbName.c_str(), anno, annoDist, nRead[o0 + k], nSample[o0 + k], nullptr, 0);
-			if(need < 0) return fail(std::string("Error: ") + hu_last_error());
-			desc.resize((size_t) need + 1);
-			hu_otucs_description(dbName.c_str(), anno, annoDist, nRead[o0 + k], nSample[o0 + k], desc.data(), (int64_t) desc.size());
-			std::string seq(seqs.data() + k * (size_t) L, (size_t) L);
-			if(noGap) seq.erase(std::remove(seq.begin(), seq.end(), '-'), seq.end());     /* PrimarySeq::removeGaps: the consensus holds no other gap symbol */
-			/* SeqIO::writeFastaSeq (src/SeqIO.cpp:121-132), DEFAULT_MAX_LINE = 60 */
-			csOut << '>' << prefix << u << ' ' << desc.data() << '\n';
-			for(size_t i = 0; i < seq.size(); i += 60) { csOut.write(seq.data() + i, (std::streamsize) std::min<size_t>(60, seq.size() - i)); csOut.put('\n'); }
-		}
-	}
-	csOut.flush();
+	if(!hu_otucs_write_fasta(csOut, cs, db, dbName, prefix, kept, nRead, nSample, effN, noGap)) return fail(std::string("Error: ") + hu_last_error());
 	if(verbose) std::cerr << kept.size() << " OTUs over " << S << " sample(s), " << nAccepted << " reads" << std::endl;
 	hu_otucs_free(cs);
 	hu_db_destroy(db);

@@ -14,7 +14,7 @@
 #include <map>
 #include <sstream>
 #include "hu_tsv_reader.h"
-#include "hu_num_format.h"
+#include "hu_otu_write.h"
 #include "hu_otu_tree.h"
 #include "../../include/hmmufotu_amd.h"
 
@@ -117,24 +117,13 @@ int main(int argc, char** argv) {
 			}
 		}
 	}
-	/* the table, OTUs in node order (src/hmmufotu-sum.cpp:405-425; OTUTable::saveTable src/OTUTable.cpp:154-164) */
-	otuOut << "# HmmUFOtu v1.5.1 OTU table generated by " << argv[0] << std::endl;       /* writeProgInfo(out, " OTU table generated by " + argv[0]) */
-	otuOut << "otuID";
-	for(const std::string& nm : sampleNames) otuOut << "\t" << nm;
-	otuOut << "\ttaxonomy" << std::endl;
-	std::vector<int32_t> kept;
-	for(auto& kv : count) {
-		long tot = 0, ns = 0;
-		for(long c : kv.second) { tot += c; ns += c > 0; }
-		if(tot >= minRead && ns >= minSample) kept.push_back(kv.first);
-	}
-	for(int32_t u : kept) {
+	/* the table, OTUs in node order (hu_otu_write.h) */
+	const std::vector<int32_t> kept = hu_otu_kept(count, minRead, minSample);
+	hu_otu_write_table(otuOut, argv[0], sampleNames, count, kept, prefix, [&](int32_t u) {
 		const char* anno = "";
 		hu_tree_info_node(ti, u, nullptr, nullptr, nullptr, nullptr, nullptr, &anno);
-		otuOut << prefix << u;
-		for(long c : count[u]) otuOut << "\t" << hu_num((double) c);
-		otuOut << "\t" << anno << std::endl;                             /* PTUNode::getTaxon(maxDist = inf) == the annotation */
-	}
+		return anno;
+	});
 	if(readOut.is_open()) { /* src/hmmufotu-sum.cpp:433-440; the info string starts without a blank there, too */
 		readOut << "# HmmUFOtu v1.5.1" << "OTU read info generated by " << argv[0] << std::endl;
 		for(int32_t u : kept) { readOut << prefix << u << "\t"; const std::vector<std::string>& r = reads[u]; for(size_t i = 0; i < r.size(); ++i) readOut << (i ? " " : "") << r[i]; readOut << std::endl; }

@@ -30,6 +30,8 @@
 #include "hu_kern_anneal.h"
 #include "hu_kern_build.h"
 #include "hu_kern_otucs.h"
+#include "hu_kern_sum.h"
+#include "hu_sum_rule.h"
 #include "hu_kern_csfm.h"
 #include "hu_kern_sm.h"
 #include "hu_kern_sim.h"
@@ -1781,6 +1783,7 @@ struct hu_batch {
 	PinnedVec<hu_place_rec> best;      /* page-locked: a device-to-host copy into pageable memory makes the runtime wait (spinning) for the stream inside the call */
 	PinnedVec<int32_t> hMeta, hBail;   /* the same for the few words the host reads between stages */
 	PinnedVec<char> hRows;            /* alignment rows of the last format call */
+	DBuf<uint32_t> dSumBits; DBuf<unsigned char> dSumCls; DBuf<int4> dSumOut; PinnedVec<int4> hSumOut; bool sumReady = false;      /* hu_batch_get_summary: match-column bits, symbol classes (built on its first call), the counts per read */
 	std::vector<char> tsvBuf; std::vector<size_t> tsvOff, tsvLen; size_t tsvSize = 0;
 };
 
@@ -3444,7 +3447,7 @@ static int64_t format_tsv_impl(hu_batch* b, const char* const* ids, const char* 
 	std::vector<size_t>& off = b->tsvOff;
 	off.assign(n + 1, 0);
 	auto put_int = [](char* p, long v) -> char* { char t[24]; int k = 0; unsigned long u = v < 0 ? 0ul - (unsigned long) v : (unsigned long) v; do { t[k++] = (char)('0' + u % 10); u /= 10; } while(u); if(v < 0) *p++ = '-'; while(k) *p++ = t[--k]; return p; };
-	auto put_gd = [](char* p, double v) -> char* { return p + snprintf(p, 40, "%g", v); };   /* operator<<(ostream&, double) at default precision == printf("%g") */
+	auto put_gd = [](char* p, double v) -> char* { return p + hu_tsv::put_gd(p, v); };   /* operator<<(ostream&, double) at default precision == printf("%g") */
 	auto put_s = [](char* p, const char* s) -> char* { const size_t k = strlen(s); memcpy(p, s, k); return p + k; };
 	auto wanted = [&](size_t r) {
 		const HuAlnDev& a = b->hAlns[r];
@@ -3537,6 +3540,59 @@ extern "C" const char* hu_tsv_header_chimera(void) {
 	       "seg5_taxon_id\tseg3_taxon_id\tseg5_taxon_anno\tseg3_taxon_anno\tchimera_lod\t"
 	       "branch_id\tbranch_ratio\ttaxon_id\ttaxon_anno\tanno_dist\tloglik\tQ_placement\tQ_taxon";
 }
+
+/* ------------------------------------------------------------------------------ the summary of a batch */
+extern "C" int hu_batch_get_summary(hu_batch* b, const hu_chimera_rec* chi, hu_sum_rec* out) try {
+	if(!b || (b->n > 0 && !out)) { hu_set_error("hu_batch_get_summary: null argument"); return HU_ERR_ARG; }
+	if(b->state < ST_FINISHED || b->fromCodes) { hu_set_error("hu_batch_get_summary: batch is not finished"); return HU_ERR_STATE; }
+	const HuDbDev& d = b->db->dev;
+	const int L = d.csLen, n = b->n;
+	if(n == 0) return HU_OK;
+	HIPCHK(hipSetDevice(b->db->device));
+	int rc;
+	if(!b->sumReady) { /* once per batch object: the symbol classes from is_symbol's own string, the match columns from the resident profile */
+		const size_t nw = ((size_t) L + 31) / 32;
+		if((rc = b->dSumCls.ensure(256)) != HU_OK || (rc = b->dSumBits.ensure(nw)) != HU_OK) return rc;
+		unsigned char cls[256];
+		for(int c = 0; c < 256; ++c) cls[c] = hu_tsv::is_symbol((char) c) ? 1 : 0;
+		HIPCHK(hipMemcpyAsync(b->dSumCls.p, cls, 256, hipMemcpyHostToDevice, b->stream));
+		HIPCHK(hipMemsetAsync(b->dSumBits.p, 0, nw * sizeof(uint32_t), b->stream));
+		(void) hipGetLastError();
+		k_sum_colbits<<<(unsigned)((d.K + 255) / 256), 256, 0, b->stream>>>(d.p2cs, d.K, L, b->dSumBits.p);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hu_wait(b->stream));      /* cls is this call's */
+		b->sumReady = true;
+	}
+	if((rc = b->dSumOut.ensure((size_t) n)) != HU_OK) return rc;
+	b->hSumOut.resize((size_t) n);
+	(void) hipGetLastError();
+	k_sum_identity<<<(unsigned)((n + HU_SUM_WAVES - 1) / HU_SUM_WAVES), HU_SUM_THREADS, 0, b->stream>>>(b->dRows.p, L, b->dAlns.p, n, b->dSumCls.p, b->dSumBits.p, b->dSumOut.p);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(b->hSumOut.data(), b->dSumOut.p, (size_t) n * sizeof(int4), hipMemcpyDeviceToHost, b->stream));
+	HIPCHK(hu_wait(b->stream));
+	for(int r = 0; r < n; ++r) {
+		const HuAlnDev& a = b->hAlns[r];
+		const hu_place_rec& pl = b->best[r];
+		const bool flagged = chi && a.status == HU_READ_OK && chi[r].is_chimera;      /* `wanted` of the formatter, which = 0 */
+		hu_sum_rec& o = out[r];
+		o.in_main = !(a.status != HU_READ_OK || flagged);
+		o.taxon = pl.c_node >= 0 ? pl.a_node : -1;                                     /* the formatter prints -1 for a read without a placement */
+		o.q_taxon = pl.c_node >= 0 ? pl.q_taxon : NAN;
+		const int4 v = b->hSumOut[(size_t) r];
+		o.n_cols = v.x; o.n_sym = v.y; o.n_match = v.z; o.n_match_sym = v.w;
+	}
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_batch_get_summary"); }
+
+extern "C" int hu_sum_accept(const hu_sum_rec* recs, int n, double min_q, double min_aln, double min_hmm, uint8_t* accept) try {
+	if(n < 0 || (n > 0 && (!recs || !accept))) { hu_set_error("hu_sum_accept: bad argument"); return HU_ERR_ARG; }
+	hu_tsv::Accept f; f.minQ = min_q; f.minAln = min_aln; f.minHmm = min_hmm;
+	for(int i = 0; i < n; ++i) {
+		const hu_sum_rec& r = recs[i];
+		accept[i] = r.in_main && hu_tsv::accept_counts(f, r.taxon, hu_tsv::through_tsv(r.q_taxon), r.n_cols, r.n_sym, r.n_match, r.n_match_sym);
+	}
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_sum_accept"); }
 
 /* ------------------------------------------------------------------------------ results */
 extern "C" int hu_batch_get_alignments(hu_batch* b, hu_align_rec* recs, char* align, char* trace, int trace_stride) try {
@@ -3897,6 +3953,7 @@ struct hu_otucs {
 	PinnedVec<unsigned char> hStage;
 	DBuf<unsigned char> dStage; DBuf<HuOtucsRow> dRows; DBuf<int32_t> dOrder; DBuf<HuOtucsWork> dWork;
 	DBuf<int32_t> dNodes, dSlots; DBuf<char> dOut;
+	DBuf<int32_t> dSrc; DBuf<uint32_t> dAdd;      /* hu_otucs_add_batch: the batch row of each staged row; hu_otucs_add_counts: the counts to add */
 	~hu_otucs() { if(dTab) (void) hipFree(dTab); if(dCls) (void) hipFree(dCls); if(stream) (void) hipStreamDestroy(stream); }
 };
 
@@ -3938,30 +3995,11 @@ static int otucs_grow(hu_otucs* h, size_t nSlots) {
 	return HU_OK;
 }
 
-extern "C" int hu_otucs_add(hu_otucs* h, int64_t n_rows, const int32_t* node_of_row, const char* rows) try {
-	if(!h || n_rows < 0 || (n_rows > 0 && (!node_of_row || !rows))) { hu_set_error("hu_otucs_add: bad argument"); return HU_ERR_ARG; }
-	const HuDbDev& d = h->db->dev;
-	const int L = d.csLen;
-	const int64_t pitch16 = (L + 15) / 16;
-	if(n_rows * pitch16 > INT32_MAX) { hu_set_error("hu_otucs_add: %lld rows of %d columns are too many for one call", (long long) n_rows, L); return HU_ERR_ARG; }
-	for(int64_t i = 0; i < n_rows; ++i) if(node_of_row[i] < 0 || node_of_row[i] >= d.nNodes) {
-		hu_set_error("hu_otucs_add: row %lld names node %d, the database has %d", (long long) i, node_of_row[i], d.nNodes); return HU_ERR_ARG;
-	}
-	if(n_rows == 0) return HU_OK;
-	HIPCHK(hipSetDevice(h->db->device));
-	const size_t n = (size_t) n_rows;
-	/* the span of each row that holds anything but '-', widened to 16-byte bounds: only that crosses the bus (an amplicon read covers a
-	 * few hundred of the alignment's columns); k_otucs_count takes every column outside it as the gap it is */
-	std::vector<HuOtucsRow> meta(n);
-	parallel_for(n, [&](size_t i) {
-		const char* r = rows + i * (size_t) L;
-		int a = 0, e = L;
-		while(a < L && r[a] == '-') ++a;
-		while(e > a && r[e - 1] == '-') --e;
-		HuOtucsRow m{0, 0, 0, 0};
-		if(a < e) { m.c0 = a & ~15; m.c1 = std::min(L, (e + 15) & ~15); }
-		meta[i] = m;
-	});
+/* The device part of hu_otucs_add / hu_otucs_add_batch for n rows described by meta (off16 not yet set): slots at first sight, the rows in slot
+ * order, one work item per HU_OTUCS_CHUNK rows of an OTU, then k_otucs_count over the stage.  fill(stageBytes) queues on h->stream whatever brings
+ * the rows' spans into h->dStage (sized by then).  Returns after the stream has drained; a failed call leaves the handle as it was. */
+template<class Fill> static int otucs_count_rows(hu_otucs* h, size_t n, const int32_t* node_of_row, std::vector<HuOtucsRow>& meta, Fill fill) {
+	const int L = h->db->dev.csLen;
 	int64_t tot16 = 0;
 	for(size_t i = 0; i < n; ++i) { meta[i].off16 = (int32_t) tot16; tot16 += (meta[i].c1 - meta[i].c0 + 15) / 16; }
 	/* slots at first sight; the batch's rows in slot order (a counting sort: the permutation alone, the rows stay) */
@@ -3988,20 +4026,10 @@ extern "C" int hu_otucs_add(hu_otucs* h, int64_t n_rows, const int32_t* node_of_
 	for(int32_t s = 0; s < nSlots; ++s)
 		for(int32_t b = first[s]; b < first[s + 1]; b += HU_OTUCS_CHUNK) work.push_back(HuOtucsWork{s, b, std::min(first[s + 1], b + HU_OTUCS_CHUNK), 0});
 	const size_t stageBytes = (size_t) tot16 * 16;
-	if(h->hStage.size() < stageBytes) h->hStage.resize(stageBytes + stageBytes / 8);
-	unsigned char* hs = h->hStage.data();
-	parallel_for(n, [&](size_t i) {
-		const HuOtucsRow& m = meta[i];
-		const size_t len = (size_t)(m.c1 - m.c0), padded = (len + 15) / 16 * 16;
-		if(!len) return;
-		unsigned char* dst = hs + (size_t) m.off16 * 16;
-		memcpy(dst, rows + i * (size_t) L + m.c0, len);
-		if(padded > len) memset(dst + len, '-', padded - len);
-	});
 	if((rc = h->dStage.ensure(std::max<size_t>(stageBytes, 16))) != HU_OK || (rc = h->dRows.ensure(n)) != HU_OK ||
 	   (rc = h->dOrder.ensure(n)) != HU_OK || (rc = h->dWork.ensure(work.size())) != HU_OK) return rc;
-	if(stageBytes) HIPCHK(hipMemcpyAsync(h->dStage.p, hs, stageBytes, hipMemcpyHostToDevice, h->stream));
 	HIPCHK(hipMemcpyAsync(h->dRows.p, meta.data(), n * sizeof(HuOtucsRow), hipMemcpyHostToDevice, h->stream));
+	if((rc = fill(stageBytes)) != HU_OK) return rc;
 	HIPCHK(hipMemcpyAsync(h->dOrder.p, order.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
 	HIPCHK(hipMemcpyAsync(h->dWork.p, work.data(), work.size() * sizeof(HuOtucsWork), hipMemcpyHostToDevice, h->stream));
 	(void) hipGetLastError();
@@ -4012,7 +4040,106 @@ extern "C" int hu_otucs_add(hu_otucs* h, int64_t n_rows, const int32_t* node_of_
 	h->nSlots = nSlots;
 	done = true;
 	return HU_OK;
+}
+
+extern "C" int hu_otucs_add(hu_otucs* h, int64_t n_rows, const int32_t* node_of_row, const char* rows) try {
+	if(!h || n_rows < 0 || (n_rows > 0 && (!node_of_row || !rows))) { hu_set_error("hu_otucs_add: bad argument"); return HU_ERR_ARG; }
+	const HuDbDev& d = h->db->dev;
+	const int L = d.csLen;
+	const int64_t pitch16 = (L + 15) / 16;
+	if(n_rows * pitch16 > INT32_MAX) { hu_set_error("hu_otucs_add: %lld rows of %d columns are too many for one call", (long long) n_rows, L); return HU_ERR_ARG; }
+	for(int64_t i = 0; i < n_rows; ++i) if(node_of_row[i] < 0 || node_of_row[i] >= d.nNodes) {
+		hu_set_error("hu_otucs_add: row %lld names node %d, the database has %d", (long long) i, node_of_row[i], d.nNodes); return HU_ERR_ARG;
+	}
+	if(n_rows == 0) return HU_OK;
+	HIPCHK(hipSetDevice(h->db->device));
+	const size_t n = (size_t) n_rows;
+	/* the span of each row that holds anything but '-', widened to 16-byte bounds: only that crosses the bus (an amplicon read covers a
+	 * few hundred of the alignment's columns); k_otucs_count takes every column outside it as the gap it is */
+	std::vector<HuOtucsRow> meta(n);
+	parallel_for(n, [&](size_t i) {
+		const char* r = rows + i * (size_t) L;
+		int a = 0, e = L;
+		while(a < L && r[a] == '-') ++a;
+		while(e > a && r[e - 1] == '-') --e;
+		HuOtucsRow m{0, 0, 0, 0};
+		if(a < e) { m.c0 = a & ~15; m.c1 = std::min(L, (e + 15) & ~15); }
+		meta[i] = m;
+	});
+	return otucs_count_rows(h, n, node_of_row, meta, [&](size_t stageBytes) -> int {
+		if(h->hStage.size() < stageBytes) h->hStage.resize(stageBytes + stageBytes / 8);
+		unsigned char* hs = h->hStage.data();
+		parallel_for(n, [&](size_t i) {
+			const HuOtucsRow& m = meta[i];
+			const size_t len = (size_t)(m.c1 - m.c0), padded = (len + 15) / 16 * 16;
+			if(!len) return;
+			unsigned char* dst = hs + (size_t) m.off16 * 16;
+			memcpy(dst, rows + i * (size_t) L + m.c0, len);
+			if(padded > len) memset(dst + len, '-', padded - len);
+		});
+		if(stageBytes) HIPCHK(hipMemcpyAsync(h->dStage.p, hs, stageBytes, hipMemcpyHostToDevice, h->stream));
+		return HU_OK;
+	});
 } catch(...) { return hu_catch_all("hu_otucs_add"); }
+
+/* hu_otucs_add for the accepted reads of a finished batch, the rows read where they lie.  Outside the columns
+ * [csStart - 1 - len, csEnd + len) a row holds nothing but the '.' it was filled with: k_align_rows writes its region, at most alnFrom - 1 < len
+ * bases of the read right before it and at most len - alnTo after it, and k_merge_rows only takes over what the mate's row holds, which obeys the
+ * same bound with the mate's length (len below: the longer of the two).  '.' counts as the gap that a column outside the span counts as. */
+extern "C" int hu_otucs_add_batch(hu_otucs* h, hu_batch* b, const uint8_t* accept) try {
+	if(!h || !b || (b->n > 0 && !accept)) { hu_set_error("hu_otucs_add_batch: null argument"); return HU_ERR_ARG; }
+	if(b->db != h->db) { hu_set_error("hu_otucs_add_batch: the batch belongs to another database than the handle"); return HU_ERR_ARG; }
+	if(b->state < ST_FINISHED || b->fromCodes) { hu_set_error("hu_otucs_add_batch: batch is not finished"); return HU_ERR_STATE; }
+	const HuDbDev& d = h->db->dev;
+	const int L = d.csLen;
+	std::vector<int32_t> src, nodes; std::vector<HuOtucsRow> meta;
+	for(int r = 0; r < b->n; ++r) {
+		if(!accept[r]) continue;
+		const HuAlnDev& a = b->hAlns[r];
+		const hu_place_rec& pl = b->best[r];
+		if(a.status != HU_READ_OK || a.csStart < 1 || a.csEnd < a.csStart || a.csEnd > L) { hu_set_error("hu_otucs_add_batch: read %d is accepted and has no alignment", r); return HU_ERR_ARG; }
+		if(pl.c_node < 0 || pl.a_node < 0 || pl.a_node >= d.nNodes) { hu_set_error("hu_otucs_add_batch: read %d is accepted and has no taxon", r); return HU_ERR_ARG; }
+		const int len = std::max(b->hDescs[r].len, b->paired ? b->hDescs[b->n + r].len : 0);
+		const int lo = std::max(0, a.csStart - 1 - len), hi = (int) std::min<int64_t>(L, (int64_t) a.csEnd + len);
+		src.push_back(r); nodes.push_back(pl.a_node);
+		meta.push_back(HuOtucsRow{0, lo & ~15, std::min(L, (hi + 15) & ~15), 0});
+	}
+	const size_t n = src.size();
+	if(n * (size_t)((L + 15) / 16) > (size_t) INT32_MAX) { hu_set_error("hu_otucs_add_batch: %zu rows of %d columns are too many for one call", n, L); return HU_ERR_ARG; }
+	HIPCHK(hipSetDevice(h->db->device));
+	HIPCHK(hu_wait(b->stream));       /* everything the batch queued has written its rows */
+	if(n == 0) return HU_OK;
+	return otucs_count_rows(h, n, nodes.data(), meta, [&](size_t) -> int {
+		int rc = h->dSrc.ensure(n);
+		if(rc != HU_OK) return rc;
+		HIPCHK(hipMemcpyAsync(h->dSrc.p, src.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+		(void) hipGetLastError();
+		k_otucs_stage<<<(unsigned)((n + HU_SUM_WAVES - 1) / HU_SUM_WAVES), HU_SUM_THREADS, 0, h->stream>>>(b->dRows.p, L, h->dSrc.p, h->dRows.p, (int) n, h->dStage.p);
+		HIPCHK(hipGetLastError());
+		return HU_OK;
+	});
+} catch(...) { return hu_catch_all("hu_otucs_add_batch"); }
+
+extern "C" int hu_otucs_add_counts(hu_otucs* h, int32_t node, const uint32_t* freq, const uint32_t* gap) try {
+	if(!h || !freq || !gap) { hu_set_error("hu_otucs_add_counts: null argument"); return HU_ERR_ARG; }
+	const int L = h->db->dev.csLen;
+	if(node < 0 || node >= h->db->dev.nNodes) { hu_set_error("hu_otucs_add_counts: node %d, the database has %d", node, h->db->dev.nNodes); return HU_ERR_ARG; }
+	HIPCHK(hipSetDevice(h->db->device));
+	int rc;
+	if((rc = h->dAdd.ensure((size_t) 5 * L)) != HU_OK) return rc;
+	int32_t& s = h->slotOfNode[node];
+	const bool fresh = s < 0;
+	if(fresh && (rc = otucs_grow(h, (size_t) h->nSlots + 1)) != HU_OK) return rc;
+	HIPCHK(hipMemcpyAsync(h->dAdd.p, freq, (size_t) 4 * L * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemcpyAsync(h->dAdd.p + (size_t) 4 * L, gap, (size_t) L * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+	(void) hipGetLastError();
+	const int32_t slot = fresh ? h->nSlots : s;
+	k_otucs_add_tab<<<(unsigned)((5 * L + 255) / 256), 256, 0, h->stream>>>(h->dTab + (size_t) slot * 5 * L, h->dAdd.p, 5 * L);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hu_wait(h->stream));
+	if(fresh) { s = slot; h->nSlots++; }
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_otucs_add_counts"); }
 
 extern "C" int hu_otucs_counts(hu_otucs* h, int32_t node, uint32_t* freq, uint32_t* gap) try {
 	if(!h || !freq || !gap) { hu_set_error("hu_otucs_counts: null argument"); return HU_ERR_ARG; }

@@ -10,6 +10,7 @@
 #include <map>
 #include <string>
 #include <vector>
+#include "hu_sum_rule.h"
 
 namespace hu_tsv {
 
@@ -72,19 +73,16 @@ struct Scanner {
 	const std::string& get(const char* name) const { static const std::string none; auto it = col.find(name); return it == col.end() || it->second >= f.size() ? none : f[it->second]; }
 };
 
-/* DegenAlphabet::isSymbol (src/DegenAlphabet.h:89-91: sym_map[c] >= 0) over IUPACNucl (src/IUPACNucl.cpp:33-50): the four bases and the
- * degenerate codes, which map to their first expansion — upper case only (inserts are lower case in an alignment and do not count):
- * what alignIdentity / hmmIdentity count (src/HmmUFOtu_main.cpp:218-239) */
-inline bool is_symbol(char c) { return c != '\0' && strchr("ACGTUMRWSYKVHDBN", c) != nullptr; }
+/* is_symbol, identity, Accept and the rule on the counts: hu_sum_rule.h */
 inline double align_identity(const std::string& aln, int start, int end) {
 	int id = 0;
 	for(int i = start; i <= end && i < (int) aln.size(); ++i) id += is_symbol(aln[i]);
-	return (double) id / (end - start + 1);
+	return identity(id, end - start + 1);
 }
 inline double hmm_identity(const std::vector<int32_t>& cs2p, const std::string& aln, int start, int end) {
 	int id = 0, n = 0;
 	for(int i = start; i <= end && i < (int) aln.size(); ++i) if(i + 1 < (int) cs2p.size() && cs2p[i + 1] != 0) { ++n; id += is_symbol(aln[i]); }
-	return (double) id / n;
+	return identity(id, n);
 }
 /* profile2CSIdx of a .hmm -> cs2ProfileIdx [L + 1] (src/BandedHMMP7.h getProfileLoc) */
 inline std::vector<int32_t> cs_to_profile(int K, int L, const std::vector<int32_t>& p2cs) {
@@ -110,15 +108,20 @@ inline bool read_sample_list(const std::string& listFn, std::vector<std::string>
 }
 
 /* "a valid assignment" of the record the scanner stands on (src/hmmufotu-sum.cpp:374-382): taxon_id >= 0, Q_taxon >= minQ and the two
- * identity filters (0: off); taxon receives atol(taxon_id) */
-struct Accept { double minQ = 0, minAln = 0, minHmm = 0; };
+ * identity filters (0: off); taxon receives atol(taxon_id).  The integers are counted here from the alignment string (only where a filter
+ * asks for them, as the reference evaluates them); the decision on them is accept_counts (hu_sum_rule.h), which a run that summarises
+ * its own batches shares */
 inline bool accepted(const Scanner& sc, const Accept& f, const std::vector<int32_t>& cs2p, long& taxon) {
 	const int csStart = atoi(sc.get("CS_start").c_str()), csEnd = atoi(sc.get("CS_end").c_str());
 	const std::string& aln = sc.get("alignment");
 	taxon = atol(sc.get("taxon_id").c_str());
 	const double qTaxon = atof(sc.get("Q_taxon").c_str());
-	return taxon >= 0 && qTaxon >= f.minQ && (f.minAln == 0 || align_identity(aln, csStart - 1, csEnd - 1) >= f.minAln)
-		&& (f.minHmm == 0 || hmm_identity(cs2p, aln, csStart - 1, csEnd - 1) >= f.minHmm);
+	if(!(taxon >= 0 && qTaxon >= f.minQ)) return false;
+	int nSym = 0, nMatch = 0, nMatchSym = 0;
+	const int start = csStart - 1, end = csEnd - 1;
+	if(f.minAln != 0) for(int i = start; i <= end && i < (int) aln.size(); ++i) nSym += is_symbol(aln[i]);                       /* align_identity */
+	if(f.minHmm != 0) for(int i = start; i <= end && i < (int) aln.size(); ++i) if(i + 1 < (int) cs2p.size() && cs2p[i + 1] != 0) { ++nMatch; nMatchSym += is_symbol(aln[i]); }      /* hmm_identity */
+	return accept_counts(f, taxon, qTaxon, end - start + 1, nSym, nMatch, nMatchSym);
 }
 
 } // namespace hu_tsv

@@ -1319,6 +1319,20 @@ class Database:
             pass
 
 
+SUM_DTYPE = np.dtype([("in_main", "i4"), ("taxon", "i4"), ("q_taxon", "f8"), ("n_cols", "i4"), ("n_sym", "i4"), ("n_match", "i4"),
+                      ("n_match_sym", "i4")])
+
+
+def sum_accept(recs, min_q=0.0, min_aln=0.0, min_hmm=0.0) -> np.ndarray:
+    """hu_sum_accept (host only): which records of Batch.summary() hmmufotu-amd-sum would accept from the reads' assignment lines: in the main
+    output, a taxon, Q_taxon (through its six printed digits) >= min_q, and the two identities (a threshold of 0 is off; 0 / 0 rejects)"""
+    recs = np.ascontiguousarray(recs, SUM_DTYPE)
+    out = np.zeros(len(recs), np.uint8)
+    _chk(load_library().hu_sum_accept(recs.ctypes.data_as(C.c_void_p), C.c_int(len(recs)), C.c_double(min_q), C.c_double(min_aln), C.c_double(min_hmm),
+                                      _p(out, C.c_uint8)))
+    return out
+
+
 def otucs_description(db_name: str, taxonomy: str, anno_dist: float, read_count: int, sample_hits: int) -> str:
     """hu_otucs_description (host only): the description of an OTU's FASTA record as hmmufotu-sum -c writes it"""
     lib = load_library()
@@ -1359,6 +1373,22 @@ class OtuConsensus:
             raise EngineError("otu_consensus.add: %d nodes for %d rows" % (len(nodes), a.shape[0]))
         _chk(load_library().hu_otucs_add(self.h, C.c_int64(len(nodes)), _p(nodes, C.c_int32), a.ctypes.data_as(C.c_char_p)))
 
+    def add_batch(self, batch: "Batch", accept):
+        """hu_otucs_add_batch: the reads of a finished batch with accept[i] != 0, each under the taxon of its best placement; the rows are
+        read where they lie on the device"""
+        acc = np.ascontiguousarray(accept, np.uint8).ravel()
+        if len(acc) != batch.n:
+            raise EngineError("otu_consensus.add_batch: %d flags for %d reads" % (len(acc), batch.n))
+        _chk(load_library().hu_otucs_add_batch(self.h, batch.h, _p(acc, C.c_uint8)))
+
+    def add_counts(self, node: int, freq, gap):
+        """hu_otucs_add_counts: freq [4][cs_len] and gap [cs_len] added to the counts of one OTU (the inverse of counts())"""
+        L = self.db.cs_len
+        freq = np.ascontiguousarray(freq, np.uint32); gap = np.ascontiguousarray(gap, np.uint32)
+        if freq.shape != (4, L) or gap.shape != (L,):
+            raise EngineError("otu_consensus.add_counts: freq must be [4][%d] and gap [%d]" % (L, L))
+        _chk(load_library().hu_otucs_add_counts(self.h, C.c_int32(node), _p(freq, C.c_uint32), _p(gap, C.c_uint32)))
+
     def counts(self, node: int):
         """(freq [4][cs_len], gap [cs_len]) of one OTU, uint32"""
         L = self.db.cs_len
@@ -1384,6 +1414,9 @@ class OtuConsensus:
             self.close()
         except Exception:
             pass
+
+
+OtuCs = OtuConsensus
 
 
 class Window(C.Structure):
@@ -1674,6 +1707,17 @@ class Batch:
         co = ChimeraOpts(num_seg, 0, opts.max_error / num_seg if max_chimera_error is None else max_chimera_error, min_chimera_lod)
         out = np.zeros(self.n, CHIMERA_DTYPE)
         _chk(load_library().hu_chimera_batch(self.h, work.h, C.byref(opts), C.byref(co), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def summary(self, chimera=None) -> np.ndarray:
+        """hu_batch_get_summary of a finished batch: per read whether its line stands in the main output, its taxon and Q_taxon, and the
+        integers behind the two identities, counted on the device (records of SUM_DTYPE).  chimera: the records of check_chimera, or None"""
+        cp = None
+        if chimera is not None:
+            chimera = np.ascontiguousarray(chimera, CHIMERA_DTYPE); assert len(chimera) == self.n
+            cp = chimera.ctypes.data_as(C.c_void_p)
+        out = np.zeros(self.n, SUM_DTYPE)
+        _chk(load_library().hu_batch_get_summary(self.h, cp, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def format_tsv(self, ids, descs=None, annos=None) -> str:

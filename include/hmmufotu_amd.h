@@ -643,6 +643,38 @@ int64_t hu_otucs_description(const char* db_name, const char* taxonomy, double a
 /* the annotation distance of a node (PTUNode::getAnnoDist), beside hu_db_get_annotation */
 int hu_db_get_anno_dist(const hu_db* db, int32_t node, double* out);
 
+/* ---- the summary of a run from its own batches (hmmufotu-amd --otu-table / --otu-cs) ----------------
+ * What hmmufotu-amd-sum and hmmufotu-amd-otu-cs would read back from the batch's assignment lines, without the lines.
+ * hu_batch_get_summary, for a finished batch of reads (hu_finish_batch done; HU_ERR_STATE otherwise): per read
+ *   in_main       1 when the read's line stands in the main assignment output (hu_batch_format_tsv_chimera, which = 0, with the same chi:
+ *                 HU_READ_OK and not flagged as a chimera), else 0
+ *   taxon         the line's taxon_id column: a_node of the best placement, -1 when the read has none
+ *   q_taxon       Q_taxon of the best placement as the engine holds it (NaN when the read has none)
+ *   n_cols        CS_end - CS_start + 1
+ *   n_sym         bytes of the columns CS_start - 1 .. CS_end - 1 of the read's alignment row that are symbols (upper-case IUPAC codes)
+ *   n_match       those of the columns that are match columns of the profile
+ *   n_match_sym   the bytes that are both
+ * The four integers are counted on the device, where the rows are (no row crosses to the host), and are 0 for a read that is not
+ * HU_READ_OK.  chi [n] from hu_chimera_batch, or NULL. */
+typedef struct {
+	int32_t in_main, taxon;
+	double q_taxon;
+	int32_t n_cols, n_sym, n_match, n_match_sym;
+} hu_sum_rec;
+int hu_batch_get_summary(hu_batch* b, const hu_chimera_rec* chi, hu_sum_rec* out /* [n] */);
+/* host only: accept[i] = 1 when record i is "a valid assignment" for hmmufotu-amd-sum reading the read's line (hu_tsv::accepted), else 0:
+ * in_main, taxon >= 0, Q_taxon >= min_q where Q_taxon is q_taxon through the line's six significant digits and back, and, each unless
+ * its threshold is 0, n_sym / n_cols >= min_aln and n_match_sym / n_match >= min_hmm (0 / 0 rejects). */
+int hu_sum_accept(const hu_sum_rec* recs, int n, double min_q, double min_aln, double min_hmm, uint8_t* accept /* [n] */);
+/* hu_otucs_add for the reads i of a finished batch with accept[i] != 0, each under the taxon of its best placement; the rows are read
+ * where they lie on the device.  The call waits for the batch's stream first and returns when the batch may be reused.  HU_ERR_STATE: the
+ * batch is not finished; HU_ERR_ARG: the batch is of another database than the handle, or an accepted read has no alignment or no
+ * taxon.  A failed call changes nothing. */
+int hu_otucs_add_batch(hu_otucs* h, hu_batch* b, const uint8_t* accept /* [n] */);
+/* the inverse of hu_otucs_counts: freq [4][cs_len] and gap [cs_len] are added to the counts of the OTU `node` (merging the handles of
+ * several replicas).  HU_ERR_ARG for a node outside [0, n_nodes). */
+int hu_otucs_add_counts(hu_otucs* h, int32_t node, const uint32_t* freq, const uint32_t* gap);
+
 /* ---- the seed index file <DB>.csfm (hmmufotu-build's csfm.build(msa) + csfm.save) -------------------------------
  * hu_suffix_array: what divsufsort(concatSeq, SA, N) returns in CSFMIndex::buildBWT (src/CSFMIndex.cpp:327-335), built on the device by
  * prefix doubling over a radix sort.  text: n bytes of 0 (separator, terminator) and 1..4 (bases), 1 <= n < 2^31; sa [n]: the start
