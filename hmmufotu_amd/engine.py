@@ -801,6 +801,83 @@ def otu_subset_timing() -> dict:
     return dict(to_device=s[0], kernels=s[1], to_host=s[2])
 
 
+class UnifracOpts(C.Structure):
+    _fields_ = [("method", C.c_int32), ("host", C.c_int32), ("alpha", C.c_double), ("slab", C.c_int64), ("mem_budget", C.c_int64)]
+
+
+class UnifracTree(C.Structure):
+    _fields_ = [("n_nodes", C.c_int32), ("parent", C.POINTER(C.c_int32)), ("blen", C.POINTER(C.c_double))]
+
+
+UNIFRAC_METHODS = {"unweighted": 0, "weighted": 1, "weighted-raw": 2, "generalized": 3, "bray-curtis": 4, "jaccard": 5}
+
+
+def unifrac_default_slab(n_sample: int, n_branch: int) -> int:
+    """hu_unifrac_default_slab: the branches per slab that a table of n_sample samples and n_branch kept branches gets"""
+    lib = load_library()
+    lib.hu_unifrac_default_slab.restype = C.c_int64
+    return int(lib.hu_unifrac_default_slab(C.c_int64(int(n_sample)), C.c_int64(int(n_branch))))
+
+
+def _unifrac_args(what, counts, otu_node, parent, blen, method, alpha, slab, host, mem_budget):
+    c = np.ascontiguousarray(counts, np.float64)
+    if c.ndim != 2:
+        raise EngineError(what + ": counts [otus][samples]")
+    if method not in UNIFRAC_METHODS:
+        raise EngineError(what + ": method one of %s, not %r" % (", ".join(UNIFRAC_METHODS), method))
+    o = UnifracOpts()
+    load_library().hu_unifrac_default_opts(C.byref(o))
+    o.method = UNIFRAC_METHODS[method]; o.host = 1 if host else 0; o.slab = int(slab or 0); o.mem_budget = int(mem_budget or 0)
+    if alpha is not None:
+        o.alpha = float(alpha)
+    keep = [c]
+    tree = None; node = None
+    if parent is not None:
+        par = np.ascontiguousarray(parent, np.int32); bl = np.ascontiguousarray(blen, np.float64)
+        if par.ndim != 1 or bl.shape != par.shape:
+            raise EngineError(what + ": parent and blen [nodes]")
+        if otu_node is None or len(otu_node) != c.shape[0]:
+            raise EngineError(what + ": one node per OTU row")
+        nd = np.ascontiguousarray(otu_node, np.int32)
+        tree = UnifracTree(len(par), _p(par, C.c_int32), _p(bl, C.c_double)); node = _p(nd, C.c_int32)
+        keep += [par, bl, nd]
+    return c, o, tree, node, keep
+
+
+def unifrac(counts, otu_node=None, parent=None, blen=None, method="weighted", alpha=None, slab=0, device=0, host=False, pd=False, mem_budget=0):
+    """hu_unifrac: the distances [samples][samples] between the columns of counts [otus][samples] on the tree (parent [nodes] with -1 for
+    the root, blen [nodes]); otu_node [otus] is the node of every row.  "bray-curtis" and "jaccard" take no tree.  slab 0: the documented
+    function of the table's size.  host: the library's host path, no device needed.  pd: also Faith's PD, returned as (dist, pd)."""
+    c, o, tree, node, keep = _unifrac_args("unifrac", counts, otu_node, parent, blen, method, alpha, slab, host, mem_budget)
+    S = c.shape[1]
+    dist = np.zeros((S, S)); fpd = np.zeros(S)
+    _chk(load_library().hu_unifrac(C.c_int(int(device)), C.byref(tree) if tree is not None else None, C.c_int64(c.shape[0]), C.c_int64(S), node, _p(c, C.c_double),
+                                   C.byref(o), _p(dist, C.c_double), _p(fpd, C.c_double) if pd else None))
+    return (dist, fpd) if pd else dist
+
+
+def unifrac_embed(counts, otu_node=None, parent=None, blen=None, method="weighted", device=0, host=False, mem_budget=0) -> dict:
+    """hu_unifrac_embed: the kept branches (in depth-first order) as dict(node [B], blen [B], P [B][samples]): P[k][j] is the share of
+    sample j's reads that lie below branch k"""
+    c, o, tree, node, keep = _unifrac_args("unifrac_embed", counts, otu_node, parent, blen, method, None, 0, host, mem_budget)
+    lib = load_library()
+    nb = C.c_int64(0)
+    args = (C.c_int(int(device)), C.byref(tree) if tree is not None else None, C.c_int64(c.shape[0]), C.c_int64(c.shape[1]), node, _p(c, C.c_double), C.byref(o), C.byref(nb))
+    _chk(lib.hu_unifrac_embed(*args, C.c_int64(0), None, None, None))
+    B = int(nb.value)
+    bn = np.zeros(B, np.int32); bl = np.zeros(B); P = np.zeros((B, c.shape[1]))
+    if B:
+        _chk(lib.hu_unifrac_embed(*args, C.c_int64(B), _p(bn, C.c_int32), _p(bl, C.c_double), _p(P, C.c_double)))
+    return dict(node=bn, blen=bl, P=P)
+
+
+def unifrac_timing() -> dict:
+    """hu_unifrac_timing: the phases of this thread's last unifrac / unifrac_embed on a device, in seconds"""
+    s = np.zeros(4)
+    _chk(load_library().hu_unifrac_timing(_p(s, C.c_double)))
+    return dict(to_device=s[0], embed=s[1], pairs=s[2], to_host=s[3])
+
+
 def tree_count_mutations(parent, cs_len: int, up_ptr: int, device=0) -> np.ndarray:
     """hu_tree_count_mutations: per column, the non-root nodes whose inferred state differs from their parent's, from the DEVICE
     fixed-rate up buffer at up_ptr ([n][cs_len][4] float64, as tree_evaluate leaves it with win_len 0)"""

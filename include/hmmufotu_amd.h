@@ -1006,6 +1006,64 @@ int hu_otu_subset(int device, int64_t n_otu, int64_t n_sample, const double* cou
 		double* out);
 int hu_otu_subset_timing(double* seconds /* [3] */);
 
+/* ---- hmmufotu-amd-unifrac: the distances between the samples of an OTU table on the database's tree ----
+ * The tree is the .ptu's, rooted at its stored root.  Branch v is the edge from node v to its parent, of length b_v (hu_tree_info_node's
+ * blen); the root has none.  HmmUFOtu places reads on inner nodes as well as on leaves: a read of OTU u lies below every branch on the
+ * path from u to the root, u's own branch included (what zero-length pseudo-leaves would give).  An OTU that is the root lies below no
+ * branch but counts in its sample's total.  With c_uj the table's cell and T_j the column sum,
+ *     p_vj = (sum of c_uj over the OTUs u in the subtree of v) / T_j,
+ * and every sum below runs over the branches with p_vi + p_vj > 0:
+ *   HU_UF_UNWEIGHTED    sum b_v |[p_vi > 0] - [p_vj > 0]| / sum b_v max([p_vi > 0], [p_vj > 0])
+ *   HU_UF_WEIGHTED      sum b_v |p_vi - p_vj| / sum b_v (p_vi + p_vj)
+ *   HU_UF_WEIGHTED_RAW  sum b_v |p_vi - p_vj|
+ *   HU_UF_GENERALIZED   sum b_v s^alpha |p_vi - p_vj| / s / sum b_v s^alpha, s = p_vi + p_vj, 0 <= alpha <= 1
+ *   HU_UF_BRAY_CURTIS, HU_UF_JACCARD: WEIGHTED and UNWEIGHTED on the identity tree, where every OTU row is its own branch of length 1;
+ *                       tree must be NULL, otu_node is not read.
+ * A denominator of 0 (both samples on the root alone) gives 0; d(i,i) is exactly 0; d(j,i) is the stored copy of d(i,j).  pd (may be
+ * NULL) [n_sample]: Faith's PD, sum b_v [p_vj > 0].
+ * hu_unifrac: counts [n_otu][n_sample] row-major, otu_node [n_otu] the node of every row (two rows may name one node), dist
+ * [n_sample][n_sample].  Only the branches on a path from some row's node to the root are kept, B of them, numbered in depth-first
+ * order (children in ascending node number); the device fills P [B][n_sample] from one column scan of the rows in that order and one
+ * gather (integer counts below 2^53 come out exact), then k_unifrac_pairs (hu_kern_unifrac.h) adds the terms: branches in ascending
+ * order within slabs of `slab` consecutive branches, the slabs then in ascending order.  The order is a function of the table, the tree
+ * and the slab alone, so a result does not depend on the run, the grid or the device, and the host path (opts->host) gives the same
+ * bits for every method but HU_UF_GENERALIZED with 0 < alpha < 1, where the two pow / sqrt differ.
+ * slab 0: hu_unifrac_default_slab(n_sample, B) = B when the nt (nt + 1) / 2 tiles, nt = ceil(n_sample / 64), number 1024 or more;
+ * otherwise max(256, 32 ceil(ceil(B / ceil(1024 / tiles)) / 32)).
+ * HU_ERR_ARG with the reason, before a device is asked for: n_sample < 1, an unknown method, alpha outside [0, 1] or given (not 0.5)
+ * without HU_UF_GENERALIZED, slab < 0, a tree with an identity method or none with a tree method, a node outside [0, n_nodes), a
+ * parent array that is no rooted tree, a kept branch whose length is negative or not finite, a cell that is negative or not finite, a
+ * sample without reads.  HU_ERR_NOMEM with the bytes needed and the bytes free (mem_budget, when > 0 and smaller) when the device
+ * cannot hold P, the scan and the partial sums.
+ * hu_unifrac_embed: *n_branch = B; with P == NULL nothing else is done (no device).  Otherwise cap_branch >= B, and branch_node [B]
+ * (may be NULL), branch_len [B] (may be NULL) and P [B][n_sample] are filled.
+ * hu_unifrac_timing: of this thread's last device call, seconds [4] = copies up, embedding, pair kernels, copy back. */
+#define HU_UF_UNWEIGHTED 0
+#define HU_UF_WEIGHTED 1
+#define HU_UF_WEIGHTED_RAW 2
+#define HU_UF_GENERALIZED 3
+#define HU_UF_BRAY_CURTIS 4
+#define HU_UF_JACCARD 5
+typedef struct {
+	int32_t method;       /* HU_UF_WEIGHTED */
+	int32_t host;         /* 0; 1: the host path, no device needed */
+	double alpha;         /* 0.5 */
+	int64_t slab;         /* 0: hu_unifrac_default_slab */
+	int64_t mem_budget;   /* 0: what the device reports free */
+} hu_unifrac_opts;
+typedef struct {
+	int32_t n_nodes;
+	const int32_t* parent;   /* [n_nodes], -1: the root */
+	const double* blen;      /* [n_nodes], the length of the branch to the parent */
+} hu_unifrac_tree;
+void hu_unifrac_default_opts(hu_unifrac_opts* o);
+int64_t hu_unifrac_default_slab(int64_t n_sample, int64_t n_branch);
+int hu_unifrac(int device, const hu_unifrac_tree* tree, int64_t n_otu, int64_t n_sample, const int32_t* otu_node, const double* counts,
+		const hu_unifrac_opts* opts, double* dist, double* pd);
+int hu_unifrac_embed(int device, const hu_unifrac_tree* tree, int64_t n_otu, int64_t n_sample, const int32_t* otu_node, const double* counts,
+		const hu_unifrac_opts* opts, int64_t* n_branch, int64_t cap_branch, int32_t* branch_node, double* branch_len, double* P);
+int hu_unifrac_timing(double* seconds /* [4] */);
+
 #ifdef __cplusplus
 }
 #endif
