@@ -1,0 +1,170 @@
+// hmmufotu-amd-tree: a neighbour-joining tree from a reference MSA, the TREE-FILE that hmmufotu-amd-train-sm and
+// hmmufotu-amd-build start from.  The reference leaves this step to another package.  Plain neighbour joining on the pairwise
+// distances of the rows, not a maximum-likelihood search: the usual starting tree of the ML packages.
+//   hmmufotu-amd-tree <MSA-FILE> [-o TREE] [-sm FILE] [--dist pdist|JC69|K80|F81|HKY85|TN93] [--dist-out FILE] [--sat DBL] [--mem GB]
+//                     [--device N] [--host] [-v]
+// The MSA is read and pruned as hmmufotu-amd-build does (hu_build_inputs.h; the columns without a residue are found on the host here,
+// the same columns hu_prune_msa finds), so the tree joins by name to the same MSA there.  The distances and the joins are
+// hu_msa_tree's: on the device (hu_kern_dist.h, hu_kern_nj.h), or with --host by the library's host path.  Every refusal comes before
+// a device is asked for, and the outputs are opened only after the computation: a refused run leaves no file.
+#include <cmath>
+#include <cstdlib>
+#include "hu_build_inputs.h"
+
+/* hu_build_inputs.h is shared with the programs that read a tree; the prune there asks for a device, the one here must not */
+static const auto unused_tree [[maybe_unused]] = &hu_load_tree;
+static const auto unused_join [[maybe_unused]] = &hu_join_msa_tree;
+static const auto unused_newick [[maybe_unused]] = &hu_is_newick_name;
+static const auto unused_prune [[maybe_unused]] = &hu_prune_msa;
+
+static void usage(const char* p) {
+	std::cerr << "Build a neighbour-joining tree (Newick, unrooted) from a multiple sequence alignment\n"
+		"Usage:    " << p << "  <MSA-FILE> [options]\n"
+		"MSA-FILE  FILE                 : a multiple-alignment sequence file, support .gz or .bz2 compressed file\n"
+		"Options:    -o  FILE           : tree output [stdout]\n"
+		"            --fmt  STR         : MSA format, supported format: 'fasta'\n"
+		"            -sm  FILE          : DNA substitution model file (hmmufotu-amd-train-sm): its type is the default of --dist, its base frequencies go into F81, HKY85 and TN93; a GTR file gives TN93\n"
+		"            --dist  STR        : pdist, JC69, K80, F81, HKY85 or TN93 [the type of -sm, or JC69]\n"
+		"            --dist-out  FILE   : also write the distance matrix: a line n, then per row its name and n values\n"
+		"            --sat  DBL         : distance of a saturated pair (its formula takes the logarithm of a value <= 0) [twice the largest finite distance]\n"
+		"            --mem  DBL         : device memory to use at the most, in GB [what the device reports free]\n"
+		"            --device  INT      : device to run on [0]\n"
+		"            --host  FLAG       : run on the host, no device needed\n"
+		"            -v  FLAG           : enable verbose information, you may set multiple -v for more details\n"
+		"            --version          : show program version and exit\n"
+		"            -h|--help          : print this message and exit\n";
+}
+
+int main(int argc, char** argv) {
+	std::vector<std::string> pos; std::string outFn, fmt, smFn, distName, distFn; bool host = false, haveSat = false; int device = 0, verbose = 0;
+	double sat = 0, memGB = 0; bool haveMem = false;
+	if(argc < 2) { usage(argv[0]); return EXIT_SUCCESS; }
+	for(int i = 1; i < argc; ++i) {
+		std::string a = argv[i];
+		auto val = [&]() -> const char* { if(i + 1 >= argc) { std::cerr << "Error: option " << a << " needs a value\n"; exit(EXIT_FAILURE); } return argv[++i]; };
+		if(a == "-h" || a == "--help") { usage(argv[0]); return EXIT_SUCCESS; }
+		else if(a == "--version") { std::cerr << argv[0] << ": v1.5.1\nPackage: HmmUFOtu v1.5.1 (file formats; hmmufotu_amd engine for gfx950)" << std::endl; return EXIT_SUCCESS; }
+		else if(a == "-o") outFn = val(); else if(a == "--fmt") fmt = val(); else if(a == "-sm") smFn = val(); else if(a == "--dist") distName = val();
+		else if(a == "--dist-out") distFn = val();
+		else if(a == "--sat") { sat = atof(val()); haveSat = true; }
+		else if(a == "--mem") { memGB = atof(val()); haveMem = true; }
+		else if(a == "--device") device = atoi(val()); else if(a == "--host") host = true;
+		else if(a.size() > 1 && a[0] == '-' && a.find_first_not_of('v', 1) == std::string::npos) verbose += (int) a.size() - 1;
+		else if(a[0] == '-' && a.size() > 1) { std::cerr << "Error: unknown option " << a << std::endl; return EXIT_FAILURE; }
+		else pos.push_back(a);
+	}
+	if(pos.size() != 1) { std::cerr << "Error:" << std::endl; usage(argv[0]); return EXIT_FAILURE; }
+	const HuInfo info = [&](const std::string& s) { if(verbose) std::cerr << s << std::endl; };
+	const std::string seqFn = pos[0];
+	if(fmt.empty() && ends_with(seqFn, ".msa")) fmt = "msa";
+	hu_guess_seq_format(seqFn, fmt);
+	if(fmt == "msa") { std::cerr << "MSA format 'msa': the reference's binary .msa database is not read here; pass the alignment as FASTA" << std::endl; return EXIT_FAILURE; }
+	if(fmt != "fasta") { std::cerr << "Unsupported sequence format '" << fmt << "'" << std::endl; return EXIT_FAILURE; }
+	if(haveSat && (!(sat > 0) || !std::isfinite(sat))) { std::cerr << "--sat must be positive" << std::endl; return EXIT_FAILURE; }
+	if(haveMem && (!(memGB > 0) || !std::isfinite(memGB))) { std::cerr << "--mem must be positive" << std::endl; return EXIT_FAILURE; }
+	if(device < 0) { std::cerr << "--device must be non-negative; --host runs without one" << std::endl; return EXIT_FAILURE; }
+	static const char* const names[] = {"pdist", "JC69", "K80", "F81", "HKY85", "TN93"};
+	int type = -1;
+	if(!distName.empty()) {
+		for(int m = 0; m < 6; ++m) if(distName == names[m]) type = m;
+		if(type < 0) { std::cerr << "Unsupported distance '" << distName << "': pdist, JC69, K80, F81, HKY85 or TN93 (GTR distances are not offered)" << std::endl; return EXIT_FAILURE; }
+		if(type >= HU_DIST_F81 && smFn.empty()) { std::cerr << "--dist " << distName << " reads the base frequencies of a model: -sm is required" << std::endl; return EXIT_FAILURE; }
+	}
+	/* the model: its type is the default distance, its pi the base frequencies */
+	double pi[4] = {0.25, 0.25, 0.25, 0.25};
+	if(!smFn.empty()) {
+		std::string text;
+		if(!read_file(smFn, text)) { std::cerr << "Unable to open '" << smFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+		/* the type is the word behind "Type:", as hmmufotu-amd-build reads the file (src/hmmufotu-build.cpp:393-405) */
+		hu_model_desc md;
+		std::istringstream in(text);
+		std::string tag, mtype, line;
+		while(in >> tag) { if(tag[0] == '#') { std::getline(in, line); continue; } if(tag == "Type:") { in >> mtype; break; } }
+		const std::string withType = mtype + "\n" + text;
+		if(mtype.empty()) { std::cerr << "Unable to load DNA Substitution Model '" << smFn << "': no Type: line" << std::endl; return EXIT_FAILURE; }
+		if(hu_model_parse_text(withType.data(), (int64_t) withType.size(), &md) != HU_OK) { std::cerr << "Unable to load DNA Substitution Model '" << smFn << "': " << hu_last_error() << std::endl; return EXIT_FAILURE; }
+		/* hu_model_desc.type: GTR TN93 HKY85 F81 K80 JC69 in the order of hmmufotu-amd-train-sm */
+		static const int ofModel[6] = {HU_DIST_TN93, HU_DIST_TN93, HU_DIST_HKY85, HU_DIST_F81, HU_DIST_K80, HU_DIST_JC69};
+		if(md.type < 0 || md.type > 5) { std::cerr << "Unknown model type in '" << smFn << "'" << std::endl; return EXIT_FAILURE; }
+		if(type < 0) {
+			type = ofModel[md.type];
+			if(md.type == 0) info("The model is GTR, whose distance is not offered: TN93 with the model's base frequencies is used");
+		}
+		for(int b = 0; b < 4; ++b) pi[b] = md.pi[b];
+		if(type >= HU_DIST_F81) for(int b = 0; b < 4; ++b) if(!(pi[b] > 0)) { std::cerr << "The model of '" << smFn << "' has a base frequency that is not positive" << std::endl; return EXIT_FAILURE; }
+	}
+	if(type < 0) type = HU_DIST_JC69;
+	info(std::string("Distance: ") + names[type]);
+
+	LineIn seqIn;
+	if(!seqIn.open(seqFn)) { std::cerr << "Unable to open MSA file '" << seqFn << "' " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+	HuBuildInputs inp;
+	if(!hu_load_msa(seqIn, seqFn, seqFn, inp, info)) return EXIT_FAILURE;
+	if(inp.nSeq < 3) { std::cerr << "A tree needs at least 3 sequences, '" << seqFn << "' has " << inp.nSeq << std::endl; return EXIT_FAILURE; }
+	/* MSA::prune: the columns without a residue go */
+	int8_t enc[256];
+	hu_msa_encode_table(enc);
+	{
+		std::vector<char> any(inp.L0, 0);
+		for(size_t i = 0; i < inp.nSeq; ++i) { const char* src = inp.msa.data() + i * inp.L0; for(size_t j = 0; j < inp.L0; ++j) if(enc[(unsigned char) src[j]] >= 0) any[j] = 1; }
+		for(size_t j = 0; j < inp.L0; ++j) if(any[j]) inp.keep.push_back((uint32_t) j);
+		inp.L = (int32_t) inp.keep.size();
+		info("MSA pruned: " + std::to_string(inp.nSeq) + " X " + std::to_string(inp.L) + " aligned sequences");
+	}
+	if(inp.L < 1) { std::cerr << "Unable to build a tree: the MSA has no column with a residue" << std::endl; return EXIT_FAILURE; }
+	if(inp.L > 65535) { std::cerr << "The pruned MSA has " << inp.L << " columns: 65535 at the most are taken" << std::endl; return EXIT_FAILURE; }
+	const size_t n = inp.nSeq, L = (size_t) inp.L;
+	std::vector<int8_t> rows(n * L);
+	for(size_t i = 0; i < n; ++i) hu_encode_row(inp, enc, i, rows.data() + i * L);
+	std::vector<char>().swap(inp.msa);
+	for(size_t i = 0; i < n; ++i) {
+		const std::string& s = inp.rowName[i];
+		for(unsigned char c : s) if(c == '\'' || c < 0x20 || c == 0x7f) { std::cerr << "Sequence name '" << s << "' holds a quote or a byte that does not print: no Newick label" << std::endl; return EXIT_FAILURE; }
+	}
+
+	hu_nj_opts o;
+	hu_nj_default_opts(&o);
+	o.host = host ? 1 : 0;
+	if(haveMem) o.mem_budget = (int64_t)(memGB * 1e9);
+	if(!host && hu_device_count() <= device) { std::cerr << "Error: device " << device << " asked for, " << hu_device_count() << " gfx950 device(s) visible; --host runs without one" << std::endl; return EXIT_FAILURE; }
+	std::vector<double> D;
+	if(!distFn.empty()) D.resize(n * n);
+	std::vector<int32_t> join(2 * (n - 3) + 1); std::vector<double> len(2 * (n - 3) + 1);
+	int32_t last3[3]; double lastLen3[3]; int64_t nSat = 0;
+	if(hu_msa_tree(host ? -1 : device, (int64_t) n, (int64_t) L, rows.data(), type, pi, sat, &o, distFn.empty() ? nullptr : D.data(), &nSat, join.data(), len.data(), last3, lastLen3) != HU_OK) {
+		std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
+	if(nSat > 0) std::cerr << "Warning: " << nSat << " pair(s) of sequences are saturated under " << names[type] << ": given "
+		<< (haveSat ? "the distance of --sat" : "twice the largest finite distance") << std::endl;
+	if(verbose && !host) {
+		double s[4];
+		hu_nj_timing(s);
+		std::cerr << "copies up and encoding " << s[0] << " s, distances " << s[1] << " s, joins " << s[2] << " s, copies back " << s[3] << " s" << std::endl;
+	}
+	std::vector<const char*> nm(n);
+	for(size_t i = 0; i < n; ++i) nm[i] = inp.rowName[i].c_str();
+	const int64_t tl = hu_nj_newick((int64_t) n, nm.data(), join.data(), len.data(), last3, lastLen3, nullptr, 0);
+	if(tl < 0) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
+	std::string text((size_t) tl + 1, '\0');
+	hu_nj_newick((int64_t) n, nm.data(), join.data(), len.data(), last3, lastLen3, &text[0], tl + 1);
+	text.resize((size_t) tl);
+	if(!distFn.empty()) {
+		FILE* f = fopen(distFn.c_str(), "w");
+		if(!f) { std::cerr << "Unable to write to '" << distFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+		fprintf(f, "%zu\n", n);
+		for(size_t i = 0; i < n; ++i) {
+			fputs(nm[i], f);
+			for(size_t j = 0; j < n; ++j) fprintf(f, "\t%.17g", D[i * n + j]);
+			fputc('\n', f);
+		}
+		if(fclose(f) != 0) { std::cerr << "Unable to write to '" << distFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+	}
+	if(outFn.empty()) { std::cout << text; std::cout.flush(); }
+	else {
+		std::ofstream of(outFn, std::ios::binary);
+		if(!of.is_open()) { std::cerr << "Unable to write to '" << outFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+		of << text; of.flush();
+		if(!of) { std::cerr << "Unable to write tree: " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+	}
+	info("Tree written");
+	return EXIT_SUCCESS;
+}

@@ -878,6 +878,89 @@ def unifrac_timing() -> dict:
     return dict(to_device=s[0], embed=s[1], pairs=s[2], to_host=s[3])
 
 
+class NjOpts(C.Structure):
+    _fields_ = [("host", C.c_int32), ("reserved", C.c_int32), ("mem_budget", C.c_int64)]
+
+
+DIST_TYPES = {"pdist": 0, "JC69": 1, "K80": 2, "F81": 3, "HKY85": 4, "TN93": 5}
+
+
+def _code_rows(rows, what) -> np.ndarray:
+    a = np.ascontiguousarray(rows, np.int8)
+    if a.ndim != 2 or a.size == 0:
+        raise EngineError(what + ": rows must be a non-empty int8 [n][cs_len] array of the codes of msa_encode_table")
+    return a
+
+
+def msa_pair_counts(rows, device=0, host=False) -> np.ndarray:
+    """hu_msa_pair_counts: int32 [n][n][4] = per pair of rows (codes of msa_encode_table, int8 [n][cs_len]) N, P_R, P_Y and Q: the
+    columns where both hold a symbol, the A<->G and the C<->T differences, the transversions.  host: the library's host path."""
+    a = _code_rows(rows, "msa_pair_counts")
+    n, L = a.shape
+    out = np.zeros((n, n, 4), np.int32)
+    _chk(load_library().hu_msa_pair_counts(C.c_int(-1 if host else int(device)), C.c_int64(n), C.c_int64(L), _p(a, C.c_int8), _p(out, C.c_int32)))
+    return out
+
+
+def msa_distances(rows, dist="JC69", pi=None, sat=None, device=0, host=False):
+    """hu_msa_distances: (D [n][n], saturated pairs) of the rows under dist (one of DIST_TYPES); pi [4] goes into F81, HKY85 and TN93;
+    sat: the distance of a saturated pair, None for twice the largest finite distance.  host: the library's host path."""
+    a = _code_rows(rows, "msa_distances")
+    if dist not in DIST_TYPES:
+        raise EngineError("msa_distances: dist one of %s, not %r" % (", ".join(DIST_TYPES), dist))
+    n, L = a.shape
+    D = np.zeros((n, n)); ns = C.c_int64(0)
+    p = np.ascontiguousarray(pi, np.float64) if pi is not None else None
+    if p is not None and p.shape != (4,):
+        raise EngineError("msa_distances: pi [4]")
+    _chk(load_library().hu_msa_distances(C.c_int(-1 if host else int(device)), C.c_int64(n), C.c_int64(L), _p(a, C.c_int8), C.c_int(DIST_TYPES[dist]),
+                                         _p(p, C.c_double) if p is not None else None, C.c_double(0.0 if sat is None else float(sat)), _p(D, C.c_double), C.byref(ns)))
+    return D, int(ns.value)
+
+
+def nj(D, device=0, host=False, mem_budget=0) -> dict:
+    """hu_nj: neighbour joining on the symmetric matrix D [n][n] with a zero diagonal: dict(join [n - 3][2], len [n - 3][2], last3 [3],
+    last_len3 [3]); join t makes node n + t.  The host path (host=True) and the device give the same bits."""
+    d = np.ascontiguousarray(D, np.float64)
+    if d.ndim != 2 or d.shape[0] != d.shape[1]:
+        raise EngineError("nj: D [n][n]")
+    n = d.shape[0]
+    o = NjOpts()
+    load_library().hu_nj_default_opts(C.byref(o))
+    o.host = 1 if host else 0; o.mem_budget = int(mem_budget or 0)
+    m = max(n - 3, 0)
+    out = dict(join=np.zeros((m, 2), np.int32), len=np.zeros((m, 2)), last3=np.zeros(3, np.int32), last_len3=np.zeros(3))
+    _chk(load_library().hu_nj(C.c_int(int(device)), C.c_int64(n), _p(d, C.c_double), C.byref(o), _p(out["join"], C.c_int32) if m else None,
+                              _p(out["len"], C.c_double) if m else None, _p(out["last3"], C.c_int32), _p(out["last_len3"], C.c_double)))
+    return out
+
+
+def nj_newick(names, tree) -> str:
+    """hu_nj_newick: the result of nj as Newick text, unrooted with three children at the top node; leaves carry names, lengths %.17g"""
+    lib = load_library()
+    lib.hu_nj_newick.restype = C.c_int64
+    n = len(names)
+    nm = (C.c_char_p * n)(*[x.encode() if isinstance(x, str) else bytes(x) for x in names])
+    j = np.ascontiguousarray(tree["join"], np.int32); l = np.ascontiguousarray(tree["len"], np.float64)
+    l3 = np.ascontiguousarray(tree["last3"], np.int32); ll3 = np.ascontiguousarray(tree["last_len3"], np.float64)
+    if j.shape != (max(n - 3, 0), 2) or l.shape != j.shape or l3.shape != (3,) or ll3.shape != (3,):
+        raise EngineError("nj_newick: the arrays of nj for %d names" % n)
+    args = (C.c_int64(n), nm, _p(j, C.c_int32) if j.size else None, _p(l, C.c_double) if l.size else None, _p(l3, C.c_int32), _p(ll3, C.c_double))
+    k = int(lib.hu_nj_newick(*args, None, C.c_int64(0)))
+    if k < 0:
+        _chk(k)
+    buf = C.create_string_buffer(k + 1)
+    _chk(min(0, int(lib.hu_nj_newick(*args, buf, C.c_int64(k + 1)))))
+    return buf.value.decode()
+
+
+def nj_timing() -> dict:
+    """hu_nj_timing: the phases of this thread's last msa_distances / nj on a device, in seconds"""
+    s = np.zeros(4)
+    _chk(load_library().hu_nj_timing(_p(s, C.c_double)))
+    return dict(to_device=s[0], distances=s[1], joins=s[2], to_host=s[3])
+
+
 def tree_count_mutations(parent, cs_len: int, up_ptr: int, device=0) -> np.ndarray:
     """hu_tree_count_mutations: per column, the non-root nodes whose inferred state differs from their parent's, from the DEVICE
     fixed-rate up buffer at up_ptr ([n][cs_len][4] float64, as tree_evaluate leaves it with win_len 0)"""

@@ -1064,6 +1064,60 @@ int hu_unifrac_embed(int device, const hu_unifrac_tree* tree, int64_t n_otu, int
 		const hu_unifrac_opts* opts, int64_t* n_branch, int64_t cap_branch, int32_t* branch_node, double* branch_len, double* P);
 int hu_unifrac_timing(double* seconds /* [4] */);
 
+/* ---- hmmufotu-amd-tree: a neighbour-joining tree from the MSA ----
+ * Plain neighbour joining (Saitou and Nei 1987, in the form of Studier and Keppler 1988) on the pairwise distances of the alignment's
+ * rows: not a maximum-likelihood search.  rows [n][cs_len]: the pruned alignment in the codes of hu_msa_encode_table (0..3 = A C G T, a
+ * negative code is no symbol; a code above 3 is refused).  A device below 0, or opts->host, runs the host path, which needs no device.
+ *
+ * hu_msa_pair_counts, for tests and small n: counts [n][n][4] = per pair N (the columns where both rows hold a symbol), P_R (A<->G
+ * differences), P_Y (C<->T differences) and Q (transversions); the diagonal holds a row against itself.  Exact integers.
+ *
+ * hu_msa_distances: D [n][n], symmetric with a zero diagonal, from the closed forms of the reference's subDist (HU_DIST_JC69: src/JC69.h:103,
+ * HU_DIST_K80: src/K80.h:120, HU_DIST_F81: src/F81.h:120, HU_DIST_HKY85: src/HKY85.h:155, HU_DIST_TN93: src/TN93.h:156) or the plain
+ * p-distance; pi [4] is read by F81, HKY85 and TN93 only.  N == 0 gives 0, as the reference does.  A pair whose formula takes the
+ * logarithm of a value <= 0 is saturated: it gets `sat` when sat > 0, and otherwise (sat == 0) twice the largest finite distance of the
+ * matrix, set in a second pass; *n_saturated (may be NULL) counts such pairs (i < j).  Refused with HU_ERR_ARG: n < 2, cs_len outside
+ * [1, 65535], a code above 3, an unknown type, a pi that is not four positive numbers where it is read, sat < 0 or not finite, and a
+ * matrix without one finite off-diagonal distance when sat == 0.  The counts are integers, so D does not depend on the grid; the
+ * device's log may differ from the host's in the last bits.
+ *
+ * hu_nj: D [n][n] (symmetric, zero diagonal, finite; anything else is refused) is not changed.  Leaves are nodes 0 .. n - 1; join t
+ * (0 <= t < n - 3) makes node n + t from join[t][0] and join[t][1] with the branch lengths len[t][0] and len[t][1]; last3 [3] are the
+ * nodes that hang on the top node, with last_len3 [3].  The order of every comparison and every sum is fixed, so the
+ * host path and the device give the same bits, whatever the grid.  n >= 3; n above 262144 is refused.
+ *
+ * hu_msa_tree: both steps with the matrix kept on the device between them, as hmmufotu-amd-tree runs them; D_out (may be NULL) [n][n]
+ * receives the distances.  Before anything is allocated the device's free memory (opts->mem_budget, when > 0 and smaller) is held
+ * against the need, the n x n FP64 matrix, the bit-planes, the rows, the vectors and 1 MB of slack: HU_ERR_NOMEM names both numbers.
+ * hu_nj and hu_msa_distances check the same way.
+ * hu_nj_timing: of this thread's last device call, seconds [4] = copies up and encoding, distances, joins, copies back.
+ *
+ * hu_nj_newick: the tree as Newick text, unrooted with three children at the top node: leaves carry names[i], inner nodes no name,
+ * lengths as %.17g.  A name that is no unquoted Newick label is written in single quotes; one that holds a quote or a byte that does
+ * not print is refused.  Returns the length (without the terminator) and writes at most cap bytes, terminator included; HU_ERR_ARG
+ * (negative) on a bad argument.  Host only. */
+#define HU_DIST_PDIST 0
+#define HU_DIST_JC69 1
+#define HU_DIST_K80 2
+#define HU_DIST_F81 3
+#define HU_DIST_HKY85 4
+#define HU_DIST_TN93 5
+typedef struct {
+	int32_t host;         /* 0; 1: the host path, no device needed */
+	int32_t reserved;
+	int64_t mem_budget;   /* 0: what the device reports free */
+} hu_nj_opts;
+void hu_nj_default_opts(hu_nj_opts* o);
+int hu_msa_pair_counts(int device, int64_t n, int64_t cs_len, const int8_t* rows, int32_t* counts);
+int hu_msa_distances(int device, int64_t n, int64_t cs_len, const int8_t* rows, int dist_type, const double* pi, double sat, double* D,
+		int64_t* n_saturated);
+int hu_nj(int device, int64_t n, const double* D, const hu_nj_opts* opts, int32_t* join, double* len, int32_t* last3, double* last_len3);
+int hu_msa_tree(int device, int64_t n, int64_t cs_len, const int8_t* rows, int dist_type, const double* pi, double sat, const hu_nj_opts* opts,
+		double* D_out, int64_t* n_saturated, int32_t* join, double* len, int32_t* last3, double* last_len3);
+int hu_nj_timing(double* seconds /* [4] */);
+int64_t hu_nj_newick(int64_t n, const char* const* names, const int32_t* join, const double* len, const int32_t* last3, const double* last_len3,
+		char* buf, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif
