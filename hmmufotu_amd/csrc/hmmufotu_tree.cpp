@@ -3,12 +3,17 @@
 // distances of the rows, not a maximum-likelihood search: the usual starting tree of the ML packages.
 //   hmmufotu-amd-tree <MSA-FILE> [-o TREE] [-sm FILE] [--dist pdist|JC69|K80|F81|HKY85|TN93] [--dist-out FILE] [--sat DBL] [--mem GB]
 //                     [--device N] [--host] [-v]
+//                     [--ml-lengths [--start-tree FILE] [--ml-rounds N] [--ml-eps DBL] [--min-len DBL] [--max-len DBL] [--ml-log FILE]]
 // The MSA is read and pruned as hmmufotu-amd-build does (hu_build_inputs.h; the columns without a residue are found on the host here,
 // the same columns hu_prune_msa finds), so the tree joins by name to the same MSA there.  The distances and the joins are
 // hu_msa_tree's: on the device (hu_kern_dist.h, hu_kern_nj.h), or with --host by the library's host path.  Every refusal comes before
 // a device is asked for, and the outputs are opened only after the computation: a refused run leaves no file.
+// --ml-lengths keeps the topology, of the joins or of --start-tree, and fits its branch lengths by maximum likelihood
+// under the fixed-rate model of -sm (hu_tree_optimize_lengths; a GTR file is used as GTR here).  The tree goes through hu_newick_parse
+// either way, and hu_newick_write puts the same topology, names and order of children back with the new lengths.
 #include <cmath>
 #include <cstdlib>
+#include <memory>
 #include "hu_build_inputs.h"
 
 /* hu_build_inputs.h is shared with the programs that read a tree; the prune there asks for a device, the one here must not */
@@ -30,6 +35,13 @@ static void usage(const char* p) {
 		"            --mem  DBL         : device memory to use at the most, in GB [what the device reports free]\n"
 		"            --device  INT      : device to run on [0]\n"
 		"            --host  FLAG       : run on the host, no device needed\n"
+		"            --ml-lengths  FLAG : keep the topology and fit the branch lengths by maximum likelihood under the fixed-rate model of -sm (required then; a GTR file is used as GTR)\n"
+		"            --start-tree  FILE : with --ml-lengths: fit the lengths of this Newick tree, no distances are computed; its leaves are the sequences of the MSA, by name\n"
+		"            --ml-rounds  INT   : rounds of simultaneous branch steps at the most [50]\n"
+		"            --ml-eps  DBL      : converged when every branch is within this of its own optimum, at least 1e-6 [1e-5]\n"
+		"            --min-len  DBL     : smallest branch length [0]\n"
+		"            --max-len  DBL     : largest branch length [10]\n"
+		"            --ml-log  FILE     : write the rounds as TSV: round, ll, s, delta, capped; a last line '# stop: REASON'\n"
 		"            -v  FLAG           : enable verbose information, you may set multiple -v for more details\n"
 		"            --version          : show program version and exit\n"
 		"            -h|--help          : print this message and exit\n";
@@ -38,6 +50,7 @@ static void usage(const char* p) {
 int main(int argc, char** argv) {
 	std::vector<std::string> pos; std::string outFn, fmt, smFn, distName, distFn; bool host = false, haveSat = false; int device = 0, verbose = 0;
 	double sat = 0, memGB = 0; bool haveMem = false;
+	bool mlLengths = false; std::string startFn, mlLogFn; int mlRounds = 50; double mlEps = 1e-5, minLen = 0.0, maxLen = 10.0;
 	if(argc < 2) { usage(argv[0]); return EXIT_SUCCESS; }
 	for(int i = 1; i < argc; ++i) {
 		std::string a = argv[i];
@@ -49,6 +62,9 @@ int main(int argc, char** argv) {
 		else if(a == "--sat") { sat = atof(val()); haveSat = true; }
 		else if(a == "--mem") { memGB = atof(val()); haveMem = true; }
 		else if(a == "--device") device = atoi(val()); else if(a == "--host") host = true;
+		else if(a == "--ml-lengths") mlLengths = true; else if(a == "--start-tree") startFn = val(); else if(a == "--ml-log") mlLogFn = val();
+		else if(a == "--ml-rounds") mlRounds = atoi(val()); else if(a == "--ml-eps") mlEps = atof(val());
+		else if(a == "--min-len") minLen = atof(val()); else if(a == "--max-len") maxLen = atof(val());
 		else if(a.size() > 1 && a[0] == '-' && a.find_first_not_of('v', 1) == std::string::npos) verbose += (int) a.size() - 1;
 		else if(a[0] == '-' && a.size() > 1) { std::cerr << "Error: unknown option " << a << std::endl; return EXIT_FAILURE; }
 		else pos.push_back(a);
@@ -63,6 +79,17 @@ int main(int argc, char** argv) {
 	if(haveSat && (!(sat > 0) || !std::isfinite(sat))) { std::cerr << "--sat must be positive" << std::endl; return EXIT_FAILURE; }
 	if(haveMem && (!(memGB > 0) || !std::isfinite(memGB))) { std::cerr << "--mem must be positive" << std::endl; return EXIT_FAILURE; }
 	if(device < 0) { std::cerr << "--device must be non-negative; --host runs without one" << std::endl; return EXIT_FAILURE; }
+	if(!mlLengths && (!startFn.empty() || !mlLogFn.empty())) { std::cerr << (startFn.empty() ? "--ml-log" : "--start-tree") << " goes with --ml-lengths" << std::endl; return EXIT_FAILURE; }
+	if(mlLengths) {
+		if(smFn.empty()) { std::cerr << "--ml-lengths fits the branch lengths under a substitution model: -sm is required" << std::endl; return EXIT_FAILURE; }
+		if(!(mlEps > 0) || !std::isfinite(mlEps)) { std::cerr << "--ml-eps must be positive" << std::endl; return EXIT_FAILURE; }
+		if(mlEps < 100 * HU_BLEN_TAU) { std::cerr << "--ml-eps must be at least " << 100 * HU_BLEN_TAU << ": 100 times the tolerance of a branch's own step" << std::endl; return EXIT_FAILURE; }
+		if(!(maxLen > 0) || !std::isfinite(maxLen)) { std::cerr << "--max-len must be positive" << std::endl; return EXIT_FAILURE; }
+		if(!(minLen >= 0)) { std::cerr << "--min-len must not be negative" << std::endl; return EXIT_FAILURE; }
+		if(!(minLen < maxLen)) { std::cerr << "--min-len must be below --max-len" << std::endl; return EXIT_FAILURE; }
+		if(mlRounds < 1) { std::cerr << "--ml-rounds must be at least 1" << std::endl; return EXIT_FAILURE; }
+		if(!startFn.empty() && !distFn.empty()) { std::cerr << "--dist-out: with --start-tree no distances are computed" << std::endl; return EXIT_FAILURE; }
+	}
 	static const char* const names[] = {"pdist", "JC69", "K80", "F81", "HKY85", "TN93"};
 	int type = -1;
 	if(!distName.empty()) {
@@ -72,11 +99,12 @@ int main(int argc, char** argv) {
 	}
 	/* the model: its type is the default distance, its pi the base frequencies */
 	double pi[4] = {0.25, 0.25, 0.25, 0.25};
+	hu_model_desc md;
+	memset(&md, 0, sizeof(md));
 	if(!smFn.empty()) {
 		std::string text;
 		if(!read_file(smFn, text)) { std::cerr << "Unable to open '" << smFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
 		/* the type is the word behind "Type:", as hmmufotu-amd-build reads the file (src/hmmufotu-build.cpp:393-405) */
-		hu_model_desc md;
 		std::istringstream in(text);
 		std::string tag, mtype, line;
 		while(in >> tag) { if(tag[0] == '#') { std::getline(in, line); continue; } if(tag == "Type:") { in >> mtype; break; } }
@@ -86,6 +114,7 @@ int main(int argc, char** argv) {
 		/* hu_model_desc.type: GTR TN93 HKY85 F81 K80 JC69 in the order of hmmufotu-amd-train-sm */
 		static const int ofModel[6] = {HU_DIST_TN93, HU_DIST_TN93, HU_DIST_HKY85, HU_DIST_F81, HU_DIST_K80, HU_DIST_JC69};
 		if(md.type < 0 || md.type > 5) { std::cerr << "Unknown model type in '" << smFn << "'" << std::endl; return EXIT_FAILURE; }
+		md.dg_k = 0;                                                       /* the fixed-rate model, as hmmufotu-amd-train-sm trained it */
 		if(type < 0) {
 			type = ofModel[md.type];
 			if(md.type == 0) info("The model is GTR, whose distance is not offered: TN93 with the model's base frequencies is used");
@@ -122,31 +151,106 @@ int main(int argc, char** argv) {
 		for(unsigned char c : s) if(c == '\'' || c < 0x20 || c == 0x7f) { std::cerr << "Sequence name '" << s << "' holds a quote or a byte that does not print: no Newick label" << std::endl; return EXIT_FAILURE; }
 	}
 
+	/* the tree of the fit: one parse, of --start-tree here or of the joins' text below, whose handle also writes the result.
+	 * --start-tree is read and joined to the MSA by name before anything is computed */
+	std::string text;
+	std::unique_ptr<hu_newick, void (*)(hu_newick*)> nw(nullptr, hu_newick_free);
+	std::vector<int32_t> parent, childOff, childIdx; std::vector<double> blen;
+	int32_t nn = 0;
+	auto parse_tree = [&](const std::string& from) {
+		hu_newick* t = nullptr;
+		if(hu_newick_parse(text.data(), (int64_t) text.size(), &t) != HU_OK) { std::cerr << "Unable to read Newick tree in '" << from << "': " << hu_last_error() << std::endl; return false; }
+		nw.reset(t);
+		hu_newick_size(t, &nn);
+		parent.resize(nn); childOff.resize((size_t) nn + 1); childIdx.resize((size_t) std::max(nn - 1, 1)); blen.resize(nn);
+		hu_newick_get(t, parent.data(), blen.data(), childOff.data(), childIdx.data());
+		return true;
+	};
+	int64_t fitNodes = 2 * (int64_t) n - 2;                    /* the joins' tree: n leaves, n - 3 joins, the top node */
+	if(!startFn.empty()) {
+		if(!read_file(startFn, text)) { std::cerr << "Unable to open '" << startFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+		if(!parse_tree(startFn)) return EXIT_FAILURE;
+		info("Newick Tree read: " + std::to_string(nn) + " nodes");
+		std::unordered_map<std::string, int32_t> seen;
+		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) {
+			const std::string leaf = hu_newick_name(nw.get(), i);
+			if(!seen.insert({leaf, i}).second) { std::cerr << "Non-unique leaf name '" << leaf << "' found in the tree '" << startFn << "'" << std::endl; return EXIT_FAILURE; }
+			if(!inp.name2row.count(leaf)) { std::cerr << "Unmatched MSA and Tree: leaf '" << leaf << "' of '" << startFn << "' is no sequence of the MSA" << std::endl; return EXIT_FAILURE; }
+		}
+		for(size_t i = 0; i < n; ++i) if(!seen.count(inp.rowName[i])) { std::cerr << "Unmatched MSA and Tree: sequence '" << inp.rowName[i] << "' is no leaf of '" << startFn << "'" << std::endl; return EXIT_FAILURE; }
+		if(nn < 2) { std::cerr << "The tree '" << startFn << "' has one node: no branch to fit" << std::endl; return EXIT_FAILURE; }
+		fitNodes = nn;
+	}
+	if(mlLengths && haveMem) {
+		const int64_t need = hu_blen_need((int32_t) fitNodes, (int32_t) L), have = (int64_t)(memGB * 1e9);
+		if(need > have) { std::cerr << "--ml-lengths: " << fitNodes << " nodes of " << L << " columns need " << need << " bytes (64 bytes per node and column for the messages), --mem allows " << have << " bytes" << std::endl; return EXIT_FAILURE; }
+	}
+
 	hu_nj_opts o;
 	hu_nj_default_opts(&o);
 	o.host = host ? 1 : 0;
 	if(haveMem) o.mem_budget = (int64_t)(memGB * 1e9);
 	if(!host && hu_device_count() <= device) { std::cerr << "Error: device " << device << " asked for, " << hu_device_count() << " gfx950 device(s) visible; --host runs without one" << std::endl; return EXIT_FAILURE; }
-	std::vector<double> D;
-	if(!distFn.empty()) D.resize(n * n);
-	std::vector<int32_t> join(2 * (n - 3) + 1); std::vector<double> len(2 * (n - 3) + 1);
-	int32_t last3[3]; double lastLen3[3]; int64_t nSat = 0;
-	if(hu_msa_tree(host ? -1 : device, (int64_t) n, (int64_t) L, rows.data(), type, pi, sat, &o, distFn.empty() ? nullptr : D.data(), &nSat, join.data(), len.data(), last3, lastLen3) != HU_OK) {
-		std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
-	if(nSat > 0) std::cerr << "Warning: " << nSat << " pair(s) of sequences are saturated under " << names[type] << ": given "
-		<< (haveSat ? "the distance of --sat" : "twice the largest finite distance") << std::endl;
-	if(verbose && !host) {
-		double s[4];
-		hu_nj_timing(s);
-		std::cerr << "copies up and encoding " << s[0] << " s, distances " << s[1] << " s, joins " << s[2] << " s, copies back " << s[3] << " s" << std::endl;
-	}
 	std::vector<const char*> nm(n);
 	for(size_t i = 0; i < n; ++i) nm[i] = inp.rowName[i].c_str();
-	const int64_t tl = hu_nj_newick((int64_t) n, nm.data(), join.data(), len.data(), last3, lastLen3, nullptr, 0);
-	if(tl < 0) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
-	std::string text((size_t) tl + 1, '\0');
-	hu_nj_newick((int64_t) n, nm.data(), join.data(), len.data(), last3, lastLen3, &text[0], tl + 1);
-	text.resize((size_t) tl);
+	std::vector<double> D;
+	if(startFn.empty()) {
+		if(!distFn.empty()) D.resize(n * n);
+		std::vector<int32_t> join(2 * (n - 3) + 1); std::vector<double> len(2 * (n - 3) + 1);
+		int32_t last3[3]; double lastLen3[3]; int64_t nSat = 0;
+		if(hu_msa_tree(host ? -1 : device, (int64_t) n, (int64_t) L, rows.data(), type, pi, sat, &o, distFn.empty() ? nullptr : D.data(), &nSat, join.data(), len.data(), last3, lastLen3) != HU_OK) {
+			std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
+		if(nSat > 0) std::cerr << "Warning: " << nSat << " pair(s) of sequences are saturated under " << names[type] << ": given "
+			<< (haveSat ? "the distance of --sat" : "twice the largest finite distance") << std::endl;
+		if(verbose && !host) {
+			double s[4];
+			hu_nj_timing(s);
+			std::cerr << "copies up and encoding " << s[0] << " s, distances " << s[1] << " s, joins " << s[2] << " s, copies back " << s[3] << " s" << std::endl;
+		}
+		const int64_t tl = hu_nj_newick((int64_t) n, nm.data(), join.data(), len.data(), last3, lastLen3, nullptr, 0);
+		if(tl < 0) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
+		text.assign((size_t) tl + 1, '\0');
+		hu_nj_newick((int64_t) n, nm.data(), join.data(), len.data(), last3, lastLen3, &text[0], tl + 1);
+		text.resize((size_t) tl);
+		if(mlLengths && !parse_tree("the joins")) return EXIT_FAILURE;
+	}
+	/* --ml-lengths: the parsed tree's arrays go into the fit, and its handle writes them back */
+	hu_blen_opts bo;
+	hu_blen_default_opts(&bo);
+	std::vector<hu_blen_round> rounds;
+	if(mlLengths) {
+		std::vector<int8_t> seq((size_t) nn * L, (int8_t) -2);
+		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(hu_newick_name(nw.get(), i)) * L, L);
+		/* a start outside the interval, a negative length of the joins' last node among them, begins at its nearer end */
+		for(int32_t i = 0; i < nn; ++i) if(parent[i] >= 0 && std::isfinite(blen[i])) blen[i] = std::min(std::max(blen[i], minLen), maxLen);
+		rounds.resize((size_t) mlRounds);
+		bo.eps = mlEps; bo.min_len = minLen; bo.max_len = maxLen; bo.max_rounds = mlRounds; bo.host = host ? 1 : 0; bo.device = device;
+		bo.mem_budget = haveMem ? (int64_t)(memGB * 1e9) : 0; bo.rounds = rounds.data(); bo.rounds_cap = mlRounds;
+		if(hu_tree_optimize_lengths(&bo, nn, (int32_t) L, parent.data(), blen.data(), seq.data(), &md) != HU_OK) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
+		static const char* const why[] = {"converged", "no improving step", "max rounds"};
+		if(verbose) {
+			char line[200];
+			snprintf(line, sizeof(line), "Branch lengths fitted: log-likelihood %.17g -> %.17g in %d round(s), stop: %s", bo.ll_start, bo.ll_final, bo.n_rounds, why[bo.stop]);
+			std::cerr << line << std::endl;
+			if(bo.n_capped > 0) std::cerr << "Warning: " << bo.n_capped << " branch step(s) hit the cap of " << HU_BLEN_MAX_NEWTON << " Newton steps" << std::endl;
+			double s[4];
+			hu_blen_timing(s);
+			std::cerr << "sweeps " << s[0] << " s, steps " << s[1] << " s, trial sweeps " << s[2] << " s, the rest " << s[3] << " s" << std::endl;
+		}
+		const int64_t wl = hu_newick_write(nw.get(), blen.data(), nullptr, 0);
+		if(wl < 0) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
+		text.assign((size_t) wl + 1, '\0');
+		hu_newick_write(nw.get(), blen.data(), &text[0], wl + 1);
+		text.resize((size_t) wl);
+		if(!mlLogFn.empty()) {
+			FILE* f = fopen(mlLogFn.c_str(), "w");
+			if(!f) { std::cerr << "Unable to write to '" << mlLogFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+			fprintf(f, "round\tll\ts\tdelta\tcapped\n0\t%.17g\t0\t0\t0\n", bo.ll_start);
+			for(int32_t r = 0; r < bo.n_rounds; ++r) fprintf(f, "%d\t%.17g\t%.17g\t%.17g\t%lld\n", r + 1, rounds[r].ll, rounds[r].s, rounds[r].delta, (long long) rounds[r].n_capped);
+			fprintf(f, "# stop: %s\n", why[bo.stop]);
+			if(fclose(f) != 0) { std::cerr << "Unable to write to '" << mlLogFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+		}
+	}
 	if(!distFn.empty()) {
 		FILE* f = fopen(distFn.c_str(), "w");
 		if(!f) { std::cerr << "Unable to write to '" << distFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }

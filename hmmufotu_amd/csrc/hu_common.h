@@ -194,5 +194,7 @@ inline void hu_write_prog_info(std::ostream& f) { const int32_t ver[3] = {1, 5, 
 /* the device steps of hu_csfm_write (hu_engine.hip): the suffix array of text[0, n), then bwt [n], marks [(n + 63) / 64] (row i at bit i & 63 of word
  * i / 64) and sampled [(n + 3) / 4], all host.  rounds: doubling rounds taken; sa_seconds: device time of the suffix array alone. */
 int hu_csfm_device_pass(int device, const uint8_t* text, int64_t n, uint8_t* bwt, uint64_t* marks, uint32_t* sampled, int32_t* rounds, double* sa_seconds);
+/* hu_tree_sweep_window's last window swept again with other branch lengths, without moving the rows (hu_engine.hip; the rounds of hu_blen.cpp) */
+int hu_tree_sweep_rerun(hu_tree_sweep* s, const hu_model_desc* model, const double* blen, int64_t win_len, double* up_dev, double* down_dev);
 /* runs f when the scope is left, by return or by exception */
 template<class F> struct HuScope { F f; explicit HuScope(F f) : f(f) {} ~HuScope() { f(); } HuScope(const HuScope&) = delete; HuScope& operator=(const HuScope&) = delete; };

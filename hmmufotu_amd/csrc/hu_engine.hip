@@ -1217,6 +1217,27 @@ extern "C" int hu_tree_sweep_window(hu_tree_sweep* s, const hu_model_desc* model
 	for(size_t u = 0; u < n; ++u) if(s->tp.childOff[u] != s->tp.childOff[u + 1]) memcpy(seq + u * L + (size_t) win_start, s->win.data() + u * W, W);     /* the inner rows */
 	return HU_OK;
 } catch(...) { return hu_catch_all("hu_tree_sweep_window"); }
+/* the last window once more with other branch lengths (the rounds of hu_tree_optimize_lengths): the rows are on the device already and
+ * stay there, 8 n bytes go up and nothing comes back */
+int hu_tree_sweep_rerun(hu_tree_sweep* s, const hu_model_desc* model, const double* blen, int64_t win_len, double* up_dev, double* down_dev) try {
+	if(!s || !model || !blen || !up_dev) { hu_set_error("hu_tree_sweep_rerun: bad argument"); return HU_ERR_ARG; }
+	if(!s->dSeq || win_len < 1 || win_len != (int64_t)(s->win.size() / (size_t) s->n)) { hu_set_error("hu_tree_sweep_rerun: no window of %lld columns was swept before", (long long) win_len); return HU_ERR_STATE; }
+	HuModelDev mdl;
+	int rc = hu_model_prepare(model, &mdl);
+	if(rc != HU_OK) return rc;
+	HIPCHK(hipSetDevice(s->device));
+	TCHK(hipMemcpy(s->td.len, blen, (size_t) s->n * 8, hipMemcpyHostToDevice));
+	s->blen.assign(blen, blen + s->n);
+	HuTreeDev t;
+	t.n = s->n; t.csLen = s->csLen; t.root = s->tp.root; t.winStart = 0; t.winLen = win_len; t.up = up_dev; t.down = down_dev;
+	t.seqStride = win_len; t.seqOff = 0; t.seq = s->dSeq;
+	s->td.bind(t);
+	(void) hipGetLastError();
+	tree_launch_levels(t, mdl, s->tp, s->td.ord, down_dev != nullptr);
+	TCHK(hipGetLastError());
+	TCHK(hipDeviceSynchronize());
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_tree_sweep_rerun"); }
 #undef TCHK
 
 /* ------------------------------------------------------------------------------ database build (hmmufotu-build) */

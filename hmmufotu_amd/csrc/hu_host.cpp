@@ -821,6 +821,40 @@ extern "C" int hu_newick_get(const hu_newick* t, int32_t* parent, double* blen, 
 	return HU_OK;
 }
 extern "C" const char* hu_newick_name(const hu_newick* t, int32_t node) { return t && node >= 0 && node < (int32_t) t->names.size() ? t->names[node].c_str() : ""; }
+/* the tree written back with other lengths (hmmufotu-amd-tree --ml-lengths): children in file order, iterative like the reader */
+extern "C" int64_t hu_newick_write(const hu_newick* t, const double* blen, char* buf, int64_t cap) try {
+	if(!t || !blen || cap < 0 || (cap > 0 && !buf)) { hu_set_error("hu_newick_write: bad argument"); return HU_ERR_ARG; }
+	const size_t n = t->parent.size();
+	std::string out;
+	char num[40];
+	auto close_node = [&](int32_t v) {
+		const std::string& s = t->names[v];
+		bool plain = true;
+		for(unsigned char c : s) if(!nw_unquoted(c)) plain = false;
+		if(plain) out += s; else { out += '\''; out += s; out += '\''; }
+		if(t->parent[v] >= 0) { snprintf(num, sizeof(num), ":%.17g", blen[v]); out += num; }
+	};
+	std::vector<std::pair<int32_t, int32_t>> st;       /* node, next child */
+	st.push_back({0, t->childOff[0]});
+	if(n > 1) out += '(';
+	while(!st.empty()) {
+		auto& f = st.back();
+		const int32_t v = f.first;
+		if(f.second < t->childOff[v + 1]) {
+			if(f.second > t->childOff[v]) out += ',';
+			const int32_t c = t->childIdx[f.second++];
+			if(t->childOff[c] != t->childOff[c + 1]) out += '(';
+			st.push_back({c, t->childOff[c]});
+			continue;
+		}
+		if(t->childOff[v] != t->childOff[v + 1]) out += ')';
+		close_node(v);
+		st.pop_back();
+	}
+	out += ";\n";
+	if(cap > 0) { const size_t k = std::min<size_t>(out.size(), (size_t) cap - 1); memcpy(buf, out.data(), k); buf[k] = 0; }
+	return (int64_t) out.size();
+} catch(...) { return hu_catch_all("hu_newick_write"); }
 
 /* ---- loadAnnotation, formatName, annotate (src/PhyloTreeUnrooted.cpp:223-240, :956-1006; src/PhyloTreeUnrooted.h:1531-1578) ---- */
 struct hu_tree_anno { std::vector<std::string> names, annos; std::vector<double> dist; };

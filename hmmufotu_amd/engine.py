@@ -961,6 +961,112 @@ def nj_timing() -> dict:
     return dict(to_device=s[0], distances=s[1], joins=s[2], to_host=s[3])
 
 
+class BlenRound(C.Structure):
+    _fields_ = [("ll", C.c_double), ("s", C.c_double), ("delta", C.c_double), ("n_capped", C.c_int64)]
+
+
+class BlenOpts(C.Structure):
+    _fields_ = [("eps", C.c_double), ("min_len", C.c_double), ("max_len", C.c_double), ("max_rounds", C.c_int32), ("host", C.c_int32),
+                ("device", C.c_int32), ("rounds_cap", C.c_int32), ("mem_budget", C.c_int64), ("rounds", C.POINTER(BlenRound)),
+                ("n_rounds", C.c_int32), ("stop", C.c_int32), ("ll_start", C.c_double), ("ll_final", C.c_double), ("n_capped", C.c_int64)]
+
+
+BLEN_TAU = 1e-8
+BLEN_LDS_COLS = 1450
+BLEN_STOP = ("converged", "no improving step", "max rounds")
+
+
+def _blen_args(what, parent, blen, seq, model, eps, min_len, max_len, max_rounds, device, host, mem_budget):
+    parent = np.ascontiguousarray(parent, np.int32); blen = np.ascontiguousarray(blen, np.float64).copy()
+    seq = np.ascontiguousarray(seq, np.int8)
+    if seq.ndim != 2 or parent.shape != (seq.shape[0],) or blen.shape != parent.shape:
+        raise EngineError(what + ": parent [n], blen [n] and seq [n][cs_len]")
+    o = BlenOpts()
+    load_library().hu_blen_default_opts(C.byref(o))
+    if eps is not None:
+        o.eps = float(eps)
+    if min_len is not None:
+        o.min_len = float(min_len)
+    if max_len is not None:
+        o.max_len = float(max_len)
+    if max_rounds is not None:
+        o.max_rounds = int(max_rounds)
+    o.host = 1 if host else 0; o.device = int(device); o.mem_budget = int(mem_budget or 0)
+    n, L = seq.shape
+    head = (C.byref(o), C.c_int32(n), C.c_int32(L), _p(parent, C.c_int32), _p(blen, C.c_double), _p(seq, C.c_int8), C.byref(model))
+    return o, blen, n, head
+
+
+def blen_need(n_nodes: int, cs_len: int) -> int:
+    """hu_blen_need: the bytes the branch-length fit holds for n_nodes x cs_len"""
+    lib = load_library()
+    lib.hu_blen_need.restype = C.c_int64
+    return int(lib.hu_blen_need(C.c_int32(n_nodes), C.c_int32(cs_len)))
+
+
+def tree_branch_scores(parent, blen, seq, model: ModelDesc, t=None, device=0, host=False, mem_budget=0) -> dict:
+    """hu_tree_branch_scores: f_u, f_u', f_u'' [n] of every branch at t [n] (None: at blen), all other lengths as in blen; seq [n][cs_len]
+    holds the leaf rows in the codes of msa_encode_table.  The root's entries are 0.  host: the library's host path."""
+    o, blen, n, head = _blen_args("tree_branch_scores", parent, blen, seq, model, None, None, None, None, device, host, mem_budget)
+    tt = np.ascontiguousarray(t, np.float64) if t is not None else None
+    if tt is not None and tt.shape != (n,):
+        raise EngineError("tree_branch_scores: t [n]")
+    out = dict(f=np.zeros(n), d1=np.zeros(n), d2=np.zeros(n))
+    _chk(load_library().hu_tree_branch_scores(*head, _p(tt, C.c_double) if tt is not None else None, _p(out["f"], C.c_double),
+                                              _p(out["d1"], C.c_double), _p(out["d2"], C.c_double)))
+    return out
+
+
+def tree_branch_step(parent, blen, seq, model: ModelDesc, min_len=None, max_len=None, device=0, host=False, mem_budget=0) -> dict:
+    """hu_tree_branch_step: t_star [n], the maximiser of every f_u on [min_len, max_len] with the other lengths as in blen, to BLEN_TAU;
+    f, d1, d2 at blen; capped [n]: the branches that hit the Newton cap"""
+    o, blen, n, head = _blen_args("tree_branch_step", parent, blen, seq, model, None, min_len, max_len, None, device, host, mem_budget)
+    out = dict(t_star=np.zeros(n), f=np.zeros(n), d1=np.zeros(n), d2=np.zeros(n), capped=np.zeros(n, np.uint8))
+    _chk(load_library().hu_tree_branch_step(*head, _p(out["t_star"], C.c_double), _p(out["f"], C.c_double), _p(out["d1"], C.c_double),
+                                            _p(out["d2"], C.c_double), _p(out["capped"], C.c_uint8)))
+    out["n_capped"] = int(o.n_capped)
+    return out
+
+
+def tree_optimize_lengths(parent, blen, seq, model: ModelDesc, eps=None, min_len=None, max_len=None, max_rounds=None, device=0, host=False,
+                          mem_budget=0) -> dict:
+    """hu_tree_optimize_lengths: rounds of simultaneous branch steps with a halved step until the log-likelihood rises.  dict(blen [n],
+    ll_start, ll_final, stop (one of BLEN_STOP), rounds: per accepted round (ll, s, delta, n_capped), n_capped, seconds)"""
+    o, blen, n, head = _blen_args("tree_optimize_lengths", parent, blen, seq, model, eps, min_len, max_len, max_rounds, device, host, mem_budget)
+    cap = max(int(o.max_rounds), 1)
+    rec = (BlenRound * cap)()
+    o.rounds = C.cast(rec, C.POINTER(BlenRound)); o.rounds_cap = cap
+    _chk(load_library().hu_tree_optimize_lengths(*head))
+    s = np.zeros(4)
+    _chk(load_library().hu_blen_timing(_p(s, C.c_double)))
+    return dict(blen=blen, ll_start=float(o.ll_start), ll_final=float(o.ll_final), stop=BLEN_STOP[o.stop], n_capped=int(o.n_capped),
+                rounds=[dict(ll=r.ll, s=r.s, delta=r.delta, n_capped=int(r.n_capped)) for r in rec[:o.n_rounds]],
+                seconds=dict(sweep=s[0], step=s[1], trial=s[2], other=s[3]))
+
+
+def newick_write(text, blen) -> str:
+    """hu_newick_parse + hu_newick_write: the tree of `text` with the lengths blen [n] (node ids of newick_parse), 17 significant digits"""
+    lib = load_library()
+    lib.hu_newick_write.restype = C.c_int64
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    h = C.c_void_p()
+    _chk(lib.hu_newick_parse(raw, C.c_int64(len(raw)), C.byref(h)))
+    try:
+        n = C.c_int32(0)
+        lib.hu_newick_size(h, C.byref(n))
+        b = np.ascontiguousarray(blen, np.float64)
+        if b.shape != (n.value,):
+            raise EngineError("newick_write: blen [%d]" % n.value)
+        k = int(lib.hu_newick_write(h, _p(b, C.c_double), None, C.c_int64(0)))
+        if k < 0:
+            _chk(k)
+        buf = C.create_string_buffer(k + 1)
+        lib.hu_newick_write(h, _p(b, C.c_double), buf, C.c_int64(k + 1))
+        return buf.value.decode()
+    finally:
+        lib.hu_newick_free(h)
+
+
 def tree_count_mutations(parent, cs_len: int, up_ptr: int, device=0) -> np.ndarray:
     """hu_tree_count_mutations: per column, the non-root nodes whose inferred state differs from their parent's, from the DEVICE
     fixed-rate up buffer at up_ptr ([n][cs_len][4] float64, as tree_evaluate leaves it with win_len 0)"""

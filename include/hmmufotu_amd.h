@@ -1118,6 +1118,76 @@ int hu_nj_timing(double* seconds /* [4] */);
 int64_t hu_nj_newick(int64_t n, const char* const* names, const int32_t* join, const double* len, const int32_t* last3, const double* last_len3,
 		char* buf, int64_t cap);
 
+/* ---- hmmufotu-amd-tree --ml-lengths: maximum-likelihood branch lengths on a fixed topology ----
+ * The tree is given as hu_tree_evaluate takes it: parent [n] (-1: the root), blen [n] (the root's is not read), seq [n][cs_len] with the
+ * leaf rows in the codes of hu_msa_encode_table (inner rows are not read).  The model is the fixed-rate one: dg_k > 0 is refused with
+ * HU_ERR_ARG, because the reference averages the rate categories at every inner node (src/PhyloTreeUnrooted.cpp:340-341), which leaves
+ * no objective of one branch that does not depend on the root.
+ *
+ * The objective of the branch above a non-root node u, all other lengths fixed.  With up[u] the message of u's subtree at u and down[u]
+ * that of everything else at u's parent (log space, neither carried over the branch: the convention of hu_tree_evaluate,
+ * src/PhyloTreeUnrooted.cpp:315-374), x = exp(up[u][j] - max), y = exp(down[u][j] - max) and P(t) = U diag(exp(lam t)) U1
+ * (hu_model_spectral; lam[0] = 0, U[.][0] = 1, U1[0][.] = pi):
+ *   L_j(t) = sum_ab pi_a x_a P_ab(t) y_b = sum_k c_jk exp(lam_k t),   c_jk = (sum_a pi_a x_a U_ak) (sum_b U1_kb y_b),
+ *   f_u(t) = sum_j log L_j(t) = sum_j [ log c_j0 + max up + max down + log(1 + sum_k>0 r_jk exp(lam_k t)) ],   r_jk = c_jk / c_j0,
+ * c_j0 = (pi . x)(pi . y) > 0.  With N_j = sum_k r_jk lam_k e_k, M_j = sum_k r_jk lam_k^2 e_k, D_j = 1 + sum_k r_jk e_k:
+ *   f_u'(t) = sum_j N_j / D_j,   f_u''(t) = sum_j [ M_j / D_j - (N_j / D_j)^2 ].
+ * f_u(blen[u]) is the tree's log-likelihood for every u (the value of hu_tree_loglik; src/PhyloTreeUnrooted.cpp:707-712).
+ *
+ * hu_tree_branch_scores: f, d1, d2 [n] = f_u, f_u', f_u'' at t[u] (t == NULL: at blen[u]); the root's entries are 0.
+ * hu_tree_branch_step: t_star [n] = the maximiser of f_u on [min_len, max_len] by safeguarded Newton on f_u': a bracket is kept, and the
+ *   step is a bisection when f_u'' >= 0 or Newton's step leaves the bracket; f_u'(min_len) <= 0 gives min_len, f_u'(max_len) >= 0 gives
+ *   max_len.  It stops at a step of at most HU_BLEN_TAU, after HU_BLEN_MAX_NEWTON steps at the latest; capped [n] (may be NULL) marks
+ *   the branches that hit that cap and opts->n_capped counts them.  f, d1, d2 (may be NULL): the scores at blen[u].  The reference
+ *   fits one branch at a time to BRANCH_EPS in the same way (optimizeBranchLength, src/PhyloTreeUnrooted.cpp:749-798).
+ * hu_tree_optimize_lengths: rounds of simultaneous steps on blen [n], in place.  From ll = the log-likelihood at blen, a round sweeps
+ *   up and down, takes t* of every branch and delta = max_u |t*_u - blen_u|; delta <= eps ends the run as converged.  Otherwise
+ *   cand = blen + s (t* - blen) for s = 1, 1/2, ... (10 values at the most), each with an up sweep and the serial column sum of
+ *   hu_tree_loglik; the first cand with a larger ll is taken, and if none is the run stops.  At most max_rounds rounds.  The report:
+ *   ll_start, ll_final, n_rounds, stop, and per accepted round (rounds, when not NULL, holds rounds_cap entries) ll, s, delta and the
+ *   branches that hit the Newton cap.  The two branches at a bifurcating root are one branch of the unrooted tree: each is fitted given
+ *   the other, and only their sum is determined.
+ * Memory: 64 n cs_len bytes of messages, n cs_len of rows, 24 n cs_len of ratios when cs_len is above HU_BLEN_LDS_COLS, 8 cs_len of column
+ * values and 1 MB of slack (hu_blen_need).  It is held against mem_budget (when > 0) before anything is allocated, on the host path too,
+ * and on the device against the free memory: HU_ERR_NOMEM names both numbers.  opts->host, or device < 0, runs the host path
+ * (hu_blen_host.cpp), which needs no device.  hu_blen_timing: seconds [4] of this thread's last hu_tree_optimize_lengths = the full
+ * sweeps, the steps, the trial sweeps with their log-likelihoods, the copies. */
+#define HU_BLEN_TAU 1e-8           /* at most eps / 100 for every eps the entries take: eps below 1e-6 is refused */
+#define HU_BLEN_MAX_NEWTON 100
+#define HU_BLEN_MAX_HALVINGS 10
+#define HU_BLEN_LDS_COLS 1450      /* the ratios of a branch stay in LDS up to this many columns: 24 cs_len + 6 KB of reduction scratch, four workgroups in a CU's 160 KB;
+                                    * with fewer workgroups per CU the global scratch, which the L2 holds, was measured faster */
+enum { HU_BLEN_CONVERGED = 0, HU_BLEN_NO_STEP = 1, HU_BLEN_MAX_ROUNDS = 2 };
+typedef struct { double ll, s, delta; int64_t n_capped; } hu_blen_round;
+typedef struct {
+	double eps;           /* 1e-5, the reference's BRANCH_EPS (src/PhyloTreeUnrooted.cpp:71) */
+	double min_len;       /* 0 */
+	double max_len;       /* 10 */
+	int32_t max_rounds;   /* 50 */
+	int32_t host;         /* 0; 1: the host path, no device needed */
+	int32_t device;       /* 0 */
+	int32_t rounds_cap;   /* entries of rounds */
+	int64_t mem_budget;   /* 0: what the device reports free */
+	hu_blen_round* rounds;
+	/* the report */
+	int32_t n_rounds, stop;
+	double ll_start, ll_final;
+	int64_t n_capped;     /* hu_tree_branch_step: branches at the Newton cap; hu_tree_optimize_lengths: of all rounds */
+} hu_blen_opts;
+void hu_blen_default_opts(hu_blen_opts* o);
+int64_t hu_blen_need(int32_t n_nodes, int32_t cs_len);
+int hu_tree_branch_scores(const hu_blen_opts* opts, int32_t n_nodes, int32_t cs_len, const int32_t* parent, const double* blen, const int8_t* seq,
+		const hu_model_desc* model, const double* t, double* f, double* d1, double* d2);
+int hu_tree_branch_step(hu_blen_opts* opts, int32_t n_nodes, int32_t cs_len, const int32_t* parent, const double* blen, const int8_t* seq,
+		const hu_model_desc* model, double* t_star, double* f, double* d1, double* d2, uint8_t* capped);
+int hu_tree_optimize_lengths(hu_blen_opts* opts, int32_t n_nodes, int32_t cs_len, const int32_t* parent, double* blen, const int8_t* seq,
+		const hu_model_desc* model);
+int hu_blen_timing(double* seconds /* [4] */);
+/* the tree of hu_newick_parse written back with other branch lengths (blen [n], the root's is not written) at 17 significant digits:
+ * the same topology, names and order of children; a name that is no unquoted label is written in single quotes.  Returns the length
+ * (without the terminator) and writes at most cap bytes, terminator included; HU_ERR_ARG (negative) on a bad argument.  Host only. */
+int64_t hu_newick_write(const hu_newick* t, const double* blen, char* buf, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif
