@@ -3,7 +3,8 @@
 // distances of the rows, not a maximum-likelihood search: the usual starting tree of the ML packages.
 //   hmmufotu-amd-tree <MSA-FILE> [-o TREE] [-sm FILE] [--dist pdist|JC69|K80|F81|HKY85|TN93] [--dist-out FILE] [--sat DBL] [--mem GB]
 //                     [--device N] [--host] [-v]
-//                     [--ml-lengths [--start-tree FILE] [--ml-rounds N] [--ml-eps DBL] [--min-len DBL] [--max-len DBL] [--ml-log FILE]]
+//                     [--ml-lengths [--start-tree FILE] [--ml-rounds N] [--ml-eps DBL] [--min-len DBL] [--max-len DBL] [--ml-log FILE]
+//                      [--nni [--nni-rounds N] [--nni-min-gain DBL] [--nni-log FILE]]]
 // The MSA is read and pruned as hmmufotu-amd-build does (hu_build_inputs.h; the columns without a residue are found on the host here,
 // the same columns hu_prune_msa finds), so the tree joins by name to the same MSA there.  The distances and the joins are
 // hu_msa_tree's: on the device (hu_kern_dist.h, hu_kern_nj.h), or with --host by the library's host path.  Every refusal comes before
@@ -11,6 +12,8 @@
 // --ml-lengths keeps the topology, of the joins or of --start-tree, and fits its branch lengths by maximum likelihood
 // under the fixed-rate model of -sm (hu_tree_optimize_lengths; a GTR file is used as GTR here).  The tree goes through hu_newick_parse
 // either way, and hu_newick_write puts the same topology, names and order of children back with the new lengths.
+// --nni lets the topology move: a hill climb over nearest-neighbour interchanges from that tree (hu_tree_nni_search),
+// written by hu_newick_from_arrays with the same node ids, names and top node.
 #include <cmath>
 #include <cstdlib>
 #include <memory>
@@ -42,6 +45,10 @@ static void usage(const char* p) {
 		"            --min-len  DBL     : smallest branch length [0]\n"
 		"            --max-len  DBL     : largest branch length [10]\n"
 		"            --ml-log  FILE     : write the rounds as TSV: round, ll, s, delta, capped; a last line '# stop: REASON'\n"
+		"            --nni  FLAG        : with --ml-lengths: improve the topology by nearest-neighbour interchanges, a hill climb on the log-likelihood\n"
+		"            --nni-rounds  INT  : rounds of interchanges at the most, at least 1 [20]\n"
+		"            --nni-min-gain  DBL: smallest gain in log-likelihood for which an interchange is tried, above 0 [1e-3]\n"
+		"            --nni-log  FILE    : write the accepted rounds as TSV: round, ll, scored, candidates, taken, applied; then '# stop: REASON' and '# skipped: N edges at polytomies'\n"
 		"            -v  FLAG           : enable verbose information, you may set multiple -v for more details\n"
 		"            --version          : show program version and exit\n"
 		"            -h|--help          : print this message and exit\n";
@@ -51,6 +58,7 @@ int main(int argc, char** argv) {
 	std::vector<std::string> pos; std::string outFn, fmt, smFn, distName, distFn; bool host = false, haveSat = false; int device = 0, verbose = 0;
 	double sat = 0, memGB = 0; bool haveMem = false;
 	bool mlLengths = false; std::string startFn, mlLogFn; int mlRounds = 50; double mlEps = 1e-5, minLen = 0.0, maxLen = 10.0;
+	bool nni = false, haveNniOpt = false; std::string nniLogFn; int nniRounds = 20; double nniMinGain = 1e-3;
 	if(argc < 2) { usage(argv[0]); return EXIT_SUCCESS; }
 	for(int i = 1; i < argc; ++i) {
 		std::string a = argv[i];
@@ -65,6 +73,9 @@ int main(int argc, char** argv) {
 		else if(a == "--ml-lengths") mlLengths = true; else if(a == "--start-tree") startFn = val(); else if(a == "--ml-log") mlLogFn = val();
 		else if(a == "--ml-rounds") mlRounds = atoi(val()); else if(a == "--ml-eps") mlEps = atof(val());
 		else if(a == "--min-len") minLen = atof(val()); else if(a == "--max-len") maxLen = atof(val());
+		else if(a == "--nni") nni = true;
+		else if(a == "--nni-rounds") { nniRounds = atoi(val()); haveNniOpt = true; } else if(a == "--nni-min-gain") { nniMinGain = atof(val()); haveNniOpt = true; }
+		else if(a == "--nni-log") { nniLogFn = val(); haveNniOpt = true; }
 		else if(a.size() > 1 && a[0] == '-' && a.find_first_not_of('v', 1) == std::string::npos) verbose += (int) a.size() - 1;
 		else if(a[0] == '-' && a.size() > 1) { std::cerr << "Error: unknown option " << a << std::endl; return EXIT_FAILURE; }
 		else pos.push_back(a);
@@ -80,6 +91,12 @@ int main(int argc, char** argv) {
 	if(haveMem && (!(memGB > 0) || !std::isfinite(memGB))) { std::cerr << "--mem must be positive" << std::endl; return EXIT_FAILURE; }
 	if(device < 0) { std::cerr << "--device must be non-negative; --host runs without one" << std::endl; return EXIT_FAILURE; }
 	if(!mlLengths && (!startFn.empty() || !mlLogFn.empty())) { std::cerr << (startFn.empty() ? "--ml-log" : "--start-tree") << " goes with --ml-lengths" << std::endl; return EXIT_FAILURE; }
+	if(nni && !mlLengths) { std::cerr << "--nni goes with --ml-lengths" << std::endl; return EXIT_FAILURE; }
+	if(haveNniOpt && !nni) { std::cerr << "--nni-rounds, --nni-min-gain and --nni-log go with --nni" << std::endl; return EXIT_FAILURE; }
+	if(nni) {
+		if(nniRounds < 1) { std::cerr << "--nni-rounds must be at least 1" << std::endl; return EXIT_FAILURE; }
+		if(!(nniMinGain > 0) || !std::isfinite(nniMinGain)) { std::cerr << "--nni-min-gain must be above 0" << std::endl; return EXIT_FAILURE; }
+	}
 	if(mlLengths) {
 		if(smFn.empty()) { std::cerr << "--ml-lengths fits the branch lengths under a substitution model: -sm is required" << std::endl; return EXIT_FAILURE; }
 		if(!(mlEps > 0) || !std::isfinite(mlEps)) { std::cerr << "--ml-eps must be positive" << std::endl; return EXIT_FAILURE; }
@@ -182,8 +199,8 @@ int main(int argc, char** argv) {
 		fitNodes = nn;
 	}
 	if(mlLengths && haveMem) {
-		const int64_t need = hu_blen_need((int32_t) fitNodes, (int32_t) L), have = (int64_t)(memGB * 1e9);
-		if(need > have) { std::cerr << "--ml-lengths: " << fitNodes << " nodes of " << L << " columns need " << need << " bytes (64 bytes per node and column for the messages), --mem allows " << have << " bytes" << std::endl; return EXIT_FAILURE; }
+		const int64_t need = nni ? hu_nni_need((int32_t) fitNodes, (int32_t) L) : hu_blen_need((int32_t) fitNodes, (int32_t) L), have = (int64_t)(memGB * 1e9);
+		if(need > have) { std::cerr << (nni ? "--nni: " : "--ml-lengths: ") << fitNodes << " nodes of " << L << " columns need " << need << " bytes (64 bytes per node and column for the messages), --mem allows " << have << " bytes" << std::endl; return EXIT_FAILURE; }
 	}
 
 	hu_nj_opts o;
@@ -218,7 +235,44 @@ int main(int argc, char** argv) {
 	hu_blen_opts bo;
 	hu_blen_default_opts(&bo);
 	std::vector<hu_blen_round> rounds;
-	if(mlLengths) {
+	if(mlLengths && nni) {
+		std::vector<int8_t> seq((size_t) nn * L, (int8_t) -2);
+		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(hu_newick_name(nw.get(), i)) * L, L);
+		for(int32_t i = 0; i < nn; ++i) if(parent[i] >= 0 && std::isfinite(blen[i])) blen[i] = std::min(std::max(blen[i], minLen), maxLen);
+		hu_nni_opts no;
+		hu_nni_default_opts(&no);
+		std::vector<hu_nni_round> nrounds((size_t) nniRounds);
+		no.blen.eps = mlEps; no.blen.min_len = minLen; no.blen.max_len = maxLen; no.blen.max_rounds = mlRounds; no.blen.host = host ? 1 : 0; no.blen.device = device;
+		no.blen.mem_budget = haveMem ? (int64_t)(memGB * 1e9) : 0;
+		no.nni_rounds = nniRounds; no.min_gain = nniMinGain; no.rounds = nrounds.data(); no.rounds_cap = nniRounds;
+		if(hu_tree_nni_search(&no, nn, (int32_t) L, parent.data(), blen.data(), seq.data(), childOff.data(), childIdx.data(), &md) != HU_OK) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
+		static const char* const why[] = {"local optimum", "no improving swap", "max rounds"};
+		if(verbose) {
+			char line[240];
+			snprintf(line, sizeof(line), "NNI search: log-likelihood %.17g -> %.17g, %lld swap(s) applied in %d round(s), stop: %s", no.ll_start, no.ll_final, (long long) no.n_swaps, no.n_rounds, why[no.stop]);
+			std::cerr << line << std::endl;
+			if(no.skipped > 0) std::cerr << no.skipped << " edge(s) at polytomies were not scored" << std::endl;
+			double s[4];
+			hu_nni_timing(s);
+			std::cerr << "fits " << s[0] << " s, scoring " << s[1] << " s, trials " << s[2] << " s, the rest " << s[3] << " s" << std::endl;
+		}
+		std::vector<const char*> nodeName((size_t) nn);
+		for(int32_t i = 0; i < nn; ++i) nodeName[i] = hu_newick_name(nw.get(), i);
+		const int64_t wl = hu_newick_from_arrays(nn, parent.data(), childOff.data(), childIdx.data(), nodeName.data(), blen.data(), nullptr, 0);
+		if(wl < 0) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
+		text.assign((size_t) wl + 1, '\0');
+		hu_newick_from_arrays(nn, parent.data(), childOff.data(), childIdx.data(), nodeName.data(), blen.data(), &text[0], wl + 1);
+		text.resize((size_t) wl);
+		if(!nniLogFn.empty()) {
+			FILE* f = fopen(nniLogFn.c_str(), "w");
+			if(!f) { std::cerr << "Unable to write to '" << nniLogFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+			fprintf(f, "round\tll\tscored\tcandidates\ttaken\tapplied\n0\t%.17g\t0\t0\t0\t0\n", no.ll_start);
+			for(int32_t r = 0; r < no.n_rounds; ++r) fprintf(f, "%d\t%.17g\t%d\t%d\t%d\t%d\n", r + 1, nrounds[r].ll, nrounds[r].scored, nrounds[r].candidates, nrounds[r].taken, nrounds[r].applied);
+			fprintf(f, "# stop: %s\n# skipped: %lld edges at polytomies\n", why[no.stop], (long long) no.skipped);
+			if(fclose(f) != 0) { std::cerr << "Unable to write to '" << nniLogFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+		}
+	}
+	else if(mlLengths) {
 		std::vector<int8_t> seq((size_t) nn * L, (int8_t) -2);
 		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(hu_newick_name(nw.get(), i)) * L, L);
 		/* a start outside the interval, a negative length of the joins' last node among them, begins at its nearer end */

@@ -1067,6 +1067,132 @@ def newick_write(text, blen) -> str:
         lib.hu_newick_free(h)
 
 
+class NniRound(C.Structure):
+    _fields_ = [("ll", C.c_double), ("scored", C.c_int32), ("candidates", C.c_int32), ("taken", C.c_int32), ("applied", C.c_int32)]
+
+
+class NniOpts(C.Structure):
+    _fields_ = [("blen", BlenOpts), ("min_gain", C.c_double), ("nni_rounds", C.c_int32), ("rounds_cap", C.c_int32),
+                ("rounds", C.POINTER(NniRound)), ("swaps", C.POINTER(C.c_int32)), ("swaps_cap", C.c_int64),
+                ("n_rounds", C.c_int32), ("stop", C.c_int32), ("n_swaps", C.c_int64), ("skipped", C.c_int64),
+                ("ll_start", C.c_double), ("ll_final", C.c_double)]
+
+
+NNI_LDS_COLS = 483
+NNI_STOP = ("local optimum", "no improving swap", "max rounds")
+
+
+def _nni_args(what, parent, blen, seq, model, eps, min_len, max_len, max_rounds, device, host, mem_budget, nni_rounds=None, min_gain=None):
+    parent = np.ascontiguousarray(parent, np.int32).copy(); blen = np.ascontiguousarray(blen, np.float64).copy()
+    seq = np.ascontiguousarray(seq, np.int8)
+    if seq.ndim != 2 or parent.shape != (seq.shape[0],) or blen.shape != parent.shape:
+        raise EngineError(what + ": parent [n], blen [n] and seq [n][cs_len]")
+    o = NniOpts()
+    load_library().hu_nni_default_opts(C.byref(o))
+    for k, v in (("eps", eps), ("min_len", min_len), ("max_len", max_len)):
+        if v is not None:
+            setattr(o.blen, k, float(v))
+    if max_rounds is not None:
+        o.blen.max_rounds = int(max_rounds)
+    if nni_rounds is not None:
+        o.nni_rounds = int(nni_rounds)
+    if min_gain is not None:
+        o.min_gain = float(min_gain)
+    o.blen.host = 1 if host else 0; o.blen.device = int(device); o.blen.mem_budget = int(mem_budget or 0)
+    return o, parent, blen, seq
+
+
+def nni_need(n_nodes: int, cs_len: int) -> int:
+    """hu_nni_need: the bytes the NNI search holds for n_nodes x cs_len"""
+    lib = load_library()
+    lib.hu_nni_need.restype = C.c_int64
+    return int(lib.hu_nni_need(C.c_int32(n_nodes), C.c_int32(cs_len)))
+
+
+def tree_nni_scores(parent, blen, seq, model: ModelDesc, min_len=None, max_len=None, device=0, host=False, mem_budget=0) -> dict:
+    """hu_tree_nni_scores: for the E eligible edges in ascending u, dict(edge_node [E], t_star [E][3], f [E][3], f0_at_blen [E], skipped):
+    the optimum and the value of the edge's three arrangements (0: as it stands, 1: B and C exchanged, 2: A and C exchanged)"""
+    o, parent, blen, seq = _nni_args("tree_nni_scores", parent, blen, seq, model, None, min_len, max_len, None, device, host, mem_budget)
+    n, L = seq.shape
+    cap = max((n - 1) // 2, 1)
+    node = np.zeros(cap, np.int32); ts = np.zeros((cap, 3)); f = np.zeros((cap, 3)); f0 = np.zeros(cap)
+    ne = C.c_int32(0); sk = C.c_int64(0)
+    _chk(load_library().hu_tree_nni_scores(C.byref(o), C.c_int32(n), C.c_int32(L), _p(parent, C.c_int32), _p(blen, C.c_double), _p(seq, C.c_int8),
+                                           C.byref(model), C.c_int32(cap), C.byref(ne), C.byref(sk), _p(node, C.c_int32), _p(ts, C.c_double),
+                                           _p(f, C.c_double), _p(f0, C.c_double)))
+    e = ne.value
+    return dict(edge_node=node[:e].copy(), t_star=ts[:e].copy(), f=f[:e].copy(), f0_at_blen=f0[:e].copy(), skipped=int(sk.value))
+
+
+def _child_arrays(parent, child_off, child_idx):
+    """the order of children: as given, or in node-id order"""
+    n = len(parent)
+    if child_off is not None:
+        return np.ascontiguousarray(child_off, np.int32).copy(), np.ascontiguousarray(child_idx, np.int32).copy()
+    off = np.zeros(n + 1, np.int32)
+    for p in parent:
+        if p >= 0:
+            off[p + 1] += 1
+    off = np.cumsum(off).astype(np.int32)
+    idx = np.zeros(max(n - 1, 1), np.int32); fill = off[:-1].copy()
+    for i, p in enumerate(parent):
+        if p >= 0:
+            idx[fill[p]] = i; fill[p] += 1
+    return off, idx
+
+
+def tree_nni_apply(parent, blen, u: int, q: int, t: float, child_off=None, child_idx=None) -> dict:
+    """hu_tree_nni_apply: arrangement q (1: B and C exchanged, 2: A and C exchanged) of the edge above u, its central length set to t.
+    dict(parent, blen, child_off, child_idx), the inputs are not changed"""
+    parent = np.ascontiguousarray(parent, np.int32).copy(); blen = np.ascontiguousarray(blen, np.float64).copy()
+    off, idx = _child_arrays(parent, child_off, child_idx)
+    _chk(load_library().hu_tree_nni_apply(C.c_int32(len(parent)), _p(parent, C.c_int32), _p(blen, C.c_double), _p(off, C.c_int32), _p(idx, C.c_int32),
+                                          C.c_int32(int(u)), C.c_int32(int(q)), C.c_double(float(t))))
+    return dict(parent=parent, blen=blen, child_off=off, child_idx=idx)
+
+
+def tree_nni_search(parent, blen, seq, model: ModelDesc, child_off=None, child_idx=None, nni_rounds=None, min_gain=None, eps=None, min_len=None,
+                    max_len=None, max_rounds=None, device=0, host=False, mem_budget=0) -> dict:
+    """hu_tree_nni_search: the hill climb over NNIs.  dict(parent, blen, child_off, child_idx, ll_start, ll_final, stop (one of NNI_STOP),
+    skipped, rounds: per accepted round (ll, scored, candidates, taken, applied), swaps: per applied swap (round, u, q), seconds)"""
+    o, parent, blen, seq = _nni_args("tree_nni_search", parent, blen, seq, model, eps, min_len, max_len, max_rounds, device, host, mem_budget,
+                                     nni_rounds, min_gain)
+    n, L = seq.shape
+    off, idx = _child_arrays(parent, child_off, child_idx)
+    cap = max(int(o.nni_rounds), 1)
+    rec = (NniRound * cap)()
+    scap = cap * max((n - 1) // 2, 1)
+    sw = np.zeros((scap, 3), np.int32)
+    o.rounds = C.cast(rec, C.POINTER(NniRound)); o.rounds_cap = cap; o.swaps = _p(sw, C.c_int32); o.swaps_cap = scap
+    _chk(load_library().hu_tree_nni_search(C.byref(o), C.c_int32(n), C.c_int32(L), _p(parent, C.c_int32), _p(blen, C.c_double), _p(seq, C.c_int8),
+                                           _p(off, C.c_int32), _p(idx, C.c_int32), C.byref(model)))
+    s = np.zeros(4)
+    _chk(load_library().hu_nni_timing(_p(s, C.c_double)))
+    return dict(parent=parent, blen=blen, child_off=off, child_idx=idx, ll_start=float(o.ll_start), ll_final=float(o.ll_final), stop=NNI_STOP[o.stop],
+                skipped=int(o.skipped),
+                rounds=[dict(ll=r.ll, scored=r.scored, candidates=r.candidates, taken=r.taken, applied=r.applied) for r in rec[:o.n_rounds]],
+                swaps=[tuple(int(x) for x in row) for row in sw[:o.n_swaps]], seconds=dict(fit=s[0], score=s[1], trial=s[2], other=s[3]))
+
+
+def newick_from_arrays(parent, child_off, child_idx, names, blen) -> str:
+    """hu_newick_from_arrays: Newick text from parent, the order of children, names ("" or None for none) and blen"""
+    lib = load_library()
+    lib.hu_newick_from_arrays.restype = C.c_int64
+    parent = np.ascontiguousarray(parent, np.int32); n = len(parent)
+    off, idx = _child_arrays(parent, child_off, child_idx)
+    b = np.ascontiguousarray(blen, np.float64)
+    if b.shape != (n,) or len(names) != n:
+        raise EngineError("newick_from_arrays: blen [n] and names [n]")
+    nm = (C.c_char_p * n)(*[(x or "").encode() for x in names])
+    head = (C.c_int32(n), _p(parent, C.c_int32), _p(off, C.c_int32), _p(idx, C.c_int32), nm, _p(b, C.c_double))
+    k = int(lib.hu_newick_from_arrays(*head, None, C.c_int64(0)))
+    if k < 0:
+        _chk(k)
+    buf = C.create_string_buffer(k + 1)
+    lib.hu_newick_from_arrays(*head, buf, C.c_int64(k + 1))
+    return buf.value.decode()
+
+
 def tree_count_mutations(parent, cs_len: int, up_ptr: int, device=0) -> np.ndarray:
     """hu_tree_count_mutations: per column, the non-root nodes whose inferred state differs from their parent's, from the DEVICE
     fixed-rate up buffer at up_ptr ([n][cs_len][4] float64, as tree_evaluate leaves it with win_len 0)"""

@@ -1188,6 +1188,67 @@ int hu_blen_timing(double* seconds /* [4] */);
  * (without the terminator) and writes at most cap bytes, terminator included; HU_ERR_ARG (negative) on a bad argument.  Host only. */
 int64_t hu_newick_write(const hu_newick* t, const double* blen, char* buf, int64_t cap);
 
+/* ---- hmmufotu-amd-tree --ml-lengths --nni: a hill climb over nearest-neighbour interchanges ----
+ * The tree, the model and the limits are those of the branch-length fit above: parent [n], blen [n], seq [n][cs_len], the fixed-rate
+ * model only, one device, no column windows.
+ *
+ * An eligible edge is an edge of the unrooted tree whose two ends have degree three; it is named by its lower end u.  With A < B the
+ * children of u (node-id order) there are three rooted cases: parent[u] = p is not the root and has the children {u, C} (the fourth
+ * subtree is everything above p, carried over blen[p]); p is the root with the children {u, C, D}, C < D; p is a bifurcating root
+ * {u, s} and s has the two children C < D: blen[u] + blen[s] is the one edge, scored from the smaller of u and s.  Leaf edges are not
+ * eligible; an edge between two inner nodes one of which has another degree is not either, and is counted (skipped).
+ * With a, b, c, d the four subtrees' partial likelihoods carried to the ends of the edge, arrangement 0 is (a.b | c.d), the tree as it
+ * stands, 1 is (a.c | b.d), B and C exchanged, and 2 is (b.c | a.d), A and C exchanged.  Each is an objective of the central length t
+ * of the form of the branch-length fit, f^q(t) = sum_j [K^q_j + log(1 + sum_k r^q_jk exp(lam_k t))], and is maximised the same way.
+ *
+ * hu_tree_nni_scores: for the E eligible edges in ascending u, edge_node [E] = u, t_star [E][3] the maximiser of f^q on
+ *   [min_len, max_len], f [E][3] = f^q(t_star), f0_at_blen [E] = f^0 at the current central length: the tree's log-likelihood.
+ *   edge_cap: the entries the outputs hold (at most the number of inner nodes are needed); *n_edges = E, *skipped the edges at
+ *   polytomies.  E = 0 is a success.
+ * hu_tree_nni_apply: arrangement q (1 or 2) of the edge of u on the arrays, the central edge set to t (a root-spanning edge splits
+ *   t in the old proportion, in halves when the old sum is 0): the exchanged subtrees keep their lengths and take each other's place
+ *   in child_off / child_idx (the order of hu_newick_get; child_idx may be NULL).  The root, the node ids and the names stay.  Host.
+ * hu_tree_nni_search: parent, blen (and child_idx) in place.  A round fits the lengths (hu_tree_optimize_lengths with opts->blen),
+ *   scores all eligible edges and takes as candidates those with gain = max(f^1, f^2) - f^0 > min_gain, each at its own t_star.
+ *   No candidate ends the run (local optimum).  The candidates go by gain descending, ties by the smaller u; every one that shares
+ *   no end node with one taken before is taken; the taken swaps are applied at once and the tree's log-likelihood is taken from an
+ *   up sweep.  If it is not above the fit's, the better half (rounded up) of the set is tried, down to one swap; if that fails too
+ *   the run ends (no improving swap).  At most nni_rounds rounds; a last fit follows the last accepted round.  The report: n_rounds,
+ *   stop, n_swaps, skipped, ll_start (after the first fit), ll_final, per accepted round (rounds, rounds_cap entries) the trial's ll,
+ *   the edges scored, the candidates, the swaps taken at first and those applied, and per applied swap (swaps, swaps_cap triples)
+ *   round, u, q.
+ * Memory (hu_nni_need): hu_blen_need plus 160 bytes of edge record and outputs per inner node and, when cs_len is above
+ *   HU_NNI_LDS_COLS, 72 cs_len bytes of ratios per inner node; held against opts->blen.mem_budget and the free memory as above.
+ * hu_nni_timing: seconds [4] of this thread's last hu_tree_nni_search = the fits, the scoring, the trials, the rest.
+ * hu_newick_from_arrays: Newick text from parent, the order of children, names (NULL or "" for none) and blen, with the quoting rule
+ *   and the 17 significant digits of hu_newick_write; the top node is the root of parent.  Returns as hu_newick_write does.  Host. */
+#define HU_NNI_LDS_COLS 483        /* the nine ratios of an edge stay in LDS up to this many columns: 72 cs_len + 6 KB of reduction scratch, four workgroups in a CU's 160 KB */
+enum { HU_NNI_LOCAL_OPTIMUM = 0, HU_NNI_NO_SWAP = 1, HU_NNI_MAX_ROUNDS = 2 };
+typedef struct { double ll; int32_t scored, candidates, taken, applied; } hu_nni_round;
+typedef struct {
+	hu_blen_opts blen;    /* of every fit: eps, min_len, max_len, max_rounds, host, device, mem_budget; its rounds are not recorded */
+	double min_gain;      /* 1e-3, in units of log-likelihood */
+	int32_t nni_rounds;   /* 20 */
+	int32_t rounds_cap;   /* entries of rounds */
+	hu_nni_round* rounds;
+	int32_t* swaps;       /* [swaps_cap][3]: round (from 1), u, q */
+	int64_t swaps_cap;
+	/* the report */
+	int32_t n_rounds, stop;
+	int64_t n_swaps, skipped;
+	double ll_start, ll_final;
+} hu_nni_opts;
+void hu_nni_default_opts(hu_nni_opts* o);
+int64_t hu_nni_need(int32_t n_nodes, int32_t cs_len);
+int hu_tree_nni_scores(const hu_nni_opts* opts, int32_t n_nodes, int32_t cs_len, const int32_t* parent, const double* blen, const int8_t* seq,
+		const hu_model_desc* model, int32_t edge_cap, int32_t* n_edges, int64_t* skipped, int32_t* edge_node, double* t_star, double* f, double* f0_at_blen);
+int hu_tree_nni_apply(int32_t n_nodes, int32_t* parent, double* blen, const int32_t* child_off, int32_t* child_idx, int32_t u, int32_t q, double t);
+int hu_tree_nni_search(hu_nni_opts* opts, int32_t n_nodes, int32_t cs_len, int32_t* parent, double* blen, const int8_t* seq,
+		const int32_t* child_off, int32_t* child_idx, const hu_model_desc* model);
+int hu_nni_timing(double* seconds /* [4] */);
+int64_t hu_newick_from_arrays(int32_t n_nodes, const int32_t* parent, const int32_t* child_off, const int32_t* child_idx, const char* const* names,
+		const double* blen, char* buf, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif
