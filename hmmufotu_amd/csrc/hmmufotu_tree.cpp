@@ -4,7 +4,8 @@
 //   hmmufotu-amd-tree <MSA-FILE> [-o TREE] [-sm FILE] [--dist pdist|JC69|K80|F81|HKY85|TN93] [--dist-out FILE] [--sat DBL] [--mem GB]
 //                     [--device N] [--host] [-v]
 //                     [--ml-lengths [--start-tree FILE] [--ml-rounds N] [--ml-eps DBL] [--min-len DBL] [--max-len DBL] [--ml-log FILE]
-//                      [--nni [--nni-rounds N] [--nni-min-gain DBL] [--nni-log FILE]]]
+//                      [--nni [--nni-rounds N] [--nni-min-gain DBL] [--nni-log FILE]]
+//                      [--support N [--support-seed N] [--support-out FILE]]]
 // The MSA is read and pruned as hmmufotu-amd-build does (hu_build_inputs.h; the columns without a residue are found on the host here,
 // the same columns hu_prune_msa finds), so the tree joins by name to the same MSA there.  The distances and the joins are
 // hu_msa_tree's: on the device (hu_kern_dist.h, hu_kern_nj.h), or with --host by the library's host path.  Every refusal comes before
@@ -14,6 +15,8 @@
 // either way, and hu_newick_write puts the same topology, names and order of children back with the new lengths.
 // --nni lets the topology move: a hill climb over nearest-neighbour interchanges from that tree (hu_tree_nni_search),
 // written by hu_newick_from_arrays with the same node ids, names and top node.
+// --support labels the inner edges of the final tree with their local bootstrap support (hu_tree_nni_support): the share
+// of N resamplings of the columns in which the edge as it stands beats both of its nearest-neighbour interchanges.
 #include <cmath>
 #include <cstdlib>
 #include <memory>
@@ -49,6 +52,9 @@ static void usage(const char* p) {
 		"            --nni-rounds  INT  : rounds of interchanges at the most, at least 1 [20]\n"
 		"            --nni-min-gain  DBL: smallest gain in log-likelihood for which an interchange is tried, above 0 [1e-3]\n"
 		"            --nni-log  FILE    : write the accepted rounds as TSV: round, ll, scored, candidates, taken, applied; then '# stop: REASON' and '# skipped: N edges at polytomies'\n"
+		"            --support  INT     : with --ml-lengths: label every inner edge between two nodes of degree three with its local bootstrap support over INT replicates, 1 to 100000: the share of resampled alignments in which the edge beats both of its nearest-neighbour interchanges\n"
+		"            --support-seed  INT: seed of the replicates [1]\n"
+		"            --support-out  FILE: write the supports as TSV: node, name, kind, leaves, t0, alrt, count, replicates, support; then '# skipped: N edges at polytomies' and '# seed: S'\n"
 		"            -v  FLAG           : enable verbose information, you may set multiple -v for more details\n"
 		"            --version          : show program version and exit\n"
 		"            -h|--help          : print this message and exit\n";
@@ -59,6 +65,7 @@ int main(int argc, char** argv) {
 	double sat = 0, memGB = 0; bool haveMem = false;
 	bool mlLengths = false; std::string startFn, mlLogFn; int mlRounds = 50; double mlEps = 1e-5, minLen = 0.0, maxLen = 10.0;
 	bool nni = false, haveNniOpt = false; std::string nniLogFn; int nniRounds = 20; double nniMinGain = 1e-3;
+	bool support = false, haveSupportOpt = false; long long supportN = 0; unsigned long long supportSeed = 1; std::string supportFn;
 	if(argc < 2) { usage(argv[0]); return EXIT_SUCCESS; }
 	for(int i = 1; i < argc; ++i) {
 		std::string a = argv[i];
@@ -76,6 +83,9 @@ int main(int argc, char** argv) {
 		else if(a == "--nni") nni = true;
 		else if(a == "--nni-rounds") { nniRounds = atoi(val()); haveNniOpt = true; } else if(a == "--nni-min-gain") { nniMinGain = atof(val()); haveNniOpt = true; }
 		else if(a == "--nni-log") { nniLogFn = val(); haveNniOpt = true; }
+		else if(a == "--support") { supportN = atoll(val()); support = true; }
+		else if(a == "--support-seed") { supportSeed = strtoull(val(), nullptr, 10); haveSupportOpt = true; }
+		else if(a == "--support-out") { supportFn = val(); haveSupportOpt = true; }
 		else if(a.size() > 1 && a[0] == '-' && a.find_first_not_of('v', 1) == std::string::npos) verbose += (int) a.size() - 1;
 		else if(a[0] == '-' && a.size() > 1) { std::cerr << "Error: unknown option " << a << std::endl; return EXIT_FAILURE; }
 		else pos.push_back(a);
@@ -93,6 +103,9 @@ int main(int argc, char** argv) {
 	if(!mlLengths && (!startFn.empty() || !mlLogFn.empty())) { std::cerr << (startFn.empty() ? "--ml-log" : "--start-tree") << " goes with --ml-lengths" << std::endl; return EXIT_FAILURE; }
 	if(nni && !mlLengths) { std::cerr << "--nni goes with --ml-lengths" << std::endl; return EXIT_FAILURE; }
 	if(haveNniOpt && !nni) { std::cerr << "--nni-rounds, --nni-min-gain and --nni-log go with --nni" << std::endl; return EXIT_FAILURE; }
+	if(support && !mlLengths) { std::cerr << "--support goes with --ml-lengths" << std::endl; return EXIT_FAILURE; }
+	if(haveSupportOpt && !support) { std::cerr << "--support-seed and --support-out go with --support" << std::endl; return EXIT_FAILURE; }
+	if(support && (supportN < 1 || supportN > HU_SUPPORT_MAX_REPLICATES)) { std::cerr << "--support must be 1 to " << HU_SUPPORT_MAX_REPLICATES << " replicates" << std::endl; return EXIT_FAILURE; }
 	if(nni) {
 		if(nniRounds < 1) { std::cerr << "--nni-rounds must be at least 1" << std::endl; return EXIT_FAILURE; }
 		if(!(nniMinGain > 0) || !std::isfinite(nniMinGain)) { std::cerr << "--nni-min-gain must be above 0" << std::endl; return EXIT_FAILURE; }
@@ -199,8 +212,8 @@ int main(int argc, char** argv) {
 		fitNodes = nn;
 	}
 	if(mlLengths && haveMem) {
-		const int64_t need = nni ? hu_nni_need((int32_t) fitNodes, (int32_t) L) : hu_blen_need((int32_t) fitNodes, (int32_t) L), have = (int64_t)(memGB * 1e9);
-		if(need > have) { std::cerr << (nni ? "--nni: " : "--ml-lengths: ") << fitNodes << " nodes of " << L << " columns need " << need << " bytes (64 bytes per node and column for the messages), --mem allows " << have << " bytes" << std::endl; return EXIT_FAILURE; }
+		const int64_t need = support ? hu_support_need((int32_t) fitNodes, (int32_t) L, (int32_t) supportN) : nni ? hu_nni_need((int32_t) fitNodes, (int32_t) L) : hu_blen_need((int32_t) fitNodes, (int32_t) L), have = (int64_t)(memGB * 1e9);
+		if(need > have) { std::cerr << (support ? "--support: " : nni ? "--nni: " : "--ml-lengths: ") << fitNodes << " nodes of " << L << " columns need " << need << " bytes (64 bytes per node and column for the messages), --mem allows " << have << " bytes" << std::endl; return EXIT_FAILURE; }
 	}
 
 	hu_nj_opts o;
@@ -303,6 +316,67 @@ int main(int argc, char** argv) {
 			for(int32_t r = 0; r < bo.n_rounds; ++r) fprintf(f, "%d\t%.17g\t%.17g\t%.17g\t%lld\n", r + 1, rounds[r].ll, rounds[r].s, rounds[r].delta, (long long) rounds[r].n_capped);
 			fprintf(f, "# stop: %s\n", why[bo.stop]);
 			if(fclose(f) != 0) { std::cerr << "Unable to write to '" << mlLogFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+		}
+	}
+	/* --support: the supports of the final tree's eligible edges become the labels of their lower ends */
+	if(support) {
+		std::vector<int8_t> seq((size_t) nn * L, (int8_t) -2);
+		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(hu_newick_name(nw.get(), i)) * L, L);
+		hu_support_opts so;
+		hu_support_default_opts(&so);
+		so.blen.min_len = minLen; so.blen.max_len = maxLen; so.blen.host = host ? 1 : 0; so.blen.device = device; so.blen.mem_budget = haveMem ? (int64_t)(memGB * 1e9) : 0;
+		so.replicates = (int32_t) supportN; so.seed = supportSeed;
+		const int32_t cap = std::max((nn - 1) / 2, 1);
+		std::vector<int32_t> eNode((size_t) cap), eCount((size_t) cap); std::vector<double> eT((size_t) cap * 3), eF((size_t) cap * 3);
+		int32_t nE = 0; int64_t skipped = 0;
+		if(hu_tree_nni_support(&so, nn, (int32_t) L, parent.data(), blen.data(), seq.data(), &md, cap, &nE, &skipped, eNode.data(), eT.data(), eF.data(), eCount.data(), nullptr) != HU_OK) {
+			std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
+		if(verbose) {
+			std::cerr << "Local supports: " << nE << " edge(s) scored over " << supportN << " replicate(s), " << skipped << " edge(s) at polytomies skipped" << std::endl;
+			double s[4];
+			hu_support_timing(s);
+			std::cerr << "sweep " << s[0] << " s, scoring " << s[1] << " s, weights " << s[2] << " s, supports " << s[3] << " s" << std::endl;
+		}
+		int32_t root = 0;
+		for(int32_t i = 0; i < nn; ++i) if(parent[i] < 0) root = i;
+		/* a root-spanning edge is scored from the smaller of the root's two children: the other one carries the label too */
+		auto other_end = [&](int32_t u) -> int32_t {
+			if(parent[u] != root || childOff[root + 1] - childOff[root] != 2) return -1;
+			const int32_t c0 = childIdx[childOff[root]], c1 = childIdx[childOff[root] + 1];
+			return c0 == u ? c1 : c0;
+		};
+		std::vector<std::string> label((size_t) nn);
+		std::vector<const char*> nodeName((size_t) nn);
+		for(int32_t i = 0; i < nn; ++i) label[i] = hu_newick_name(nw.get(), i);
+		for(int32_t e = 0; e < nE; ++e) {
+			char num[32];
+			snprintf(num, sizeof(num), "%.3f", (double) eCount[e] / (double) supportN);
+			const int32_t u = eNode[e], s = other_end(u);
+			if(label[u].empty()) label[u] = num;
+			if(s >= 0 && label[s].empty()) label[s] = num;
+		}
+		for(int32_t i = 0; i < nn; ++i) nodeName[i] = label[i].c_str();
+		const int64_t wl = hu_newick_from_arrays(nn, parent.data(), childOff.data(), childIdx.data(), nodeName.data(), blen.data(), nullptr, 0);
+		if(wl < 0) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
+		text.assign((size_t) wl + 1, '\0');
+		hu_newick_from_arrays(nn, parent.data(), childOff.data(), childIdx.data(), nodeName.data(), blen.data(), &text[0], wl + 1);
+		text.resize((size_t) wl);
+		if(!supportFn.empty()) {
+			/* the leaves below every node, counted upwards from every leaf */
+			std::vector<int32_t> leaves((size_t) nn, 0);
+			for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) for(int32_t v = i; v >= 0; v = parent[v]) leaves[v]++;
+			FILE* f = fopen(supportFn.c_str(), "w");
+			if(!f) { std::cerr << "Unable to write to '" << supportFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+			fprintf(f, "node\tname\tkind\tleaves\tt0\talrt\tcount\treplicates\tsupport\n");
+			for(int32_t e = 0; e < nE; ++e) {
+				const int32_t u = eNode[e], s = other_end(u);
+				const bool root3 = parent[u] == root && s < 0;
+				const double t0 = s >= 0 ? blen[u] + blen[s] : blen[u], alrt = 2.0 * (eF[(size_t) e * 3] - std::max(eF[(size_t) e * 3 + 1], eF[(size_t) e * 3 + 2]));
+				fprintf(f, "%d\t%s\t%s\t%d\t%.17g\t%.17g\t%d\t%lld\t%.17g\n", u, hu_newick_name(nw.get(), u), s >= 0 ? "root2" : root3 ? "root3" : "inner", leaves[u], t0, alrt,
+					eCount[e], supportN, (double) eCount[e] / (double) supportN);
+			}
+			fprintf(f, "# skipped: %lld edges at polytomies\n# seed: %llu\n", (long long) skipped, supportSeed);
+			if(fclose(f) != 0) { std::cerr << "Unable to write to '" << supportFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
 		}
 	}
 	if(!distFn.empty()) {

@@ -1193,6 +1193,75 @@ def newick_from_arrays(parent, child_off, child_idx, names, blen) -> str:
     return buf.value.decode()
 
 
+class SupportOpts(C.Structure):
+    _fields_ = [("blen", BlenOpts), ("replicates", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
+SUPPORT_TIE = 2.0 ** -40
+SUPPORT_LDS_COLS = 4736
+
+
+def support_weights(cs_len: int, replicates: int, seed: int = 1, device=None) -> np.ndarray:
+    """hu_support_weights: w [replicates][cs_len] uint16, how often replicate b drew column j.  device: the table of the device's kernel
+    (hu_support_weights_device) instead of the host's"""
+    lib = load_library()
+    if cs_len < 1 or replicates < 1:
+        raise EngineError("support_weights: at least one column and one replicate")
+    w = np.zeros((int(replicates), int(cs_len)), np.uint16)
+    if device is None:
+        _chk(lib.hu_support_weights(C.c_int32(cs_len), C.c_int32(replicates), C.c_uint64(seed), _p(w, C.c_uint16)))
+    else:
+        _chk(lib.hu_support_weights_device(C.c_int32(device), C.c_int32(cs_len), C.c_int32(replicates), C.c_uint64(seed), _p(w, C.c_uint16)))
+    return w
+
+
+def support_need(n_nodes: int, cs_len: int, replicates: int) -> int:
+    """hu_support_need: the bytes the local supports hold for n_nodes x cs_len and `replicates` replicates"""
+    lib = load_library()
+    lib.hu_support_need.restype = C.c_int64
+    return int(lib.hu_support_need(C.c_int32(n_nodes), C.c_int32(cs_len), C.c_int32(replicates)))
+
+
+def tree_nni_support(parent, blen, seq, model: ModelDesc, replicates=None, seed=None, min_len=None, max_len=None, device=0, host=False,
+                     mem_budget=0, with_sums=False) -> dict:
+    """hu_tree_nni_support: for the E eligible edges in ascending u, dict(edge_node [E], t_star [E][3], f [E][3], alrt [E] =
+    2 (f^0 - max(f^1, f^2)), count [E] the replicates that support the edge, support [E] = count / replicates, replicates, skipped,
+    seconds) and, with_sums, sums [E][B][2] = (S^1_b, S^2_b)"""
+    parent = np.ascontiguousarray(parent, np.int32); blen = np.ascontiguousarray(blen, np.float64); seq = np.ascontiguousarray(seq, np.int8)
+    if seq.ndim != 2 or parent.shape != (seq.shape[0],) or blen.shape != parent.shape:
+        raise EngineError("tree_nni_support: parent [n], blen [n] and seq [n][cs_len]")
+    lib = load_library()
+    o = SupportOpts()
+    lib.hu_support_default_opts(C.byref(o))
+    if replicates is not None:
+        o.replicates = int(replicates)
+    if seed is not None:
+        o.seed = int(seed)
+    if min_len is not None:
+        o.blen.min_len = float(min_len)
+    if max_len is not None:
+        o.blen.max_len = float(max_len)
+    o.blen.host = 1 if host else 0; o.blen.device = int(device); o.blen.mem_budget = int(mem_budget or 0)
+    n, L = seq.shape
+    B = int(o.replicates)
+    cap = max((n - 1) // 2, 1)
+    node = np.zeros(cap, np.int32); ts = np.zeros((cap, 3)); f = np.zeros((cap, 3)); cnt = np.zeros(cap, np.int32)
+    sums = np.zeros((cap, B, 2)) if with_sums and 1 <= B <= 100000 else None
+    ne = C.c_int32(0); sk = C.c_int64(0)
+    _chk(lib.hu_tree_nni_support(C.byref(o), C.c_int32(n), C.c_int32(L), _p(parent, C.c_int32), _p(blen, C.c_double), _p(seq, C.c_int8),
+                                 C.byref(model), C.c_int32(cap), C.byref(ne), C.byref(sk), _p(node, C.c_int32), _p(ts, C.c_double),
+                                 _p(f, C.c_double), _p(cnt, C.c_int32), _p(sums, C.c_double) if sums is not None else None))
+    e = ne.value
+    s = np.zeros(4)
+    _chk(lib.hu_support_timing(_p(s, C.c_double)))
+    out = dict(edge_node=node[:e].copy(), t_star=ts[:e].copy(), f=f[:e].copy(), alrt=2.0 * (f[:e, 0] - np.maximum(f[:e, 1], f[:e, 2])),
+               count=cnt[:e].copy(), support=cnt[:e] / float(B) if B > 0 else np.zeros(e), replicates=B, skipped=int(sk.value),
+               seconds=dict(sweep=s[0], score=s[1], weights=s[2], support=s[3]))
+    if sums is not None:
+        out["sums"] = sums[:e].copy()
+    return out
+
+
 def tree_count_mutations(parent, cs_len: int, up_ptr: int, device=0) -> np.ndarray:
     """hu_tree_count_mutations: per column, the non-root nodes whose inferred state differs from their parent's, from the DEVICE
     fixed-rate up buffer at up_ptr ([n][cs_len][4] float64, as tree_evaluate leaves it with win_len 0)"""

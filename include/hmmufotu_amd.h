@@ -1249,6 +1249,45 @@ int hu_nni_timing(double* seconds /* [4] */);
 int64_t hu_newick_from_arrays(int32_t n_nodes, const int32_t* parent, const int32_t* child_off, const int32_t* child_idx, const char* const* names,
 		const double* blen, char* buf, int64_t cap);
 
+/* ---- hmmufotu-amd-tree --support: local branch supports of the eligible edges ----
+ * The tree, the model, the limits and the eligible edges are those of the NNI search above.  For every eligible edge e, with its three
+ * arrangements q each at its own optimum t*_q on [min_len, max_len]:
+ *   l^q_j = K^q_j + log D^q_j(t*_q), the log-likelihood of column j, whose sum over j is f^q(t*_q);
+ *   alrt_e = 2 (f^0 - max(f^1, f^2)), left to the caller: f is returned;
+ *   d^q_j = max(l^q_j - l^0_j, -DBL_MAX) for q = 1, 2.  A column with l^0_j not finite refuses the call: the tree has likelihood 0.
+ * Replicate b draws cs_len columns with replacement; w_bj counts the draws of column j.  Draw i is word i % 4 of
+ * Philox4x32-10(counter (i / 4, b, 0, 0x53555050), key (seed low word, seed high word)), col = (uint64(word) * cs_len) >> 32: the same
+ * for every edge, and the first B' replicates of a run with B are those of a run with B'.  S^q_b = sum_j w_bj d^q_j, serially in
+ * ascending j, a multiply and then an add.  Replicate b supports the edge when S^1_b < -eta and S^2_b < -eta, eta = HU_SUPPORT_TIE
+ * |f^0(t*_0)|: on a collapsed edge, whose three arrangements are one star, d is rounding noise and the count is 0.  count [E] is the
+ * number of supporting replicates, support = count / replicates.
+ *
+ * hu_support_weights: w [replicates][cs_len], host only.  hu_support_weights_device: the same table from the device's kernel.
+ * hu_tree_nni_support: edge_node [E], t_star [E][3], f [E][3] as hu_tree_nni_scores gives them, count [E], and sums [E][B][2] =
+ *   (S^1_b, S^2_b) when not NULL: for tests and small inputs.  E = 0 is a success.
+ * Memory (hu_support_need): hu_nni_need, the table of weights (2 bytes per column and replicate, the replicates padded to a multiple
+ *   of 4), 32 bytes of outputs per inner node and the sums of one launch's edges (at most 16 MB); d lies in LDS up to
+ *   HU_SUPPORT_LDS_COLS columns and in the ratio scratch of the scoring beyond.  Held against opts->blen.mem_budget and the free memory.
+ * hu_support_timing: seconds [4] of this thread's last hu_tree_nni_support = the sweep, the scoring, the weights, the support kernel. */
+#define HU_SUPPORT_TIE 0x1p-40     /* 16 times the measured bar of f, 2^-44 */
+#define HU_SUPPORT_LDS_COLS 4736   /* d of an edge stays in LDS up to this many columns: 16 cs_len + 6 KB of reduction scratch, two workgroups in a CU's 160 KB; with one
+                                    * workgroup per CU the global scratch was measured faster */
+#define HU_SUPPORT_MAX_REPLICATES 100000
+typedef struct {
+	hu_blen_opts blen;    /* min_len, max_len, device, host, mem_budget are read */
+	int32_t replicates;   /* 1,000; 1 .. HU_SUPPORT_MAX_REPLICATES */
+	int32_t reserved;
+	uint64_t seed;        /* 1 */
+} hu_support_opts;
+void hu_support_default_opts(hu_support_opts* o);
+int hu_support_weights(int32_t cs_len, int32_t replicates, uint64_t seed, uint16_t* w /* [replicates][cs_len] */);
+int hu_support_weights_device(int32_t device, int32_t cs_len, int32_t replicates, uint64_t seed, uint16_t* w /* [replicates][cs_len] */);
+int64_t hu_support_need(int32_t n_nodes, int32_t cs_len, int32_t replicates);
+int hu_tree_nni_support(const hu_support_opts* opts, int32_t n_nodes, int32_t cs_len, const int32_t* parent, const double* blen, const int8_t* seq,
+		const hu_model_desc* model, int32_t edge_cap, int32_t* n_edges, int64_t* skipped, int32_t* edge_node, double* t_star, double* f,
+		int32_t* count, double* sums);
+int hu_support_timing(double* seconds /* [4] */);
+
 #ifdef __cplusplus
 }
 #endif
