@@ -418,15 +418,17 @@ __device__ __attribute__((noinline)) double hu_log_call(double x) { return log(x
  * exchange + 200 of tail.  Shortening the second half — row sums only on the DPP network, the 4 NW row sums handed over through LDS as a
  * broadcast read, the tail's factors computed before the exchange — changed nothing (8.80 against 8.86 ms), nor did the stage-by-stage
  * arithmetic below (8.90 against 8.87): a step lasts as long as the SLOWER of the two waves needs for its arithmetic beside whatever shares
- * its SIMD; the chain behind it is waiting for the partner, not instruction latency. */
+ * its SIMD; the chain behind it is waiting for the partner, not instruction latency.
+ * q0 = hu_exp_call(-w0) of the branch's starting length w0 comes from the caller: the table build in front of the sweep evaluates it on a
+ * lane that its own exponentials leave idle (k_place_blk), where every lane of every wave used to run the whole chain here. */
 template<int SPT, int NW, int EMV, int RED>
-__device__ inline double em_branch_blk(const double (&rho)[SPT], int nvalidWave, double w0, double maxL,
+__device__ inline double em_branch_blk(const double (&rho)[SPT], int nvalidWave, double q0, double maxL,
 		double* red, double* redc, int& phase, int& emIters, long long* st = nullptr) {
 	/* st (diagnostic build only): s_memtime ticks of a step's arithmetic, wave reduction, exchange between the waves, tail */
 	long long tl = st ? (long long) __builtin_amdgcn_s_memtime() : 0;
 	auto stamp = [&](int i) { if(st) { const long long t = (long long) __builtin_amdgcn_s_memtime(); st[i] += t - tl; tl = t; } };
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	double q0 = hu_exp_call(-w0), p0 = 1 - q0, p = p0, q = q0, rc = 0;
+	double p0 = 1 - q0, p = p0, q = q0, rc = 0;
 	if(lane == 0) redc[(phase & 1) * NW + wave] = (double) nvalidWave;
 	for(int it = 0; it < HU_MAX_ITER && p >= 0 && p <= 1; ++it) {
 		double s = 0;
@@ -558,6 +560,19 @@ __global__ __launch_bounds__(64) void k_site_perm(HuDbDev db, int n, const int8_
 	}
 }
 
+/* one entry of G or G': sum_k a[4 k] b[4 k] over the rate categories, in the order of k.  With the trip count known (one category, or the four of
+ * the usual dGamma) the 2 K reads of Etab are issued before the first use; the loop with a run-time count waits for every pair in turn. */
+__device__ __forceinline__ double hu_gtab_entry(const double* a, const double* b, int Kc) {
+	double g = 0;
+	if(Kc == 4) {
+		const double a0 = a[0], a1 = a[4], a2 = a[8], a3 = a[12], b0 = b[0], b1 = b[4], b2 = b[8], b3 = b[12];
+		g += a0 * b0; g += a1 * b1; g += a2 * b2; g += a3 * b3;
+	}
+	else if(Kc == 1) g += a[0] * b[0];
+	else for(int k = 0; k < Kc; ++k) g += a[k * 4] * b[k * 4];
+	return g;
+}
+
 /* GS > 0: the sites of a read are taken in the order of its site list (k_site_perm): gap sites in slots 0 .. GS-1, base sites
  * in slots GS .. SPT-1.  The sweeps over the gap slots are straight-line code on ONE table held in registers (every lane
  * would read the same 160 bytes per site and sweep from LDS: the sweeps are bound by the LDS return path, and 82 % of a
@@ -578,6 +593,8 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_place_blk(HuDbDev db, HuModelD
 	__shared__ double Gtab[16];
 	__shared__ __attribute__((aligned(16))) double tabM[5 * HU_TP];
 	__shared__ __attribute__((aligned(16))) double tabD[6 * 4];             /* sweep (i): row 0 = G_mm; sweep (ii): row b = T^b_mm */
+	__shared__ double q0s[2];                          /* exp(-w_nr), exp(-w_ur): where the EM call behind sweep (i), (ii) starts (a slot each: an EM call
+	                                                    * that takes no step has no barrier between its read and the next build) */
 	__shared__ double vl[VL == 1 ? SPT * 64 * NW : 1];
 	extern __shared__ double vdyn[];                   /* VL == 3: [3][SPT * THREADS] */
 	const int tid = threadIdx.x;
@@ -645,26 +662,33 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_place_blk(HuDbDev db, HuModelD
 	double wur = wur0, wnr = wnr0;
 	int iter = 0, emIters = 0, phase = 0;
 	double rho[SPT];
+	/* the first phase of a table build: the nE exponentials of the lengths len0 (Etab row wh0) and len1 (row wh0 + 1), and as entry nE, on a
+	 * lane that they leave idle, exp(-w) for the EM call behind the sweep — the same call on the same argument, so the same bits as the call
+	 * that every lane of every wave used to make at the start of em_branch_blk, a chain of ~45 dependent FP64 instructions per EM call */
+	auto build_exp = [&](int wh0, int nE, double len0, double len1, double w, double* q0p) __attribute__((always_inline)) {
+		for(int e = vt; e <= nE; e += THREADS) { /* one entry per thread up to four rate categories (with sixteen and two waves, one thread has two) */
+			const bool second = e >= 4 * Kc;
+			const int wh = wh0 + (second ? 1 : 0), k = (e >> 2) % Kc, m = e & 3;
+			const double len = second ? len1 : len0;
+			const double x = hu_exp_call(e == nE ? -w : clam[m] * (len * crate[k]));
+			if(e == nE) *q0p = x;
+			else Etab[(wh * HU_MAX_DGK + k) * 4 + m] = x;
+		}
+		lds_barrier();
+	};
 	if(DBG) { double x = 0; for(int t = 0; t < SPT; ++t) x += u[t][0] + u[t][1]; if(x == 1.2345e-300) tk[7] = 1; } /* wait for the loads */
 	stamp(0);
 	for(; iter < HU_MAX_ITER && 0 <= wur && wur <= w0j; ++iter) {
-		if(vt < 8 * Kc) {
-			const int which = vt / (4 * Kc), k = (vt >> 2) % Kc, m = vt & 3;
-			Etab[(which * HU_MAX_DGK + k) * 4 + m] = hu_exp_call(clam[m] * ((which ? lenVR : lenUR) * crate[k]));
-		}
-		lds_barrier();
-		if(vt < 16) { /* G_mn = mean_k exp(lam_m w_ur r_k) exp(lam_n w_vr r_k) */
-			const int m = vt >> 2, nn = vt & 3;
-			double g = 0;
-			for(int k = 0; k < Kc; ++k) g += Etab[k * 4 + m] * Etab[(HU_MAX_DGK + k) * 4 + nn];
-			Gtab[vt] = g * rKc;
-		}
+		build_exp(0, 8 * Kc, lenUR, lenVR, lenNR, q0s);
+		if(vt < 16) /* G_mn = mean_k exp(lam_m w_ur r_k) exp(lam_n w_vr r_k) */
+			Gtab[vt] = hu_gtab_entry(Etab + (vt >> 2), Etab + HU_MAX_DGK * 4 + (vt & 3), Kc) * rKc;
 		lds_barrier();
 		for(int e = vt; e < 84; e += THREADS) { /* one entry per thread when the workgroup has two or more waves */
 			if(e < 80) tabM[(e >> 4) * HU_TP + (e & 15)] = cW[e] * Gtab[e & 15];
 			else tabD[e - 80] = Gtab[(e - 80) * 5];
 		}
 		lds_barrier();
+		const double q0n = q0s[0];
 		stamp(1);
 		/* (i) message r->n from children u, v against the read's leaf message; EM on the n-r branch */
 		int nv = 0;
@@ -697,20 +721,12 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_place_blk(HuDbDev db, HuModelD
 			}
 		}
 		stamp(2);
-		wnr = em_branch_blk<SPT, NW, EMV, RED>(rho, nv, lenNR, 1.0, red, redc, phase, emIters, DBG ? te : nullptr);
+		wnr = em_branch_blk<SPT, NW, EMV, RED>(rho, nv, q0n, 1.0, red, redc, phase, emIters, DBG ? te : nullptr);
 		lenNR = wnr;
 		stamp(3);
-		if(vt < 4 * Kc) {
-			const int k = vt >> 2, m = vt & 3;
-			Etab[(2 * HU_MAX_DGK + k) * 4 + m] = hu_exp_call(clam[m] * (lenNR * crate[k]));
-		}
-		lds_barrier();
-		if(vt < 16) { /* G'_mn = mean_k exp(lam_m w_vr r_k) exp(lam_n w_nr r_k) */
-			const int m = vt >> 2, nn = vt & 3;
-			double g = 0;
-			for(int k = 0; k < Kc; ++k) g += Etab[(HU_MAX_DGK + k) * 4 + m] * Etab[(2 * HU_MAX_DGK + k) * 4 + nn];
-			Gtab[vt] = g * rKc;
-		}
+		build_exp(2, 4 * Kc, lenNR, lenNR, lenUR, q0s + 1);
+		if(vt < 16) /* G'_mn = mean_k exp(lam_m w_vr r_k) exp(lam_n w_nr r_k) */
+			Gtab[vt] = hu_gtab_entry(Etab + HU_MAX_DGK * 4 + (vt >> 2), Etab + 2 * HU_MAX_DGK * 4 + (vt & 3), Kc) * rKc;
 		lds_barrier();
 		for(int e = vt; e < 100; e += THREADS) {
 			if(e < 80) { /* T^b_mn = c^b_n G'_mn; Z^b_mk = sum_n T^b_mn C_mnk */
@@ -723,6 +739,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_place_blk(HuDbDev db, HuModelD
 			else { const int b = (e - 80) >> 2, m = (e - 80) & 3; tabD[b * 4 + m] = ccb[b * 4 + m] * Gtab[m * 5]; }
 		}
 		lds_barrier();
+		const double q0u = q0s[1];
 		stamp(1);
 		/* (ii) message r->u from children v, n against u's own message; EM on the u-r branch */
 		nv = 0;
@@ -758,7 +775,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void k_place_blk(HuDbDev db, HuModelD
 			}
 		}
 		stamp(2);
-		wur = em_branch_blk<SPT, NW, EMV, RED>(rho, nv, lenUR, w0j, red, redc, phase, emIters, DBG ? te : nullptr);
+		wur = em_branch_blk<SPT, NW, EMV, RED>(rho, nv, q0u, w0j, red, redc, phase, emIters, DBG ? te : nullptr);
 		lenUR = wur;
 		lenVR = w0j - wur;
 		stamp(3);
