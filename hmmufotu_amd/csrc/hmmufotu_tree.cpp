@@ -5,6 +5,7 @@
 //                     [--device N] [--host] [-v]
 //                     [--ml-lengths [--start-tree FILE] [--ml-rounds N] [--ml-eps DBL] [--min-len DBL] [--max-len DBL] [--ml-log FILE]
 //                      [--nni [--nni-rounds N] [--nni-min-gain DBL] [--nni-log FILE]]
+//                      [--spr [--spr-radius N] [--spr-rounds N] [--spr-min-gain DBL] [--spr-log FILE]]
 //                      [--support N [--support-seed N] [--support-out FILE]]]
 // The MSA is read and pruned as hmmufotu-amd-build does (hu_build_inputs.h; the columns without a residue are found on the host here,
 // the same columns hu_prune_msa finds), so the tree joins by name to the same MSA there.  The distances and the joins are
@@ -15,6 +16,8 @@
 // either way, and hu_newick_write puts the same topology, names and order of children back with the new lengths.
 // --nni lets the topology move: a hill climb over nearest-neighbour interchanges from that tree (hu_tree_nni_search),
 // written by hu_newick_from_arrays with the same node ids, names and top node.
+// --spr moves whole subtrees: a hill climb over subtree pruning and regrafting within a radius (hu_tree_spr_search).  With
+// --nni the interchanges run first, then the SPR search, then the interchanges once more if a subtree was moved.
 // --support labels the inner edges of the final tree with their local bootstrap support (hu_tree_nni_support): the share
 // of N resamplings of the columns in which the edge as it stands beats both of its nearest-neighbour interchanges.
 #include <cmath>
@@ -52,6 +55,11 @@ static void usage(const char* p) {
 		"            --nni-rounds  INT  : rounds of interchanges at the most, at least 1 [20]\n"
 		"            --nni-min-gain  DBL: smallest gain in log-likelihood for which an interchange is tried, above 0 [1e-3]\n"
 		"            --nni-log  FILE    : write the accepted rounds as TSV: round, ll, scored, candidates, taken, applied; then '# stop: REASON' and '# skipped: N edges at polytomies'\n"
+		"            --spr  FLAG        : with --ml-lengths: improve the topology by subtree pruning and regrafting, a hill climb on the log-likelihood; with --nni the interchanges run before it and, if a subtree was moved, once more after it\n"
+		"            --spr-radius  INT  : a pruned subtree is tried in the edges up to this many nodes away, 1 to 32 [5]\n"
+		"            --spr-rounds  INT  : rounds of moves at the most, at least 1 [10]\n"
+		"            --spr-min-gain  DBL: smallest gain in log-likelihood for which a move is tried, above 0 [1e-3]\n"
+		"            --spr-log  FILE    : write the accepted rounds as TSV: round, ll, pruned, targets, candidates, taken, applied; then '# stop: REASON' and '# skipped: N nodes'\n"
 		"            --support  INT     : with --ml-lengths: label every inner edge between two nodes of degree three with its local bootstrap support over INT replicates, 1 to 100000: the share of resampled alignments in which the edge beats both of its nearest-neighbour interchanges\n"
 		"            --support-seed  INT: seed of the replicates [1]\n"
 		"            --support-out  FILE: write the supports as TSV: node, name, kind, leaves, t0, alrt, count, replicates, support; then '# skipped: N edges at polytomies' and '# seed: S'\n"
@@ -65,6 +73,7 @@ int main(int argc, char** argv) {
 	double sat = 0, memGB = 0; bool haveMem = false;
 	bool mlLengths = false; std::string startFn, mlLogFn; int mlRounds = 50; double mlEps = 1e-5, minLen = 0.0, maxLen = 10.0;
 	bool nni = false, haveNniOpt = false; std::string nniLogFn; int nniRounds = 20; double nniMinGain = 1e-3;
+	bool spr = false, haveSprOpt = false; std::string sprLogFn; int sprRadius = 5, sprRounds = 10; double sprMinGain = 1e-3;
 	bool support = false, haveSupportOpt = false; long long supportN = 0; unsigned long long supportSeed = 1; std::string supportFn;
 	if(argc < 2) { usage(argv[0]); return EXIT_SUCCESS; }
 	for(int i = 1; i < argc; ++i) {
@@ -83,6 +92,9 @@ int main(int argc, char** argv) {
 		else if(a == "--nni") nni = true;
 		else if(a == "--nni-rounds") { nniRounds = atoi(val()); haveNniOpt = true; } else if(a == "--nni-min-gain") { nniMinGain = atof(val()); haveNniOpt = true; }
 		else if(a == "--nni-log") { nniLogFn = val(); haveNniOpt = true; }
+		else if(a == "--spr") spr = true;
+		else if(a == "--spr-radius") { sprRadius = atoi(val()); haveSprOpt = true; } else if(a == "--spr-rounds") { sprRounds = atoi(val()); haveSprOpt = true; }
+		else if(a == "--spr-min-gain") { sprMinGain = atof(val()); haveSprOpt = true; } else if(a == "--spr-log") { sprLogFn = val(); haveSprOpt = true; }
 		else if(a == "--support") { supportN = atoll(val()); support = true; }
 		else if(a == "--support-seed") { supportSeed = strtoull(val(), nullptr, 10); haveSupportOpt = true; }
 		else if(a == "--support-out") { supportFn = val(); haveSupportOpt = true; }
@@ -103,6 +115,13 @@ int main(int argc, char** argv) {
 	if(!mlLengths && (!startFn.empty() || !mlLogFn.empty())) { std::cerr << (startFn.empty() ? "--ml-log" : "--start-tree") << " goes with --ml-lengths" << std::endl; return EXIT_FAILURE; }
 	if(nni && !mlLengths) { std::cerr << "--nni goes with --ml-lengths" << std::endl; return EXIT_FAILURE; }
 	if(haveNniOpt && !nni) { std::cerr << "--nni-rounds, --nni-min-gain and --nni-log go with --nni" << std::endl; return EXIT_FAILURE; }
+	if(spr && !mlLengths) { std::cerr << "--spr goes with --ml-lengths" << std::endl; return EXIT_FAILURE; }
+	if(haveSprOpt && !spr) { std::cerr << "--spr-radius, --spr-rounds, --spr-min-gain and --spr-log go with --spr" << std::endl; return EXIT_FAILURE; }
+	if(spr) {
+		if(sprRadius < 1 || sprRadius > HU_SPR_MAX_RADIUS) { std::cerr << "--spr-radius must be 1 to " << HU_SPR_MAX_RADIUS << std::endl; return EXIT_FAILURE; }
+		if(sprRounds < 1) { std::cerr << "--spr-rounds must be at least 1" << std::endl; return EXIT_FAILURE; }
+		if(!(sprMinGain > 0) || !std::isfinite(sprMinGain)) { std::cerr << "--spr-min-gain must be above 0" << std::endl; return EXIT_FAILURE; }
+	}
 	if(support && !mlLengths) { std::cerr << "--support goes with --ml-lengths" << std::endl; return EXIT_FAILURE; }
 	if(haveSupportOpt && !support) { std::cerr << "--support-seed and --support-out go with --support" << std::endl; return EXIT_FAILURE; }
 	if(support && (supportN < 1 || supportN > HU_SUPPORT_MAX_REPLICATES)) { std::cerr << "--support must be 1 to " << HU_SUPPORT_MAX_REPLICATES << " replicates" << std::endl; return EXIT_FAILURE; }
@@ -213,6 +232,8 @@ int main(int argc, char** argv) {
 	}
 	if(mlLengths && haveMem) {
 		const int64_t need = support ? hu_support_need((int32_t) fitNodes, (int32_t) L, (int32_t) supportN) : nni ? hu_nni_need((int32_t) fitNodes, (int32_t) L) : hu_blen_need((int32_t) fitNodes, (int32_t) L), have = (int64_t)(memGB * 1e9);
+		const int64_t sprNeed = spr ? hu_spr_need((int32_t) fitNodes, (int32_t) L, sprRadius) : 0;
+		if(sprNeed > have && sprNeed >= need) { std::cerr << "--spr: " << fitNodes << " nodes of " << L << " columns at radius " << sprRadius << " need " << sprNeed << " bytes (64 bytes per node and column for the messages), --mem allows " << have << " bytes" << std::endl; return EXIT_FAILURE; }
 		if(need > have) { std::cerr << (support ? "--support: " : nni ? "--nni: " : "--ml-lengths: ") << fitNodes << " nodes of " << L << " columns need " << need << " bytes (64 bytes per node and column for the messages), --mem allows " << have << " bytes" << std::endl; return EXIT_FAILURE; }
 	}
 
@@ -248,6 +269,42 @@ int main(int argc, char** argv) {
 	hu_blen_opts bo;
 	hu_blen_default_opts(&bo);
 	std::vector<hu_blen_round> rounds;
+	/* --spr: the search on the arrays in place, its report and its log; the moves applied, or -1 after an error */
+	auto run_spr = [&](const std::vector<int8_t>& seq) -> long long {
+		hu_spr_opts so;
+		hu_spr_default_opts(&so);
+		std::vector<hu_spr_round> srounds((size_t) sprRounds);
+		std::vector<int32_t> moves((size_t) sprRounds * (size_t) nn * 5);
+		so.blen.eps = mlEps; so.blen.min_len = minLen; so.blen.max_len = maxLen; so.blen.max_rounds = mlRounds; so.blen.host = host ? 1 : 0; so.blen.device = device;
+		so.blen.mem_budget = haveMem ? (int64_t)(memGB * 1e9) : 0;
+		so.radius = sprRadius; so.spr_rounds = sprRounds; so.min_gain = sprMinGain; so.rounds = srounds.data(); so.rounds_cap = sprRounds;
+		so.moves = moves.data(); so.moves_cap = (int64_t) sprRounds * nn;
+		if(hu_tree_spr_search(&so, nn, (int32_t) L, parent.data(), blen.data(), seq.data(), childOff.data(), childIdx.data(), &md) != HU_OK) { std::cerr << hu_last_error() << std::endl; return -1; }
+		static const char* const why[] = {"local optimum", "no improving move", "max rounds"};
+		if(verbose) {
+			char line[240];
+			snprintf(line, sizeof(line), "SPR search: log-likelihood %.17g -> %.17g, %lld move(s) applied in %d round(s) at radius %d, stop: %s", so.ll_start, so.ll_final, (long long) so.n_moves, so.n_rounds, sprRadius, why[so.stop]);
+			std::cerr << line << std::endl;
+			for(int64_t k = 0; k < so.n_moves && k < so.moves_cap; ++k) {
+				const int32_t* mv = moves.data() + k * 5;
+				snprintf(line, sizeof(line), "round %d: the subtree of node %d from the edge of node %d into the edge of node %d, distance %d", mv[0], mv[1], mv[2], mv[3], mv[4]);
+				std::cerr << line << std::endl;
+			}
+			if(so.skipped > 0) std::cerr << so.skipped << " node(s) were not pruned: their parent is the top node or a polytomy" << std::endl;
+			double s[4];
+			hu_spr_timing(s);
+			std::cerr << "SPR fits " << s[0] << " s, scoring " << s[1] << " s, trials " << s[2] << " s, the rest " << s[3] << " s" << std::endl;
+		}
+		if(!sprLogFn.empty()) {
+			FILE* f = fopen(sprLogFn.c_str(), "w");
+			if(!f) { std::cerr << "Unable to write to '" << sprLogFn << "': " << strerror(errno) << std::endl; return -1; }
+			fprintf(f, "round\tll\tpruned\ttargets\tcandidates\ttaken\tapplied\n0\t%.17g\t0\t0\t0\t0\t0\n", so.ll_start);
+			for(int32_t r = 0; r < so.n_rounds; ++r) fprintf(f, "%d\t%.17g\t%d\t%lld\t%d\t%d\t%d\n", r + 1, srounds[r].ll, srounds[r].pruned, (long long) srounds[r].targets, srounds[r].candidates, srounds[r].taken, srounds[r].applied);
+			fprintf(f, "# stop: %s\n# skipped: %lld nodes\n", why[so.stop], (long long) so.skipped);
+			if(fclose(f) != 0) { std::cerr << "Unable to write to '" << sprLogFn << "': " << strerror(errno) << std::endl; return -1; }
+		}
+		return (long long) so.n_moves;
+	};
 	if(mlLengths && nni) {
 		std::vector<int8_t> seq((size_t) nn * L, (int8_t) -2);
 		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(hu_newick_name(nw.get(), i)) * L, L);
@@ -269,6 +326,22 @@ int main(int argc, char** argv) {
 			hu_nni_timing(s);
 			std::cerr << "fits " << s[0] << " s, scoring " << s[1] << " s, trials " << s[2] << " s, the rest " << s[3] << " s" << std::endl;
 		}
+		if(spr) {
+			const long long moved = run_spr(seq);
+			if(moved < 0) return EXIT_FAILURE;
+			if(moved > 0) {
+				/* the interchanges once more, on the tree the moves left; --nni-log holds the first search */
+				hu_nni_opts no2;
+				hu_nni_default_opts(&no2);
+				no2.blen = no.blen; no2.nni_rounds = nniRounds; no2.min_gain = nniMinGain;
+				if(hu_tree_nni_search(&no2, nn, (int32_t) L, parent.data(), blen.data(), seq.data(), childOff.data(), childIdx.data(), &md) != HU_OK) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
+				if(verbose) {
+					char line[240];
+					snprintf(line, sizeof(line), "NNI search after the moves: log-likelihood %.17g -> %.17g, %lld swap(s) applied in %d round(s), stop: %s", no2.ll_start, no2.ll_final, (long long) no2.n_swaps, no2.n_rounds, why[no2.stop]);
+					std::cerr << line << std::endl;
+				}
+			}
+		}
 		std::vector<const char*> nodeName((size_t) nn);
 		for(int32_t i = 0; i < nn; ++i) nodeName[i] = hu_newick_name(nw.get(), i);
 		const int64_t wl = hu_newick_from_arrays(nn, parent.data(), childOff.data(), childIdx.data(), nodeName.data(), blen.data(), nullptr, 0);
@@ -284,6 +357,19 @@ int main(int argc, char** argv) {
 			fprintf(f, "# stop: %s\n# skipped: %lld edges at polytomies\n", why[no.stop], (long long) no.skipped);
 			if(fclose(f) != 0) { std::cerr << "Unable to write to '" << nniLogFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
 		}
+	}
+	else if(mlLengths && spr) {
+		std::vector<int8_t> seq((size_t) nn * L, (int8_t) -2);
+		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(hu_newick_name(nw.get(), i)) * L, L);
+		for(int32_t i = 0; i < nn; ++i) if(parent[i] >= 0 && std::isfinite(blen[i])) blen[i] = std::min(std::max(blen[i], minLen), maxLen);
+		if(run_spr(seq) < 0) return EXIT_FAILURE;
+		std::vector<const char*> nodeName((size_t) nn);
+		for(int32_t i = 0; i < nn; ++i) nodeName[i] = hu_newick_name(nw.get(), i);
+		const int64_t wl = hu_newick_from_arrays(nn, parent.data(), childOff.data(), childIdx.data(), nodeName.data(), blen.data(), nullptr, 0);
+		if(wl < 0) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
+		text.assign((size_t) wl + 1, '\0');
+		hu_newick_from_arrays(nn, parent.data(), childOff.data(), childIdx.data(), nodeName.data(), blen.data(), &text[0], wl + 1);
+		text.resize((size_t) wl);
 	}
 	else if(mlLengths) {
 		std::vector<int8_t> seq((size_t) nn * L, (int8_t) -2);

@@ -1262,6 +1262,107 @@ def tree_nni_support(parent, blen, seq, model: ModelDesc, replicates=None, seed=
     return out
 
 
+class SprRound(C.Structure):
+    _fields_ = [("ll", C.c_double), ("targets", C.c_int64), ("pruned", C.c_int32), ("candidates", C.c_int32), ("taken", C.c_int32),
+                ("applied", C.c_int32)]
+
+
+class SprOpts(C.Structure):
+    _fields_ = [("blen", BlenOpts), ("min_gain", C.c_double), ("radius", C.c_int32), ("spr_rounds", C.c_int32), ("rounds_cap", C.c_int32),
+                ("slab", C.c_int32), ("rounds", C.POINTER(SprRound)), ("moves", C.POINTER(C.c_int32)), ("moves_cap", C.c_int64),
+                ("n_rounds", C.c_int32), ("stop", C.c_int32), ("n_moves", C.c_int64), ("skipped", C.c_int64),
+                ("ll_start", C.c_double), ("ll_final", C.c_double)]
+
+
+SPR_MAX_RADIUS = 32
+SPR_STOP = ("local optimum", "no improving move", "max rounds")
+
+
+def _spr_args(what, parent, blen, seq, model, eps, min_len, max_len, max_rounds, device, host, mem_budget, radius, slab, spr_rounds=None, min_gain=None):
+    parent = np.ascontiguousarray(parent, np.int32).copy(); blen = np.ascontiguousarray(blen, np.float64).copy()
+    seq = np.ascontiguousarray(seq, np.int8)
+    if seq.ndim != 2 or parent.shape != (seq.shape[0],) or blen.shape != parent.shape:
+        raise EngineError(what + ": parent [n], blen [n] and seq [n][cs_len]")
+    o = SprOpts()
+    load_library().hu_spr_default_opts(C.byref(o))
+    for k, v in (("eps", eps), ("min_len", min_len), ("max_len", max_len)):
+        if v is not None:
+            setattr(o.blen, k, float(v))
+    if max_rounds is not None:
+        o.blen.max_rounds = int(max_rounds)
+    for k, v in (("radius", radius), ("slab", slab), ("spr_rounds", spr_rounds)):
+        if v is not None:
+            setattr(o, k, int(v))
+    if min_gain is not None:
+        o.min_gain = float(min_gain)
+    o.blen.host = 1 if host else 0; o.blen.device = int(device); o.blen.mem_budget = int(mem_budget or 0)
+    return o, parent, blen, seq
+
+
+def spr_need(n_nodes: int, cs_len: int, radius: int = 5) -> int:
+    """hu_spr_need: the bytes the SPR search holds for n_nodes x cs_len at this radius"""
+    lib = load_library()
+    lib.hu_spr_need.restype = C.c_int64
+    return int(lib.hu_spr_need(C.c_int32(n_nodes), C.c_int32(cs_len), C.c_int32(radius)))
+
+
+def tree_spr_scores(parent, blen, seq, model: ModelDesc, radius=None, min_len=None, max_len=None, device=0, host=False, mem_budget=0,
+                    slab=None) -> dict:
+    """hu_tree_spr_scores: for the P prunable nodes in ascending v, dict(prune_node [P], v_off [P + 1], base_t [P], base_f [P] (the
+    baseline with the pendant at its optimum), f_at_blen [P] (the baseline as the tree stands: the tree's log-likelihood), and per
+    target in the order of the walk target_node, dist, t_star, f; skipped)"""
+    o, parent, blen, seq = _spr_args("tree_spr_scores", parent, blen, seq, model, None, min_len, max_len, None, device, host, mem_budget, radius, slab)
+    n, L = seq.shape
+    lib = load_library()
+    npr = C.c_int32(0); nt = C.c_int64(0); sk = C.c_int64(0)
+    head = (C.byref(o), C.c_int32(n), C.c_int32(L), _p(parent, C.c_int32), _p(blen, C.c_double), _p(seq, C.c_int8), C.byref(model))
+    _chk(lib.hu_tree_spr_scores(*head, C.c_int32(0), C.c_int64(0), C.byref(npr), C.byref(nt), C.byref(sk), *([None] * 9)))
+    P, T = max(npr.value, 1), max(nt.value, 1)
+    node = np.zeros(P, np.int32); off = np.zeros(P + 1, np.int64); bt = np.zeros(P); bf = np.zeros(P); f0 = np.zeros(P)
+    w = np.zeros(T, np.int32); d = np.zeros(T, np.int32); ts = np.zeros(T); f = np.zeros(T)
+    _chk(lib.hu_tree_spr_scores(*head, C.c_int32(P), C.c_int64(T), C.byref(npr), C.byref(nt), C.byref(sk), _p(node, C.c_int32), _p(off, C.c_int64),
+                                _p(bt, C.c_double), _p(bf, C.c_double), _p(f0, C.c_double), _p(w, C.c_int32), _p(d, C.c_int32), _p(ts, C.c_double),
+                                _p(f, C.c_double)))
+    P, T = npr.value, nt.value
+    return dict(prune_node=node[:P].copy(), v_off=off[:P + 1].copy(), base_t=bt[:P].copy(), base_f=bf[:P].copy(), f_at_blen=f0[:P].copy(),
+                target_node=w[:T].copy(), dist=d[:T].copy(), t_star=ts[:T].copy(), f=f[:T].copy(), skipped=int(sk.value))
+
+
+def tree_spr_apply(parent, blen, v: int, w: int, t: float, child_off=None, child_idx=None) -> dict:
+    """hu_tree_spr_apply: the subtree of v pruned and regrafted into the edge above w, that edge split in halves, the pendant set to t.
+    dict(parent, blen, child_off, child_idx), the inputs are not changed"""
+    parent = np.ascontiguousarray(parent, np.int32).copy(); blen = np.ascontiguousarray(blen, np.float64).copy()
+    off, idx = _child_arrays(parent, child_off, child_idx)
+    _chk(load_library().hu_tree_spr_apply(C.c_int32(len(parent)), _p(parent, C.c_int32), _p(blen, C.c_double), _p(off, C.c_int32), _p(idx, C.c_int32),
+                                          C.c_int32(int(v)), C.c_int32(int(w)), C.c_double(float(t))))
+    return dict(parent=parent, blen=blen, child_off=off, child_idx=idx)
+
+
+def tree_spr_search(parent, blen, seq, model: ModelDesc, child_off=None, child_idx=None, radius=None, spr_rounds=None, min_gain=None, eps=None,
+                    min_len=None, max_len=None, max_rounds=None, device=0, host=False, mem_budget=0, slab=None) -> dict:
+    """hu_tree_spr_search: the hill climb over SPR moves.  dict(parent, blen, child_off, child_idx, ll_start, ll_final, stop (one of
+    SPR_STOP), skipped, rounds: per accepted round (ll, pruned, targets, candidates, taken, applied), moves: per applied move (round, v,
+    w_from, w_to, dist), seconds)"""
+    o, parent, blen, seq = _spr_args("tree_spr_search", parent, blen, seq, model, eps, min_len, max_len, max_rounds, device, host, mem_budget,
+                                     radius, slab, spr_rounds, min_gain)
+    n, L = seq.shape
+    off, idx = _child_arrays(parent, child_off, child_idx)
+    cap = max(int(o.spr_rounds), 1)
+    rec = (SprRound * cap)()
+    mcap = cap * max(n, 1)
+    mv = np.zeros((mcap, 5), np.int32)
+    o.rounds = C.cast(rec, C.POINTER(SprRound)); o.rounds_cap = cap; o.moves = _p(mv, C.c_int32); o.moves_cap = mcap
+    _chk(load_library().hu_tree_spr_search(C.byref(o), C.c_int32(n), C.c_int32(L), _p(parent, C.c_int32), _p(blen, C.c_double), _p(seq, C.c_int8),
+                                           _p(off, C.c_int32), _p(idx, C.c_int32), C.byref(model)))
+    s = np.zeros(4)
+    _chk(load_library().hu_spr_timing(_p(s, C.c_double)))
+    return dict(parent=parent, blen=blen, child_off=off, child_idx=idx, ll_start=float(o.ll_start), ll_final=float(o.ll_final), stop=SPR_STOP[o.stop],
+                skipped=int(o.skipped),
+                rounds=[dict(ll=r.ll, pruned=r.pruned, targets=int(r.targets), candidates=r.candidates, taken=r.taken, applied=r.applied)
+                        for r in rec[:o.n_rounds]],
+                moves=[tuple(int(x) for x in row) for row in mv[:o.n_moves]], seconds=dict(fit=s[0], score=s[1], trial=s[2], other=s[3]))
+
+
 def tree_count_mutations(parent, cs_len: int, up_ptr: int, device=0) -> np.ndarray:
     """hu_tree_count_mutations: per column, the non-root nodes whose inferred state differs from their parent's, from the DEVICE
     fixed-rate up buffer at up_ptr ([n][cs_len][4] float64, as tree_evaluate leaves it with win_len 0)"""

@@ -1288,6 +1288,84 @@ int hu_tree_nni_support(const hu_support_opts* opts, int32_t n_nodes, int32_t cs
 		int32_t* count, double* sums);
 int hu_support_timing(double* seconds /* [4] */);
 
+/* ---- hmmufotu-amd-tree --ml-lengths --spr: subtree pruning and regrafting ----
+ * The tree, the model and the limits are those of the branch-length fit above: parent [n], blen [n], seq [n][cs_len], the fixed-rate
+ * model only, one device, no column windows.  All definitions are on the rooted arrays as they stand.
+ *
+ * A node v is prunable when it is not the root and p = parent[v] is not the root and has exactly the two children {v, s}; g = parent[p].
+ * Every other non-root v is not pruned and is counted (skipped): p the root, p a polytomy.  In the pruned tree T' the subtree of v and
+ * the node p are lifted out and s hangs on g with the length blen[s] + blen[p].  An edge of T' is named by its lower end w.
+ * The targets of v are the edges w of T' whose distance from the edge of s is 1 .. radius; the distance is the number of nodes on the
+ * path that joins the two edges, so edges that share a node are at distance 1, and a bifurcating root is a node like any other: its
+ * two branches are two targets.  A binary neighbourhood has 2^(d+1) targets at distance d.  The edge of s is distance 0, the position
+ * as it stands: the baseline, no move.  The targets come in the order of a depth-first walk from the edge of s: first into the subtree
+ * of s, then from g; at a node its children in node-id order, then the edge above it; behind every target what lies beyond it.
+ * Regraft at w: p goes into the edge of w, parent[p] = parent'(w), parent[w] = p, the children of p become {w, v}, parent[s] = g.  The
+ * edge's length L_w in T' is split in halves between blen[w] and blen[p], blen[s] takes blen[s] + blen[p] and the pendant blen[v]
+ * takes t.  Node ids, names and the root stay; in child_idx p takes w's place below parent'(w), s takes p's place below g and w takes
+ * s's place below p.  The baseline keeps the real split (blen[s], blen[p]).
+ * With x_j the product at the junction of the two sides of the target edge, each carried over its half, and y_j = up[v],
+ *   f_w(t) = sum_j log sum_ab pi_a x_a P_ab(t) y_b
+ * is an objective of the pendant length of the form of the branch-length fit (three ratios and a K_j per column, the same clamps and
+ * -inf rules) and is maximised the same way from blen[v] on [min_len, max_len].  gain_w = f_w(t*_w) - f_s(t*_s): the pendant is at its
+ * optimum on both sides.  f_s(blen[v]) is the tree's log-likelihood.  Of the two sides of a target the one away from s is a message of
+ * the level sweeps (up[w] where w is no ancestor of p, down[w] where it is; down[p] over the merged length above s); the other one is
+ * recomputed without v, one message per step of the walk, as the product of the carried messages of the node's other neighbours.  A
+ * node of any degree is walked through.
+ *
+ * hu_tree_spr_scores: for the P prunable nodes in ascending v: prune_node [P] = v, v_off [P + 1] the CSR offsets of its targets,
+ *   base_t [P] = t*_s, base_f [P] = f_s(t*_s), f_at_blen [P] = f_s(blen[v]); per target target_node = w, dist, t_star = t*_w,
+ *   f = f_w(t*_w).  node_cap and target_cap: the entries the outputs hold; *n_pruned = P and *n_targets are set before they are held
+ *   against the caps, and a call with both caps 0 only counts.  *skipped as above.  P = 0 is a success.
+ * hu_tree_spr_apply: the regraft of v at w with the pendant t on the arrays (child_idx may be NULL).  Host.  Refused: a v that is not
+ *   prunable, and a w that is no target position: the root, v, p, s (where v hangs) or a node inside v's subtree.  No radius is held.
+ * hu_tree_spr_search: parent, blen (and child_idx) in place.  A round fits the lengths (hu_tree_optimize_lengths with opts->blen),
+ *   scores every prunable v and takes as candidate the best target of every v (the largest f, ties by the smaller w) when its gain is
+ *   above min_gain.  No candidate ends the run (local optimum).  The candidates go by gain descending, ties by the smaller v, then the
+ *   smaller w; one is taken when none of {v, p, s, g, w, parent'(w)} and none of the nodes on the path from p to w is marked by one
+ *   taken before.  The taken moves are applied at once and the tree's log-likelihood is taken from an up sweep.  If it is not above
+ *   the fit's, the better half (rounded up) of the set is tried, down to one move; if that fails too the run ends (no improving
+ *   move).  At most spr_rounds rounds; a last fit follows the last accepted round; ll never decreases.  The report: n_rounds, stop,
+ *   n_moves, skipped (of the last scoring), ll_start (after the first fit), ll_final, per accepted round (rounds, rounds_cap entries)
+ *   the trial's ll, the nodes pruned, the targets scored, the candidates, the moves taken at first and those applied, and per applied
+ *   move (moves, moves_cap entries of five) round, v, w_from = s, w_to, dist.
+ * Memory (hu_spr_need): hu_blen_need, plus 32 bytes per node, plus 96 bytes of record and outputs per target, at most
+ *   min(2^(radius+2) - 3, n) targets per node and HU_SPR_REC_BYTES per launch, plus the scratch of a launch's workgroups: radius
+ *   messages of 32 cs_len bytes each and, above HU_BLEN_LDS_COLS columns, 24 cs_len bytes of ratios, HU_SPR_SLAB_BYTES at the most and
+ *   one workgroup's at the least.  Launches are cut into slabs of prune nodes that keep within these bounds (opts->slab > 0: at most so
+ *   many nodes); the result does not depend on the slab.  Held against opts->blen.mem_budget and the free memory as above.
+ * hu_spr_timing: seconds [4] of this thread's last hu_tree_spr_search = the fits, the scoring, the trials, the rest. */
+#define HU_SPR_MAX_RADIUS 32
+#define HU_SPR_SLAB_BYTES ((int64_t) 1 << 30)
+#define HU_SPR_REC_BYTES ((int64_t) 1 << 26)
+enum { HU_SPR_LOCAL_OPTIMUM = 0, HU_SPR_NO_MOVE = 1, HU_SPR_MAX_ROUNDS = 2 };
+typedef struct { double ll; int64_t targets; int32_t pruned, candidates, taken, applied; } hu_spr_round;
+typedef struct {
+	hu_blen_opts blen;    /* of every fit: eps, min_len, max_len, max_rounds, host, device, mem_budget; its rounds are not recorded */
+	double min_gain;      /* 1e-3, in units of log-likelihood */
+	int32_t radius;       /* 5; 1 .. HU_SPR_MAX_RADIUS */
+	int32_t spr_rounds;   /* 10 */
+	int32_t rounds_cap;   /* entries of rounds */
+	int32_t slab;         /* 0: what the bounds allow; > 0: at most this many prune nodes per launch */
+	hu_spr_round* rounds;
+	int32_t* moves;       /* [moves_cap][5]: round (from 1), v, w_from, w_to, dist */
+	int64_t moves_cap;
+	/* the report */
+	int32_t n_rounds, stop;
+	int64_t n_moves, skipped;
+	double ll_start, ll_final;
+} hu_spr_opts;
+void hu_spr_default_opts(hu_spr_opts* o);
+int64_t hu_spr_need(int32_t n_nodes, int32_t cs_len, int32_t radius);
+int hu_tree_spr_scores(const hu_spr_opts* opts, int32_t n_nodes, int32_t cs_len, const int32_t* parent, const double* blen, const int8_t* seq,
+		const hu_model_desc* model, int32_t node_cap, int64_t target_cap, int32_t* n_pruned, int64_t* n_targets, int64_t* skipped,
+		int32_t* prune_node, int64_t* v_off, double* base_t, double* base_f, double* f_at_blen,
+		int32_t* target_node, int32_t* dist, double* t_star, double* f);
+int hu_tree_spr_apply(int32_t n_nodes, int32_t* parent, double* blen, const int32_t* child_off, int32_t* child_idx, int32_t v, int32_t w, double t);
+int hu_tree_spr_search(hu_spr_opts* opts, int32_t n_nodes, int32_t cs_len, int32_t* parent, double* blen, const int8_t* seq,
+		const int32_t* child_off, int32_t* child_idx, const hu_model_desc* model);
+int hu_spr_timing(double* seconds /* [4] */);
+
 #ifdef __cplusplus
 }
 #endif
