@@ -6,7 +6,8 @@
 //                     [--ml-lengths [--start-tree FILE] [--ml-rounds N] [--ml-eps DBL] [--min-len DBL] [--max-len DBL] [--ml-log FILE]
 //                      [--nni [--nni-rounds N] [--nni-min-gain DBL] [--nni-log FILE]]
 //                      [--spr [--spr-radius N] [--spr-rounds N] [--spr-min-gain DBL] [--spr-log FILE]]
-//                      [--support N [--support-seed N] [--support-out FILE]]]
+//                      [--support N [--support-seed N] [--support-out FILE]]
+//                      [--start-tree FILE --add [--add-log FILE]]]
 // The MSA is read and pruned as hmmufotu-amd-build does (hu_build_inputs.h; the columns without a residue are found on the host here,
 // the same columns hu_prune_msa finds), so the tree joins by name to the same MSA there.  The distances and the joins are
 // hu_msa_tree's: on the device (hu_kern_dist.h, hu_kern_nj.h), or with --host by the library's host path.  Every refusal comes before
@@ -18,6 +19,8 @@
 // written by hu_newick_from_arrays with the same node ids, names and top node.
 // --spr moves whole subtrees: a hill climb over subtree pruning and regrafting within a radius (hu_tree_spr_search).  With
 // --nni the interchanges run first, then the SPR search, then the interchanges once more if a subtree was moved.
+// --add keeps a tree current: the sequences of the MSA that are no leaf of --start-tree are inserted into it
+// (hu_tree_add_search), and everything else runs on the grown tree.
 // --support labels the inner edges of the final tree with their local bootstrap support (hu_tree_nni_support): the share
 // of N resamplings of the columns in which the edge as it stands beats both of its nearest-neighbour interchanges.
 #include <cmath>
@@ -60,6 +63,8 @@ static void usage(const char* p) {
 		"            --spr-rounds  INT  : rounds of moves at the most, at least 1 [10]\n"
 		"            --spr-min-gain  DBL: smallest gain in log-likelihood for which a move is tried, above 0 [1e-3]\n"
 		"            --spr-log  FILE    : write the accepted rounds as TSV: round, ll, pruned, targets, candidates, taken, applied; then '# stop: REASON' and '# skipped: N nodes'\n"
+		"            --add  FLAG        : with --ml-lengths --start-tree: the sequences of the MSA that are no leaf of the start tree are inserted into it, each into the edge where the tree's likelihood is largest with its pendant at its optimum; a round takes one sequence per edge, the others are scored again against the grown tree\n"
+		"            --add-log  FILE    : write the rounds as TSV: round, ll, scored, inserted; then per sequence '# insert: round name node edge t f' and '# stop: all inserted'\n"
 		"            --support  INT     : with --ml-lengths: label every inner edge between two nodes of degree three with its local bootstrap support over INT replicates, 1 to 100000: the share of resampled alignments in which the edge beats both of its nearest-neighbour interchanges\n"
 		"            --support-seed  INT: seed of the replicates [1]\n"
 		"            --support-out  FILE: write the supports as TSV: node, name, kind, leaves, t0, alrt, count, replicates, support; then '# skipped: N edges at polytomies' and '# seed: S'\n"
@@ -74,6 +79,7 @@ int main(int argc, char** argv) {
 	bool mlLengths = false; std::string startFn, mlLogFn; int mlRounds = 50; double mlEps = 1e-5, minLen = 0.0, maxLen = 10.0;
 	bool nni = false, haveNniOpt = false; std::string nniLogFn; int nniRounds = 20; double nniMinGain = 1e-3;
 	bool spr = false, haveSprOpt = false; std::string sprLogFn; int sprRadius = 5, sprRounds = 10; double sprMinGain = 1e-3;
+	bool add = false; std::string addLogFn;
 	bool support = false, haveSupportOpt = false; long long supportN = 0; unsigned long long supportSeed = 1; std::string supportFn;
 	if(argc < 2) { usage(argv[0]); return EXIT_SUCCESS; }
 	for(int i = 1; i < argc; ++i) {
@@ -95,6 +101,7 @@ int main(int argc, char** argv) {
 		else if(a == "--spr") spr = true;
 		else if(a == "--spr-radius") { sprRadius = atoi(val()); haveSprOpt = true; } else if(a == "--spr-rounds") { sprRounds = atoi(val()); haveSprOpt = true; }
 		else if(a == "--spr-min-gain") { sprMinGain = atof(val()); haveSprOpt = true; } else if(a == "--spr-log") { sprLogFn = val(); haveSprOpt = true; }
+		else if(a == "--add") add = true; else if(a == "--add-log") addLogFn = val();
 		else if(a == "--support") { supportN = atoll(val()); support = true; }
 		else if(a == "--support-seed") { supportSeed = strtoull(val(), nullptr, 10); haveSupportOpt = true; }
 		else if(a == "--support-out") { supportFn = val(); haveSupportOpt = true; }
@@ -113,6 +120,8 @@ int main(int argc, char** argv) {
 	if(haveMem && (!(memGB > 0) || !std::isfinite(memGB))) { std::cerr << "--mem must be positive" << std::endl; return EXIT_FAILURE; }
 	if(device < 0) { std::cerr << "--device must be non-negative; --host runs without one" << std::endl; return EXIT_FAILURE; }
 	if(!mlLengths && (!startFn.empty() || !mlLogFn.empty())) { std::cerr << (startFn.empty() ? "--ml-log" : "--start-tree") << " goes with --ml-lengths" << std::endl; return EXIT_FAILURE; }
+	if(add && startFn.empty()) { std::cerr << "--add goes with --ml-lengths --start-tree: the new sequences are inserted into a start tree" << std::endl; return EXIT_FAILURE; }
+	if(!addLogFn.empty() && !add) { std::cerr << "--add-log goes with --add" << std::endl; return EXIT_FAILURE; }
 	if(nni && !mlLengths) { std::cerr << "--nni goes with --ml-lengths" << std::endl; return EXIT_FAILURE; }
 	if(haveNniOpt && !nni) { std::cerr << "--nni-rounds, --nni-min-gain and --nni-log go with --nni" << std::endl; return EXIT_FAILURE; }
 	if(spr && !mlLengths) { std::cerr << "--spr goes with --ml-lengths" << std::endl; return EXIT_FAILURE; }
@@ -206,6 +215,8 @@ int main(int argc, char** argv) {
 	std::unique_ptr<hu_newick, void (*)(hu_newick*)> nw(nullptr, hu_newick_free);
 	std::vector<int32_t> parent, childOff, childIdx; std::vector<double> blen;
 	int32_t nn = 0;
+	std::vector<std::string> nodeNames;                       /* of the parsed tree, and of the leaves --add appends */
+	std::vector<size_t> queryRow;                             /* --add: the rows of the MSA that are no leaf of --start-tree, ascending */
 	auto parse_tree = [&](const std::string& from) {
 		hu_newick* t = nullptr;
 		if(hu_newick_parse(text.data(), (int64_t) text.size(), &t) != HU_OK) { std::cerr << "Unable to read Newick tree in '" << from << "': " << hu_last_error() << std::endl; return false; }
@@ -213,6 +224,8 @@ int main(int argc, char** argv) {
 		hu_newick_size(t, &nn);
 		parent.resize(nn); childOff.resize((size_t) nn + 1); childIdx.resize((size_t) std::max(nn - 1, 1)); blen.resize(nn);
 		hu_newick_get(t, parent.data(), blen.data(), childOff.data(), childIdx.data());
+		nodeNames.resize((size_t) nn);
+		for(int32_t i = 0; i < nn; ++i) nodeNames[i] = hu_newick_name(t, i);
 		return true;
 	};
 	int64_t fitNodes = 2 * (int64_t) n - 2;                    /* the joins' tree: n leaves, n - 3 joins, the top node */
@@ -222,16 +235,19 @@ int main(int argc, char** argv) {
 		info("Newick Tree read: " + std::to_string(nn) + " nodes");
 		std::unordered_map<std::string, int32_t> seen;
 		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) {
-			const std::string leaf = hu_newick_name(nw.get(), i);
+			const std::string leaf = nodeNames[i].c_str();
 			if(!seen.insert({leaf, i}).second) { std::cerr << "Non-unique leaf name '" << leaf << "' found in the tree '" << startFn << "'" << std::endl; return EXIT_FAILURE; }
 			if(!inp.name2row.count(leaf)) { std::cerr << "Unmatched MSA and Tree: leaf '" << leaf << "' of '" << startFn << "' is no sequence of the MSA" << std::endl; return EXIT_FAILURE; }
 		}
-		for(size_t i = 0; i < n; ++i) if(!seen.count(inp.rowName[i])) { std::cerr << "Unmatched MSA and Tree: sequence '" << inp.rowName[i] << "' is no leaf of '" << startFn << "'" << std::endl; return EXIT_FAILURE; }
+		for(size_t i = 0; i < n; ++i) if(!seen.count(inp.rowName[i])) { if(add) { queryRow.push_back(i); continue; } std::cerr << "Unmatched MSA and Tree: sequence '" << inp.rowName[i] << "' is no leaf of '" << startFn << "'" << std::endl; return EXIT_FAILURE; }
 		if(nn < 2) { std::cerr << "The tree '" << startFn << "' has one node: no branch to fit" << std::endl; return EXIT_FAILURE; }
-		fitNodes = nn;
+		fitNodes = (int64_t) nn + 2 * (int64_t) queryRow.size();
+		if(fitNodes > INT32_MAX) { std::cerr << "--add: " << queryRow.size() << " new sequences give a tree of too many nodes" << std::endl; return EXIT_FAILURE; }
 	}
 	if(mlLengths && haveMem) {
 		const int64_t need = support ? hu_support_need((int32_t) fitNodes, (int32_t) L, (int32_t) supportN) : nni ? hu_nni_need((int32_t) fitNodes, (int32_t) L) : hu_blen_need((int32_t) fitNodes, (int32_t) L), have = (int64_t)(memGB * 1e9);
+		const int64_t addNeed = queryRow.empty() ? 0 : hu_add_need((int32_t) fitNodes, (int32_t) L, (int32_t) queryRow.size());
+		if(addNeed > have) { std::cerr << "--add: " << fitNodes << " nodes of " << L << " columns after " << queryRow.size() << " insertions need " << addNeed << " bytes (64 bytes per node and column for the messages), --mem allows " << have << " bytes" << std::endl; return EXIT_FAILURE; }
 		const int64_t sprNeed = spr ? hu_spr_need((int32_t) fitNodes, (int32_t) L, sprRadius) : 0;
 		if(sprNeed > have && sprNeed >= need) { std::cerr << "--spr: " << fitNodes << " nodes of " << L << " columns at radius " << sprRadius << " need " << sprNeed << " bytes (64 bytes per node and column for the messages), --mem allows " << have << " bytes" << std::endl; return EXIT_FAILURE; }
 		if(need > have) { std::cerr << (support ? "--support: " : nni ? "--nni: " : "--ml-lengths: ") << fitNodes << " nodes of " << L << " columns need " << need << " bytes (64 bytes per node and column for the messages), --mem allows " << have << " bytes" << std::endl; return EXIT_FAILURE; }
@@ -264,6 +280,56 @@ int main(int argc, char** argv) {
 		hu_nj_newick((int64_t) n, nm.data(), join.data(), len.data(), last3, lastLen3, &text[0], tl + 1);
 		text.resize((size_t) tl);
 		if(mlLengths && !parse_tree("the joins")) return EXIT_FAILURE;
+	}
+	/* --add: the sequences that are no leaf of --start-tree are inserted first; the arrays grow by two nodes per sequence, and whatever
+	 * follows (the fit, --nni, --spr, --support) runs on the grown tree.  Without such a sequence the run is the run without the flag */
+	bool grown = false;
+	if(add && (!queryRow.empty() || !addLogFn.empty())) {
+		const size_t q = queryRow.size(), N = (size_t) nn + 2 * q;
+		std::vector<int8_t> seq(N * L, (int8_t) -2), qrows(std::max<size_t>(q, 1) * L);
+		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(nodeNames[i]) * L, L);
+		for(size_t k = 0; k < q; ++k) memcpy(qrows.data() + k * L, rows.data() + queryRow[k] * L, L);
+		std::vector<int32_t> par(parent), off(childOff), idx(childIdx), qnode(std::max<size_t>(q, 1), -1);
+		std::vector<double> bl(blen);
+		par.resize(N, -1); bl.resize(N, 0.0); off.resize(N + 1, 0); idx.resize(std::max<size_t>(N - 1, 1), 0);
+		for(int32_t i = 0; i < nn; ++i) if(par[i] >= 0 && std::isfinite(bl[i])) bl[i] = std::min(std::max(bl[i], minLen), maxLen);
+		hu_add_opts ao;
+		hu_add_default_opts(&ao);
+		std::vector<hu_add_round> arounds(std::max<size_t>(q, 1));
+		std::vector<hu_add_insert> ains(std::max<size_t>(q, 1));
+		ao.blen.eps = mlEps; ao.blen.min_len = minLen; ao.blen.max_len = maxLen; ao.blen.max_rounds = mlRounds; ao.blen.host = host ? 1 : 0; ao.blen.device = device;
+		ao.blen.mem_budget = haveMem ? (int64_t)(memGB * 1e9) : 0;
+		ao.rounds = arounds.data(); ao.rounds_cap = (int32_t) arounds.size(); ao.inserts = ains.data(); ao.inserts_cap = (int64_t) ains.size();
+		if(hu_tree_add_search(&ao, nn, (int32_t) L, (int32_t) q, par.data(), bl.data(), seq.data(), off.data(), idx.data(), qrows.data(), qnode.data(), &md) != HU_OK) {
+			std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
+		if(verbose) {
+			char line[240];
+			snprintf(line, sizeof(line), "Sequences inserted: %d in %d round(s), log-likelihood %.17g of the start tree, %.17g of the grown tree of %zu nodes", ao.n_inserted, ao.n_rounds, ao.ll_start, ao.ll_final, N);
+			std::cerr << line << std::endl;
+			for(int32_t r = 0; r < ao.n_rounds; ++r) {
+				snprintf(line, sizeof(line), "round %d: %d scored, %d inserted, log-likelihood %.17g", r + 1, arounds[r].scored, arounds[r].inserted, arounds[r].ll);
+				std::cerr << line << std::endl;
+			}
+			double s[4];
+			hu_add_timing(s);
+			std::cerr << "insertion sweeps " << s[0] << " s, scoring " << s[1] << " s, fits " << s[2] << " s, the rest " << s[3] << " s" << std::endl;
+		}
+		if(!addLogFn.empty()) {
+			FILE* f = fopen(addLogFn.c_str(), "w");
+			if(!f) { std::cerr << "Unable to write to '" << addLogFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+			fprintf(f, "round\tll\tscored\tinserted\n0\t%.17g\t0\t0\n", ao.ll_start);
+			for(int32_t r = 0; r < ao.n_rounds; ++r) fprintf(f, "%d\t%.17g\t%d\t%d\n", r + 1, arounds[r].ll, arounds[r].scored, arounds[r].inserted);
+			for(int32_t k = 0; k < ao.n_inserted; ++k) fprintf(f, "# insert: %d\t%s\t%d\t%d\t%.17g\t%.17g\n", ains[k].round, inp.rowName[queryRow[(size_t) ains[k].query]].c_str(), ains[k].v, ains[k].w, ains[k].t, ains[k].f);
+			fprintf(f, "# stop: all inserted\n");
+			if(fclose(f) != 0) { std::cerr << "Unable to write to '" << addLogFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+		}
+		if(q > 0) {
+			parent.swap(par); blen.swap(bl); childOff.swap(off); childIdx.swap(idx);
+			nodeNames.resize(N);
+			for(size_t k = 0; k < q; ++k) nodeNames[(size_t) qnode[k]] = inp.rowName[queryRow[k]];
+			nn = (int32_t) N;
+			grown = true;
+		}
 	}
 	/* --ml-lengths: the parsed tree's arrays go into the fit, and its handle writes them back */
 	hu_blen_opts bo;
@@ -307,7 +373,7 @@ int main(int argc, char** argv) {
 	};
 	if(mlLengths && nni) {
 		std::vector<int8_t> seq((size_t) nn * L, (int8_t) -2);
-		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(hu_newick_name(nw.get(), i)) * L, L);
+		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(nodeNames[i]) * L, L);
 		for(int32_t i = 0; i < nn; ++i) if(parent[i] >= 0 && std::isfinite(blen[i])) blen[i] = std::min(std::max(blen[i], minLen), maxLen);
 		hu_nni_opts no;
 		hu_nni_default_opts(&no);
@@ -343,7 +409,7 @@ int main(int argc, char** argv) {
 			}
 		}
 		std::vector<const char*> nodeName((size_t) nn);
-		for(int32_t i = 0; i < nn; ++i) nodeName[i] = hu_newick_name(nw.get(), i);
+		for(int32_t i = 0; i < nn; ++i) nodeName[i] = nodeNames[i].c_str();
 		const int64_t wl = hu_newick_from_arrays(nn, parent.data(), childOff.data(), childIdx.data(), nodeName.data(), blen.data(), nullptr, 0);
 		if(wl < 0) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
 		text.assign((size_t) wl + 1, '\0');
@@ -360,11 +426,11 @@ int main(int argc, char** argv) {
 	}
 	else if(mlLengths && spr) {
 		std::vector<int8_t> seq((size_t) nn * L, (int8_t) -2);
-		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(hu_newick_name(nw.get(), i)) * L, L);
+		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(nodeNames[i]) * L, L);
 		for(int32_t i = 0; i < nn; ++i) if(parent[i] >= 0 && std::isfinite(blen[i])) blen[i] = std::min(std::max(blen[i], minLen), maxLen);
 		if(run_spr(seq) < 0) return EXIT_FAILURE;
 		std::vector<const char*> nodeName((size_t) nn);
-		for(int32_t i = 0; i < nn; ++i) nodeName[i] = hu_newick_name(nw.get(), i);
+		for(int32_t i = 0; i < nn; ++i) nodeName[i] = nodeNames[i].c_str();
 		const int64_t wl = hu_newick_from_arrays(nn, parent.data(), childOff.data(), childIdx.data(), nodeName.data(), blen.data(), nullptr, 0);
 		if(wl < 0) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
 		text.assign((size_t) wl + 1, '\0');
@@ -373,7 +439,7 @@ int main(int argc, char** argv) {
 	}
 	else if(mlLengths) {
 		std::vector<int8_t> seq((size_t) nn * L, (int8_t) -2);
-		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(hu_newick_name(nw.get(), i)) * L, L);
+		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(nodeNames[i]) * L, L);
 		/* a start outside the interval, a negative length of the joins' last node among them, begins at its nearer end */
 		for(int32_t i = 0; i < nn; ++i) if(parent[i] >= 0 && std::isfinite(blen[i])) blen[i] = std::min(std::max(blen[i], minLen), maxLen);
 		rounds.resize((size_t) mlRounds);
@@ -390,10 +456,14 @@ int main(int argc, char** argv) {
 			hu_blen_timing(s);
 			std::cerr << "sweeps " << s[0] << " s, steps " << s[1] << " s, trial sweeps " << s[2] << " s, the rest " << s[3] << " s" << std::endl;
 		}
-		const int64_t wl = hu_newick_write(nw.get(), blen.data(), nullptr, 0);
+		/* the handle knows the start tree alone: a grown tree is written from its arrays */
+		std::vector<const char*> nodeName((size_t) nn);
+		for(int32_t i = 0; i < nn; ++i) nodeName[i] = nodeNames[i].c_str();
+		const int64_t wl = grown ? hu_newick_from_arrays(nn, parent.data(), childOff.data(), childIdx.data(), nodeName.data(), blen.data(), nullptr, 0) : hu_newick_write(nw.get(), blen.data(), nullptr, 0);
 		if(wl < 0) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
 		text.assign((size_t) wl + 1, '\0');
-		hu_newick_write(nw.get(), blen.data(), &text[0], wl + 1);
+		if(grown) hu_newick_from_arrays(nn, parent.data(), childOff.data(), childIdx.data(), nodeName.data(), blen.data(), &text[0], wl + 1);
+		else hu_newick_write(nw.get(), blen.data(), &text[0], wl + 1);
 		text.resize((size_t) wl);
 		if(!mlLogFn.empty()) {
 			FILE* f = fopen(mlLogFn.c_str(), "w");
@@ -407,7 +477,7 @@ int main(int argc, char** argv) {
 	/* --support: the supports of the final tree's eligible edges become the labels of their lower ends */
 	if(support) {
 		std::vector<int8_t> seq((size_t) nn * L, (int8_t) -2);
-		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(hu_newick_name(nw.get(), i)) * L, L);
+		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(nodeNames[i]) * L, L);
 		hu_support_opts so;
 		hu_support_default_opts(&so);
 		so.blen.min_len = minLen; so.blen.max_len = maxLen; so.blen.host = host ? 1 : 0; so.blen.device = device; so.blen.mem_budget = haveMem ? (int64_t)(memGB * 1e9) : 0;
@@ -433,7 +503,7 @@ int main(int argc, char** argv) {
 		};
 		std::vector<std::string> label((size_t) nn);
 		std::vector<const char*> nodeName((size_t) nn);
-		for(int32_t i = 0; i < nn; ++i) label[i] = hu_newick_name(nw.get(), i);
+		for(int32_t i = 0; i < nn; ++i) label[i] = nodeNames[i];
 		for(int32_t e = 0; e < nE; ++e) {
 			char num[32];
 			snprintf(num, sizeof(num), "%.3f", (double) eCount[e] / (double) supportN);
@@ -458,7 +528,7 @@ int main(int argc, char** argv) {
 				const int32_t u = eNode[e], s = other_end(u);
 				const bool root3 = parent[u] == root && s < 0;
 				const double t0 = s >= 0 ? blen[u] + blen[s] : blen[u], alrt = 2.0 * (eF[(size_t) e * 3] - std::max(eF[(size_t) e * 3 + 1], eF[(size_t) e * 3 + 2]));
-				fprintf(f, "%d\t%s\t%s\t%d\t%.17g\t%.17g\t%d\t%lld\t%.17g\n", u, hu_newick_name(nw.get(), u), s >= 0 ? "root2" : root3 ? "root3" : "inner", leaves[u], t0, alrt,
+				fprintf(f, "%d\t%s\t%s\t%d\t%.17g\t%.17g\t%d\t%lld\t%.17g\n", u, nodeNames[u].c_str(), s >= 0 ? "root2" : root3 ? "root3" : "inner", leaves[u], t0, alrt,
 					eCount[e], supportN, (double) eCount[e] / (double) supportN);
 			}
 			fprintf(f, "# skipped: %lld edges at polytomies\n# seed: %llu\n", (long long) skipped, supportSeed);

@@ -1363,6 +1363,107 @@ def tree_spr_search(parent, blen, seq, model: ModelDesc, child_off=None, child_i
                 moves=[tuple(int(x) for x in row) for row in mv[:o.n_moves]], seconds=dict(fit=s[0], score=s[1], trial=s[2], other=s[3]))
 
 
+class AddRound(C.Structure):
+    _fields_ = [("ll", C.c_double), ("scored", C.c_int32), ("inserted", C.c_int32)]
+
+
+class AddInsert(C.Structure):
+    _fields_ = [("round", C.c_int32), ("query", C.c_int32), ("v", C.c_int32), ("w", C.c_int32), ("t", C.c_double), ("f", C.c_double)]
+
+
+class AddOpts(C.Structure):
+    _fields_ = [("blen", BlenOpts), ("slab", C.c_int32), ("tile", C.c_int32), ("rounds_cap", C.c_int32), ("reserved", C.c_int32),
+                ("rounds", C.POINTER(AddRound)), ("inserts", C.POINTER(AddInsert)), ("inserts_cap", C.c_int64),
+                ("n_rounds", C.c_int32), ("n_inserted", C.c_int32), ("ll_start", C.c_double), ("ll_final", C.c_double)]
+
+
+ADD_TILE = 16
+
+
+def _add_args(what, parent, blen, seq, queries, eps, min_len, max_len, max_rounds, device, host, mem_budget, slab, tile):
+    parent = np.ascontiguousarray(parent, np.int32).copy(); blen = np.ascontiguousarray(blen, np.float64).copy()
+    seq = np.ascontiguousarray(seq, np.int8)
+    if seq.ndim != 2 or parent.shape != (seq.shape[0],) or blen.shape != parent.shape:
+        raise EngineError(what + ": parent [n], blen [n] and seq [n][cs_len]")
+    queries = np.ascontiguousarray(queries, np.int8).reshape(-1, seq.shape[1]) if len(queries) else np.zeros((0, seq.shape[1]), np.int8)
+    o = AddOpts()
+    load_library().hu_add_default_opts(C.byref(o))
+    for k, v in (("eps", eps), ("min_len", min_len), ("max_len", max_len)):
+        if v is not None:
+            setattr(o.blen, k, float(v))
+    if max_rounds is not None:
+        o.blen.max_rounds = int(max_rounds)
+    for k, v in (("slab", slab), ("tile", tile)):
+        if v is not None:
+            setattr(o, k, int(v))
+    o.blen.host = 1 if host else 0; o.blen.device = int(device); o.blen.mem_budget = int(mem_budget or 0)
+    return o, parent, blen, seq, queries
+
+
+def add_need(final_nodes: int, cs_len: int, n_query: int) -> int:
+    """hu_add_need: the bytes the insertion of n_query sequences holds for a grown tree of final_nodes x cs_len"""
+    lib = load_library()
+    lib.hu_add_need.restype = C.c_int64
+    return int(lib.hu_add_need(C.c_int32(final_nodes), C.c_int32(cs_len), C.c_int32(n_query)))
+
+
+def tree_add_scores(parent, blen, seq, queries, model: ModelDesc, min_len=None, max_len=None, device=0, host=False, mem_budget=0,
+                    slab=None, tile=None) -> dict:
+    """hu_tree_add_scores: queries [q][cs_len] against every edge of the tree.  dict(t_star [q][n], f [q][n] (the root's entries 0 and
+    -inf), best_w [q], best_t [q], best_f [q]: the best edge of every query, the largest f and the smaller w among equals)"""
+    o, parent, blen, seq, qs = _add_args("tree_add_scores", parent, blen, seq, queries, None, min_len, max_len, None, device, host, mem_budget, slab, tile)
+    n, L = seq.shape
+    q = len(qs)
+    ts = np.zeros((q, n)); f = np.zeros((q, n)); bw = np.zeros(max(q, 1), np.int32); bt = np.zeros(max(q, 1)); bf = np.zeros(max(q, 1))
+    _chk(load_library().hu_tree_add_scores(C.byref(o), C.c_int32(n), C.c_int32(L), _p(parent, C.c_int32), _p(blen, C.c_double), _p(seq, C.c_int8),
+                                           C.byref(model), C.c_int32(q), _p(qs, C.c_int8) if q else None, _p(ts, C.c_double) if q else None,
+                                           _p(f, C.c_double) if q else None, _p(bw, C.c_int32), _p(bt, C.c_double), _p(bf, C.c_double)))
+    return dict(t_star=ts, f=f, best_w=bw[:q].copy(), best_t=bt[:q].copy(), best_f=bf[:q].copy())
+
+
+def tree_add_apply(parent, blen, w: int, t: float, child_off=None, child_idx=None, min_len=0.0, max_len=10.0) -> dict:
+    """hu_tree_add_apply: a new leaf hung into the middle of the edge above w with the pendant t: the nodes p = n and v = n + 1 are
+    appended.  dict(parent [n + 2], blen [n + 2], child_off [n + 3], child_idx [n + 1]), the inputs are not changed"""
+    n = len(parent)
+    off, idx = _child_arrays(np.ascontiguousarray(parent, np.int32), child_off, child_idx)
+    par = np.full(n + 2, -1, np.int32); par[:n] = parent
+    bl = np.zeros(n + 2); bl[:n] = blen
+    off2 = np.zeros(n + 3, np.int32); off2[:n + 1] = off[:n + 1]
+    idx2 = np.zeros(n + 1, np.int32); idx2[:max(n - 1, 0)] = idx[:max(n - 1, 0)]
+    _chk(load_library().hu_tree_add_apply(C.c_int32(n), _p(par, C.c_int32), _p(bl, C.c_double), _p(off2, C.c_int32), _p(idx2, C.c_int32),
+                                          C.c_int32(int(w)), C.c_double(float(t)), C.c_double(float(min_len)), C.c_double(float(max_len))))
+    return dict(parent=par, blen=bl, child_off=off2, child_idx=idx2)
+
+
+def tree_add_search(parent, blen, seq, queries, model: ModelDesc, child_off=None, child_idx=None, eps=None, min_len=None, max_len=None,
+                    max_rounds=None, device=0, host=False, mem_budget=0, slab=None, tile=None) -> dict:
+    """hu_tree_add_search: every query inserted into the tree, round by round.  dict(parent, blen, seq, child_off, child_idx of the
+    grown tree of n + 2 q nodes, query_node [q] the leaf of every query, ll_start, ll_final, rounds: per round (ll, scored, inserted),
+    inserts: per insertion (round, query, v, w, t, f), seconds)"""
+    o, parent, blen, seq, qs = _add_args("tree_add_search", parent, blen, seq, queries, eps, min_len, max_len, max_rounds, device, host, mem_budget,
+                                         slab, tile)
+    n, L = seq.shape
+    q = len(qs); N = n + 2 * q
+    off, idx = _child_arrays(parent, child_off, child_idx)
+    par = np.full(N, -1, np.int32); par[:n] = parent
+    bl = np.zeros(N); bl[:n] = blen
+    sq = np.full((N, L), -2, np.int8); sq[:n] = seq
+    off2 = np.zeros(N + 1, np.int32); off2[:n + 1] = off[:n + 1]
+    idx2 = np.zeros(max(N - 1, 1), np.int32); idx2[:max(n - 1, 0)] = idx[:max(n - 1, 0)]
+    qn = np.full(max(q, 1), -1, np.int32)
+    cap = max(q, 1)
+    rec = (AddRound * cap)(); ins = (AddInsert * cap)()
+    o.rounds = C.cast(rec, C.POINTER(AddRound)); o.rounds_cap = cap; o.inserts = C.cast(ins, C.POINTER(AddInsert)); o.inserts_cap = cap
+    _chk(load_library().hu_tree_add_search(C.byref(o), C.c_int32(n), C.c_int32(L), C.c_int32(q), _p(par, C.c_int32), _p(bl, C.c_double), _p(sq, C.c_int8),
+                                           _p(off2, C.c_int32), _p(idx2, C.c_int32), _p(qs, C.c_int8) if q else None, _p(qn, C.c_int32), C.byref(model)))
+    s = np.zeros(4)
+    _chk(load_library().hu_add_timing(_p(s, C.c_double)))
+    return dict(parent=par, blen=bl, seq=sq, child_off=off2, child_idx=idx2, query_node=qn[:q].copy(), ll_start=float(o.ll_start),
+                ll_final=float(o.ll_final), rounds=[dict(ll=r.ll, scored=r.scored, inserted=r.inserted) for r in rec[:o.n_rounds]],
+                inserts=[dict(round=i.round, query=i.query, v=i.v, w=i.w, t=i.t, f=i.f) for i in ins[:o.n_inserted]],
+                seconds=dict(sweep=s[0], score=s[1], fit=s[2], other=s[3]))
+
+
 def tree_count_mutations(parent, cs_len: int, up_ptr: int, device=0) -> np.ndarray:
     """hu_tree_count_mutations: per column, the non-root nodes whose inferred state differs from their parent's, from the DEVICE
     fixed-rate up buffer at up_ptr ([n][cs_len][4] float64, as tree_evaluate leaves it with win_len 0)"""

@@ -1366,6 +1366,70 @@ int hu_tree_spr_search(hu_spr_opts* opts, int32_t n_nodes, int32_t cs_len, int32
 		const int32_t* child_off, int32_t* child_idx, const hu_model_desc* model);
 int hu_spr_timing(double* seconds /* [4] */);
 
+/* ---- hmmufotu-amd-tree --ml-lengths --start-tree T --add: new sequences inserted into a start tree ----
+ * The tree, the model and the limits are those of the branch-length fit above: parent [n], blen [n], seq [n][cs_len], the fixed-rate
+ * model only, one device, no column windows.  All definitions are on the rooted arrays as they stand.
+ *
+ * A query is a row of the alignment that is no leaf of the tree: qseq [n_query][cs_len] in the codes of seq, numbered in the order
+ * given (the program gives them in ascending row of the MSA).  An edge is named by its lower end w, any non-root node.
+ * Insert query r at w with the pendant t: two nodes are appended, p = n (inner, unnamed) and v = n + 1 (a leaf with r's row);
+ * parent[p] = parent[w], parent[w] = p, parent[v] = p; blen[w] and blen[p] each take half of the old blen[w], blen[v] = t.  In the
+ * child lists p takes w's place below parent(w), and the children of p are w, then v.  Existing ids, names and the top node stay.
+ * With x_j the product at the junction of up[w] and down[w], each carried over half of blen[w], and y_j the leaf message of r's
+ * column (one-hot where the row has a symbol, log pi where it has none),
+ *   f_{w,r}(t) = sum_j log sum_ab pi_a x_a P_ab(t) y_b
+ * is the log-likelihood of the tree with r inserted at w.  It has the form of the branch-length fit (three ratios and a K_j per
+ * column, the same D_j >= DBL_MIN clamp and -inf rules: never a NaN) and is maximised the same way on [min_len, max_len], from the
+ * mean length of the tree's non-root branches clipped to the interval.  The score of (w, r) is f_{w,r}(t*).  The junction does not
+ * depend on the query and the query's side is a look-up: c_jk = A_jk T[k][s_rj], A_jk = sum_a pi_a x_a U_ak, T[k][s] = sum_b U1_kb
+ * y^(s)_b over the five symbols, so an edge's ratios A_jk / A_j0 are computed once for a tile of queries.
+ *
+ * hu_tree_add_scores: t_star, f [n_query][n_nodes] (may both be NULL) = t* and f(t*) of every (query, edge), the root's entries 0 and
+ *   -inf; best_w, best_t, best_f [n_query]: the best edge of every query, the largest f and the smaller w among equals.
+ * hu_tree_add_apply: the insertion at w with the pendant t on arrays with room for two more nodes: parent, blen [n + 2], child_off
+ *   [n + 3], child_idx [n + 1], the child lists rebuilt by the rule above (both may be NULL).  Host.  Refused: w the root or out of
+ *   range, t outside [min_len, max_len].
+ * hu_tree_add_search: arrays with room for n + 2 n_query nodes (seq [n + 2 n_query][cs_len], child_off [n + 2 n_query + 1],
+ *   child_idx [n + 2 n_query - 1]), updated in place.  The lengths of the start tree are fitted on its own leaves
+ *   (hu_tree_optimize_lengths with opts->blen).  Then rounds until no query is left: sweep up and down, score every remaining query
+ *   against every edge, per edge take the one query with the largest f among those whose best edge it is (ties: the smaller query),
+ *   insert the taken ones in ascending query, which fixes the new ids, and fit the lengths again.  The others wait for the next
+ *   round, where they are scored against the grown tree.  Every round inserts at least one query.  query_node [n_query]: the leaf v
+ *   of every query.  The report: n_rounds, n_inserted, ll_start (after the first fit), ll_final, per round (rounds, rounds_cap
+ *   entries) ll after its fit, the queries scored and inserted, and per insertion (inserts, inserts_cap entries) round, query, v, w,
+ *   t*, f.  n_query = 0 is the fit alone.
+ * Memory (hu_add_need): hu_blen_need of the final tree plus a launch: per tile of HU_ADD_TILE queries 16 bytes of outputs per node
+ *   and query, the queries' rows and records and, above HU_BLEN_LDS_COLS columns, 24 cs_len bytes of ratios per node;
+ *   HU_ADD_SLAB_BYTES at the most and one tile at the least.  Launches are cut into slabs of queries that keep within these bounds
+ *   (opts->slab > 0: at most so many queries; opts->tile > 0: so many queries per workgroup); the result does not depend on either,
+ *   to the bit.  Held against opts->blen.mem_budget and the free memory as above.
+ * hu_add_timing: seconds [4] of this thread's last hu_tree_add_search = the sweeps, the scoring, the fits, the rest. */
+#define HU_ADD_TILE 16             /* queries of a workgroup of k_add_score */
+#define HU_ADD_SLAB_BYTES ((int64_t) 1 << 32)
+typedef struct { double ll; int32_t scored, inserted; } hu_add_round;
+typedef struct { int32_t round, query, v, w; double t, f; } hu_add_insert;
+typedef struct {
+	hu_blen_opts blen;    /* of every fit: eps, min_len, max_len, max_rounds, host, device, mem_budget; its rounds are not recorded */
+	int32_t slab;         /* 0: what the bounds allow; > 0: at most this many queries per launch */
+	int32_t tile;         /* 0: HU_ADD_TILE; > 0: this many queries per workgroup */
+	int32_t rounds_cap;   /* entries of rounds */
+	int32_t reserved;
+	hu_add_round* rounds;
+	hu_add_insert* inserts;
+	int64_t inserts_cap;
+	/* the report */
+	int32_t n_rounds, n_inserted;
+	double ll_start, ll_final;
+} hu_add_opts;
+void hu_add_default_opts(hu_add_opts* o);
+int64_t hu_add_need(int32_t final_nodes, int32_t cs_len, int32_t n_query);
+int hu_tree_add_scores(const hu_add_opts* opts, int32_t n_nodes, int32_t cs_len, const int32_t* parent, const double* blen, const int8_t* seq,
+		const hu_model_desc* model, int32_t n_query, const int8_t* qseq, double* t_star, double* f, int32_t* best_w, double* best_t, double* best_f);
+int hu_tree_add_apply(int32_t n_nodes, int32_t* parent, double* blen, int32_t* child_off, int32_t* child_idx, int32_t w, double t, double min_len, double max_len);
+int hu_tree_add_search(hu_add_opts* opts, int32_t n_nodes, int32_t cs_len, int32_t n_query, int32_t* parent, double* blen, int8_t* seq,
+		int32_t* child_off, int32_t* child_idx, const int8_t* qseq, int32_t* query_node, const hu_model_desc* model);
+int hu_add_timing(double* seconds /* [4] */);
+
 #ifdef __cplusplus
 }
 #endif
