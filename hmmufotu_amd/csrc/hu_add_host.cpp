@@ -4,7 +4,6 @@
 // The arithmetic of a column is hu_tree_add.h's, shared with the kernel; the sweeps, the fit's round loop and the Newton rule are
 // hu_blen_host.cpp's and hu_tree_blen.h's.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include "hu_tree_add.h"
@@ -141,16 +140,14 @@ extern "C" int hu_tree_add_apply(int32_t n, int32_t* parent, double* blen, int32
 } catch(...) { return hu_catch_all("hu_tree_add_apply"); }
 
 /* ---- the round loop ---- */
-static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 int hu_add_rounds(const char* fn, hu_add_opts* o, int32_t n, int32_t cs_len, int32_t n_query, int32_t* parent, double* blen, int8_t* seq,
 		int32_t* child_off, int32_t* child_idx, const int8_t* qseq, int32_t* query_node, const HuAddOps& ops, double* sec) {
 	const size_t L = (size_t) cs_len;
 	o->n_rounds = 0; o->n_inserted = 0;
 	int rc;
-	double ll = 0, t0 = now_s();
+	double ll = 0, t0 = hu_now_s();
 	if((rc = ops.fit(n, parent, blen, seq, &ll)) != HU_OK) return rc;
-	sec[2] += now_s() - t0;
+	sec[2] += hu_now_s() - t0;
 	o->ll_start = o->ll_final = ll;
 	std::vector<int32_t> rem((size_t) n_query), bw, owner, take;
 	for(int32_t r = 0; r < n_query; ++r) rem[(size_t) r] = r;
@@ -162,15 +159,15 @@ int hu_add_rounds(const char* fn, hu_add_opts* o, int32_t n, int32_t cs_len, int
 		hu_blen_opts bo = o->blen;
 		bo.mem_budget = 0;
 		if((rc = hu_blen_check(fn, &bo, n, cs_len, parent, blen, seq, 0, &tp)) != HU_OK) return rc;
-		t0 = now_s();
+		t0 = hu_now_s();
 		if((rc = ops.sweep(n, parent, blen, seq, tp)) != HU_OK) return rc;
-		sec[0] += now_s() - t0;
+		sec[0] += hu_now_s() - t0;
 		rows.resize((size_t) nq * L);
 		for(int32_t i = 0; i < nq; ++i) memcpy(rows.data() + (size_t) i * L, qseq + (size_t) rem[(size_t) i] * L, L);
 		bw.assign((size_t) nq, -1); bt.assign((size_t) nq, 0.0); bf.assign((size_t) nq, 0.0);
-		t0 = now_s();
+		t0 = hu_now_s();
 		if((rc = ops.score(n, tp.root, blen, hu_add_start(n, parent, blen, o->blen.min_len, o->blen.max_len), nq, rows.data(), bw.data(), bt.data(), bf.data())) != HU_OK) return rc;
-		sec[1] += now_s() - t0;
+		sec[1] += hu_now_s() - t0;
 		/* per edge the one query with the largest f among those whose best edge it is; rem is ascending, so a tie keeps the smaller query */
 		owner.assign((size_t) n, -1);
 		for(int32_t i = 0; i < nq; ++i) {
@@ -195,9 +192,9 @@ int hu_add_rounds(const char* fn, hu_add_opts* o, int32_t n, int32_t cs_len, int
 			n += 2;
 		}
 		for(size_t k = take.size(); k-- > 0;) rem.erase(rem.begin() + take[k]);
-		t0 = now_s();
+		t0 = hu_now_s();
 		if((rc = ops.fit(n, parent, blen, seq, &ll)) != HU_OK) return rc;
-		sec[2] += now_s() - t0;
+		sec[2] += hu_now_s() - t0;
 		o->ll_final = ll;
 		if(o->rounds && o->n_rounds < o->rounds_cap) { hu_add_round& R = o->rounds[o->n_rounds]; R.ll = ll; R.scored = nq; R.inserted = (int32_t) take.size(); }
 		o->n_rounds++;
@@ -226,33 +223,14 @@ int hu_add_host_search_entry(const char* fn, hu_add_opts* o, int32_t n, int32_t 
 	HuBlenTopo tp0;
 	int rc = hu_add_check(fn, o, n, cs_len, parent, blen, seq, n_query, qseq, true, 0, &tp0);
 	if(rc != HU_OK) return rc;
-	const int64_t L = cs_len;
-	const size_t cells = ((size_t) n + 2 * (size_t) n_query) * (size_t) cs_len * 4;
-	std::vector<double> up(cells), down(cells), ts, fv;
-	const double lo = o->blen.min_len, hi = o->blen.max_len;
+	HuBlenHost h(m, (int64_t) n + 2 * (int64_t) n_query, cs_len, o->blen);
+	std::vector<double> ts, fv;
 	HuAddOps ops;
-	ops.fit = [&](int32_t nn, const int32_t* par, double* b, const int8_t* sq, double* ll) {
-		HuBlenTopo tp;
-		hu_blen_opts bo = o->blen;
-		bo.rounds = nullptr; bo.rounds_cap = 0; bo.mem_budget = 0;
-		int rc2 = hu_blen_check(fn, &bo, nn, cs_len, par, b, sq, 0, &tp);
-		if(rc2 != HU_OK) return rc2;
-		HuBlenOps bops;
-		bops.sweep = [&](const double* x, bool withDown) { hu_blen_host_sweep(tp, m, par, L, x, sq, up.data(), withDown ? down.data() : nullptr); return (int) HU_OK; };
-		bops.loglik = [&](double* out) { *out = hu_blen_host_loglik(m, L, up.data() + (size_t) tp.root * L * 4); return (int) HU_OK; };
-		bops.step = [&](const double* x, double* t, int64_t* c) { *c = hu_blen_host_step(tp, m, L, x, up.data(), down.data(), lo, hi, t, nullptr, nullptr, nullptr, nullptr); return (int) HU_OK; };
-		double s4[4] = {0, 0, 0, 0};
-		rc2 = hu_blen_rounds(fn, &bo, nn, tp.root, b, bops, s4);
-		*ll = bo.ll_final;
-		return rc2;
-	};
-	ops.sweep = [&](int32_t, const int32_t* par, const double* b, const int8_t* sq, const HuBlenTopo& tp) {
-		hu_blen_host_sweep(tp, m, par, L, b, sq, up.data(), down.data());
-		return (int) HU_OK;
-	};
+	ops.fit = [&](int32_t nn, const int32_t* par, double* b, const int8_t* sq, double* ll) { return h.fit(fn, &o->blen, nn, par, b, sq, ll); };
+	ops.sweep = [&](int32_t, const int32_t* par, const double* b, const int8_t* sq, const HuBlenTopo& tp) { h.sweep(tp, par, b, sq, true); return (int) HU_OK; };
 	ops.score = [&](int32_t nn, int32_t root, const double* b, double t0, int32_t nq, const int8_t* rows, int32_t* bw, double* bt, double* bf) {
 		ts.resize((size_t) nq * (size_t) nn); fv.resize((size_t) nq * (size_t) nn);
-		hu_add_host_score(m, nn, L, root, b, up.data(), down.data(), lo, hi, t0, nq, rows, ts.data(), fv.data());
+		hu_add_host_score(m, nn, cs_len, root, b, h.up.data(), h.down.data(), h.lo, h.hi, t0, nq, rows, ts.data(), fv.data());
 		hu_add_host_best(nn, root, nq, ts.data(), fv.data(), bw, bt, bf);
 		return (int) HU_OK;
 	};

@@ -2,15 +2,12 @@
 // hmmufotu-amd-tree --ml-lengths.  The checks, the host path and the round loop are hu_blen_host.cpp's; the step kernel is
 // hu_kern_blen.h's; the messages come from the level sweeps of the build (hu_tree_sweep_*) and the objective from hu_tree_loglik.
 // The need is held against the budget and the free memory before anything is allocated.
-#include <chrono>
 #include <cstring>
 #include <vector>
-#include "hu_common.h"
+#include "hu_tree_dev.h"
 #include "hu_kern_blen.h"
 
 static thread_local double g_blenTiming[4] = {0, 0, 0, 0};
-
-#define BCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { hu_set_error("%s: %s failed: %s", fn, #call, hipGetErrorString(e_)); return HU_ERR_DEVICE; } } while(0)
 
 extern "C" int hu_blen_timing(double* seconds) {
 	if(!seconds) return HU_ERR_ARG;
@@ -19,8 +16,6 @@ extern "C" int hu_blen_timing(double* seconds) {
 }
 
 namespace {
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 /* either half behind the three operations of a round */
 struct BlenRun {
 	const char* fn; int32_t n = 0, L = 0; const int32_t* parent = nullptr; const int8_t* seq = nullptr; hu_model_desc model;
@@ -40,17 +35,17 @@ struct BlenRun {
 		const size_t cells = (size_t) n * (size_t) L;
 		if(host) { hUp.resize(cells * 4); hDown.resize(cells * 4); return HU_OK; }
 		if(hu_device_count() <= 0) { hu_set_error("%s: no gfx950 device visible: the host path needs none", fn); return HU_ERR_DEVICE; }
-		BCHK(hipSetDevice(device));
+		TCHK(hipSetDevice(device));
 		size_t freeB = 0, totB = 0;
-		BCHK(hipMemGetInfo(&freeB, &totB));
+		TCHK(hipMemGetInfo(&freeB, &totB));
 		const size_t need = (size_t) hu_blen_need(n, L);
 		if(need > freeB) {
 			hu_set_error("%s: %d nodes of %d columns need %zu bytes of device memory (%zu of them for the messages), %zu bytes are free", fn, n, L, need, cells * 64, freeB);
 			return HU_ERR_NOMEM;
 		}
-		BCHK(hipMalloc((void**) &up, cells * 32)); BCHK(hipMalloc((void**) &down, cells * 32));
-		if(L > HU_BLEN_LDS_COLS) BCHK(hipMalloc((void**) &ratio, cells * 24));
-		BCHK(hipMalloc((void**) &vec, (size_t) n * 40)); BCHK(hipMalloc((void**) &iters, (size_t) n * 4));
+		TCHK(hipMalloc((void**) &up, cells * 32)); TCHK(hipMalloc((void**) &down, cells * 32));
+		if(L > HU_BLEN_LDS_COLS) TCHK(hipMalloc((void**) &ratio, cells * 24));
+		TCHK(hipMalloc((void**) &vec, (size_t) n * 40)); TCHK(hipMalloc((void**) &iters, (size_t) n * 4));
 		rows.assign(seq, seq + cells);
 		return HU_OK;
 	}
@@ -74,8 +69,8 @@ struct BlenRun {
 		*nCap = 0;
 		if(host) { *nCap = hu_blen_host_step(tp, m, L, t, hUp.data(), hDown.data(), lo, hi, tStar, f, d1, d2, capped); return HU_OK; }
 		const size_t N = (size_t) n;
-		BCHK(hipMemcpy(vec, t, N * 8, hipMemcpyHostToDevice));
-		BCHK(hipMemset(vec + N, 0, N * 32)); BCHK(hipMemset(iters, 0, N * 4));
+		TCHK(hipMemcpy(vec, t, N * 8, hipMemcpyHostToDevice));
+		TCHK(hipMemset(vec + N, 0, N * 32)); TCHK(hipMemset(iters, 0, N * 4));
 		HuBlenArgs a; memset(&a, 0, sizeof(a));
 		a.up = up; a.down = down; a.t = vec; a.csLen = L; a.n = n; a.root = tp.root; a.doStep = tStar ? 1 : 0; a.lo = lo; a.hi = hi;
 		a.ratio = ratio; a.tStar = vec + N; a.f = vec + 2 * N; a.d1 = vec + 3 * N; a.d2 = vec + 4 * N; a.iters = iters; a.m = m;
@@ -85,10 +80,10 @@ struct BlenRun {
 			k_blen_step<true><<<(unsigned) n, HU_BLEN_WG, lds>>>(a);
 		}
 		else k_blen_step<false><<<(unsigned) n, HU_BLEN_WG, (size_t) 3 * HU_BLEN_WG * 8>>>(a);
-		BCHK(hipGetLastError());
-		BCHK(hipDeviceSynchronize());
+		TCHK(hipGetLastError());
+		TCHK(hipDeviceSynchronize());
 		std::vector<double> out(N * 4); std::vector<int32_t> it(N);
-		BCHK(hipMemcpy(out.data(), vec + N, N * 32, hipMemcpyDeviceToHost)); BCHK(hipMemcpy(it.data(), iters, N * 4, hipMemcpyDeviceToHost));
+		TCHK(hipMemcpy(out.data(), vec + N, N * 32, hipMemcpyDeviceToHost)); TCHK(hipMemcpy(it.data(), iters, N * 4, hipMemcpyDeviceToHost));
 		for(size_t u = 0; u < N; ++u) {
 			const bool cap = it[u] > HU_BLEN_MAX_NEWTON;
 			if(tStar) tStar[u] = (int32_t) u == tp.root ? t[u] : out[u];
@@ -155,8 +150,8 @@ extern "C" int hu_tree_optimize_lengths(hu_blen_opts* opts, int32_t n, int32_t c
 	ops.loglik = [&](double* ll) { return r.loglik(ll); };
 	ops.step = [&](const double* b, double* ts, int64_t* nCap) { return r.step(b, ts, nullptr, nullptr, nullptr, nullptr, nCap); };
 	g_blenTiming[0] = g_blenTiming[1] = g_blenTiming[2] = g_blenTiming[3] = 0;
-	const double t0 = now_s();
+	const double t0 = hu_now_s();
 	rc = hu_blen_rounds(fn, opts, n, r.tp.root, blen, ops, g_blenTiming);
-	g_blenTiming[3] = now_s() - t0 - g_blenTiming[0] - g_blenTiming[1] - g_blenTiming[2];
+	g_blenTiming[3] = hu_now_s() - t0 - g_blenTiming[0] - g_blenTiming[1] - g_blenTiming[2];
 	return rc;
 } catch(...) { return hu_catch_all("hu_tree_optimize_lengths"); }

@@ -2,7 +2,6 @@
 // reference of the device tests, and what tests/san/blen_driver.cpp runs under the sanitizers.  No HIP headers: a plain C++ compiler
 // builds this file.  The arithmetic of a column and the rule of a Newton step are hu_tree_blen.h's, shared with the kernels.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -153,27 +152,25 @@ int64_t hu_blen_host_step(const HuBlenTopo& tp, const HuBlenModel& m, int64_t L,
 	return nCap;
 }
 
-static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 int hu_blen_rounds(const char* fn, hu_blen_opts* o, int32_t n, int32_t root, double* blen, const HuBlenOps& ops, double* sec) {
 	std::vector<double> ts((size_t) n), cand((size_t) n);
 	int rc;
-	double t0 = now_s();
+	double t0 = hu_now_s();
 	double ll = 0;
 	if((rc = ops.sweep(blen, true)) != HU_OK || (rc = ops.loglik(&ll)) != HU_OK) return rc;
-	sec[0] += now_s() - t0;
+	sec[0] += hu_now_s() - t0;
 	if(!(ll == ll) || ll == -INFINITY) { hu_set_error("%s: the log-likelihood of the start tree is %g: no objective to improve", fn, ll); return HU_ERR_ARG; }
 	o->ll_start = o->ll_final = ll; o->n_rounds = 0; o->n_capped = 0; o->stop = HU_BLEN_MAX_ROUNDS;
 	for(int32_t r = 0; r < o->max_rounds; ++r) {
-		if(r > 0) { t0 = now_s(); if((rc = ops.sweep(blen, true)) != HU_OK) return rc; sec[0] += now_s() - t0; }
-		t0 = now_s();
+		if(r > 0) { t0 = hu_now_s(); if((rc = ops.sweep(blen, true)) != HU_OK) return rc; sec[0] += hu_now_s() - t0; }
+		t0 = hu_now_s();
 		int64_t nCap = 0;
 		if((rc = ops.step(blen, ts.data(), &nCap)) != HU_OK) return rc;
-		sec[1] += now_s() - t0;
+		sec[1] += hu_now_s() - t0;
 		double delta = 0;
 		for(int32_t u = 0; u < n; ++u) if(u != root) delta = std::max(delta, std::fabs(ts[(size_t) u] - blen[u]));
 		if(delta <= o->eps) { o->stop = HU_BLEN_CONVERGED; return HU_OK; }
-		t0 = now_s();
+		t0 = hu_now_s();
 		double s = 1.0, llNew = ll;
 		bool taken = false;
 		for(int k = 0; k < HU_BLEN_MAX_HALVINGS; ++k, s *= 0.5) {
@@ -181,12 +178,86 @@ int hu_blen_rounds(const char* fn, hu_blen_opts* o, int32_t n, int32_t root, dou
 			if((rc = ops.sweep(cand.data(), false)) != HU_OK || (rc = ops.loglik(&llNew)) != HU_OK) return rc;
 			if(llNew > ll) { taken = true; break; }
 		}
-		sec[2] += now_s() - t0;
+		sec[2] += hu_now_s() - t0;
 		if(!taken) { o->stop = HU_BLEN_NO_STEP; return HU_OK; }
 		memcpy(blen, cand.data(), (size_t) n * 8);
 		ll = llNew;
 		if(o->rounds && o->n_rounds < o->rounds_cap) { hu_blen_round& R = o->rounds[o->n_rounds]; R.ll = ll; R.s = s; R.delta = delta; R.n_capped = nCap; }
 		o->n_rounds++; o->n_capped += nCap; o->ll_final = ll;
+	}
+	return HU_OK;
+}
+
+/* ---- what the searches over topologies share ---- */
+int HuBlenHost::fit(const char* fn, const hu_blen_opts* o, int32_t n, const int32_t* parent, double* blen, const int8_t* seq, double* ll) {
+	hu_blen_opts bo = hu_search_fit_opts(*o);
+	HuBlenTopo tp;
+	int rc = hu_blen_check(fn, &bo, n, (int32_t) L, parent, blen, seq, 0, &tp);
+	if(rc != HU_OK) return rc;
+	HuBlenOps ops;
+	ops.sweep = [&](const double* x, bool withDown) { sweep(tp, parent, x, seq, withDown); return (int) HU_OK; };
+	ops.loglik = [&](double* out) { *out = hu_blen_host_loglik(m, L, up.data() + (size_t) tp.root * L * 4); return (int) HU_OK; };
+	ops.step = [&](const double* x, double* t, int64_t* c) { *c = hu_blen_host_step(tp, m, L, x, up.data(), down.data(), lo, hi, t, nullptr, nullptr, nullptr, nullptr); return (int) HU_OK; };
+	double s4[4] = {0, 0, 0, 0};
+	rc = hu_blen_rounds(fn, &bo, n, tp.root, blen, ops, s4);
+	*ll = bo.ll_final;
+	return rc;
+}
+
+int HuBlenHost::trial(const char* fn, const hu_blen_opts* o, int32_t n, const int32_t* parent, const double* blen, const int8_t* seq, double* ll) {
+	HuBlenTopo tp;
+	const int rc = hu_blen_check(fn, o, n, (int32_t) L, parent, blen, seq, 0, &tp);
+	if(rc != HU_OK) return rc;
+	sweep(tp, parent, blen, seq, false);
+	*ll = hu_blen_host_loglik(m, L, up.data() + (size_t) tp.root * L * 4);
+	return HU_OK;
+}
+
+bool hu_nni_halve(std::vector<int32_t>* taken) {
+	if(taken->size() <= 1) return false;
+	taken->resize((taken->size() + 1) / 2);
+	return true;
+}
+
+int hu_search_rounds(const char* fn, const hu_blen_opts* bo, int32_t rounds, int32_t n, int32_t cs_len, int32_t* parent, double* blen, const int8_t* seq,
+		const int32_t* child_off, int32_t* child_idx, const HuSearchOps& ops, double* ll_start, double* ll_final, int32_t* stop, double* sec) {
+	const size_t N = (size_t) n, nIdx = child_off && child_idx ? (size_t) child_off[n] : 0;
+	std::vector<int32_t> par(N), idx(nIdx), taken;
+	std::vector<double> bl(N);
+	HuBlenTopo tp;
+	*stop = HU_SEARCH_MAX_ROUNDS;
+	int rc;
+	double ll = 0;
+	for(int32_t r = 0; r <= rounds; ++r) {
+		double t0 = hu_now_s();
+		if((rc = ops.fit(parent, blen, &ll)) != HU_OK) return rc;
+		sec[0] += hu_now_s() - t0;
+		if(r == 0) *ll_start = ll;
+		*ll_final = ll;
+		if(r == rounds) break;                                  /* the fit after the last round allowed */
+		t0 = hu_now_s();
+		if((rc = hu_blen_check(fn, bo, n, cs_len, parent, blen, seq, 0, &tp)) != HU_OK) return rc;
+		if((rc = ops.score(tp)) != HU_OK) return rc;
+		sec[1] += hu_now_s() - t0;
+		taken.clear();
+		ops.select(tp, &taken);
+		if(taken.empty()) { *stop = HU_SEARCH_LOCAL_OPTIMUM; return HU_OK; }
+		const size_t nTaken = taken.size();
+		t0 = hu_now_s();
+		double llNew = ll;
+		for(;;) {
+			par.assign(parent, parent + N); bl.assign(blen, blen + N);
+			if(nIdx) idx.assign(child_idx, child_idx + nIdx);
+			if((rc = ops.apply(taken, par.data(), bl.data(), nIdx ? idx.data() : nullptr)) != HU_OK) return rc;
+			if((rc = ops.trial(par.data(), bl.data(), &llNew)) != HU_OK) return rc;
+			if(llNew > ll) break;
+			if(!hu_nni_halve(&taken)) { sec[2] += hu_now_s() - t0; *stop = HU_SEARCH_NO_MOVE; return HU_OK; }
+		}
+		sec[2] += hu_now_s() - t0;
+		memcpy(parent, par.data(), N * 4); memcpy(blen, bl.data(), N * 8);
+		if(nIdx) memcpy(child_idx, idx.data(), nIdx * 4);
+		ll = llNew; *ll_final = ll;
+		ops.record(r + 1, ll, nTaken, taken);
 	}
 	return HU_OK;
 }

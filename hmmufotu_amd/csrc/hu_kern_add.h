@@ -53,9 +53,7 @@ template<bool LDS> __global__ __launch_bounds__(HU_ADD_WG) __attribute__((amdgpu
 	double vk[1] = {0.0};
 	for(int64_t j = tid; j < L; j += HU_ADD_WG) {
 		double Mu[4], Md[4], r[3], K;
-		const double2 p0 = *reinterpret_cast<const double2*>(mu + j * 4), p1 = *reinterpret_cast<const double2*>(mu + j * 4 + 2);
-		const double2 c0 = *reinterpret_cast<const double2*>(md + j * 4), c1 = *reinterpret_cast<const double2*>(md + j * 4 + 2);
-		Mu[0] = p0.x; Mu[1] = p0.y; Mu[2] = p1.x; Mu[3] = p1.y; Md[0] = c0.x; Md[1] = c0.y; Md[2] = c1.x; Md[3] = c1.y;
+		blen_ld4(mu + j * 4, Mu); blen_ld4(md + j * 4, Md);
 		hu_add_edge_column(m, P, Mu, Md, r, &K);
 		R[j] = r[0]; R[L + j] = r[1]; R[2 * L + j] = r[2];
 		vk[0] += K;
@@ -75,30 +73,11 @@ template<bool LDS> __global__ __launch_bounds__(HU_ADD_WG) __attribute__((amdgpu
 			v[0] += tab[15 + s]; v[1] += g; v[2] += h;
 		}
 		blen_reduce<1>(red, v); blen_reduce<2>(red, v + 1);
-		/* f' and f'' at x; the same value in every thread, so the control flow is uniform */
-		auto eval = [&](double x, double* g, double* h) {
-			hu_blen_exp(m, x, &E);
-			double u[2] = {0.0, 0.0};
-			for(int64_t j = tid; j < L; j += HU_ADD_WG) {
-				double r[3], p, c;
-				hu_add_ratio(tab, hu_add_sym(row[j]), R[j], R[L + j], R[2 * L + j], r);
-				hu_blen_terms(E, r, &p, &c);
-				u[0] += p; u[1] += c;
-			}
-			blen_reduce<2>(red, u);
-			*g = u[0]; *h = u[1];
-		};
+		auto ratioAt = [&](int64_t j, double* r) { hu_add_ratio(tab, hu_add_sym(row[j]), R[j], R[L + j], R[2 * L + j], r); };
 		int it = 0;
-		const double x = hu_blen_solve(t0, v[1], v[2], a.lo, a.hi, eval, &it);
-		hu_blen_exp(m, x, &E);
-		double u[1] = {0.0};
-		for(int64_t j = tid; j < L; j += HU_ADD_WG) {
-			double r[3];
-			hu_add_ratio(tab, hu_add_sym(row[j]), R[j], R[L + j], R[2 * L + j], r);
-			u[0] += log(hu_blen_den(E, r));
-		}
-		blen_reduce<1>(red, u);
-		if(tid == 0) { a.tStar[q * n + w] = x; a.f[q * n + w] = (vk[0] + v[0]) + u[0]; }
+		const double x = blen_solve_wg(m, t0, v[1], v[2], a.lo, a.hi, red, L, ratioAt, &it);
+		const double u = blen_logden_wg(m, x, red, L, ratioAt);
+		if(tid == 0) { a.tStar[q * n + w] = x; a.f[q * n + w] = (vk[0] + v[0]) + u; }
 	}
 }
 

@@ -34,6 +34,46 @@ template<int NV> __device__ inline void blen_reduce(double* red, double* v) {
 	__syncthreads();
 }
 
+/* a message's four entries of one column: 32 bytes as two 16-byte accesses */
+__device__ inline void blen_ld4(const double* p, double* M) {
+	const double2 a = *reinterpret_cast<const double2*>(p), b = *reinterpret_cast<const double2*>(p + 2);
+	M[0] = a.x; M[1] = a.y; M[2] = b.x; M[3] = b.y;
+}
+__device__ inline void blen_st4(double* p, const double* M) {
+	*reinterpret_cast<double2*>(p) = make_double2(M[0], M[1]); *reinterpret_cast<double2*>(p + 2) = make_double2(M[2], M[3]);
+}
+
+/* the Newton tail of every scorer of the family, for the whole workgroup: the maximiser of f on [lo, hi] from t0, where f' and f'' are
+ * g0 and h0 already (hu_blen_solve).  ratioAt(j, r) gives the three ratios of column j; column j belongs to thread j % HU_BLEN_WG, the
+ * sums run serially per thread in ascending column and then down blen_reduce's tree, so every thread holds the same f' and f'' and the
+ * control flow is uniform.  red [2][HU_BLEN_WG] */
+template<class Ratio> __device__ inline double blen_solve_wg(const HuBlenModel& m, double t0, double g0, double h0, double lo, double hi, double* red, int64_t L,
+		const Ratio& ratioAt, int* it) {
+	HuBlenExp E;
+	auto eval = [&](double x, double* g, double* h) {
+		hu_blen_exp(m, x, &E);
+		double w[2] = {0.0, 0.0};
+		for(int64_t j = threadIdx.x; j < L; j += HU_BLEN_WG) {
+			double r[3], p, q;
+			ratioAt(j, r);
+			hu_blen_terms(E, r, &p, &q);
+			w[0] += p; w[1] += q;
+		}
+		blen_reduce<2>(red, w);
+		*g = w[0]; *h = w[1];
+	};
+	return hu_blen_solve(t0, g0, h0, lo, hi, eval, it);
+}
+/* sum_j log D_j(x) over the workgroup, in every thread: what f(x) adds to the sum of the columns' constants.  red [HU_BLEN_WG] */
+template<class Ratio> __device__ inline double blen_logden_wg(const HuBlenModel& m, double x, double* red, int64_t L, const Ratio& ratioAt) {
+	HuBlenExp E;
+	hu_blen_exp(m, x, &E);
+	double w[1] = {0.0};
+	for(int64_t j = threadIdx.x; j < L; j += HU_BLEN_WG) { double r[3]; ratioAt(j, r); w[0] += log(hu_blen_den(E, r)); }
+	blen_reduce<1>(red, w);
+	return w[0];
+}
+
 template<bool LDS> __global__ __launch_bounds__(HU_BLEN_WG) void k_blen_step(HuBlenArgs a) {
 	extern __shared__ __attribute__((aligned(16))) double blen_sm[];
 	const int64_t u = blockIdx.x, L = a.csLen;
@@ -50,9 +90,7 @@ template<bool LDS> __global__ __launch_bounds__(HU_BLEN_WG) void k_blen_step(HuB
 	double v[3] = {0.0, 0.0, 0.0};
 	for(int64_t j = tid; j < L; j += HU_BLEN_WG) {
 		double Mu[4], Md[4], r[3], K, g, h;
-		const double2 p0 = *reinterpret_cast<const double2*>(mu + j * 4), p1 = *reinterpret_cast<const double2*>(mu + j * 4 + 2);
-		const double2 q0 = *reinterpret_cast<const double2*>(md + j * 4), q1 = *reinterpret_cast<const double2*>(md + j * 4 + 2);
-		Mu[0] = p0.x; Mu[1] = p0.y; Mu[2] = p1.x; Mu[3] = p1.y; Md[0] = q0.x; Md[1] = q0.y; Md[2] = q1.x; Md[3] = q1.y;
+		blen_ld4(mu + j * 4, Mu); blen_ld4(md + j * 4, Md);
 		hu_blen_column(a.m, Mu, Md, r, &K);
 		R[j] = r[0]; R[L + j] = r[1]; R[2 * L + j] = r[2];
 		hu_blen_terms(E, r, &g, &h);
@@ -62,20 +100,7 @@ template<bool LDS> __global__ __launch_bounds__(HU_BLEN_WG) void k_blen_step(HuB
 	const double g0 = v[1], h0 = v[2];
 	if(tid == 0) { a.f[u] = v[0]; a.d1[u] = g0; a.d2[u] = h0; }
 	if(!a.doStep) return;
-	/* f' and f'' at x from the ratios; the same value in every thread, so the control flow below is uniform */
-	auto eval = [&](double x, double* g, double* h) {
-		hu_blen_exp(a.m, x, &E);
-		double w[2] = {0.0, 0.0};
-		for(int64_t j = tid; j < L; j += HU_BLEN_WG) {
-			const double r[3] = {R[j], R[L + j], R[2 * L + j]};
-			double p, q;
-			hu_blen_terms(E, r, &p, &q);
-			w[0] += p; w[1] += q;
-		}
-		blen_reduce<2>(red, w);
-		*g = w[0]; *h = w[1];
-	};
 	int it = 0;
-	const double x = hu_blen_solve(t0, g0, h0, a.lo, a.hi, eval, &it);
+	const double x = blen_solve_wg(a.m, t0, g0, h0, a.lo, a.hi, red, L, [&](int64_t j, double* r) { r[0] = R[j]; r[1] = R[L + j]; r[2] = R[2 * L + j]; }, &it);
 	if(tid == 0) { a.tStar[u] = x; a.iters[u] = it; }
 }

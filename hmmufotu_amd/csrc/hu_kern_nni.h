@@ -46,10 +46,7 @@ template<bool LDS> __global__ __launch_bounds__(HU_NNI_WG) void k_nni_score(HuNn
 	double sK[3] = {0.0, 0.0, 0.0}, sD[3] = {0.0, 0.0, 0.0}, sg[3] = {0.0, 0.0, 0.0}, sh[3] = {0.0, 0.0, 0.0};
 	for(int64_t j = tid; j < L; j += HU_NNI_WG) {
 		double M[16], r[9], K[3];
-		for(int k = 0; k < 4; ++k) {
-			const double2 p0 = *reinterpret_cast<const double2*>(src[k] + j * 4), p1 = *reinterpret_cast<const double2*>(src[k] + j * 4 + 2);
-			M[k * 4] = p0.x; M[k * 4 + 1] = p0.y; M[k * 4 + 2] = p1.x; M[k * 4 + 3] = p1.y;
-		}
+		for(int k = 0; k < 4; ++k) blen_ld4(src[k] + j * 4, M + k * 4);
 		hu_nni_column(m, red, M, r, K);
 		for(int i = 0; i < 9; ++i) R[i * L + j] = r[i];
 		for(int q = 0; q < 3; ++q) {
@@ -63,25 +60,10 @@ template<bool LDS> __global__ __launch_bounds__(HU_NNI_WG) void k_nni_score(HuNn
 	if(tid == 0) a.f0[e] = sK[0] + sD[0];
 	for(int q = 0; q < 3; ++q) {
 		const double* Rq = R + (int64_t) q * 3 * L;
-		/* f' and f'' at x from the ratios; the same value in every thread, so the control flow is uniform */
-		auto eval = [&](double x, double* g, double* h) {
-			hu_blen_exp(m, x, &E);
-			double w[2] = {0.0, 0.0};
-			for(int64_t j = tid; j < L; j += HU_NNI_WG) {
-				const double r[3] = {Rq[j], Rq[L + j], Rq[2 * L + j]};
-				double p, s;
-				hu_blen_terms(E, r, &p, &s);
-				w[0] += p; w[1] += s;
-			}
-			blen_reduce<2>(red, w);
-			*g = w[0]; *h = w[1];
-		};
+		auto ratioAt = [&](int64_t j, double* r) { r[0] = Rq[j]; r[1] = Rq[L + j]; r[2] = Rq[2 * L + j]; };
 		int it = 0;
-		const double x = hu_blen_solve(t0, sg[q], sh[q], a.lo, a.hi, eval, &it);
-		hu_blen_exp(m, x, &E);
-		double w[1] = {0.0};
-		for(int64_t j = tid; j < L; j += HU_NNI_WG) { const double r[3] = {Rq[j], Rq[L + j], Rq[2 * L + j]}; w[0] += log(hu_blen_den(E, r)); }
-		blen_reduce<1>(red, w);
-		if(tid == 0) { a.tStar[e * 3 + q] = x; a.f[e * 3 + q] = sK[q] + w[0]; a.iters[e * 3 + q] = it; }
+		const double x = blen_solve_wg(m, t0, sg[q], sh[q], a.lo, a.hi, red, L, ratioAt, &it);
+		const double w = blen_logden_wg(m, x, red, L, ratioAt);
+		if(tid == 0) { a.tStar[e * 3 + q] = x; a.f[e * 3 + q] = sK[q] + w; a.iters[e * 3 + q] = it; }
 	}
 }

@@ -32,14 +32,6 @@ struct HuSprArgs {
 	int32_t* iters;                            /* as tStar; HU_BLEN_MAX_NEWTON + 1: the cap was hit */
 };
 
-__device__ inline void spr_ld4(const double* p, double* M) {
-	const double2 a = *reinterpret_cast<const double2*>(p), b = *reinterpret_cast<const double2*>(p + 2);
-	M[0] = a.x; M[1] = a.y; M[2] = b.x; M[3] = b.y;
-}
-__device__ inline void spr_st4(double* p, const double* M) {
-	*reinterpret_cast<double2*>(p) = make_double2(M[0], M[1]); *reinterpret_cast<double2*>(p + 2) = make_double2(M[2], M[3]);
-}
-
 template<bool LDS> __global__ __launch_bounds__(HU_SPR_WG) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_spr_score(HuSprArgs a) {
 	extern __shared__ __attribute__((aligned(16))) double spr_sm[];
 	const int64_t b = blockIdx.x, L = a.csLen;
@@ -73,16 +65,16 @@ template<bool LDS> __global__ __launch_bounds__(HU_SPR_WG) __attribute__((amdgpu
 			double Y[4] = {0.0, 0.0, 0.0, 0.0};
 			if(hasDst) {
 				double M[4], Z[4];
-				spr_ld4(s0 + j * 4, M);
+				blen_ld4(s0 + j * 4, M);
 				hu_spr_conv(red, M, Y);
-				if(s1) { spr_ld4(s1 + j * 4, M); hu_spr_conv(red + 16, M, Z); for(int i = 0; i < 4; ++i) Y[i] += Z[i]; }
-				if(rc.acc) { spr_ld4(dst + j * 4, M); for(int i = 0; i < 4; ++i) Y[i] += M[i]; }
-				spr_st4(dst + j * 4, Y);
+				if(s1) { blen_ld4(s1 + j * 4, M); hu_spr_conv(red + 16, M, Z); for(int i = 0; i < 4; ++i) Y[i] += Z[i]; }
+				if(rc.acc) { blen_ld4(dst + j * 4, M); for(int i = 0; i < 4; ++i) Y[i] += M[i]; }
+				blen_st4(dst + j * 4, Y);
 			}
 			if(hasT) {
 				double B[4], V[4], r[3], K, g, h;
-				if(!ownA) spr_ld4(pa + j * 4, Y);
-				spr_ld4(pb + j * 4, B); spr_ld4(yv + j * 4, V);
+				if(!ownA) blen_ld4(pa + j * 4, Y);
+				blen_ld4(pb + j * 4, B); blen_ld4(yv + j * 4, V);
 				hu_spr_column(m, red + 32, Y, red + 48, B, V, r, &K);
 				R[j] = r[0]; R[L + j] = r[1]; R[2 * L + j] = r[2];
 				hu_blen_terms(E, r, &g, &h);
@@ -94,25 +86,10 @@ template<bool LDS> __global__ __launch_bounds__(HU_SPR_WG) __attribute__((amdgpu
 		blen_reduce<2>(red, v); blen_reduce<2>(red, v + 2);
 		const int64_t o = nd.outOff - a.outBase + rc.out;
 		if(tid == 0 && rc.dist == 0) a.f0[b] = v[0] + v[1];
-		/* f' and f'' at x from the ratios; the same value in every thread, so the control flow is uniform */
-		auto eval = [&](double x, double* g, double* h) {
-			hu_blen_exp(m, x, &E);
-			double w[2] = {0.0, 0.0};
-			for(int64_t j = tid; j < L; j += HU_SPR_WG) {
-				const double r[3] = {R[j], R[L + j], R[2 * L + j]};
-				double p, q;
-				hu_blen_terms(E, r, &p, &q);
-				w[0] += p; w[1] += q;
-			}
-			blen_reduce<2>(red, w);
-			*g = w[0]; *h = w[1];
-		};
+		auto ratioAt = [&](int64_t j, double* r) { r[0] = R[j]; r[1] = R[L + j]; r[2] = R[2 * L + j]; };
 		int it = 0;
-		const double x = hu_blen_solve(t0, v[2], v[3], a.lo, a.hi, eval, &it);
-		hu_blen_exp(m, x, &E);
-		double w[1] = {0.0};
-		for(int64_t j = tid; j < L; j += HU_SPR_WG) { const double r[3] = {R[j], R[L + j], R[2 * L + j]}; w[0] += log(hu_blen_den(E, r)); }
-		blen_reduce<1>(red, w);
-		if(tid == 0) { a.tStar[o] = x; a.f[o] = v[0] + w[0]; a.iters[o] = it; }
+		const double x = blen_solve_wg(m, t0, v[2], v[3], a.lo, a.hi, red, L, ratioAt, &it);
+		const double w = blen_logden_wg(m, x, red, L, ratioAt);
+		if(tid == 0) { a.tStar[o] = x; a.f[o] = v[0] + w; a.iters[o] = it; }
 	}
 }

@@ -64,10 +64,7 @@ template<bool LDS, int RPT> __global__ __launch_bounds__(HU_NNI_WG) void k_nni_s
 	int nBad = 0;
 	for(int64_t j = tid; j < L; j += HU_NNI_WG) {
 		double M[16], K[3], lD[3], d[2];
-		for(int k = 0; k < 4; ++k) {
-			const double2 p0 = *reinterpret_cast<const double2*>(src[k] + j * 4), p1 = *reinterpret_cast<const double2*>(src[k] + j * 4 + 2);
-			M[k * 4] = p0.x; M[k * 4 + 1] = p0.y; M[k * 4 + 2] = p1.x; M[k * 4 + 3] = p1.y;
-		}
+		for(int k = 0; k < 4; ++k) blen_ld4(src[k] + j * 4, M + k * 4);
 		if(!hu_support_column(m, red, M, E, K, lD, d)) ++nBad;
 		Dp[j] = make_double2(d[0], d[1]);
 		for(int q = 0; q < 3; ++q) { sK[q] += K[q]; sD[q] += lD[q]; }

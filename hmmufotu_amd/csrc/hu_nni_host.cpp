@@ -3,7 +3,6 @@
 // builds this file.  The arithmetic of a column is hu_tree_nni.h's, shared with the kernel; the sweeps, the fit's round loop and the
 // Newton rule are hu_blen_host.cpp's and hu_tree_blen.h's.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -159,74 +158,41 @@ void hu_nni_select(const std::vector<HuNniEdge>& edges, const double* gain, doub
 	}
 }
 
-bool hu_nni_halve(std::vector<int32_t>* taken) {
-	if(taken->size() <= 1) return false;
-	taken->resize((taken->size() + 1) / 2);
-	return true;
-}
-
-static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 int hu_nni_rounds(const char* fn, hu_nni_opts* o, int32_t n, int32_t cs_len, int32_t* parent, double* blen, const int8_t* seq, const int32_t* child_off,
 		int32_t* child_idx, const HuNniOps& ops, double* sec) {
-	const size_t N = (size_t) n, nIdx = child_off && child_idx ? (size_t) child_off[n] : 0;
-	std::vector<int32_t> par(N), idx(nIdx), order, taken;
-	std::vector<double> bl(N), ts, f, f0, gain;
+	std::vector<int32_t> order;
+	std::vector<double> ts, f, f0, gain;
 	std::vector<HuNniEdge> edges;
-	HuBlenTopo tp;
-	o->n_rounds = 0; o->n_swaps = 0; o->skipped = 0; o->stop = HU_NNI_MAX_ROUNDS;
-	int rc;
-	double ll = 0;
-	for(int32_t r = 0; r <= o->nni_rounds; ++r) {
-		double t0 = now_s();
-		if((rc = ops.fit(parent, blen, &ll)) != HU_OK) return rc;
-		sec[0] += now_s() - t0;
-		if(r == 0) o->ll_start = ll;
-		o->ll_final = ll;
-		if(r == o->nni_rounds) break;                           /* the fit after the last round allowed */
-		t0 = now_s();
-		if((rc = hu_blen_check(fn, &o->blen, n, cs_len, parent, blen, seq, 0, &tp)) != HU_OK) return rc;
+	o->n_rounds = 0; o->n_swaps = 0; o->skipped = 0;
+	auto better = [&](int32_t e) { return f[(size_t) e * 3 + 1] >= f[(size_t) e * 3 + 2] ? 1 : 2; };
+	HuSearchOps so;
+	so.fit = ops.fit; so.trial = ops.trial;
+	so.score = [&](const HuBlenTopo& tp) {
 		hu_nni_edges(tp, parent, blen, &edges, &o->skipped);
 		const size_t E = edges.size();
-		if(E == 0) { o->stop = HU_NNI_LOCAL_OPTIMUM; return HU_OK; }
 		ts.assign(E * 3, 0.0); f.assign(E * 3, 0.0); f0.assign(E, 0.0); gain.assign(E, 0.0);
-		if((rc = ops.score(parent, blen, edges, ts.data(), f.data(), f0.data())) != HU_OK) return rc;
-		sec[1] += now_s() - t0;
-		for(size_t e = 0; e < E; ++e) gain[e] = std::fmax(f[e * 3 + 1], f[e * 3 + 2]) - f[e * 3];
-		hu_nni_select(edges, gain.data(), o->min_gain, &order, &taken);
-		if(order.empty()) { o->stop = HU_NNI_LOCAL_OPTIMUM; return HU_OK; }
-		const size_t nCand = order.size(), nTaken = taken.size();
-		t0 = now_s();
-		double llNew = ll;
-		for(;;) {
-			par.assign(parent, parent + N); bl.assign(blen, blen + N);
-			if(nIdx) idx.assign(child_idx, child_idx + nIdx);
-			for(int32_t e : taken) {
-				const int q = f[(size_t) e * 3 + 1] >= f[(size_t) e * 3 + 2] ? 1 : 2;
-				hu_nni_apply_edge(edges[(size_t) e], q, ts[(size_t) e * 3 + q], par.data(), bl.data(), child_off, nIdx ? idx.data() : nullptr);
-			}
-			if((rc = ops.trial(par.data(), bl.data(), &llNew)) != HU_OK) return rc;
-			if(llNew > ll) break;
-			if(!hu_nni_halve(&taken)) { sec[2] += now_s() - t0; o->stop = HU_NNI_NO_SWAP; return HU_OK; }
-		}
-		sec[2] += now_s() - t0;
-		memcpy(parent, par.data(), N * 4); memcpy(blen, bl.data(), N * 8);
-		if(nIdx) memcpy(child_idx, idx.data(), nIdx * 4);
-		ll = llNew; o->ll_final = ll;
+		return E == 0 ? (int) HU_OK : ops.score(parent, blen, edges, ts.data(), f.data(), f0.data());
+	};
+	so.select = [&](const HuBlenTopo&, std::vector<int32_t>* taken) {
+		for(size_t e = 0; e < edges.size(); ++e) gain[e] = std::fmax(f[e * 3 + 1], f[e * 3 + 2]) - f[e * 3];
+		hu_nni_select(edges, gain.data(), o->min_gain, &order, taken);
+	};
+	so.apply = [&](const std::vector<int32_t>& taken, int32_t* par, double* bl, int32_t* idx) {
+		for(int32_t e : taken) hu_nni_apply_edge(edges[(size_t) e], better(e), ts[(size_t) e * 3 + better(e)], par, bl, child_off, idx);
+		return (int) HU_OK;
+	};
+	so.record = [&](int32_t round, double ll, size_t nTaken, const std::vector<int32_t>& taken) {
 		if(o->rounds && o->n_rounds < o->rounds_cap) {
 			hu_nni_round& R = o->rounds[o->n_rounds];
-			R.ll = ll; R.scored = (int32_t) E; R.candidates = (int32_t) nCand; R.taken = (int32_t) nTaken; R.applied = (int32_t) taken.size();
+			R.ll = ll; R.scored = (int32_t) edges.size(); R.candidates = (int32_t) order.size(); R.taken = (int32_t) nTaken; R.applied = (int32_t) taken.size();
 		}
 		for(int32_t e : taken) {
-			if(o->swaps && o->n_swaps < o->swaps_cap) {
-				int32_t* s = o->swaps + o->n_swaps * 3;
-				s[0] = r + 1; s[1] = edges[(size_t) e].u; s[2] = f[(size_t) e * 3 + 1] >= f[(size_t) e * 3 + 2] ? 1 : 2;
-			}
+			if(o->swaps && o->n_swaps < o->swaps_cap) { int32_t* s = o->swaps + o->n_swaps * 3; s[0] = round; s[1] = edges[(size_t) e].u; s[2] = better(e); }
 			o->n_swaps++;
 		}
 		o->n_rounds++;
-	}
-	return HU_OK;
+	};
+	return hu_search_rounds(fn, &o->blen, o->nni_rounds, n, cs_len, parent, blen, seq, child_off, child_idx, so, &o->ll_start, &o->ll_final, &o->stop, sec);
 }
 
 /* ---- the host path of the two entries ---- */
@@ -253,43 +219,18 @@ int hu_nni_host_search_entry(const char* fn, hu_nni_opts* o, int32_t n, int32_t 
 	HuBlenTopo tp0;
 	int rc = hu_nni_check(fn, o, n, cs_len, parent, blen, seq, 0, &tp0);
 	if(rc != HU_OK) return rc;
-	const int64_t L = cs_len;
-	const size_t cells = (size_t) n * (size_t) cs_len * 4;
-	std::vector<double> up(cells), down(cells);
-	const double lo = o->blen.min_len, hi = o->blen.max_len;
-	auto topo = [&](const int32_t* par, const double* b, HuBlenTopo* tp) { return hu_blen_check(fn, &o->blen, n, cs_len, par, b, seq, 0, tp); };
+	HuBlenHost h(m, n, cs_len, o->blen);
 	HuNniOps ops;
-	ops.fit = [&](const int32_t* par, double* b, double* ll) {
-		HuBlenTopo tp;
-		int rc2 = topo(par, b, &tp);
-		if(rc2 != HU_OK) return rc2;
-		hu_blen_opts bo = o->blen;
-		bo.rounds = nullptr; bo.rounds_cap = 0;
-		HuBlenOps bops;
-		bops.sweep = [&](const double* x, bool withDown) { hu_blen_host_sweep(tp, m, par, L, x, seq, up.data(), withDown ? down.data() : nullptr); return (int) HU_OK; };
-		bops.loglik = [&](double* out) { *out = hu_blen_host_loglik(m, L, up.data() + (size_t) tp.root * L * 4); return (int) HU_OK; };
-		bops.step = [&](const double* x, double* t, int64_t* c) { *c = hu_blen_host_step(tp, m, L, x, up.data(), down.data(), lo, hi, t, nullptr, nullptr, nullptr, nullptr); return (int) HU_OK; };
-		double s4[4] = {0, 0, 0, 0};
-		rc2 = hu_blen_rounds(fn, &bo, n, tp.root, b, bops, s4);
-		*ll = bo.ll_final;
-		return rc2;
-	};
+	ops.fit = [&](const int32_t* par, double* b, double* ll) { return h.fit(fn, &o->blen, n, par, b, seq, ll); };
 	ops.score = [&](const int32_t* par, const double* b, const std::vector<HuNniEdge>& edges, double* ts, double* f, double* f0) {
 		HuBlenTopo tp;
-		int rc2 = topo(par, b, &tp);
+		const int rc2 = hu_blen_check(fn, &o->blen, n, cs_len, par, b, seq, 0, &tp);
 		if(rc2 != HU_OK) return rc2;
-		hu_blen_host_sweep(tp, m, par, L, b, seq, up.data(), down.data());
-		hu_nni_host_score(m, n, L, edges, up.data(), down.data(), lo, hi, ts, f, f0);
+		h.sweep(tp, par, b, seq, true);
+		hu_nni_host_score(m, n, cs_len, edges, h.up.data(), h.down.data(), h.lo, h.hi, ts, f, f0);
 		return (int) HU_OK;
 	};
-	ops.trial = [&](const int32_t* par, const double* b, double* ll) {
-		HuBlenTopo tp;
-		int rc2 = topo(par, b, &tp);
-		if(rc2 != HU_OK) return rc2;
-		hu_blen_host_sweep(tp, m, par, L, b, seq, up.data(), nullptr);
-		*ll = hu_blen_host_loglik(m, L, up.data() + (size_t) tp.root * L * 4);
-		return (int) HU_OK;
-	};
+	ops.trial = [&](const int32_t* par, const double* b, double* ll) { return h.trial(fn, &o->blen, n, par, b, seq, ll); };
 	return hu_nni_rounds(fn, o, n, cs_len, parent, blen, seq, child_off, child_idx, ops, sec);
 }
 

@@ -3,13 +3,10 @@
 // the messages come from the level sweeps of the build (hu_tree_sweep_*), the fit from hu_tree_optimize_lengths and the objective from
 // hu_tree_loglik.  A move changes the topology, so every sweep of a round has a sweep handle of its own.  The need is held against the
 // budget and the free memory before anything is allocated; the buffers of the scoring are released while a fit holds its own.
-#include <chrono>
 #include <cstring>
 #include <vector>
-#include "hu_common.h"
+#include "hu_tree_dev.h"
 #include "hu_kern_spr.h"
-
-#define SCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { hu_set_error("%s: %s failed: %s", fn, #call, hipGetErrorString(e_)); return HU_ERR_DEVICE; } } while(0)
 
 static thread_local double g_sprTiming[4] = {0, 0, 0, 0};
 
@@ -20,60 +17,23 @@ extern "C" int hu_spr_timing(double* seconds) {
 }
 
 namespace {
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-/* the device half behind the operations of a round */
+/* the buffers of the scoring behind the operations of a round; msg: the messages */
 struct SprDev {
-	const char* fn; int32_t n = 0, L = 0, device = 0, radius = 0; const int8_t* seq = nullptr; hu_model_desc model; HuBlenModel m; double lo = 0, hi = 0;
+	HuTreeDev msg; const char* fn; int32_t n = 0, L = 0, radius = 0; double lo = 0, hi = 0;
 	size_t nodeCap = 0, recCap = 0, outCap = 0;
-	double *up = nullptr, *down = nullptr, *stack = nullptr, *ratio = nullptr, *vec = nullptr, *f0 = nullptr;   /* vec: tStar [outCap], f [outCap] */
-	int32_t* iters = nullptr; HuSprNode* nodes = nullptr; HuSprRec* recs = nullptr; HuBlenModel* dm = nullptr;
-	std::vector<int8_t> rows;
+	double *stack = nullptr, *ratio = nullptr, *vec = nullptr, *f0 = nullptr;   /* vec: tStar [outCap], f [outCap] */
+	int32_t* iters = nullptr; HuSprNode* nodes = nullptr; HuSprRec* recs = nullptr;
 	~SprDev() { release(); }
 	void release_slab() {
 		(void) hipFree(stack); (void) hipFree(ratio); (void) hipFree(vec); (void) hipFree(f0); (void) hipFree(iters); (void) hipFree(nodes); (void) hipFree(recs);
 		stack = ratio = vec = f0 = nullptr; iters = nullptr; nodes = nullptr; recs = nullptr; nodeCap = recCap = outCap = 0;
 	}
-	void release() {
-		release_slab();
-		(void) hipFree(up); (void) hipFree(down); (void) hipFree(dm);
-		up = down = nullptr; dm = nullptr;
-	}
-	int open() {
-		if(hu_device_count() <= 0) { hu_set_error("%s: no gfx950 device visible: the host path needs none", fn); return HU_ERR_DEVICE; }
-		SCHK(hipSetDevice(device));
-		size_t freeB = 0, totB = 0;
-		SCHK(hipMemGetInfo(&freeB, &totB));
-		const size_t need = (size_t) hu_spr_need(n, L, radius);
-		if(need > freeB) {
-			hu_set_error("%s: %d nodes of %d columns at radius %d need %zu bytes of device memory (%zu of them for the messages), %zu bytes are free", fn, n, L,
-				radius, need, (size_t) n * (size_t) L * 64, freeB);
-			return HU_ERR_NOMEM;
-		}
-		return HU_OK;
-	}
-	int alloc() {
-		if(up) return HU_OK;
-		const size_t cells = (size_t) n * (size_t) L;
-		SCHK(hipMalloc((void**) &up, cells * 32)); SCHK(hipMalloc((void**) &down, cells * 32));
-		SCHK(hipMalloc((void**) &dm, sizeof(HuBlenModel)));
-		SCHK(hipMemcpy(dm, &m, sizeof(HuBlenModel), hipMemcpyHostToDevice));
-		return HU_OK;
-	}
-	int sweep(const int32_t* parent, const double* blen, bool withDown) {
-		int rc = alloc();
-		if(rc != HU_OK) return rc;
-		hu_tree_sweep* sw = nullptr;
-		if((rc = hu_tree_sweep_create(n, L, parent, blen, device, &sw)) != HU_OK) return rc;
-		rows.assign(seq, seq + (size_t) n * (size_t) L);
-		rc = hu_tree_sweep_window(sw, &model, rows.data(), 0, L, up, withDown ? down : nullptr);
-		hu_tree_sweep_destroy(sw);
-		return rc;
-	}
-	int loglik(const int32_t* parent, double* ll) {
-		int32_t root = 0;
-		for(int32_t i = 0; i < n; ++i) if(parent[i] < 0) root = i;
-		return hu_tree_loglik(device, n, L, root, &model, up, nullptr, ll);
+	void release() { release_slab(); msg.release(); }
+	int open(const char* fn_, const hu_spr_opts* o, int32_t n_, int32_t cs_len, const hu_model_desc* model, const HuBlenModel& m) {
+		fn = fn_; n = n_; L = cs_len; radius = o->radius; lo = o->blen.min_len; hi = o->blen.max_len;
+		char what[80];
+		snprintf(what, sizeof(what), "%d nodes of %d columns at radius %d", n, L, radius);
+		return msg.open(fn, o->blen, n, L, model, m, (size_t) hu_spr_need(n, L, radius), what);
 	}
 	/* one slab; the messages are those of the last full sweep */
 	int score(const HuSprNode* nd, size_t nNodes, const HuSprRec* rc, size_t nRecs, int64_t recBase, int64_t outBase, size_t nOut, double* ts, double* f, double* f0h) {
@@ -94,17 +54,17 @@ struct SprDev {
 		if(nNodes > nodeCap || nRecs > recCap || nOut > outCap) {
 			release_slab();
 			const size_t sL = (size_t) L;
-			SCHK(hipMalloc((void**) &stack, nNodes * (size_t) radius * sL * 32));
-			if(L > HU_BLEN_LDS_COLS) SCHK(hipMalloc((void**) &ratio, nNodes * 24 * sL));
-			SCHK(hipMalloc((void**) &vec, nOut * 16)); SCHK(hipMalloc((void**) &iters, nOut * 4)); SCHK(hipMalloc((void**) &f0, nNodes * 8));
-			SCHK(hipMalloc((void**) &nodes, nNodes * sizeof(HuSprNode))); SCHK(hipMalloc((void**) &recs, nRecs * sizeof(HuSprRec)));
+			TCHK(hipMalloc((void**) &stack, nNodes * (size_t) radius * sL * 32));
+			if(L > HU_BLEN_LDS_COLS) TCHK(hipMalloc((void**) &ratio, nNodes * 24 * sL));
+			TCHK(hipMalloc((void**) &vec, nOut * 16)); TCHK(hipMalloc((void**) &iters, nOut * 4)); TCHK(hipMalloc((void**) &f0, nNodes * 8));
+			TCHK(hipMalloc((void**) &nodes, nNodes * sizeof(HuSprNode))); TCHK(hipMalloc((void**) &recs, nRecs * sizeof(HuSprRec)));
 			nodeCap = nNodes; recCap = nRecs; outCap = nOut;
 		}
-		SCHK(hipMemcpy(nodes, nd, nNodes * sizeof(HuSprNode), hipMemcpyHostToDevice));
-		SCHK(hipMemcpy(recs, rc, nRecs * sizeof(HuSprRec), hipMemcpyHostToDevice));
-		SCHK(hipMemset(vec, 0, nOut * 16)); SCHK(hipMemset(iters, 0, nOut * 4)); SCHK(hipMemset(f0, 0, nNodes * 8));
+		TCHK(hipMemcpy(nodes, nd, nNodes * sizeof(HuSprNode), hipMemcpyHostToDevice));
+		TCHK(hipMemcpy(recs, rc, nRecs * sizeof(HuSprRec), hipMemcpyHostToDevice));
+		TCHK(hipMemset(vec, 0, nOut * 16)); TCHK(hipMemset(iters, 0, nOut * 4)); TCHK(hipMemset(f0, 0, nNodes * 8));
 		HuSprArgs a; memset(&a, 0, sizeof(a));
-		a.up = up; a.down = down; a.nodes = nodes; a.recs = recs; a.m = dm; a.csLen = L; a.recBase = recBase; a.outBase = outBase;
+		a.up = msg.up; a.down = msg.down; a.nodes = nodes; a.recs = recs; a.m = msg.dm; a.csLen = L; a.recBase = recBase; a.outBase = outBase;
 		a.n = n; a.nNodes = (int32_t) nNodes; a.slots = radius; a.lo = lo; a.hi = hi;
 		a.stack = stack; a.ratio = ratio; a.tStar = vec; a.f = vec + nOut; a.f0 = f0; a.iters = iters;
 		(void) hipGetLastError();
@@ -113,10 +73,10 @@ struct SprDev {
 			k_spr_score<true><<<(unsigned) nNodes, HU_SPR_WG, lds>>>(a);
 		}
 		else k_spr_score<false><<<(unsigned) nNodes, HU_SPR_WG, (size_t) 3 * HU_SPR_WG * 8>>>(a);
-		SCHK(hipGetLastError());
-		SCHK(hipDeviceSynchronize());
-		SCHK(hipMemcpy(ts, vec, nOut * 8, hipMemcpyDeviceToHost)); SCHK(hipMemcpy(f, vec + nOut, nOut * 8, hipMemcpyDeviceToHost));
-		SCHK(hipMemcpy(f0h, f0, nNodes * 8, hipMemcpyDeviceToHost));
+		TCHK(hipGetLastError());
+		TCHK(hipDeviceSynchronize());
+		TCHK(hipMemcpy(ts, vec, nOut * 8, hipMemcpyDeviceToHost)); TCHK(hipMemcpy(f, vec + nOut, nOut * 8, hipMemcpyDeviceToHost));
+		TCHK(hipMemcpy(f0h, f0, nNodes * 8, hipMemcpyDeviceToHost));
 		return HU_OK;
 	}
 	HuSprSlabFn slab() {
@@ -126,20 +86,6 @@ struct SprDev {
 	}
 };
 
-int spr_model(const char* fn, const hu_spr_opts* o, const hu_model_desc* model, HuBlenModel* m) {
-	if(!o || !model) { hu_set_error("%s: null argument", fn); return HU_ERR_ARG; }
-	if(model->dg_k != 0) { hu_set_error("%s: a model with %d discrete Gamma categories: the search runs under the fixed-rate model only", fn, model->dg_k); return HU_ERR_ARG; }
-	HuModelDev d;
-	const int rc = hu_model_prepare(model, &d);
-	if(rc != HU_OK) return rc;
-	hu_blen_model_set(m, d.U, d.lam, d.U1);
-	return HU_OK;
-}
-
-int spr_dev_setup(SprDev& r, const char* fn, const hu_spr_opts* o, int32_t n, int32_t cs_len, const int8_t* seq, const hu_model_desc* model, const HuBlenModel& m) {
-	r.fn = fn; r.n = n; r.L = cs_len; r.device = o->blen.device; r.radius = o->radius; r.seq = seq; r.model = *model; r.m = m; r.lo = o->blen.min_len; r.hi = o->blen.max_len;
-	return r.open();
-}
 }
 
 extern "C" int hu_tree_spr_scores(const hu_spr_opts* opts, int32_t n, int32_t cs_len, const int32_t* parent, const double* blen, const int8_t* seq,
@@ -150,7 +96,7 @@ extern "C" int hu_tree_spr_scores(const hu_spr_opts* opts, int32_t n, int32_t cs
 	if(!n_pruned || !n_targets || !skipped || node_cap < 0 || target_cap < 0 || (node_cap > 0 && (!prune_node || !v_off || !base_t || !base_f || !f_at_blen)) ||
 			(target_cap > 0 && (!target_node || !dist || !t_star || !f))) { hu_set_error("%s: null output", fn); return HU_ERR_ARG; }
 	HuBlenModel m;
-	int rc = spr_model(fn, opts, model, &m);
+	int rc = hu_search_model(fn, opts, model, "the search runs", &m);
 	if(rc != HU_OK) return rc;
 	const bool host = opts->blen.host != 0 || opts->blen.device < 0;
 	HuSprScores sc;
@@ -167,9 +113,9 @@ extern "C" int hu_tree_spr_scores(const hu_spr_opts* opts, int32_t n, int32_t cs
 	if(host) rc = hu_spr_host_scores_entry(fn, opts, n, cs_len, parent, blen, seq, m, false, &sc);
 	else {
 		SprDev r;
-		if((rc = spr_dev_setup(r, fn, opts, n, cs_len, seq, model, m)) != HU_OK) return rc;
+		if((rc = r.open(fn, opts, n, cs_len, model, m)) != HU_OK) return rc;
 		if(sc.v.empty()) { if(v_off) v_off[0] = 0; return HU_OK; }
-		if((rc = r.sweep(parent, blen, true)) != HU_OK) return rc;
+		if((rc = r.msg.sweep(n, parent, blen, seq, true)) != HU_OK) return rc;
 		rc = hu_spr_scores(fn, opts, tp, cs_len, parent, blen, false, r.slab(), &sc);
 	}
 	if(rc != HU_OK) return rc;
@@ -184,38 +130,27 @@ extern "C" int hu_tree_spr_search(hu_spr_opts* opts, int32_t n, int32_t cs_len, 
 		const int32_t* child_off, int32_t* child_idx, const hu_model_desc* model) try {
 	const char* fn = "hu_tree_spr_search";
 	HuBlenModel m;
-	int rc = spr_model(fn, opts, model, &m);
+	int rc = hu_search_model(fn, opts, model, "the search runs", &m);
 	if(rc != HU_OK) return rc;
 	if((child_off == nullptr) != (child_idx == nullptr)) { hu_set_error("%s: child_off and child_idx go together", fn); return HU_ERR_ARG; }
 	g_sprTiming[0] = g_sprTiming[1] = g_sprTiming[2] = g_sprTiming[3] = 0;
-	const double t0 = now_s();
+	const double t0 = hu_now_s();
 	if(opts->blen.host != 0 || opts->blen.device < 0) rc = hu_spr_host_search_entry(fn, opts, n, cs_len, parent, blen, seq, child_off, child_idx, m, g_sprTiming);
 	else {
 		HuBlenTopo tp;
 		if((rc = hu_spr_check(fn, opts, n, cs_len, parent, blen, seq, 0, &tp)) != HU_OK) return rc;
 		SprDev r;
-		if((rc = spr_dev_setup(r, fn, opts, n, cs_len, seq, model, m)) != HU_OK) return rc;
+		if((rc = r.open(fn, opts, n, cs_len, model, m)) != HU_OK) return rc;
 		HuSprOps ops;
-		ops.fit = [&](const int32_t* par, double* b, double* ll) {
-			r.release();                                       /* the fit holds messages of its own */
-			hu_blen_opts bo = opts->blen;
-			bo.rounds = nullptr; bo.rounds_cap = 0;
-			const int rc2 = hu_tree_optimize_lengths(&bo, n, cs_len, par, b, seq, model);
-			*ll = bo.ll_final;
-			return rc2;
-		};
+		ops.fit = [&](const int32_t* par, double* b, double* ll) { return hu_search_fit_device(r, opts->blen, n, par, b, seq, ll); };
 		ops.score = [&](const int32_t* par, const double* b, const HuBlenTopo& tpr, HuSprScores* out) {
-			int rc2 = r.sweep(par, b, true);
+			int rc2 = r.msg.sweep(n, par, b, seq, true);
 			if(rc2 == HU_OK) rc2 = hu_spr_scores(fn, opts, tpr, cs_len, par, b, false, r.slab(), out);
 			return rc2;
 		};
-		ops.trial = [&](const int32_t* par, const double* b, double* ll) {
-			int rc2 = r.sweep(par, b, false);
-			if(rc2 == HU_OK) rc2 = r.loglik(par, ll);
-			return rc2;
-		};
+		ops.trial = [&](const int32_t* par, const double* b, double* ll) { return r.msg.trial(n, par, b, seq, ll); };
 		rc = hu_spr_rounds(fn, opts, n, cs_len, parent, blen, seq, child_off, child_idx, ops, g_sprTiming);
 	}
-	g_sprTiming[3] = now_s() - t0 - g_sprTiming[0] - g_sprTiming[1] - g_sprTiming[2];
+	g_sprTiming[3] = hu_now_s() - t0 - g_sprTiming[0] - g_sprTiming[1] - g_sprTiming[2];
 	return rc;
 } catch(...) { return hu_catch_all("hu_tree_spr_search"); }

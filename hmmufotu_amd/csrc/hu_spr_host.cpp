@@ -1,9 +1,8 @@
 // The checks, the walk, the host path, the selection and the round loop of the SPR search: hmmufotu-amd-tree
 // --ml-lengths --spr --host, the reference of the device tests, and what tests/san/spr_driver.cpp runs under the sanitizers.  No HIP
 // headers: a plain C++ compiler builds this file.  The arithmetic of a column is hu_tree_spr.h's, shared with the kernel; the sweeps,
-// the fit's round loop and the Newton rule are hu_blen_host.cpp's and hu_tree_blen.h's, the halving of a rejected set hu_nni_host.cpp's.
+// the fit's round loop, the search's round loop (hu_search_rounds) and the Newton rule are hu_blen_host.cpp's and hu_tree_blen.h's.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include "hu_tree_spr.h"
@@ -256,34 +255,21 @@ extern "C" int hu_tree_spr_apply(int32_t n, int32_t* parent, double* blen, const
 } catch(...) { return hu_catch_all("hu_tree_spr_apply"); }
 
 /* ---- the round loop ---- */
-static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 namespace {
 struct Cand { int32_t v, w, dist, s; double t, gain; };
 }
 
 int hu_spr_rounds(const char* fn, hu_spr_opts* o, int32_t n, int32_t cs_len, int32_t* parent, double* blen, const int8_t* seq, const int32_t* child_off,
 		int32_t* child_idx, const HuSprOps& ops, double* sec) {
-	const size_t N = (size_t) n, nIdx = child_off && child_idx ? (size_t) child_off[n] : 0;
-	std::vector<int32_t> par(N), idx(nIdx), taken, stamp(N);
-	std::vector<double> bl(N);
+	const size_t N = (size_t) n;
+	std::vector<int32_t> stamp(N);
 	std::vector<Cand> cand;
 	HuSprScores sc;
-	HuBlenTopo tp;
-	o->n_rounds = 0; o->n_moves = 0; o->skipped = 0; o->stop = HU_SPR_MAX_ROUNDS;
-	int rc;
-	double ll = 0;
-	for(int32_t r = 0; r <= o->spr_rounds; ++r) {
-		double t0 = now_s();
-		if((rc = ops.fit(parent, blen, &ll)) != HU_OK) return rc;
-		sec[0] += now_s() - t0;
-		if(r == 0) o->ll_start = ll;
-		o->ll_final = ll;
-		if(r == o->spr_rounds) break;                           /* the fit after the last round allowed */
-		t0 = now_s();
-		if((rc = hu_blen_check(fn, &o->blen, n, cs_len, parent, blen, seq, 0, &tp)) != HU_OK) return rc;
-		if((rc = ops.score(parent, blen, tp, &sc)) != HU_OK) return rc;
-		sec[1] += now_s() - t0;
+	o->n_rounds = 0; o->n_moves = 0; o->skipped = 0;
+	HuSearchOps so;
+	so.fit = ops.fit; so.trial = ops.trial;
+	so.score = [&](const HuBlenTopo& tp) { return ops.score(parent, blen, tp, &sc); };
+	so.select = [&](const HuBlenTopo& tp, std::vector<int32_t>* taken) {
 		o->skipped = sc.skipped;
 		/* the best target of every pruned node: the largest f, the smaller w among equals */
 		cand.clear();
@@ -298,12 +284,10 @@ int hu_spr_rounds(const char* fn, hu_spr_opts* o, int32_t n, int32_t cs_len, int
 			const int32_t s = tp.childIdx[tp.childOff[p]] == v ? tp.childIdx[tp.childOff[p] + 1] : tp.childIdx[tp.childOff[p]];
 			cand.push_back({v, sc.w[(size_t) best], sc.dist[(size_t) best], s, sc.t[(size_t) best], gain});
 		}
-		if(cand.empty()) { o->stop = HU_SPR_LOCAL_OPTIMUM; return HU_OK; }
 		std::sort(cand.begin(), cand.end(), [](const Cand& a, const Cand& b) { return a.gain != b.gain ? a.gain > b.gain : a.v != b.v ? a.v < b.v : a.w < b.w; });
 		/* taken: none of its own nodes and none on the path from p to w is marked by one taken before */
 		std::vector<char> used(N, 0);
 		std::vector<int32_t> mine;
-		taken.clear();
 		std::fill(stamp.begin(), stamp.end(), -1);
 		for(size_t c = 0; c < cand.size(); ++c) {
 			const Cand& x = cand[c];
@@ -318,41 +302,32 @@ int hu_spr_rounds(const char* fn, hu_spr_opts* o, int32_t n, int32_t cs_len, int
 			for(int32_t a : mine) if(used[(size_t) a]) freeOf = false;
 			if(!freeOf) continue;
 			for(int32_t a : mine) used[(size_t) a] = 1;
-			taken.push_back((int32_t) c);
+			taken->push_back((int32_t) c);
 		}
-		const size_t nCand = cand.size(), nTaken = taken.size();
-		t0 = now_s();
-		double llNew = ll;
-		for(;;) {
-			par.assign(parent, parent + N); bl.assign(blen, blen + N);
-			if(nIdx) idx.assign(child_idx, child_idx + nIdx);
-			for(int32_t c : taken) {
-				const Cand& x = cand[(size_t) c];
-				if(hu_spr_apply(fn, n, par.data(), bl.data(), nIdx ? child_off : nullptr, nIdx ? idx.data() : nullptr, x.v, x.w, x.t) != HU_OK) return HU_ERR_STATE;
-			}
-			if((rc = ops.trial(par.data(), bl.data(), &llNew)) != HU_OK) return rc;
-			if(llNew > ll) break;
-			if(!hu_nni_halve(&taken)) { sec[2] += now_s() - t0; o->stop = HU_SPR_NO_MOVE; return HU_OK; }
+	};
+	so.apply = [&](const std::vector<int32_t>& taken, int32_t* par, double* bl, int32_t* idx) {
+		for(int32_t c : taken) {
+			const Cand& x = cand[(size_t) c];
+			if(hu_spr_apply(fn, n, par, bl, idx ? child_off : nullptr, idx, x.v, x.w, x.t) != HU_OK) return (int) HU_ERR_STATE;
 		}
-		sec[2] += now_s() - t0;
-		memcpy(parent, par.data(), N * 4); memcpy(blen, bl.data(), N * 8);
-		if(nIdx) memcpy(child_idx, idx.data(), nIdx * 4);
-		ll = llNew; o->ll_final = ll;
+		return (int) HU_OK;
+	};
+	so.record = [&](int32_t round, double ll, size_t nTaken, const std::vector<int32_t>& taken) {
 		if(o->rounds && o->n_rounds < o->rounds_cap) {
 			hu_spr_round& R = o->rounds[o->n_rounds];
-			R.ll = ll; R.targets = (int64_t) sc.w.size(); R.pruned = (int32_t) sc.v.size(); R.candidates = (int32_t) nCand; R.taken = (int32_t) nTaken; R.applied = (int32_t) taken.size();
+			R.ll = ll; R.targets = (int64_t) sc.w.size(); R.pruned = (int32_t) sc.v.size(); R.candidates = (int32_t) cand.size(); R.taken = (int32_t) nTaken; R.applied = (int32_t) taken.size();
 		}
 		for(int32_t c : taken) {
 			if(o->moves && o->n_moves < o->moves_cap) {
 				const Cand& x = cand[(size_t) c];
 				int32_t* mv = o->moves + o->n_moves * 5;
-				mv[0] = r + 1; mv[1] = x.v; mv[2] = x.s; mv[3] = x.w; mv[4] = x.dist;
+				mv[0] = round; mv[1] = x.v; mv[2] = x.s; mv[3] = x.w; mv[4] = x.dist;
 			}
 			o->n_moves++;
 		}
 		o->n_rounds++;
-	}
-	return HU_OK;
+	};
+	return hu_search_rounds(fn, &o->blen, o->spr_rounds, n, cs_len, parent, blen, seq, child_off, child_idx, so, &o->ll_start, &o->ll_final, &o->stop, sec);
 }
 
 /* ---- the host path of the two entries ---- */
@@ -381,38 +356,14 @@ int hu_spr_host_search_entry(const char* fn, hu_spr_opts* o, int32_t n, int32_t 
 	HuBlenTopo tp0;
 	int rc = hu_spr_check(fn, o, n, cs_len, parent, blen, seq, 0, &tp0);
 	if(rc != HU_OK) return rc;
-	const int64_t L = cs_len;
-	const size_t cells = (size_t) n * (size_t) cs_len * 4;
-	std::vector<double> up(cells), down(cells), stack;
-	const double lo = o->blen.min_len, hi = o->blen.max_len;
-	auto topo = [&](const int32_t* par, const double* b, HuBlenTopo* tp) { return hu_blen_check(fn, &o->blen, n, cs_len, par, b, seq, 0, tp); };
+	HuBlenHost h(m, n, cs_len, o->blen);
+	std::vector<double> stack;
 	HuSprOps ops;
-	ops.fit = [&](const int32_t* par, double* b, double* ll) {
-		HuBlenTopo tp;
-		int rc2 = topo(par, b, &tp);
-		if(rc2 != HU_OK) return rc2;
-		hu_blen_opts bo = o->blen;
-		bo.rounds = nullptr; bo.rounds_cap = 0;
-		HuBlenOps bops;
-		bops.sweep = [&](const double* x, bool withDown) { hu_blen_host_sweep(tp, m, par, L, x, seq, up.data(), withDown ? down.data() : nullptr); return (int) HU_OK; };
-		bops.loglik = [&](double* out) { *out = hu_blen_host_loglik(m, L, up.data() + (size_t) tp.root * L * 4); return (int) HU_OK; };
-		bops.step = [&](const double* x, double* t, int64_t* c) { *c = hu_blen_host_step(tp, m, L, x, up.data(), down.data(), lo, hi, t, nullptr, nullptr, nullptr, nullptr); return (int) HU_OK; };
-		double s4[4] = {0, 0, 0, 0};
-		rc2 = hu_blen_rounds(fn, &bo, n, tp.root, b, bops, s4);
-		*ll = bo.ll_final;
-		return rc2;
-	};
+	ops.fit = [&](const int32_t* par, double* b, double* ll) { return h.fit(fn, &o->blen, n, par, b, seq, ll); };
 	ops.score = [&](const int32_t* par, const double* b, const HuBlenTopo& tp, HuSprScores* out) {
-		hu_blen_host_sweep(tp, m, par, L, b, seq, up.data(), down.data());
-		return hu_spr_scores(fn, o, tp, cs_len, par, b, false, host_slab(o, m, n, L, up.data(), down.data(), &stack), out);
+		h.sweep(tp, par, b, seq, true);
+		return hu_spr_scores(fn, o, tp, cs_len, par, b, false, host_slab(o, m, n, cs_len, h.up.data(), h.down.data(), &stack), out);
 	};
-	ops.trial = [&](const int32_t* par, const double* b, double* ll) {
-		HuBlenTopo tp;
-		int rc2 = topo(par, b, &tp);
-		if(rc2 != HU_OK) return rc2;
-		hu_blen_host_sweep(tp, m, par, L, b, seq, up.data(), nullptr);
-		*ll = hu_blen_host_loglik(m, L, up.data() + (size_t) tp.root * L * 4);
-		return (int) HU_OK;
-	};
+	ops.trial = [&](const int32_t* par, const double* b, double* ll) { return h.trial(fn, &o->blen, n, par, b, seq, ll); };
 	return hu_spr_rounds(fn, o, n, cs_len, parent, blen, seq, child_off, child_idx, ops, sec);
 }

@@ -3,7 +3,6 @@
 // compiler builds this file.  The arithmetic of a column is hu_tree_support.h's, shared with the kernel; the sweeps are
 // hu_blen_host.cpp's and the scoring is hu_nni_host.cpp's.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include "hu_tree_support.h"
@@ -114,8 +113,6 @@ int hu_support_verify(const char* fn, const std::vector<HuNniEdge>& edges, const
 	return HU_OK;
 }
 
-static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 int hu_support_host_entry(const char* fn, const hu_support_opts* o, int32_t n, int32_t cs_len, const int32_t* parent, const double* blen, const int8_t* seq,
 		const HuBlenModel& m, int32_t edge_cap, int32_t* n_edges, int64_t* skipped, int32_t* edge_node, double* t_star, double* f, int32_t* count,
 		double* sums, double* sec) {
@@ -130,18 +127,18 @@ int hu_support_host_entry(const char* fn, const hu_support_opts* o, int32_t n, i
 	if(edges.empty()) return HU_OK;
 	const size_t E = edges.size(), cells = (size_t) n * (size_t) cs_len * 4;
 	const int64_t L = cs_len, B = o->replicates;
-	double t0 = now_s();
+	double t0 = hu_now_s();
 	std::vector<double> up(cells), down(cells), f0(E), f2(E * 3);
 	hu_blen_host_sweep(tp, m, parent, L, blen, seq, up.data(), down.data());
-	sec[0] = now_s() - t0; t0 = now_s();
+	sec[0] = hu_now_s() - t0; t0 = hu_now_s();
 	hu_nni_host_score(m, n, L, edges, up.data(), down.data(), o->blen.min_len, o->blen.max_len, t_star, f, f0.data());
-	sec[1] = now_s() - t0; t0 = now_s();
+	sec[1] = hu_now_s() - t0; t0 = hu_now_s();
 	std::vector<uint16_t> w((size_t) B * (size_t) L);
 	if((rc = hu_support_weights(cs_len, o->replicates, o->seed, w.data())) != HU_OK) return rc;
-	sec[2] = now_s() - t0; t0 = now_s();
+	sec[2] = hu_now_s() - t0; t0 = hu_now_s();
 	int64_t bad = -1;
 	hu_support_host_edges(m, n, L, B, edges, up.data(), down.data(), t_star, w.data(), f2.data(), count, sums, &bad);
-	sec[3] = now_s() - t0;
+	sec[3] = hu_now_s() - t0;
 	if((rc = hu_support_verify(fn, edges, f, f2.data(), bad)) != HU_OK) return rc;
 	for(size_t e = 0; e < E; ++e) edge_node[e] = edges[e].u;
 	return HU_OK;

@@ -2,16 +2,13 @@
 // The checks, the host path and the Newick writer are hu_nj_host.cpp's; the kernels are those of hu_kern_dist.h and hu_kern_nj.h.
 // One work area holds everything a call needs on the device, and its size is held against the free memory before it is allocated.
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <vector>
-#include "hu_common.h"
+#include "hu_tree_dev.h"
 #include "hu_kern_dist.h"
 #include "hu_kern_nj.h"
 
 static thread_local double g_njTiming[4] = {0, 0, 0, 0};
-
-#define TCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { hu_set_error("%s: %s failed: %s", fn, #call, hipGetErrorString(e_)); return HU_ERR_DEVICE; } } while(0)
 
 extern "C" int hu_nj_timing(double* seconds) {
 	if(!seconds) return HU_ERR_ARG;
@@ -142,8 +139,6 @@ static int tree_nj(const char* fn, TreeWork& w, int64_t n, int32_t* join, double
 	return HU_OK;
 }
 
-static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 extern "C" int hu_msa_pair_counts(int device, int64_t n, int64_t cs_len, const int8_t* rows, int32_t* counts) try {
 	const char* fn = "hu_msa_pair_counts";
 	if(!counts) { hu_set_error("%s: null output", fn); return HU_ERR_ARG; }
@@ -190,7 +185,7 @@ static int tree_run(const char* fn, int device, int64_t n, int64_t cs_len, const
 	const int rr = tree_reserve(fn, device, n, cs_len, s, o.mem_budget);
 	if(rr != HU_OK) return rr;
 	TreeWork w;
-	double t0 = now_s();
+	double t0 = hu_now_s();
 	TCHK(hipMalloc((void**) &w.D, s.D));
 	if(dist) {
 		const int re = tree_encode(fn, w, s, n, cs_len, rows);
@@ -198,19 +193,19 @@ static int tree_run(const char* fn, int device, int64_t n, int64_t cs_len, const
 	}
 	else TCHK(hipMemcpy(w.D, D_in, s.D, hipMemcpyHostToDevice));
 	TCHK(hipDeviceSynchronize());
-	g_njTiming[0] = now_s() - t0; t0 = now_s();
+	g_njTiming[0] = hu_now_s() - t0; t0 = hu_now_s();
 	if(dist) {
 		const int rd = tree_distances(fn, w, s, n, dist_type, pi, sat, n_sat);
 		if(rd != HU_OK) return rd;
 		TCHK(hipDeviceSynchronize());
-		g_njTiming[1] = now_s() - t0; t0 = now_s();
+		g_njTiming[1] = hu_now_s() - t0; t0 = hu_now_s();
 		if(D_out) TCHK(hipMemcpy(D_out, w.D, s.D, hipMemcpyDeviceToHost));
-		g_njTiming[3] = now_s() - t0; t0 = now_s();
+		g_njTiming[3] = hu_now_s() - t0; t0 = hu_now_s();
 	}
 	if(nj) {
 		const int rn = tree_nj(fn, w, n, join, len, last3, last_len3);
 		if(rn != HU_OK) return rn;
-		g_njTiming[2] = now_s() - t0;
+		g_njTiming[2] = hu_now_s() - t0;
 	}
 	return HU_OK;
 }

@@ -1,10 +1,12 @@
 // What the host half (hu_blen_host.cpp, a plain C++ compiler) and the device half (hu_blen.cpp, hu_kern_blen.h) of the branch-length
 // fit share: the model in the form the step reads, the arithmetic of one column and the rule of one Newton step.
 // Every function here is compiled for both sides from this one text, and both translation units are built with -ffp-contract=off.
+// Below the fit's own host half: what the searches over topologies (§23, §25, §26) share on the host path, their round loop included.
 #pragma once
 #include <float.h>
 #include <math.h>
 #include <stdint.h>
+#include <chrono>
 #include <functional>
 #include <vector>
 #include "../../include/hmmufotu_amd.h"
@@ -121,3 +123,49 @@ struct HuBlenOps {
 int hu_blen_rounds(const char* fn, hu_blen_opts* o, int32_t n, int32_t root, double* blen, const HuBlenOps& ops, double* seconds);
 void hu_set_error(const char* fmt, ...);
 int hu_catch_all(const char* fn) noexcept;
+/* the clock of every phase time of the tree family */
+inline double hu_now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+/* ---- what the searches over topologies (NNI, SPR, insertion) share on the host path ---- */
+/* the messages of a tree of up to nCap nodes, and the two operations of a search's round that need no scores */
+struct HuBlenHost {
+	const HuBlenModel& m; int64_t L; double lo, hi;
+	std::vector<double> up, down;
+	HuBlenHost(const HuBlenModel& model, int64_t nCap, int64_t cs_len, const hu_blen_opts& bo)
+		: m(model), L(cs_len), lo(bo.min_len), hi(bo.max_len), up((size_t)(nCap * cs_len * 4)), down((size_t)(nCap * cs_len * 4)) {}
+	void sweep(const HuBlenTopo& tp, const int32_t* parent, const double* blen, const int8_t* seq, bool withDown) {
+		hu_blen_host_sweep(tp, m, parent, L, blen, seq, up.data(), withDown ? down.data() : nullptr);
+	}
+	/* hu_blen_rounds in place under bo, without its round records; ll: the log-likelihood it ends at */
+	int fit(const char* fn, const hu_blen_opts* bo, int32_t n, const int32_t* parent, double* blen, const int8_t* seq, double* ll);
+	/* one up sweep and the log-likelihood */
+	int trial(const char* fn, const hu_blen_opts* bo, int32_t n, const int32_t* parent, const double* blen, const int8_t* seq, double* ll);
+};
+/* the options of a search's fit: the search's own hu_blen_opts without the round records.  The budget is not the fit's to hold: every
+ * search has held it against its own need, which includes hu_blen_need of the largest tree it fits (hu_nni_check, hu_spr_check,
+ * hu_add_check), so the fit's check of it could never fire */
+inline hu_blen_opts hu_search_fit_opts(const hu_blen_opts& o) { hu_blen_opts bo = o; bo.rounds = nullptr; bo.rounds_cap = 0; bo.mem_budget = 0; return bo; }
+
+/* the set tried after a rejected one: its better half, rounded up; false when a single move was rejected */
+bool hu_nni_halve(std::vector<int32_t>* taken);
+/* the round loop of the NNI and the SPR search over either half: fit, stop after the last fit allowed, score, select, try the taken set and
+ * halve it until the log-likelihood rises, commit, record.
+ *   fit(parent, blen, &ll): hu_tree_optimize_lengths in place;  trial(parent, blen, &ll): one up sweep and hu_tree_loglik
+ *   score(tp): scores the tree as it stands;  select(tp, &taken): the indices of the moves to try, the best first; none: a local optimum
+ *   apply(taken, parent, blen, child_idx): the moves on copies of the arrays (child_idx NULL without an order of children)
+ *   record(round, ll, nTaken, taken): the accepted round and its moves, round counted from 1; nTaken: the set before any halving
+ * stop: one of HU_SEARCH_*, which HU_NNI_* and HU_SPR_* both equal.  seconds [0..2] += fit, score (with the check of the tree), trials;
+ * the selection is timed in none of them */
+enum { HU_SEARCH_LOCAL_OPTIMUM = HU_NNI_LOCAL_OPTIMUM, HU_SEARCH_NO_MOVE = HU_NNI_NO_SWAP, HU_SEARCH_MAX_ROUNDS = HU_NNI_MAX_ROUNDS };
+static_assert((int) HU_SPR_LOCAL_OPTIMUM == (int) HU_SEARCH_LOCAL_OPTIMUM && (int) HU_SPR_NO_MOVE == (int) HU_SEARCH_NO_MOVE &&
+	(int) HU_SPR_MAX_ROUNDS == (int) HU_SEARCH_MAX_ROUNDS, "the SPR search reports hu_search_rounds' stop as its own");
+struct HuSearchOps {
+	std::function<int(const int32_t*, double*, double*)> fit;
+	std::function<int(const int32_t*, const double*, double*)> trial;
+	std::function<int(const HuBlenTopo&)> score;
+	std::function<void(const HuBlenTopo&, std::vector<int32_t>*)> select;
+	std::function<int(const std::vector<int32_t>&, int32_t*, double*, int32_t*)> apply;
+	std::function<void(int32_t, double, size_t, const std::vector<int32_t>&)> record;
+};
+int hu_search_rounds(const char* fn, const hu_blen_opts* bo, int32_t rounds, int32_t n, int32_t cs_len, int32_t* parent, double* blen, const int8_t* seq,
+		const int32_t* child_off, int32_t* child_idx, const HuSearchOps& ops, double* ll_start, double* ll_final, int32_t* stop, double* seconds);
