@@ -185,7 +185,8 @@ def dgamma(K: int, alpha: float):
 class SynthDB:
     n_nodes: int
     cs_len: int
-    parent: np.ndarray      # int32 [n], -1 for root (node 0); preorder numbering (parent < child)
+    parent: np.ndarray      # int32 [n], -1 for the root.  make_db: the root is node 0 and the numbering preorder (parent < child); a copy
+                            # relabelled by tests/tree_shapes.relabel has the root anywhere and parents before or behind their children
     blen: np.ndarray        # float64 [n], length of the branch to the parent (0 for root)
     seq: np.ndarray         # int8 [n, cs_len]; leaves: 0..3 / -2 gaps, inner nodes: inferred (no gaps)
     up: np.ndarray          # float64 [n, cs_len, 4]  message node -> parent (root row: root loglik)
@@ -396,15 +397,17 @@ def build_hmm(leaf_seq: np.ndarray, symfrac: float = 0.5, name: str = "synth") -
 
 def make_db(n_leaves: int, cs_len: int, model_name: str = "GTR", dg_k: int = 0, dg_alpha: float = 0.5,
             n_match: int | None = None, seed: int = 97, mean_blen: float = 0.05,
-            match_gap: float = 0.02, sparse_gap: float = 0.999, n_taxa: int = 8, pi=None) -> SynthDB:
-    """pi: base frequencies in place of the model file's (TN93 / HKY85 / F81 only) — e.g. two equal pairs, which makes the A and G
+            match_gap: float = 0.02, sparse_gap: float = 0.999, n_taxa: int = 8, pi=None, tree=None) -> SynthDB:
+    """tree: (parent, blen, is_leaf) in preorder numbering with the root at node 0, in place of make_tree's binary tree (n_leaves is then
+    not read): any number of children per node.  Everything after the tree is drawn from the seed as it is without the keyword.
+    pi: base frequencies in place of the model file's (TN93 / HKY85 / F81 only) — e.g. two equal pairs, which makes the A and G
     components of every all-gap column tie in exact arithmetic; such a database is for in-memory tests (its model text is not rewritten)."""
     rng = np.random.default_rng(seed)
     model = load_model(model_name)
     if pi is not None:
         assert model_name in ("TN93", "HKY85", "F81") and abs(sum(pi) - 1.0) < 1e-12
         model = SubModel(model.name, np.asarray(pi, np.float64), model.par, "")
-    parent, blen, is_leaf = make_tree(n_leaves, rng, mean_blen)
+    parent, blen, is_leaf = make_tree(n_leaves, rng, mean_blen) if tree is None else tree
     n = len(parent)
     if dg_k > 0:
         b, r = dgamma(dg_k, dg_alpha)

@@ -214,7 +214,7 @@ def tree_evaluate(parent, blen, leaf_seq, model: Model, dg_r=None):
     up = np.zeros((n, L, 4)); down = np.zeros((n, L, 4)); root = np.zeros((L, 4)); h = np.zeros(n)
     lib().orc_tree_evaluate(C.c_int(n), C.c_int(L), _p(parent, C.c_int), _p(blen, C.c_double), _p(seq, C.c_int8), model.h,
                             C.c_int(len(dgr)), _p(dgr, C.c_double), _p(up, C.c_double), _p(down, C.c_double), _p(root, C.c_double), _p(h, C.c_double))
-    up[0] = root
+    up[int(np.nonzero(parent < 0)[0][0])] = root           # the root's row holds the root message, wherever the root is numbered
     return up, down, seq, h
 
 

@@ -349,11 +349,17 @@ def test_pe_merge_parity():
 def test_sep_parity(cfg):
     """seed scan, top-k, estimate, filter, place, q-values vs the oracle, stage by stage.  seed_order: 1 (default) = the reference's own
     (literal std::sort on dist alone: oracle TIE_LIBSTDCXX, engine HU_SEED_ORDER_LIBSTDCXX), 0 = (dist, node id) on both sides."""
+    db = get_db(cfg["n_leaves"], cfg["cs_len"], cfg["model"], dg_k=cfg["dg_k"], **cfg.get("db_kw", {}))
+    reads, vps = sim_reads(db, cfg.get("n_reads", 40), cfg["read_len"])
+    sep_parity(db, reads, vps, cfg)
+
+
+def sep_parity(db, reads, vps, cfg):
+    """the body of test_sep_parity on a given database (any node numbering: the root is wherever db.parent says) and given reads;
+    of cfg it reads max_nseed, seed_order and db_kw"""
     E = _engine()
     from oracle import oracle_py as O
-    db = get_db(cfg["n_leaves"], cfg["cs_len"], cfg["model"], dg_k=cfg["dg_k"], **cfg.get("db_kw", {}))
     _, H, T = oracle_objects(db)
-    reads, vps = sim_reads(db, cfg.get("n_reads", 40), cfg["read_len"])
     order = cfg.get("seed_order", 1)
     opts = E.default_opts(max_nseed=cfg.get("max_nseed", 50), seed_order=order)
     D, B = _run_stages(E, db, reads, vps, opts)
