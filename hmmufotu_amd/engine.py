@@ -878,6 +878,76 @@ def unifrac_timing() -> dict:
     return dict(to_device=s[0], embed=s[1], pairs=s[2], to_host=s[3])
 
 
+class PermanovaOpts(C.Structure):
+    _fields_ = [("perms", C.c_int64), ("seed", C.c_uint64), ("host", C.c_int32), ("reserved", C.c_int32), ("chunk", C.c_int64), ("mem_budget", C.c_int64)]
+
+
+class PermanovaResult(C.Structure):
+    _fields_ = [("n", C.c_int64), ("a", C.c_int64), ("perms", C.c_int64), ("ss_total", C.c_double), ("ss_within", C.c_double), ("ss_among", C.c_double),
+                ("F", C.c_double), ("R2", C.c_double), ("count_le", C.c_int64), ("p", C.c_double)]
+
+
+def permanova(dist, group, perms=999, seed=1, chunk=0, device=0, host=False, mem_budget=0) -> dict:
+    """hu_permanova: PERMANOVA of the labels group [n] (0 .. a-1) on the distance matrix dist [n][n]: dict(n, a, perms, ss_total, ss_within,
+    ss_among, F, R2, count_le, p, ssw_perm [perms]).  chunk 0: as many permutations per launch as the memory holds.  host: the library's
+    host path, no device needed; it gives the same bits."""
+    d = np.ascontiguousarray(dist, np.float64); g = np.ascontiguousarray(group, np.int32)
+    if d.ndim != 2 or d.shape[0] != d.shape[1] or g.shape != (d.shape[0],):
+        raise EngineError("permanova: dist [n][n] and group [n]")
+    lib = load_library()
+    o = PermanovaOpts()
+    lib.hu_permanova_default_opts(C.byref(o))
+    o.perms = int(perms); o.seed = int(seed) & (2 ** 64 - 1); o.host = 1 if host else 0; o.chunk = int(chunk or 0); o.mem_budget = int(mem_budget or 0)
+    r = PermanovaResult()
+    ssw = np.zeros(max(int(perms), 0))
+    _chk(lib.hu_permanova(C.c_int(int(device)), C.c_int64(d.shape[0]), _p(d, C.c_double), _p(g, C.c_int32), C.byref(o), C.byref(r), _p(ssw, C.c_double) if len(ssw) else None))
+    out = {k: getattr(r, k) for k, _ in PermanovaResult._fields_}
+    out["ssw_perm"] = ssw
+    return out
+
+
+def permanova_labels(group, seed=1, first=0, count=1) -> np.ndarray:
+    """hu_permanova_labels (host only): [count][n], the labellings of permutations first .. first + count - 1 of the labels group [n]"""
+    g = np.ascontiguousarray(group, np.int32)
+    if g.ndim != 1:
+        raise EngineError("permanova_labels: group [n]")
+    out = np.zeros((int(count), len(g)), np.int32)
+    _chk(load_library().hu_permanova_labels(C.c_int64(len(g)), _p(g, C.c_int32), C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_int64(int(first)), C.c_int64(int(count)),
+                                            _p(out, C.c_int32)))
+    return out
+
+
+def permanova_need(n: int, a: int, chunk: int) -> int:
+    """hu_permanova_need: the bytes of device memory that n samples in a groups take with `chunk` permutations per launch"""
+    lib = load_library()
+    lib.hu_permanova_need.restype = C.c_int64
+    return int(lib.hu_permanova_need(C.c_int64(int(n)), C.c_int64(int(a)), C.c_int64(int(chunk))))
+
+
+def permanova_timing() -> dict:
+    """hu_permanova_timing: the phases of this thread's last permanova on a device, in seconds"""
+    s = np.zeros(4)
+    _chk(load_library().hu_permanova_timing(_p(s, C.c_double)))
+    return dict(to_device=s[0], shuffle=s[1], pairs=s[2], finish=s[3])
+
+
+def dist_matrix_read(path) -> dict:
+    """hu_dist_matrix_read (host only): the matrix hmmufotu-amd-unifrac -o writes, as dict(samples, dist [n][n])"""
+    lib = load_library()
+    h = C.c_void_p()
+    _chk(lib.hu_dist_matrix_read(os.fsencode(str(path)), C.byref(h)))
+    try:
+        n = C.c_int64()
+        _chk(lib.hu_dist_matrix_dims(h, C.byref(n)))
+        lib.hu_dist_matrix_sample.restype = C.c_char_p
+        lib.hu_dist_matrix_values.restype = C.POINTER(C.c_double)
+        names = [lib.hu_dist_matrix_sample(h, C.c_int64(i)).decode() for i in range(n.value)]
+        d = np.ctypeslib.as_array(lib.hu_dist_matrix_values(h), shape=(n.value, n.value)).copy() if n.value else np.zeros((0, 0))
+        return dict(samples=names, dist=d)
+    finally:
+        lib.hu_dist_matrix_free(h)
+
+
 class NjOpts(C.Structure):
     _fields_ = [("host", C.c_int32), ("reserved", C.c_int32), ("mem_budget", C.c_int64)]
 

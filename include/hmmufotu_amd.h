@@ -1064,6 +1064,59 @@ int hu_unifrac_embed(int device, const hu_unifrac_tree* tree, int64_t n_otu, int
 		const hu_unifrac_opts* opts, int64_t* n_branch, int64_t cap_branch, int32_t* branch_node, double* branch_len, double* P);
 int hu_unifrac_timing(double* seconds /* [4] */);
 
+/* ---- hmmufotu-amd-permanova: do the sample groups differ on a distance matrix? (PERMANOVA, Anderson 2001) ----
+ * dist [n][n] row-major: symmetric, non-negative, finite, zero on the diagonal.  group [n]: a label in 0 .. a-1 per sample, n_g the
+ * group sizes.  With D2_ij = d_ij * d_ij (one rounded product):
+ *     SS_T = (1/n) sum_{i<j} D2_ij,  SS_W = sum_{i<j, g_i == g_j} D2_ij / n_{g_i},  SS_A = SS_T - SS_W,
+ *     F = (SS_A / (a-1)) / (SS_W / (n-a)),  R2 = SS_A / SS_T,  p = (1 + #{pi : SS_W(pi) <= SS_W(observed)}) / (perms + 1).
+ * The order of every sum is a function of n alone: the samples in tiles of 64, the tiles (I, J), I <= J, in ascending row-major order;
+ * in a tile, for i ascending, r_i = the matching D2_ij of the tile, j ascending, j > i, by plain adds from +0, then s = fma(1/n_{g_i},
+ * r_i, s) over i ascending from +0; the tile sums then by plain adds in tile order from +0.  SS_T: the same with every pair matching
+ * and plain adds of r_i, divided by n at the end.  So relabellings that induce one partition give the same bits, the result depends
+ * on neither chunk nor the device, and the host path (opts->host, or device < 0: one thread, no device needed) gives the same bits.
+ * Permutation p (0-based) is a Fisher-Yates shuffle of the observed labels, for i = n-1 down to 1: w = Philox4x32-10 (hu_sim_philox) of
+ * the counter (i & 0xffffffff, i >> 32, p & 0xffffffff, p >> 32) under the key (seed & 0xffffffff, seed >> 32), x = w[1] << 32 | w[0],
+ * j = the high 64 bits of x (i + 1), swap g[i] and g[j].  No rejection: j is off the uniform by (i + 1) / 2^64 at the most.
+ * hu_permanova: ssw_perm (may be NULL) [perms] receives SS_W of every permutation.  chunk: permutations per launch (0: as many as the
+ * memory holds, 16,384 at the most); the device works on chunks padded to whole workgroups of 256.
+ * HU_ERR_ARG with the reason, before a device is asked for: n < 3, a negative label, labels not dense in 0 .. a-1, a < 2, a > n-1,
+ * a > 65,535, perms < 1 or > 10^7, chunk < 0, a cell that is negative, not finite or above 2^511 (its square
+ * would not be finite), d_ij != d_ji (with both indices), a non-zero
+ * diagonal, every distance 0.  HU_ERR_NOMEM with the bytes needed and the bytes free when hu_permanova_need exceeds mem_budget (checked
+ * before a device is asked for) or what the device reports free.  SS_W == 0 gives F = +inf; p still comes from the SS_W comparison.
+ * hu_permanova_labels: host only, out [count][n] the labellings of permutations first .. first + count - 1.
+ * hu_permanova_need: the bytes on the device for a chunk: 8 n^2 for the matrix, and with c = chunk rounded up to 256 and t the tiles,
+ * 2 n c for the labels, 8 t c for the partial sums, 8 c for the outputs, 8 a + 2 n for the tables and 1 MB of slack; -1 on a bad argument.
+ * hu_permanova_timing: of this thread's last device call, seconds [4] = copies up, shuffles, pair kernel, finish and copy back.
+ * hu_dist_matrix_read: the file hmmufotu-amd-unifrac -o writes: a first line of names, each after a tab, then per sample its name and n
+ * numbers, tab-separated.  HU_ERR_IO with the line otherwise.  The pointers the getters return stay valid until the matrix is freed. */
+typedef struct {
+	int64_t perms;        /* 999 */
+	uint64_t seed;        /* 1 */
+	int32_t host;         /* 0; 1: the host path, no device needed */
+	int32_t reserved;
+	int64_t chunk;        /* 0: chosen from n and the memory */
+	int64_t mem_budget;   /* 0: what the device reports free */
+} hu_permanova_opts;
+typedef struct {
+	int64_t n, a, perms;
+	double ss_total, ss_within, ss_among, F, R2;
+	int64_t count_le;
+	double p;
+} hu_permanova_result;
+void hu_permanova_default_opts(hu_permanova_opts* o);
+int hu_permanova(int device, int64_t n, const double* dist, const int32_t* group, const hu_permanova_opts* opts, hu_permanova_result* out,
+		double* ssw_perm /* [perms] or NULL */);
+int hu_permanova_labels(int64_t n, const int32_t* group, uint64_t seed, int64_t first, int64_t count, int32_t* out /* [count][n] */);
+int64_t hu_permanova_need(int64_t n, int64_t a, int64_t chunk);
+int hu_permanova_timing(double* seconds /* [4] */);
+typedef struct hu_dist_matrix hu_dist_matrix;
+int hu_dist_matrix_read(const char* path, hu_dist_matrix** out);
+void hu_dist_matrix_free(hu_dist_matrix* m);
+int hu_dist_matrix_dims(const hu_dist_matrix* m, int64_t* n);
+const char* hu_dist_matrix_sample(const hu_dist_matrix* m, int64_t i);
+const double* hu_dist_matrix_values(const hu_dist_matrix* m);     /* [n][n], row-major */
+
 /* ---- hmmufotu-amd-tree: a neighbour-joining tree from the MSA ----
  * Plain neighbour joining (Saitou and Nei 1987, in the form of Studier and Keppler 1988) on the pairwise distances of the alignment's
  * rows: not a maximum-likelihood search.  rows [n][cs_len]: the pruned alignment in the codes of hu_msa_encode_table (0..3 = A C G T, a
