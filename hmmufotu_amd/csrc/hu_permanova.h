@@ -42,6 +42,8 @@ inline int64_t hu_pm_pad(int64_t chunk) { return (chunk + HU_PM_WG - 1) / HU_PM_
 
 /* the arguments of hu_permanova, checked, and the plan */
 int hu_pm_plan(const char* fn, int64_t n, const double* dist, const int32_t* group, const hu_permanova_opts* opts, HuPmPlan& pl);
+/* the matrix alone: finite, non-negative, squares finite, zero diagonal, symmetric, not all zero; hu_pcoa refuses by the same code */
+int hu_pm_check_matrix(const char* fn, int64_t n, const double* dist);
 /* SS_T: no label in it, so both paths take it from here */
 double hu_pm_ss_total(int64_t n, const double* dist);
 /* the host path: SS_W of the labelling g [n] on D2 [n][n] (the squares; only j > i is read) */

@@ -25,6 +25,23 @@ extern "C" int64_t hu_permanova_need(int64_t n, int64_t a, int64_t chunk) {
 	return 8 * n * n + 2 * n * c + 8 * t * c + 8 * c + 8 * a + 2 * n + (1 << 20);
 }
 
+int hu_pm_check_matrix(const char* fn, int64_t n, const double* dist) {
+	bool any = false;
+	/* the cells with j >= i, in blocks of 64 x 64 so that the mirrored cell is in the cache; a mirrored cell is held to its twin alone */
+	for(int64_t ib = 0; ib < n; ib += HU_PM_TILE) for(int64_t jb = ib; jb < n; jb += HU_PM_TILE)
+	for(int64_t i = ib; i < std::min(n, ib + HU_PM_TILE); ++i) for(int64_t j = std::max(jb, i); j < std::min(n, jb + HU_PM_TILE); ++j) {
+		const double v = dist[i * n + j], w = dist[j * n + i];
+		if(!(v >= 0) || !std::isfinite(v)) { hu_set_error("%s: the distance of samples %lld and %lld is negative or not finite", fn, (long long) i, (long long) j); return HU_ERR_ARG; }
+		if(v > 0x1p511) { hu_set_error("%s: the distance of samples %lld and %lld is %g: its square is not finite", fn, (long long) i, (long long) j, v); return HU_ERR_ARG; }
+		if(i == j && v != 0) { hu_set_error("%s: sample %lld is at the distance %g from itself", fn, (long long) i, v); return HU_ERR_ARG; }
+		if(!(w == v)) { hu_set_error("%s: the matrix is not symmetric: d(%lld, %lld) = %.17g, d(%lld, %lld) = %.17g", fn,
+			(long long) i, (long long) j, v, (long long) j, (long long) i, w); return HU_ERR_ARG; }
+		any = any || v > 0;
+	}
+	if(!any) { hu_set_error("%s: every distance is 0: nothing to partition", fn); return HU_ERR_ARG; }
+	return HU_OK;
+}
+
 int hu_pm_plan(const char* fn, int64_t n, const double* dist, const int32_t* group, const hu_permanova_opts* opts, HuPmPlan& pl) {
 	hu_permanova_opts o;
 	if(opts) o = *opts; else hu_permanova_default_opts(&o);
@@ -47,19 +64,7 @@ int hu_pm_plan(const char* fn, int64_t n, const double* dist, const int32_t* gro
 	if(a < 2) { hu_set_error("%s: one group: a test needs 2 at the least", fn); return HU_ERR_ARG; }
 	if(a > n - 1) { hu_set_error("%s: %lld groups of %lld samples: every group is a single sample, nothing varies within", fn, (long long) a, (long long) n); return HU_ERR_ARG; }
 	if(a > HU_PM_MAX_GROUPS) { hu_set_error("%s: %lld groups: %d at the most", fn, (long long) a, HU_PM_MAX_GROUPS); return HU_ERR_ARG; }
-	bool any = false;
-	/* the cells with j >= i, in blocks of 64 x 64 so that the mirrored cell is in the cache; a mirrored cell is held to its twin alone */
-	for(int64_t ib = 0; ib < n; ib += HU_PM_TILE) for(int64_t jb = ib; jb < n; jb += HU_PM_TILE)
-	for(int64_t i = ib; i < std::min(n, ib + HU_PM_TILE); ++i) for(int64_t j = std::max(jb, i); j < std::min(n, jb + HU_PM_TILE); ++j) {
-		const double v = dist[i * n + j], w = dist[j * n + i];
-		if(!(v >= 0) || !std::isfinite(v)) { hu_set_error("%s: the distance of samples %lld and %lld is negative or not finite", fn, (long long) i, (long long) j); return HU_ERR_ARG; }
-		if(v > 0x1p511) { hu_set_error("%s: the distance of samples %lld and %lld is %g: its square is not finite", fn, (long long) i, (long long) j, v); return HU_ERR_ARG; }
-		if(i == j && v != 0) { hu_set_error("%s: sample %lld is at the distance %g from itself", fn, (long long) i, v); return HU_ERR_ARG; }
-		if(!(w == v)) { hu_set_error("%s: the matrix is not symmetric: d(%lld, %lld) = %.17g, d(%lld, %lld) = %.17g", fn,
-			(long long) i, (long long) j, v, (long long) j, (long long) i, w); return HU_ERR_ARG; }
-		any = any || v > 0;
-	}
-	if(!any) { hu_set_error("%s: every distance is 0: nothing to partition", fn); return HU_ERR_ARG; }
+	{ const int rc = hu_pm_check_matrix(fn, n, dist); if(rc != HU_OK) return rc; }
 	pl.n = n; pl.a = a; pl.perms = o.perms; pl.chunk = o.chunk; pl.budget = o.mem_budget > 0 ? o.mem_budget : 0; pl.seed = o.seed; pl.host = o.host != 0;
 	pl.inv.resize((size_t) a); pl.lab.resize((size_t) n);
 	for(int64_t g = 0; g < a; ++g) pl.inv[(size_t) g] = 1.0 / (double) size[(size_t) g];

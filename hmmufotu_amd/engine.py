@@ -948,6 +948,57 @@ def dist_matrix_read(path) -> dict:
         lib.hu_dist_matrix_free(h)
 
 
+class PcoaOpts(C.Structure):
+    _fields_ = [("k", C.c_int64), ("oversample", C.c_int64), ("tol", C.c_double), ("max_it", C.c_int64), ("seed", C.c_uint64), ("host", C.c_int32), ("reserved", C.c_int32),
+                ("mem_budget", C.c_int64)]
+
+
+class PcoaResult(C.Structure):
+    _fields_ = [("n", C.c_int64), ("k", C.c_int64), ("m_final", C.c_int64), ("iterations", C.c_int64), ("trace", C.c_double), ("positive_in_block", C.c_int64)]
+
+
+def pcoa(dist, k=3, oversample=8, tol=1e-10, max_it=1000, seed=1, device=0, host=False, mem_budget=0) -> dict:
+    """hu_pcoa: the k leading principal coordinates of the distance matrix dist [n][n]: dict(n, k, m_final, iterations, trace,
+    positive_in_block, coords [n][k], eigval [k], resid [k], prop [k] = eigval / trace).  host: the library's host path, no device needed;
+    the two paths agree within their residuals, not in their bits."""
+    d = np.ascontiguousarray(dist, np.float64)
+    if d.ndim != 2 or d.shape[0] != d.shape[1]:
+        raise EngineError("pcoa: dist [n][n]")
+    lib = load_library()
+    o = PcoaOpts()
+    lib.hu_pcoa_default_opts(C.byref(o))
+    o.k = int(k); o.oversample = int(oversample); o.tol = float(tol); o.max_it = int(max_it); o.seed = int(seed) & (2 ** 64 - 1); o.host = 1 if host else 0
+    o.mem_budget = int(mem_budget or 0)
+    r = PcoaResult()
+    kk = max(int(k), 1)
+    coords = np.zeros((d.shape[0], kk)); eig = np.zeros(kk); res = np.zeros(kk)
+    _chk(lib.hu_pcoa(C.c_int(int(device)), C.c_int64(d.shape[0]), _p(d, C.c_double), C.byref(o), C.byref(r), _p(coords, C.c_double), _p(eig, C.c_double), _p(res, C.c_double)))
+    out = {f: getattr(r, f) for f, _ in PcoaResult._fields_}
+    out.update(coords=coords, eigval=eig, resid=res, prop=eig / r.trace)
+    return out
+
+
+def pcoa_need(n: int, k: int, oversample: int) -> int:
+    """hu_pcoa_need: the bytes of device memory that n samples take with a block of min(k + oversample, n - 1) columns"""
+    lib = load_library()
+    lib.hu_pcoa_need.restype = C.c_int64
+    return int(lib.hu_pcoa_need(C.c_int64(int(n)), C.c_int64(int(k)), C.c_int64(int(oversample))))
+
+
+def pcoa_slabs(n: int) -> int:
+    """hu_pcoa_slabs: the K slabs of the product kernel for n samples"""
+    lib = load_library()
+    lib.hu_pcoa_slabs.restype = C.c_int64
+    return int(lib.hu_pcoa_slabs(C.c_int64(int(n))))
+
+
+def pcoa_timing() -> dict:
+    """hu_pcoa_timing: the phases of this thread's last pcoa, in seconds"""
+    s = np.zeros(6)
+    _chk(load_library().hu_pcoa_timing(_p(s, C.c_double)))
+    return dict(to_device=s[0], square=s[1], product=s[2], small=s[3], host_mxm=s[4], to_host=s[5])
+
+
 class NjOpts(C.Structure):
     _fields_ = [("host", C.c_int32), ("reserved", C.c_int32), ("mem_budget", C.c_int64)]
 

@@ -28,7 +28,8 @@ typedef enum {
 	HU_ERR_DEVICE = -2,   /* no gfx950 device / HIP failure: the engine has NO CPU fallback      */
 	HU_ERR_IO = -3,       /* unreadable or malformed database file                                */
 	HU_ERR_NOMEM = -4,
-	HU_ERR_STATE = -5     /* stage called out of order                                            */
+	HU_ERR_STATE = -5,    /* stage called out of order                                            */
+	HU_ERR_NUMERIC = -6   /* an iteration that did not converge, or an answer the input does not have */
 } hu_status;
 
 /* align_mode of src/BandedHMMP7.h:168-173 */
@@ -1482,6 +1483,59 @@ int hu_tree_add_apply(int32_t n_nodes, int32_t* parent, double* blen, int32_t* c
 int hu_tree_add_search(hu_add_opts* opts, int32_t n_nodes, int32_t cs_len, int32_t n_query, int32_t* parent, double* blen, int8_t* seq,
 		int32_t* child_off, int32_t* child_idx, const int8_t* qseq, int32_t* query_node, const hu_model_desc* model);
 int hu_add_timing(double* seconds /* [4] */);
+
+/* ---- hmmufotu-amd-pcoa: the principal coordinates of a distance matrix (PCoA, classical scaling, Gower 1966) ----
+ * dist [n][n] row-major with the properties hu_permanova requires (symmetric, finite, non-negative, zero on the diagonal, not all zero;
+ * the same code checks them).  With D2_ij = d_ij * d_ij (one rounded product) and J = I - 11'/n:
+ *     B      = -1/2 J D2 J                  (Gower's centred matrix; never stored)
+ *     B u_a  = lambda_a u_a,  |u_a| = 1,  lambda_1 >= lambda_2 >= ...  (algebraic order)
+ *     x_ia   = u_ia * sqrt(lambda_a)        the coordinates, for the k largest lambda_a, all of which must be > 0
+ *     prop_a = lambda_a / trace(B),  trace(B) = (1/n) sum_{i<j} D2_ij = SS_T of hu_permanova, by the same code and so the same bits.
+ * UniFrac and Bray-Curtis matrices are not Euclidean: B then has negative eigenvalues, the positive ones add up to more than the trace,
+ * and prop_a is a share of the trace, not of that sum (which nobody knows without all n eigenvalues).
+ * Sign: u_a is flipped so that its entry of largest magnitude (the lowest index on a tie) is positive.
+ * resid [k]: res_a = | B u_a - lambda_a u_a |_2, from one more product with the final vectors after the last iteration; by Weyl's theorem
+ * an eigenvalue of B lies within res_a of lambda_a, so a result certifies itself.
+ * The method is a block subspace iteration with Rayleigh-Ritz on m = min(k + oversample, n - 1) columns (64 at the most), started from
+ * Philox4x32-10 (hu_sim_philox): entry (row, col) of the start block is hu_sim_u01(w[1], w[0]) - 1/2 of the counter (row & 0xffffffff,
+ * row >> 32, col & 0xffffffff, col >> 32) under the key (seed & 0xffffffff, seed >> 32).  A result is a function of (dist, k, oversample,
+ * seed, tol, max_it) and of the path (device or host) alone; the two paths agree within their residuals, not in their bits.  It stops when
+ * res_a <= tol * lambda_1 for the k axes kept.  A block with fewer than k positive Ritz values after 3 iterations doubles oversample
+ * (0 becomes 8) and starts again; the iterations count on.
+ * coords [n][k], eigval [k], resid [k].  opts->host, or device < 0: the host path, one thread, no device needed.
+ * HU_ERR_ARG with the reason, before a device is asked for: the matrix refusals of hu_permanova, n < 3, k < 1 or k > n - 1,
+ * oversample < 0, min(k + oversample, n - 1) > 64, tol outside (0, 1e-3], max_it < 1.  HU_ERR_NOMEM with the bytes needed and the bytes
+ * free when hu_pcoa_need exceeds mem_budget (checked before a device is asked for) or what the device reports free.  HU_ERR_NUMERIC: no
+ * convergence within max_it iterations (the worst axis and its residual are named), or fewer than k positive axes ("only P positive
+ * axes; k asked": exact, at m = n - 1; or at the block's ceiling of 64 columns, once its Ritz values have settled, "P positive axes found
+ * in a settled block of 64 columns, the widest; k asked").
+ * hu_pcoa_need: the bytes on the device, with m = min(k + oversample, n - 1), mp = m rounded up to 16, S = hu_pcoa_slabs(n) and
+ * c = ceil(n / 256): 8 n^2 for the squares, 8 (S + 4) n mp for the partial products and four blocks, 8 (c + 3) mp^2 + 8 c mp for the
+ * partial Gram matrices, the small matrices and the column sums, and 1 MB of slack; -1 on a bad argument.
+ * hu_pcoa_slabs: the K slabs of the product kernel, min(8, ceil(n / 128)): a function of n alone; -1 for n < 1.
+ * hu_pcoa_timing: of this thread's last call, seconds [6] = copies up, the squares, the product kernel, the small kernels, the host's
+ * m x m work, the copy back. */
+typedef struct {
+	int64_t k;            /* 3: the axes wanted */
+	int64_t oversample;   /* 8: columns of the block beyond k */
+	double tol;           /* 1e-10 */
+	int64_t max_it;       /* 1000 */
+	uint64_t seed;        /* 1 */
+	int32_t host;         /* 0; 1: the host path, no device needed */
+	int32_t reserved;
+	int64_t mem_budget;   /* 0: what the device reports free */
+} hu_pcoa_opts;
+typedef struct {
+	int64_t n, k, m_final, iterations;
+	double trace;
+	int64_t positive_in_block;
+} hu_pcoa_result;
+void hu_pcoa_default_opts(hu_pcoa_opts* o);
+int hu_pcoa(int device, int64_t n, const double* dist, const hu_pcoa_opts* opts, hu_pcoa_result* out, double* coords /* [n][k] */,
+		double* eigval /* [k] */, double* resid /* [k] */);
+int64_t hu_pcoa_need(int64_t n, int64_t k, int64_t oversample);
+int64_t hu_pcoa_slabs(int64_t n);
+int hu_pcoa_timing(double* seconds /* [6] */);
 
 #ifdef __cplusplus
 }
