@@ -16,6 +16,8 @@
 /* HU_MAX_SEEDS (64: capacity of the per-read seed lists) is part of the ABI: include/hmmufotu_amd.h */
 #define HU_READ_TILE 16          /* reads per workgroup tile in the seed p-distance scan        */
 #define HU_MAX_INS 24            /* bases of one read outside the profile columns handled as a list */
+#define HU_TILEQ_MASK_SHIFT 16   /* an entry of a scan tile's quad list: quad (< 512) | mask of its four 32-site words << this  */
+#define HU_TILEW_QUAD (4 * HU_READ_TILE * 3)   /* dwords of a quad in a scan tile's word-major planes: four words x sixteen reads x three planes */
 #define HU_NODE_PAD 256          /* node count is padded to a multiple of this                  */
 #define HU_MIN_LOGLIK_EXP (-510.0) /* DBL_MIN_EXP / 2 in integer arithmetic, PhyloTreeUnrooted.cpp:68 */
 #define HU_BRANCH_EPS 1e-5

@@ -1759,7 +1759,7 @@ struct hu_batch {
 	DBuf<uint16_t> dPerm;
 	DBuf<uint32_t> dRp, dPairs, dSeedDN, dParDN, dBmin, dRSpan, dTileSpan;     /* dRSpan / dTileSpan: uint2 per read / tile */
 	DBuf<int32_t> dTileQ, dSlotRead, dReadSlot;
-	DBuf<uint32_t> dRq;
+	DBuf<uint32_t> dRq, dTileW;      /* dTileW: the planes of a tile's listed words, word-major (k_tile_lists) */
 	DBuf<unsigned long long> dRefScratch;      /* k_seed_refsort: two key arrays + the level tables per resident workgroup */
 	DBuf<int32_t> dHv, dZeroPar; DBuf<unsigned long long> dPairsC; int refHvCount = 0; double refHvHeight = NAN;      /* the reference-order mode under a height filter: the nodes that pass, the compacted pair rows */
 	DBuf<int32_t> dBail, dNanCnt, dNanId; DBuf<uint32_t> dNanDN;      /* dNan*: the (dist, node id) selection of a batch whose reads met NaN distances in the reference-order mode */
@@ -1996,6 +1996,7 @@ static int ensure_read_buffers(hu_batch* b) {
 	if((rc = b->dEnd.ensure(n)) != HU_OK) return rc;
 	if((rc = b->dRp.ensure(tiles * d.WQ * HU_READ_TILE * 16)) != HU_OK) return rc;
 	if((rc = b->dTileQ.ensure(tiles * (d.WQ + 1))) != HU_OK) return rc;
+	if((rc = b->dTileW.ensure(std::max<size_t>(tiles, 1) * d.WQ * HU_TILEW_QUAD)) != HU_OK) return rc;
 	if((rc = b->dSlotRead.ensure(std::max<size_t>(tiles, 1) * HU_READ_TILE)) != HU_OK) return rc;
 	if((rc = b->dReadSlot.ensure(std::max<size_t>(n, 1))) != HU_OK) return rc;
 	if((rc = b->dRq.ensure(std::max<size_t>(n, 1) * ((d.WQ + 31) / 32))) != HU_OK) return rc;
@@ -2079,7 +2080,7 @@ static int set_aligned_impl(hu_batch* b, int n, const int8_t* codes, hipMemcpyKi
 		HIPCHK(hipMemsetAsync(b->dRp.p, 0, (size_t) tiles * d.WQ * HU_READ_TILE * 16 * 4, b->stream));
 		if((rc = tile_reads(b, nullptr)) != HU_OK) return rc;
 		k_planes_from_codes<<<n, 64, 0, b->stream>>>(d, b->dCodes.p, b->dStart.p, b->dEnd.p, b->dRp.p, b->dRq.p, b->dIns.p, b->dReadSlot.p, (uint2*) b->dRSpan.p);
-		k_tile_lists<<<tiles, 64, 0, b->stream>>>(d, n, b->dRq.p, b->dIns.p, b->dTileQ.p, b->dTileIns.p, b->dSlotRead.p, (const uint2*) b->dRSpan.p, (uint2*) b->dTileSpan.p);
+		k_tile_lists<<<tiles, 64, 0, b->stream>>>(d, n, b->dRp.p, b->dRq.p, b->dIns.p, b->dTileQ.p, b->dTileW.p, b->dTileIns.p, b->dSlotRead.p, (const uint2*) b->dRSpan.p, (uint2*) b->dTileSpan.p);
 		HIPCHK(hipGetLastError());
 	}
 	b->state = ST_ALIGNED;
@@ -2255,7 +2256,7 @@ extern "C" int hu_align_batch(hu_batch* b, const hu_opts* o) try {
 			HIPCHK(hipMemsetAsync(b->dRp.p, 0, (size_t) tiles * d.WQ * HU_READ_TILE * 16 * 4, b->stream));
 			if((rc = tile_reads(b, b->dAlns.p)) != HU_OK) return rc;
 			k_encode_rows<<<b->n, 64, 0, b->stream>>>(d, b->dRows.p, b->dAlns.p, b->dCodes.p, b->dStart.p, b->dEnd.p, b->dRp.p, b->dRq.p, b->dIns.p, b->dReadSlot.p, (uint2*) b->dRSpan.p);
-			k_tile_lists<<<tiles, 64, 0, b->stream>>>(d, b->n, b->dRq.p, b->dIns.p, b->dTileQ.p, b->dTileIns.p, b->dSlotRead.p, (const uint2*) b->dRSpan.p, (uint2*) b->dTileSpan.p);
+			k_tile_lists<<<tiles, 64, 0, b->stream>>>(d, b->n, b->dRp.p, b->dRq.p, b->dIns.p, b->dTileQ.p, b->dTileW.p, b->dTileIns.p, b->dSlotRead.p, (const uint2*) b->dRSpan.p, (uint2*) b->dTileSpan.p);
 		}
 		HIPCHK(hipGetLastError());
 		b->hAlns.resize(b->nSeq);
@@ -2689,10 +2690,10 @@ extern "C" int hu_seed_batch(hu_batch* b, const hu_opts* o) try {
 			const dim3 grid4(tiles, (d.nNodesPad + 1023) / 1024);
 			if(dOnly && narrow) k_seed_dscan4<uint8_t><<<grid4, 256, (size_t)(b->knob.scan_lds_pad > 0 && b->knob.scan_lds_pad <= 44 ? b->knob.scan_lds_pad : 0) * 1024, b->stream>>>(d, b->dRp.p, b->dTileQ.p, (uint8_t*) b->dPairs.p, b->dSlotRead.p, bmin, (const uint2*) b->dTileSpan.p);
 			else if(dOnly) k_seed_dscan4<uint16_t><<<grid4, 256, 0, b->stream>>>(d, b->dRp.p, b->dTileQ.p, (uint16_t*) b->dPairs.p, b->dSlotRead.p, bmin, (const uint2*) b->dTileSpan.p);
-			else if(b->refFused && b->pair16) k_seed_pdist2<uint16_t, true><<<grid, 256, 0, b->stream>>>(d, b->dRp.p, b->dTileQ.p, b->dTileIns.p, (uint16_t*) b->dPairs.p, b->dSlotRead.p, b->dRefPiv.p, b->dRefL0.p);
-			else if(b->refFused) k_seed_pdist2<uint32_t, true><<<grid, 256, 0, b->stream>>>(d, b->dRp.p, b->dTileQ.p, b->dTileIns.p, b->dPairs.p, b->dSlotRead.p, b->dRefPiv.p, b->dRefL0.p);
-			else if(b->pair16) k_seed_pdist2<uint16_t><<<grid, 256, 0, b->stream>>>(d, b->dRp.p, b->dTileQ.p, b->dTileIns.p, (uint16_t*) b->dPairs.p, b->dSlotRead.p);
-			else k_seed_pdist2<uint32_t><<<grid, 256, 0, b->stream>>>(d, b->dRp.p, b->dTileQ.p, b->dTileIns.p, b->dPairs.p, b->dSlotRead.p);
+			else if(b->refFused && b->pair16) k_seed_pdist2<uint16_t, true><<<grid, 256, 0, b->stream>>>(d, b->dTileW.p, b->dTileQ.p, b->dTileIns.p, (uint16_t*) b->dPairs.p, b->dSlotRead.p, b->dRefPiv.p, b->dRefL0.p);
+			else if(b->refFused) k_seed_pdist2<uint32_t, true><<<grid, 256, 0, b->stream>>>(d, b->dTileW.p, b->dTileQ.p, b->dTileIns.p, b->dPairs.p, b->dSlotRead.p, b->dRefPiv.p, b->dRefL0.p);
+			else if(b->pair16) k_seed_pdist2<uint16_t><<<grid, 256, 0, b->stream>>>(d, b->dTileW.p, b->dTileQ.p, b->dTileIns.p, (uint16_t*) b->dPairs.p, b->dSlotRead.p);
+			else k_seed_pdist2<uint32_t><<<grid, 256, 0, b->stream>>>(d, b->dTileW.p, b->dTileQ.p, b->dTileIns.p, b->dPairs.p, b->dSlotRead.p);
 		}
 		{
 			Timer t(b, HU_T_SEED_TOPK);

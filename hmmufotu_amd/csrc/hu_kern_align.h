@@ -1258,19 +1258,39 @@ __global__ void k_tile_slots(int n, int nSlots, const uint32_t* __restrict__ sor
 	else slotRead[s] = -1;
 }
 
-/* per scan tile: the quads in which any of its reads has a base -> tileQ[tile][0] = count, [1..] = quads; and the
+/* per scan tile: the quads in which any of its reads has a base -> tileQ[tile][0] = count, [1..] = quad | word mask << HU_TILEQ_MASK_SHIFT
+ * (bit w of the mask: some read of the tile has a base in the quad's 32-site word w; in a word without one every read's validity word
+ * is zero and the word adds nothing to d or N, so the pair scan runs the words of the mask only); the planes of those words once
+ * more, word by word in list order, tileW[tile][j][read t][plane] — what the pair scan needs of one word is then 48 consecutive
+ * dwords; and the
  * reads' insert lists as one list, tileIns[tile][0] = count, [1..] = read t << 24 | (scan position << 2 | base) */
-__global__ __launch_bounds__(64) void k_tile_lists(HuDbDev db, int n, const uint32_t* __restrict__ rq, const int32_t* __restrict__ ins,
-		int32_t* __restrict__ tileQ, int32_t* __restrict__ tileIns, const int32_t* __restrict__ slotRead, const uint2* __restrict__ rspan, uint2* __restrict__ tileSpan) {
+__global__ __launch_bounds__(64) void k_tile_lists(HuDbDev db, int n, const uint32_t* __restrict__ rp, const uint32_t* __restrict__ rq, const int32_t* __restrict__ ins,
+		int32_t* __restrict__ tileQ, uint32_t* __restrict__ tileW, int32_t* __restrict__ tileIns, const int32_t* __restrict__ slotRead, const uint2* __restrict__ rspan,
+		uint2* __restrict__ tileSpan) {
+	static_assert(HU_READ_TILE == 16, "sixteen reads x four validity words of a quad = one dword per lane");
 	const int tile = blockIdx.x, lane = threadIdx.x;
 	const int nw32 = (db.WQ + 31) / 32;
 	int32_t* out = tileQ + (size_t) tile * (db.WQ + 1);
+	uint32_t* wout = tileW + (size_t) tile * db.WQ * HU_TILEW_QUAD;
 	int cnt = 0;
-	for(int w = 0; w < nw32; ++w) { /* WQ <= 512: at most 16 words; lane 0 writes the compacted list */
+	for(int w = 0; w < nw32; ++w) { /* WQ <= 512: at most 16 words; the union is the same in every lane, lane 0 writes the compacted list */
 		uint32_t m = 0;
 		if(lane < HU_READ_TILE) { const int r = slotRead[tile * HU_READ_TILE + lane]; if(r >= 0) m = rq[(size_t) r * nw32 + w]; }
 		for(int s = 32; s > 0; s >>= 1) m |= __shfl_xor(m, s);
-		if(lane == 0) while(m) { const int b = __ffs(m) - 1; m &= m - 1; out[1 + cnt++] = w * 32 + b; }
+		while(m) {
+			const int q = w * 32 + __ffs(m) - 1; m &= m - 1;
+			const uint32_t* __restrict__ rt = rp + ((size_t) tile * db.WQ + q) * (HU_READ_TILE * 16);
+			unsigned long long b = __ballot(rt[(lane >> 2) * 16 + 8 + (lane & 3)] != 0u);      /* lane = slot t * 4 + word: the validity words; a slot without a read holds zeros */
+			b |= b >> 32; b |= b >> 16; b |= b >> 8; b |= b >> 4;
+			uint32_t mk = (uint32_t) b & 15u;
+			if(lane == 0) out[1 + cnt] = q | (int) mk << HU_TILEQ_MASK_SHIFT;
+			++cnt;
+			while(mk) {
+				const int wd = __ffs(mk) - 1; mk &= mk - 1;
+				if(lane < HU_READ_TILE * 3) wout[lane] = rt[(lane / 3) * 16 + (lane % 3) * 4 + wd];
+				wout += HU_READ_TILE * 3;
+			}
+		}
 	}
 	if(lane == 0) {
 		out[0] = cnt;

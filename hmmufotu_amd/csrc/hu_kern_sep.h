@@ -19,7 +19,14 @@
  *     planes[(q*3 + p) * nNodesPad + node]          q = site / 128
  * so that one wave reads 64 consecutive nodes x 16 B = 1 KiB per plane per quad, coalesced.
  * A lane owns one node and HU_READ_TILE reads; the reads' planes are wave-uniform and come in
- * through the scalar cache:   rp[((tile*WQ + q) * T + t) * 16 + p*4 + w].
+ * through the scalar cache.  They exist twice (k_tile_lists): quad by quad for every read,
+ *     rp[((tile*WQ + q) * T + t) * 16 + p*4 + w]        (k_seed_dscan4, pair_exact, read_bases)
+ * and, for the pair scan, word by word for the words of the tile's listed quads in which a read of the tile has a base,
+ *     tileW[(tile * WQ * 4 + j) * T * 3 + t * 3 + p]    j = place of the word in the tile's list order
+ * The tile's quad list carries a 4-bit word mask per quad (tileQ entry = quad | mask << HU_TILEQ_MASK_SHIFT).  k_seed_pdist2 loads a
+ * listed quad of its node once and runs only the words of the mask, each behind a scalar branch: in a word without a base every
+ * read's validity word is zero and its six instructions per read add nothing to d or N.  A 250-base read sits in 8-9 consecutive
+ * words, which touch three quads = 12 words: 8.0 of 12 words run on the headline workload (profiles/r07_scan_words.md).
  * Per (node, read, 32 sites): 2 xor + or + 2 and + 2 popcount-accumulate.
  * Grid: x = read tile (fastest: consecutive workgroups re-use one node block from L2),
  *       y = node block of 256. */
@@ -109,8 +116,25 @@ __device__ inline uint32_t dpp_min_full(uint32_t v) {
  * one bit per node: bit (node & 63) of l0m[(read * np / 64 + node / 64) * 2 + {0: !(e < pivot), 1: !(pivot < e)}].  The sort kernel then starts
  * from 16 bytes per 64 nodes instead of a counting pass over the 128 (256) bytes of their pairs: that pass was a quarter of its time.
  * A compared-site count of zero (dist = 0 / 0, std::sort undefined) is flagged in piv[read * 4 + 3]. */
+/* One 32-site word of a listed quad against the tile's sixteen reads: `r` = the word's 48 consecutive dwords of the tile's word-major
+ * planes (k_tile_lists: [read][b0, b1, v]).  The compiler requests them in four groups of about four reads and waits once per group,
+ * the rate of the quad-major form (one wait per read and quad); d[] and N[] stay in their registers (v_bcnt_u32_b32 accumulates in
+ * place), 63 VGPRs under the bound of eight waves per SIMD (without the bound the requests of a word go out at once and the kernel
+ * takes 85 VGPRs, five waves).
+ * Measured and not kept: the quad-major planes with one body per mask value (fifteen instances of the read loop with the skipped
+ * words compiled out, one scalar jump per quad): the counters of the fifteen bodies meet in 32 more registers (87 VGPRs, five waves
+ * per SIMD) and the narrower requests of a partial mask are two to six per read: 4.60 ms against the parent's 3.90 and the 3.35 of
+ * this form (profiles/r07_scan_words.md). */
+__device__ __forceinline__ void hu_scan_word(uint32_t n0, uint32_t n1, uint32_t nv, const uint32_t* __restrict__ r, uint32_t (&d)[HU_READ_TILE], uint32_t (&N)[HU_READ_TILE]) {
+#pragma unroll
+	for(int t = 0; t < HU_READ_TILE; ++t) {
+		const uint32_t k = nv & r[t * 3 + 2], x = ((n0 ^ r[t * 3]) | (n1 ^ r[t * 3 + 1])) & k;
+		d[t] += __popc(x); N[t] += __popc(k);
+	}
+}
+
 template<class PT, bool L0 = false>
-__global__ __launch_bounds__(256) void k_seed_pdist2(HuDbDev db, const uint32_t* __restrict__ rp,
+__global__ __launch_bounds__(256, 8) void k_seed_pdist2(HuDbDev db, const uint32_t* __restrict__ tileW,
 		const int32_t* __restrict__ tileQ, const int32_t* __restrict__ tileIns, PT* __restrict__ pairs, const int32_t* __restrict__ slotRead,
 		uint32_t* __restrict__ piv = nullptr, unsigned long long* __restrict__ l0m = nullptr) {
 	constexpr int T = HU_READ_TILE;
@@ -128,19 +152,15 @@ __global__ __launch_bounds__(256) void k_seed_pdist2(HuDbDev db, const uint32_t*
 		for(int t = 0; t < T; ++t) acc[t][tid] = 0;
 	}
 	const size_t np = (size_t) db.nNodesPad;
+	const uint32_t* __restrict__ wr = (const uint32_t*) __builtin_assume_aligned(tileW + (size_t) tile * db.WQ * HU_TILEW_QUAD, 64);      /* a word's 48 dwords: 192 bytes */
 	for(int qi = 0; qi < nq; ++qi) {
-		const int q = ql[1 + qi];
+		const int ent = ql[1 + qi], q = ent & ((1 << HU_TILEQ_MASK_SHIFT) - 1);
 		const uint4 n0 = db.planes[((size_t) q * 3 + 0) * np + node], n1 = db.planes[((size_t) q * 3 + 1) * np + node], nv = db.planes[((size_t) q * 3 + 2) * np + node];
-		const uint32_t* __restrict__ r = rp + (((size_t) tile * db.WQ + q) * T) * 16;
-#pragma unroll
-		for(int t = 0; t < T; ++t) {
-			const uint32_t* rt = r + t * 16;
-			uint32_t k, x;
-			k = nv.x & rt[8];  x = ((n0.x ^ rt[0]) | (n1.x ^ rt[4])) & k; d[t] += __popc(x); N[t] += __popc(k);
-			k = nv.y & rt[9];  x = ((n0.y ^ rt[1]) | (n1.y ^ rt[5])) & k; d[t] += __popc(x); N[t] += __popc(k);
-			k = nv.z & rt[10]; x = ((n0.z ^ rt[2]) | (n1.z ^ rt[6])) & k; d[t] += __popc(x); N[t] += __popc(k);
-			k = nv.w & rt[11]; x = ((n0.w ^ rt[3]) | (n1.w ^ rt[7])) & k; d[t] += __popc(x); N[t] += __popc(k);
-		}
+		/* the words of the tile's mask only: the mask is the same in every lane (a scalar load), so each test is a scalar branch */
+		if(ent & (1 << HU_TILEQ_MASK_SHIFT)) { hu_scan_word(n0.x, n1.x, nv.x, wr, d, N); wr += T * 3; }
+		if(ent & (2 << HU_TILEQ_MASK_SHIFT)) { hu_scan_word(n0.y, n1.y, nv.y, wr, d, N); wr += T * 3; }
+		if(ent & (4 << HU_TILEQ_MASK_SHIFT)) { hu_scan_word(n0.z, n1.z, nv.z, wr, d, N); wr += T * 3; }
+		if(ent & (8 << HU_TILEQ_MASK_SHIFT)) { hu_scan_word(n0.w, n1.w, nv.w, wr, d, N); wr += T * 3; }
 	}
 	{ /* inserts: three wave-uniform 8-byte words per position (bit = node within the wave's 64) */
 		const size_t npw = np / 64;
@@ -223,7 +243,7 @@ __global__ __launch_bounds__(256, 3) void k_seed_dscan4(HuDbDev db, const uint32
 		for(int m = 0; m < M; ++m) d[t][m] = 0;
 	const size_t np = (size_t) db.nNodesPad;
 	for(int qi = 0; qi < nq; ++qi) {
-		const int q = ql[1 + qi];
+		const int q = ql[1 + qi] & ((1 << HU_TILEQ_MASK_SHIFT) - 1);
 		const uint32_t mine = rp[((size_t) tile * db.WQ + q) * (T * 16) + tid];
 		uint4 n0[M], n1[M], nv[M];
 #pragma unroll
