@@ -7,7 +7,8 @@
 //                      [--nni [--nni-rounds N] [--nni-min-gain DBL] [--nni-log FILE]]
 //                      [--spr [--spr-radius N] [--spr-rounds N] [--spr-min-gain DBL] [--spr-log FILE]]
 //                      [--support N [--support-seed N] [--support-out FILE]]
-//                      [--start-tree FILE --add [--add-log FILE]]]
+//                      [--start-tree FILE --add [--add-log FILE]]
+//                      [--gamma K [--gamma-alpha DBL] [--gamma-rounds N] [--gamma-eps DBL] [--gamma-log FILE]]]
 // The MSA is read and pruned as hmmufotu-amd-build does (hu_build_inputs.h; the columns without a residue are found on the host here,
 // the same columns hu_prune_msa finds), so the tree joins by name to the same MSA there.  The distances and the joins are
 // hu_msa_tree's: on the device (hu_kern_dist.h, hu_kern_nj.h), or with --host by the library's host path.  Every refusal comes before
@@ -23,6 +24,8 @@
 // (hu_tree_add_search), and everything else runs on the grown tree.
 // --support labels the inner edges of the final tree with their local bootstrap support (hu_tree_nni_support): the share
 // of N resamplings of the columns in which the edge as it stands beats both of its nearest-neighbour interchanges.
+// --gamma K is the last stage: on the tree everything above left, the lengths and the shape alpha are fitted under the
+// discrete Gamma of K rates with mean 1 (hu_tree_gamma_fit).  Only the lengths change; the supports, computed before it, keep their place.
 #include <cmath>
 #include <cstdlib>
 #include <memory>
@@ -68,6 +71,11 @@ static void usage(const char* p) {
 		"            --support  INT     : with --ml-lengths: label every inner edge between two nodes of degree three with its local bootstrap support over INT replicates, 1 to 100000: the share of resampled alignments in which the edge beats both of its nearest-neighbour interchanges\n"
 		"            --support-seed  INT: seed of the replicates [1]\n"
 		"            --support-out  FILE: write the supports as TSV: node, name, kind, leaves, t0, alrt, count, replicates, support; then '# skipped: N edges at polytomies' and '# seed: S'\n"
+		"            --gamma  INT       : with --ml-lengths, as the last stage: fit the branch lengths and the shape alpha under the discrete Gamma of INT rate categories with mean rate 1, 2 to 16; everything before it, the supports included, runs under the fixed-rate model\n"
+		"            --gamma-alpha  DBL : keep the shape at this value, 0.05 to 100 [estimated by maximum likelihood]\n"
+		"            --gamma-rounds  INT: passes of 'shape, then lengths' at the most, at least 1 [10]\n"
+		"            --gamma-eps  DBL   : stop when a pass gains less than this in log-likelihood, above 0 [0.01]\n"
+		"            --gamma-log  FILE  : write the passes as TSV: pass, alpha, ll, rounds; then '# rates: R1 ... RK' and '# stop: REASON'\n"
 		"            -v  FLAG           : enable verbose information, you may set multiple -v for more details\n"
 		"            --version          : show program version and exit\n"
 		"            -h|--help          : print this message and exit\n";
@@ -81,6 +89,7 @@ int main(int argc, char** argv) {
 	bool spr = false, haveSprOpt = false; std::string sprLogFn; int sprRadius = 5, sprRounds = 10; double sprMinGain = 1e-3;
 	bool add = false; std::string addLogFn;
 	bool support = false, haveSupportOpt = false; long long supportN = 0; unsigned long long supportSeed = 1; std::string supportFn;
+	bool gamma = false, haveGammaOpt = false, haveGammaAlpha = false; int gammaK = 0, gammaRounds = 10; double gammaAlpha = 0, gammaEps = 0.01; std::string gammaLogFn;
 	if(argc < 2) { usage(argv[0]); return EXIT_SUCCESS; }
 	for(int i = 1; i < argc; ++i) {
 		std::string a = argv[i];
@@ -105,6 +114,10 @@ int main(int argc, char** argv) {
 		else if(a == "--support") { supportN = atoll(val()); support = true; }
 		else if(a == "--support-seed") { supportSeed = strtoull(val(), nullptr, 10); haveSupportOpt = true; }
 		else if(a == "--support-out") { supportFn = val(); haveSupportOpt = true; }
+		else if(a == "--gamma") { gammaK = atoi(val()); gamma = true; }
+		else if(a == "--gamma-alpha") { gammaAlpha = atof(val()); haveGammaOpt = haveGammaAlpha = true; }
+		else if(a == "--gamma-rounds") { gammaRounds = atoi(val()); haveGammaOpt = true; } else if(a == "--gamma-eps") { gammaEps = atof(val()); haveGammaOpt = true; }
+		else if(a == "--gamma-log") { gammaLogFn = val(); haveGammaOpt = true; }
 		else if(a.size() > 1 && a[0] == '-' && a.find_first_not_of('v', 1) == std::string::npos) verbose += (int) a.size() - 1;
 		else if(a[0] == '-' && a.size() > 1) { std::cerr << "Error: unknown option " << a << std::endl; return EXIT_FAILURE; }
 		else pos.push_back(a);
@@ -134,6 +147,14 @@ int main(int argc, char** argv) {
 	if(support && !mlLengths) { std::cerr << "--support goes with --ml-lengths" << std::endl; return EXIT_FAILURE; }
 	if(haveSupportOpt && !support) { std::cerr << "--support-seed and --support-out go with --support" << std::endl; return EXIT_FAILURE; }
 	if(support && (supportN < 1 || supportN > HU_SUPPORT_MAX_REPLICATES)) { std::cerr << "--support must be 1 to " << HU_SUPPORT_MAX_REPLICATES << " replicates" << std::endl; return EXIT_FAILURE; }
+	if(gamma && !mlLengths) { std::cerr << "--gamma goes with --ml-lengths" << std::endl; return EXIT_FAILURE; }
+	if(haveGammaOpt && !gamma) { std::cerr << "--gamma-alpha, --gamma-rounds, --gamma-eps and --gamma-log go with --gamma" << std::endl; return EXIT_FAILURE; }
+	if(gamma) {
+		if(gammaK < 2 || gammaK > 16) { std::cerr << "--gamma must be 2 to 16 rate categories" << std::endl; return EXIT_FAILURE; }
+		if(haveGammaAlpha && (!(gammaAlpha >= HU_GAMMA_ALPHA_MIN) || !(gammaAlpha <= HU_GAMMA_ALPHA_MAX))) { std::cerr << "--gamma-alpha must be " << HU_GAMMA_ALPHA_MIN << " to " << HU_GAMMA_ALPHA_MAX << std::endl; return EXIT_FAILURE; }
+		if(gammaRounds < 1) { std::cerr << "--gamma-rounds must be at least 1" << std::endl; return EXIT_FAILURE; }
+		if(!(gammaEps > 0) || !std::isfinite(gammaEps)) { std::cerr << "--gamma-eps must be above 0" << std::endl; return EXIT_FAILURE; }
+	}
 	if(nni) {
 		if(nniRounds < 1) { std::cerr << "--nni-rounds must be at least 1" << std::endl; return EXIT_FAILURE; }
 		if(!(nniMinGain > 0) || !std::isfinite(nniMinGain)) { std::cerr << "--nni-min-gain must be above 0" << std::endl; return EXIT_FAILURE; }
@@ -250,6 +271,8 @@ int main(int argc, char** argv) {
 		if(addNeed > have) { std::cerr << "--add: " << fitNodes << " nodes of " << L << " columns after " << queryRow.size() << " insertions need " << addNeed << " bytes (64 bytes per node and column for the messages), --mem allows " << have << " bytes" << std::endl; return EXIT_FAILURE; }
 		const int64_t sprNeed = spr ? hu_spr_need((int32_t) fitNodes, (int32_t) L, sprRadius) : 0;
 		if(sprNeed > have && sprNeed >= need) { std::cerr << "--spr: " << fitNodes << " nodes of " << L << " columns at radius " << sprRadius << " need " << sprNeed << " bytes (64 bytes per node and column for the messages), --mem allows " << have << " bytes" << std::endl; return EXIT_FAILURE; }
+		const int64_t gammaNeed = gamma ? hu_gamma_need((int32_t) fitNodes, (int32_t) L, gammaK) : 0;
+		if(gammaNeed > have && gammaNeed >= need) { std::cerr << "--gamma: " << fitNodes << " nodes of " << L << " columns in " << gammaK << " rate categories need " << gammaNeed << " bytes (64 bytes per node, column and category for the messages), --mem allows " << have << " bytes" << std::endl; return EXIT_FAILURE; }
 		if(need > have) { std::cerr << (support ? "--support: " : nni ? "--nni: " : "--ml-lengths: ") << fitNodes << " nodes of " << L << " columns need " << need << " bytes (64 bytes per node and column for the messages), --mem allows " << have << " bytes" << std::endl; return EXIT_FAILURE; }
 	}
 
@@ -475,6 +498,7 @@ int main(int argc, char** argv) {
 		}
 	}
 	/* --support: the supports of the final tree's eligible edges become the labels of their lower ends */
+	std::vector<std::string> finalLabel;                      /* of the tree as written, when --support has set labels */
 	if(support) {
 		std::vector<int8_t> seq((size_t) nn * L, (int8_t) -2);
 		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(nodeNames[i]) * L, L);
@@ -511,6 +535,7 @@ int main(int argc, char** argv) {
 			if(label[u].empty()) label[u] = num;
 			if(s >= 0 && label[s].empty()) label[s] = num;
 		}
+		finalLabel = label;
 		for(int32_t i = 0; i < nn; ++i) nodeName[i] = label[i].c_str();
 		const int64_t wl = hu_newick_from_arrays(nn, parent.data(), childOff.data(), childIdx.data(), nodeName.data(), blen.data(), nullptr, 0);
 		if(wl < 0) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
@@ -533,6 +558,56 @@ int main(int argc, char** argv) {
 			}
 			fprintf(f, "# skipped: %lld edges at polytomies\n# seed: %llu\n", (long long) skipped, supportSeed);
 			if(fclose(f) != 0) { std::cerr << "Unable to write to '" << supportFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+		}
+	}
+	/* --gamma: the last stage.  The lengths of the tree as it stands and the shape under the discrete Gamma of rates; the topology, the
+	 * names, the order of children and the top node stay, and so do the labels of --support, which were computed on the lengths before */
+	if(gamma) {
+		std::vector<int8_t> seq((size_t) nn * L, (int8_t) -2);
+		for(int32_t i = 0; i < nn; ++i) if(childOff[i] == childOff[i + 1]) memcpy(seq.data() + (size_t) i * L, rows.data() + (size_t) inp.name2row.at(nodeNames[i]) * L, L);
+		hu_gamma_opts go;
+		hu_gamma_default_opts(&go);
+		std::vector<hu_gamma_pass> passes((size_t) gammaRounds);
+		go.blen.eps = mlEps; go.blen.min_len = minLen; go.blen.max_len = maxLen; go.blen.max_rounds = mlRounds; go.blen.host = host ? 1 : 0; go.blen.device = device;
+		go.blen.mem_budget = haveMem ? (int64_t)(memGB * 1e9) : 0;
+		go.k = gammaK; go.alpha = haveGammaAlpha ? gammaAlpha : 0.0; go.max_outer = gammaRounds; go.eps_ll = gammaEps; go.passes = passes.data(); go.passes_cap = gammaRounds;
+		if(hu_tree_gamma_fit(&go, nn, (int32_t) L, parent.data(), blen.data(), seq.data(), &md) != HU_OK) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
+		static const char* const why[] = {"converged", "max passes", "fixed alpha"};
+		if(verbose) {
+			char line[240];
+			snprintf(line, sizeof(line), "Discrete Gamma of %d rates fitted: alpha %.17g, log-likelihood %.17g -> %.17g in %d pass(es), stop: %s", gammaK, go.alpha_fit, go.ll_start, go.ll_final, go.n_outer, why[go.stop]);
+			std::cerr << line << std::endl;
+			std::cerr << "rates:";
+			for(int c = 0; c < gammaK; ++c) { snprintf(line, sizeof(line), " %.6g", go.rates[c]); std::cerr << line; }
+			std::cerr << std::endl;
+			for(int32_t r = 0; r < go.n_outer; ++r) {
+				snprintf(line, sizeof(line), "pass %d: alpha %.17g, log-likelihood %.17g, %d round(s)", r + 1, passes[r].alpha, passes[r].ll, passes[r].n_rounds);
+				std::cerr << line << std::endl;
+			}
+			if(go.n_capped > 0) std::cerr << "Warning: " << go.n_capped << " branch step(s) hit the cap of " << HU_BLEN_MAX_NEWTON << " Newton steps" << std::endl;
+			double s[5];
+			hu_gamma_timing(s);
+			std::cerr << "shape searches " << s[0] << " s, sweeps " << s[1] << " s, steps " << s[2] << " s, trial sweeps " << s[3] << " s, the rest " << s[4] << " s" << std::endl;
+		}
+		/* written as the stage before wrote it: by the handle of the parsed tree, or from the arrays with the labels it gave */
+		const bool fromArrays = grown || nni || spr || support;
+		std::vector<const char*> nodeName((size_t) nn);
+		for(int32_t i = 0; i < nn; ++i) nodeName[i] = finalLabel.empty() ? nodeNames[i].c_str() : finalLabel[i].c_str();
+		const int64_t wl = fromArrays ? hu_newick_from_arrays(nn, parent.data(), childOff.data(), childIdx.data(), nodeName.data(), blen.data(), nullptr, 0) : hu_newick_write(nw.get(), blen.data(), nullptr, 0);
+		if(wl < 0) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }
+		text.assign((size_t) wl + 1, '\0');
+		if(fromArrays) hu_newick_from_arrays(nn, parent.data(), childOff.data(), childIdx.data(), nodeName.data(), blen.data(), &text[0], wl + 1);
+		else hu_newick_write(nw.get(), blen.data(), &text[0], wl + 1);
+		text.resize((size_t) wl);
+		if(!gammaLogFn.empty()) {
+			FILE* f = fopen(gammaLogFn.c_str(), "w");
+			if(!f) { std::cerr << "Unable to write to '" << gammaLogFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
+			fprintf(f, "pass\talpha\tll\trounds\n0\t%.17g\t%.17g\t0\n", haveGammaAlpha ? gammaAlpha : 1.0, go.ll_start);
+			for(int32_t r = 0; r < go.n_outer; ++r) fprintf(f, "%d\t%.17g\t%.17g\t%d\n", r + 1, passes[r].alpha, passes[r].ll, passes[r].n_rounds);
+			fprintf(f, "# rates:");
+			for(int c = 0; c < gammaK; ++c) fprintf(f, "%c%.17g", c ? '\t' : ' ', go.rates[c]);
+			fprintf(f, "\n# stop: %s\n", why[go.stop]);
+			if(fclose(f) != 0) { std::cerr << "Unable to write to '" << gammaLogFn << "': " << strerror(errno) << std::endl; return EXIT_FAILURE; }
 		}
 	}
 	if(!distFn.empty()) {

@@ -113,14 +113,7 @@ void hu_blen_host_sweep(const HuBlenTopo& tp, const HuBlenModel& m, const int32_
 
 double hu_blen_host_loglik(const HuBlenModel& m, int64_t L, const double* v) {
 	double sum = 0;
-	for(int64_t j = 0; j < L; ++j) {
-		const double* M = v + j * 4;
-		const double mx = hu_blen_max4(M);
-		const double s = (mx != -INFINITY && mx < HU_BLEN_MIN_LOGLIK_EXP) ? HU_BLEN_MIN_LOGLIK_EXP - mx : 0.0;
-		double d = 0;
-		for(int i = 0; i < 4; ++i) d += m.pi[i] * exp(M[i] + s);
-		sum += log(d) - s;
-	}
+	for(int64_t j = 0; j < L; ++j) sum += hu_blen_host_loglik_column(m, v + j * 4);
 	return sum;
 }
 

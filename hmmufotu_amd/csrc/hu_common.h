@@ -198,5 +198,9 @@ inline void hu_write_prog_info(std::ostream& f) { const int32_t ver[3] = {1, 5, 
 int hu_csfm_device_pass(int device, const uint8_t* text, int64_t n, uint8_t* bwt, uint64_t* marks, uint32_t* sampled, int32_t* rounds, double* sa_seconds);
 /* hu_tree_sweep_window's last window swept again with other branch lengths, without moving the rows (hu_engine.hip; the rounds of hu_blen.cpp) */
 int hu_tree_sweep_rerun(hu_tree_sweep* s, const hu_model_desc* model, const double* blen, int64_t win_len, double* up_dev, double* down_dev);
+/* the sweeps of K trees of the handle's topology with the lengths blen_cat [K][n], a level of all of them in one launch: up_dev, down_dev
+ * [K][n][win_len][4]; seq: the leaf rows [n][win_len], NULL: those a call before sent (hu_engine.hip; the rate categories of hu_gamma.cpp) */
+int hu_tree_sweep_cat(hu_tree_sweep* s, const hu_model_desc* model, const int8_t* seq, int32_t K, const double* blen_cat, int64_t win_len,
+		double* up_dev, double* down_dev);
 /* runs f when the scope is left, by return or by exception */
 template<class F> struct HuScope { F f; explicit HuScope(F f) : f(f) {} ~HuScope() { f(); } HuScope(const HuScope&) = delete; HuScope& operator=(const HuScope&) = delete; };

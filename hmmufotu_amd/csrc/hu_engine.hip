@@ -1162,7 +1162,8 @@ struct hu_tree_sweep {
 	HuTreeTopo tp; HuTreeTopoDev td;
 	int8_t* dSeq = nullptr; int64_t seqCap = 0;        /* [n][seqCap]: grown to the widest window seen */
 	std::vector<int8_t> win;                           /* the window's bytes on the host, packed [n][win_len] */
-	~hu_tree_sweep() { (void) hipFree(dSeq); }
+	double* dLenCat = nullptr; int32_t catCap = 0;     /* hu_tree_sweep_cat: [catCap][n] branch lengths */
+	~hu_tree_sweep() { (void) hipFree(dSeq); (void) hipFree(dLenCat); }
 };
 extern "C" int hu_tree_sweep_create(int32_t n, int32_t cs_len, const int32_t* parent, const double* blen, int device, hu_tree_sweep** out) try {
 	if(!out) { hu_set_error("hu_tree_sweep_create: bad argument"); return HU_ERR_ARG; }
@@ -1238,6 +1239,52 @@ int hu_tree_sweep_rerun(hu_tree_sweep* s, const hu_model_desc* model, const doub
 	TCHK(hipDeviceSynchronize());
 	return HU_OK;
 } catch(...) { return hu_catch_all("hu_tree_sweep_rerun"); }
+/* K trees of this topology that differ in their branch lengths alone (blen_cat [K][n], host), every level of all of them in one launch
+ * (k_tree_up_cat, k_tree_down_cat): up_dev, down_dev [K][n][win_len][4].  seq: the leaf rows [n][win_len] on the host, sent once; NULL:
+ * those a call before left on the device.  The model is the fixed-rate one.  Inner rows are not inferred */
+int hu_tree_sweep_cat(hu_tree_sweep* s, const hu_model_desc* model, const int8_t* seq, int32_t K, const double* blen_cat, int64_t win_len,
+		double* up_dev, double* down_dev) try {
+	if(!s || !model || !blen_cat || !up_dev || K < 1 || K > HU_MAX_DGK || model->dg_k != 0) { hu_set_error("hu_tree_sweep_cat: bad argument"); return HU_ERR_ARG; }
+	if(win_len < 1 || win_len != s->csLen) { hu_set_error("hu_tree_sweep_cat: %lld columns, the tree has %d", (long long) win_len, s->csLen); return HU_ERR_ARG; }
+	const size_t n = (size_t) s->n, bytes = n * (size_t) win_len;
+	if(!seq && (!s->dSeq || s->win.size() != bytes)) { hu_set_error("hu_tree_sweep_cat: no rows of %lld columns were sent before", (long long) win_len); return HU_ERR_STATE; }
+	HuModelDev mdl;
+	int rc = hu_model_prepare(model, &mdl);
+	if(rc != HU_OK) return rc;
+	HIPCHK(hipSetDevice(s->device));
+	if(seq) {
+		if(win_len > s->seqCap) {
+			(void) hipFree(s->dSeq); s->dSeq = nullptr; s->seqCap = 0;
+			TCHK(hipMalloc((void**) &s->dSeq, bytes));
+			s->seqCap = win_len;
+		}
+		s->win.assign(seq, seq + bytes);
+		TCHK(hipMemcpy(s->dSeq, seq, bytes, hipMemcpyHostToDevice));
+	}
+	if(K > s->catCap) {
+		(void) hipFree(s->dLenCat); s->dLenCat = nullptr; s->catCap = 0;
+		TCHK(hipMalloc((void**) &s->dLenCat, (size_t) K * n * 8));
+		s->catCap = K;
+	}
+	TCHK(hipMemcpy(s->dLenCat, blen_cat, (size_t) K * n * 8, hipMemcpyHostToDevice));
+	HuTreeCatDev t;
+	t.n = s->n; t.root = s->tp.root; t.L = win_len; t.parent = s->td.par; t.childOff = s->td.off; t.childIdx = s->td.idx; t.seq = s->dSeq;
+	t.blen = s->dLenCat; t.up = up_dev; t.down = down_dev;
+	const HuTreeTopo& tp = s->tp;
+	const unsigned gx = (unsigned)((win_len + 255) / 256);
+	(void) hipGetLastError();
+	for(int d = tp.maxD; d >= 0; --d) {
+		const int m = tp.lvOff[d + 1] - tp.lvOff[d];
+		for(int a = 0; a < m; a += 65535) k_tree_up_cat<<<dim3(gx, std::min(65535, m - a), (unsigned) K), 256>>>(t, mdl, s->td.ord + tp.lvOff[d] + a);
+	}
+	if(down_dev) for(int d = 1; d <= tp.maxD; ++d) {
+		const int m = tp.lvOff[d + 1] - tp.lvOff[d];
+		for(int a = 0; a < m; a += 65535) k_tree_down_cat<<<dim3(gx, std::min(65535, m - a), (unsigned) K), 256>>>(t, mdl, s->td.ord + tp.lvOff[d] + a);
+	}
+	TCHK(hipGetLastError());
+	TCHK(hipDeviceSynchronize());
+	return HU_OK;
+} catch(...) { return hu_catch_all("hu_tree_sweep_cat"); }
 #undef TCHK
 
 /* ------------------------------------------------------------------------------ database build (hmmufotu-build) */

@@ -107,3 +107,64 @@ __global__ __launch_bounds__(256) void k_tree_down(HuTreeDev t, HuModelDev mdl, 
 	*reinterpret_cast<double2*>(dst) = make_double2(out[0], out[1]);
 	*reinterpret_cast<double2*>(dst + 2) = make_double2(out[2], out[3]);
 }
+
+/* The sweeps of K trees that differ in their branch lengths alone, a level of all of them in one launch (the rate categories of
+ * hmmufotu-amd-tree --gamma): grid (sites/256, nodes, K), blen [K][n], up and down [K][n][L][4].  The model is the
+ * fixed-rate one, and a message has the bits k_tree_up / k_tree_down give it at the same lengths: the same tree_conv per child in the
+ * same order, summed from 0.  Inner rows are not inferred. */
+struct HuTreeCatDev {
+	int32_t n, root; int64_t L;
+	const int32_t* parent; const int32_t* childOff; const int32_t* childIdx;
+	const int8_t* seq;                                    /* [n][L], leaf rows */
+	const double* blen; double* up; double* down;
+};
+
+__global__ __launch_bounds__(256) void k_tree_up_cat(HuTreeCatDev t, HuModelDev mdl, const int32_t* __restrict__ nodes) {
+	const int u = nodes[blockIdx.y];
+	const int64_t w = (int64_t) blockIdx.x * 256 + threadIdx.x;
+	if(w >= t.L) return;
+	const size_t cat = blockIdx.z;
+	const double* len = t.blen + cat * (size_t) t.n;
+	double* up = t.up + cat * (size_t) t.n * (size_t) t.L * 4;
+	double out[4];
+	const int c0 = t.childOff[u], c1 = t.childOff[u + 1];
+	if(c0 == c1) {
+		const int b = t.seq[(size_t) u * t.L + w];
+		for(int i = 0; i < 4; ++i) out[i] = b >= 0 ? (i == b ? 0.0 : -INFINITY) : mdl.logpi[i];
+	}
+	else {
+		for(int i = 0; i < 4; ++i) out[i] = 0;
+		for(int c = c0; c < c1; ++c) {
+			const int v = t.childIdx[c];
+			double M[4], Y[4]; load4(up + ((size_t) v * t.L + w) * 4, M);
+			tree_conv(mdl, len[v], M, Y);
+			for(int i = 0; i < 4; ++i) out[i] += Y[i];
+		}
+	}
+	double* dst = up + ((size_t) u * t.L + w) * 4;
+	*reinterpret_cast<double2*>(dst) = make_double2(out[0], out[1]);
+	*reinterpret_cast<double2*>(dst + 2) = make_double2(out[2], out[3]);
+}
+
+__global__ __launch_bounds__(256) void k_tree_down_cat(HuTreeCatDev t, HuModelDev mdl, const int32_t* __restrict__ nodes) {
+	const int u = nodes[blockIdx.y];
+	const int64_t w = (int64_t) blockIdx.x * 256 + threadIdx.x;
+	if(w >= t.L) return;
+	const size_t cat = blockIdx.z, off = cat * (size_t) t.n * (size_t) t.L * 4;
+	const double* len = t.blen + cat * (size_t) t.n;
+	const double* up = t.up + off;
+	double* down = t.down + off;
+	const int p = t.parent[u];
+	double out[4] = {0, 0, 0, 0}, M[4], Y[4];
+	if(p != t.root) { load4(down + ((size_t) p * t.L + w) * 4, M); tree_conv(mdl, len[p], M, Y); for(int i = 0; i < 4; ++i) out[i] += Y[i]; }
+	for(int c = t.childOff[p]; c < t.childOff[p + 1]; ++c) {
+		const int v = t.childIdx[c];
+		if(v == u) continue;
+		load4(up + ((size_t) v * t.L + w) * 4, M);
+		tree_conv(mdl, len[v], M, Y);
+		for(int i = 0; i < 4; ++i) out[i] += Y[i];
+	}
+	double* dst = down + ((size_t) u * t.L + w) * 4;
+	*reinterpret_cast<double2*>(dst) = make_double2(out[0], out[1]);
+	*reinterpret_cast<double2*>(dst + 2) = make_double2(out[2], out[3]);
+}

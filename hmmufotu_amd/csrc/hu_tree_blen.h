@@ -109,6 +109,14 @@ int hu_blen_check(const char* fn, const hu_blen_opts* o, int32_t n, int32_t cs_l
 /* up, down [n][cs_len][4] in log space with the reference's scaling rule; down == NULL: the up sweep alone */
 void hu_blen_host_sweep(const HuBlenTopo& tp, const HuBlenModel& m, const int32_t* parent, int64_t cs_len, const double* blen, const int8_t* seq,
 		double* up, double* down);
+/* dot_product_scaled(pi, M) of one column of the root message */
+static inline double hu_blen_host_loglik_column(const HuBlenModel& m, const double* M) {
+	const double mx = hu_blen_max4(M);
+	const double s = (mx != -INFINITY && mx < HU_BLEN_MIN_LOGLIK_EXP) ? HU_BLEN_MIN_LOGLIK_EXP - mx : 0.0;
+	double d = 0;
+	for(int i = 0; i < 4; ++i) d += m.pi[i] * exp(M[i] + s);
+	return log(d) - s;
+}
 /* treeLoglik: the serial sum over the columns of dot_product_scaled(pi, up[root]) */
 double hu_blen_host_loglik(const HuBlenModel& m, int64_t cs_len, const double* up_root);
 /* scores at t[u] and, with t_star, the step of every non-root branch; returns the branches at the Newton cap */

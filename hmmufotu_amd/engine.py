@@ -1165,6 +1165,124 @@ def tree_optimize_lengths(parent, blen, seq, model: ModelDesc, eps=None, min_len
                 seconds=dict(sweep=s[0], step=s[1], trial=s[2], other=s[3]))
 
 
+class GammaPass(C.Structure):
+    _fields_ = [("alpha", C.c_double), ("ll", C.c_double), ("n_rounds", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GammaOpts(C.Structure):
+    _fields_ = [("blen", BlenOpts), ("k", C.c_int32), ("max_outer", C.c_int32), ("alpha", C.c_double), ("eps_ll", C.c_double),
+                ("sweep_reruns", C.c_int32), ("passes_cap", C.c_int32), ("passes", C.POINTER(GammaPass)),
+                ("n_outer", C.c_int32), ("stop", C.c_int32), ("alpha_fit", C.c_double), ("rates", C.c_double * 16),
+                ("ll_start", C.c_double), ("ll_final", C.c_double), ("n_capped", C.c_int64)]
+
+
+GAMMA_ALPHA_MIN, GAMMA_ALPHA_MAX = 0.05, 100.0
+GAMMA_LDS_BYTES = 40960
+GAMMA_STOP = ("converged", "max passes", "fixed alpha")
+
+
+def gamma_lds_cols(k: int) -> int:
+    """the columns up to which the 4 K values of a branch's columns stay in LDS (hu_gamma_in_lds)"""
+    return (GAMMA_LDS_BYTES // 8 - 3 * 256 - (9 * k + (9 * k & 1))) // (4 * k)
+
+
+def gamma_rates(k: int, alpha: float) -> np.ndarray:
+    """hu_gamma_rates: the K category rates of the discrete Gamma with shape alpha, mean 1"""
+    r = np.zeros(max(int(k), 1))
+    _chk(load_library().hu_gamma_rates(C.c_int32(int(k)), C.c_double(float(alpha)), _p(r, C.c_double)))
+    return r
+
+
+def gamma_need(n_nodes: int, cs_len: int, k: int) -> int:
+    """hu_gamma_need: the bytes the fit under the discrete Gamma holds for n_nodes x cs_len in k categories"""
+    lib = load_library()
+    lib.hu_gamma_need.restype = C.c_int64
+    return int(lib.hu_gamma_need(C.c_int32(n_nodes), C.c_int32(cs_len), C.c_int32(k)))
+
+
+def _gamma_args(what, parent, blen, seq, model, k, alpha, eps, min_len, max_len, max_rounds, device, host, mem_budget, max_outer=None, eps_ll=None,
+                sweep_reruns=False):
+    parent = np.ascontiguousarray(parent, np.int32); blen = np.ascontiguousarray(blen, np.float64).copy()
+    seq = np.ascontiguousarray(seq, np.int8)
+    if seq.ndim != 2 or parent.shape != (seq.shape[0],) or blen.shape != parent.shape:
+        raise EngineError(what + ": parent [n], blen [n] and seq [n][cs_len]")
+    o = GammaOpts()
+    load_library().hu_gamma_default_opts(C.byref(o))
+    for key, v in (("eps", eps), ("min_len", min_len), ("max_len", max_len)):
+        if v is not None:
+            setattr(o.blen, key, float(v))
+    if max_rounds is not None:
+        o.blen.max_rounds = int(max_rounds)
+    o.blen.host = 1 if host else 0; o.blen.device = int(device); o.blen.mem_budget = int(mem_budget or 0)
+    o.k = int(k); o.alpha = float(alpha or 0.0); o.sweep_reruns = 1 if sweep_reruns else 0
+    if max_outer is not None:
+        o.max_outer = int(max_outer)
+    if eps_ll is not None:
+        o.eps_ll = float(eps_ll)
+    n, L = seq.shape
+    head = (C.byref(o), C.c_int32(n), C.c_int32(L), _p(parent, C.c_int32), _p(blen, C.c_double), _p(seq, C.c_int8), C.byref(model))
+    return o, blen, n, L, head
+
+
+def tree_gamma_loglik(parent, blen, seq, model: ModelDesc, k=4, alpha=1.0, device=0, host=False, mem_budget=0, sweep_reruns=False) -> dict:
+    """hu_tree_gamma_loglik: dict(ll, per_col [cs_len], per_cat [k][cs_len]) under the discrete Gamma of k rates with shape alpha"""
+    o, blen, n, L, head = _gamma_args("tree_gamma_loglik", parent, blen, seq, model, k, alpha, None, None, None, None, device, host, mem_budget,
+                                      sweep_reruns=sweep_reruns)
+    out = dict(per_col=np.zeros(L), per_cat=np.zeros((max(int(k), 1), L)))
+    ll = C.c_double(0)
+    _chk(load_library().hu_tree_gamma_loglik(*head, _p(out["per_col"], C.c_double), _p(out["per_cat"], C.c_double), C.byref(ll)))
+    out["ll"] = float(ll.value)
+    return out
+
+
+def tree_gamma_branch_scores(parent, blen, seq, model: ModelDesc, k=4, alpha=1.0, t=None, device=0, host=False, mem_budget=0) -> dict:
+    """hu_tree_gamma_branch_scores: tree_branch_scores for the objective under the discrete Gamma of k rates with shape alpha"""
+    o, blen, n, L, head = _gamma_args("tree_gamma_branch_scores", parent, blen, seq, model, k, alpha, None, None, None, None, device, host, mem_budget)
+    tt = np.ascontiguousarray(t, np.float64) if t is not None else None
+    if tt is not None and tt.shape != (n,):
+        raise EngineError("tree_gamma_branch_scores: t [n]")
+    out = dict(f=np.zeros(n), d1=np.zeros(n), d2=np.zeros(n))
+    _chk(load_library().hu_tree_gamma_branch_scores(*head, _p(tt, C.c_double) if tt is not None else None, _p(out["f"], C.c_double),
+                                                    _p(out["d1"], C.c_double), _p(out["d2"], C.c_double)))
+    return out
+
+
+def tree_gamma_branch_step(parent, blen, seq, model: ModelDesc, k=4, alpha=1.0, min_len=None, max_len=None, device=0, host=False, mem_budget=0) -> dict:
+    """hu_tree_gamma_branch_step: tree_branch_step for the objective under the discrete Gamma of k rates with shape alpha"""
+    o, blen, n, L, head = _gamma_args("tree_gamma_branch_step", parent, blen, seq, model, k, alpha, None, min_len, max_len, None, device, host, mem_budget)
+    out = dict(t_star=np.zeros(n), f=np.zeros(n), d1=np.zeros(n), d2=np.zeros(n), capped=np.zeros(n, np.uint8))
+    _chk(load_library().hu_tree_gamma_branch_step(*head, _p(out["t_star"], C.c_double), _p(out["f"], C.c_double), _p(out["d1"], C.c_double),
+                                                  _p(out["d2"], C.c_double), _p(out["capped"], C.c_uint8)))
+    out["n_capped"] = int(o.n_capped)
+    return out
+
+
+def tree_gamma_fit(parent, blen, seq, model: ModelDesc, k=4, alpha=None, max_outer=None, eps_ll=None, eps=None, min_len=None, max_len=None,
+                   max_rounds=None, device=0, host=False, mem_budget=0, sweep_reruns=False) -> dict:
+    """hu_tree_gamma_fit: the lengths and, with alpha None, the shape by maximum likelihood under the discrete Gamma of k rates.
+    dict(blen [n], alpha, rates [k], ll_start, ll_final, stop (one of GAMMA_STOP), passes: per pass (alpha, ll, n_rounds), n_capped, seconds)"""
+    o, blen, n, L, head = _gamma_args("tree_gamma_fit", parent, blen, seq, model, k, alpha, eps, min_len, max_len, max_rounds, device, host, mem_budget,
+                                      max_outer, eps_ll, sweep_reruns)
+    cap = max(int(o.max_outer), 1)
+    rec = (GammaPass * cap)()
+    o.passes = C.cast(rec, C.POINTER(GammaPass)); o.passes_cap = cap
+    _chk(load_library().hu_tree_gamma_fit(*head))
+    s = np.zeros(5)
+    _chk(load_library().hu_gamma_timing(_p(s, C.c_double)))
+    return dict(blen=blen, alpha=float(o.alpha_fit), rates=np.array(o.rates[:int(k)]), ll_start=float(o.ll_start), ll_final=float(o.ll_final),
+                stop=GAMMA_STOP[o.stop], n_capped=int(o.n_capped),
+                passes=[dict(alpha=r.alpha, ll=r.ll, n_rounds=int(r.n_rounds)) for r in rec[:o.n_outer]],
+                seconds=dict(shape=s[0], sweep=s[1], step=s[2], trial=s[3], other=s[4]))
+
+
+def gamma_profile(parent, blen, seq, model: ModelDesc, k=4, alpha=1.0, reps=6, device=0, sweep_reruns=False) -> np.ndarray:
+    """hu_gamma_profile: seconds [reps][3] of a full sweep, a step and a trial sweep with its log-likelihood on the device"""
+    o, blen, n, L, head = _gamma_args("gamma_profile", parent, blen, seq, model, k, alpha, None, None, None, None, device, False, 0, sweep_reruns=sweep_reruns)
+    s = np.zeros((int(reps), 3))
+    _chk(load_library().hu_gamma_profile(*head, C.c_int32(int(reps)), _p(s, C.c_double)))
+    return s
+
+
 def newick_write(text, blen) -> str:
     """hu_newick_parse + hu_newick_write: the tree of `text` with the lengths blen [n] (node ids of newick_parse), 17 significant digits"""
     lib = load_library()

@@ -1242,6 +1242,87 @@ int hu_blen_timing(double* seconds /* [4] */);
  * (without the terminator) and writes at most cap bytes, terminator included; HU_ERR_ARG (negative) on a bad argument.  Host only. */
 int64_t hu_newick_write(const hu_newick* t, const double* blen, char* buf, int64_t cap);
 
+/* ---- hmmufotu-amd-tree --ml-lengths --gamma K: branch lengths and the shape under the discrete Gamma of rates ----
+ * The textbook model (Yang 1994): every column has one of K equally probable rates, and its likelihood is the mean over the K
+ * fixed-rate likelihoods with all lengths multiplied by the rate.  It is NOT the reference's DiscreteGammaModel (hu_dg_model), which
+ * averages the categories at every inner node and whose rates sum to 1: here the rates sum to K, the mean rate is 1, and a length stays
+ * substitutions per site in the unit of the model file.  `model` is the fixed-rate model: dg_k != 0 is refused as in §22.
+ *
+ * hu_gamma_rates: rates [K], ascending: rate_i = K [P(alpha + 1, q_{i+1}) - P(alpha + 1, q_i)] with q_i the i/K quantile of
+ *   Gamma(shape alpha, scale 1), q_K = inf and P the regularised incomplete gamma function: the mean of Gamma(shape alpha, rate alpha)
+ *   over its i-th K-quantile.  K is 1 to 16 (HU_MAX_DGK), alpha in [HU_GAMMA_ALPHA_MIN, HU_GAMMA_ALPHA_MAX].  Host only.
+ *
+ * The objective of the branch above u.  Category c has the messages up_c, down_c of the sweeps at the lengths rate_c blen, and a column
+ * of it has the ratios r_jcm and the constant K_jc of §22.  With K_j = max_c K_jc, w_jc = exp(K_jc - K_j), e_cm = exp(lam_m rate_c t):
+ *   S_j = sum_c w_jc (1 + sum_m r_jcm e_cm),  N_j = sum_c w_jc rate_c sum_m r_jcm lam_m e_cm,  M_j = sum_c w_jc rate_c^2 sum_m r_jcm lam_m^2 e_cm,
+ *   f_u(t) = sum_j [K_j - log K + log S_j],   f_u' = sum_j N_j / S_j,   f_u'' = sum_j [M_j / S_j - (N_j / S_j)^2].
+ * f_u(blen[u]) is the tree's log-likelihood under the model for every u.  A branch keeps w_jc and w_jc r_jcm of every column, 4 K
+ * doubles, and an evaluation costs 3 K exp per branch and none per column.  With K = 1 every entry computes what its fixed-rate
+ * counterpart computes.
+ *
+ * hu_tree_gamma_loglik: the log-likelihood at blen.  Per category the column values of hu_tree_loglik at the root message (per_cat
+ *   [K][cs_len], may be NULL), per column log of the mean of their exp, taken above their maximum (per_col [cs_len], may be NULL),
+ *   *ll their sum in serial column order on the host.
+ * hu_tree_gamma_branch_scores, hu_tree_gamma_branch_step: hu_tree_branch_scores and hu_tree_branch_step for the objective above; the
+ *   same rule of a step (hu_blen_solve), opts->n_capped counts the branches at the Newton cap.
+ * These three read opts->k and opts->alpha (0: alpha = 1).
+ * hu_tree_gamma_fit: blen [n] in place.  With opts->alpha > 0 it is one fit of the lengths (the rounds of hu_tree_optimize_lengths
+ *   over the objective above) at that alpha.  With alpha 0 it starts at alpha = 1, and a pass (a) searches log alpha on
+ *   [log HU_GAMMA_ALPHA_MIN, log HU_GAMMA_ALPHA_MAX] with the lengths held, by golden section with HU_GAMMA_SHAPE_EVALS evaluations, each
+ *   the up sweeps and the log-likelihood, and takes the best point evaluated if it beats the alpha it has, then (b) fits the lengths with
+ *   alpha held.  It stops when a pass gains less than eps_ll, or after max_outer passes.  The log-likelihood never falls.  The report:
+ *   alpha_fit, rates, ll_start (at the given lengths and the first alpha), ll_final, n_outer, stop, and per pass (passes, when not NULL,
+ *   holds passes_cap entries) alpha, ll and the rounds of its fit.
+ * Memory (hu_gamma_need): 64 K n cs_len bytes of messages, n cs_len of rows, 8 (K + 1) cs_len of column values, the scratch of the
+ *   step and 1 MB of slack.  The 4 K values of a branch's columns stay in LDS while 32 K cs_len + 72 K + 6 KB fit HU_GAMMA_LDS_BYTES
+ *   (four workgroups in a CU's 160 KB: 1085, 541, 269 and 65 columns at K = 1, 2, 4 and 16); beyond that the step runs over slabs of
+ *   max(HU_GAMMA_SLAB_MIN, n / 32) branches per launch (n at the most) with 32 K cs_len bytes of scratch per branch of a slab: 1/64 of
+ *   the messages on a large tree.  The need is held against blen.mem_budget (when > 0) before anything is allocated, on the host path
+ *   too, and on the device against the free memory: HU_ERR_NOMEM names both numbers.  Column windows are not offered: a tree of
+ *   gg_97's size needs 391 GB at K = 4 and is refused on one device.
+ * hu_gamma_timing: seconds [5] of this thread's last hu_tree_gamma_fit = the shape searches, the full sweeps, the steps, the trial
+ *   sweeps with their log-likelihoods, the rest. */
+#define HU_GAMMA_ALPHA_MIN 0.05    /* a choice, not a measurement: below it the lowest category's rate underflows any use */
+#define HU_GAMMA_ALPHA_MAX 100.0   /* likewise: above it the rates are within a few percent of 1 */
+#define HU_GAMMA_SHAPE_EVALS 24    /* of a golden-section search: the bracket of log alpha shrinks from 7.6 to 1.2e-4 */
+#define HU_GAMMA_LDS_BYTES 40960   /* of a workgroup of k_gamma_step<true>: a quarter of a CU's 160 KB */
+#define HU_GAMMA_SLAB_MIN 1024     /* branches of a launch of k_gamma_step<false> at the least: four workgroups for each of 256 CUs */
+enum { HU_GAMMA_CONVERGED = 0, HU_GAMMA_MAX_OUTER = 1, HU_GAMMA_FIXED_ALPHA = 2 };
+typedef struct { double alpha, ll; int32_t n_rounds, reserved; } hu_gamma_pass;
+typedef struct {
+	hu_blen_opts blen;    /* of every fit of the lengths: eps, min_len, max_len, max_rounds, host, device, mem_budget; its rounds are not recorded */
+	int32_t k;            /* 4: the categories, 1 to 16 */
+	int32_t max_outer;    /* 10: passes at the most */
+	double alpha;         /* 0: estimated; above 0: kept at this value */
+	double eps_ll;        /* 0.01: a pass that gains less ends the run */
+	int32_t sweep_reruns; /* 0; 1: a sweep is K runs of the fixed-rate level kernels in place of the launches over all categories: the same
+	                       * bits, for the comparison of profiles/gamma_rate.py */
+	int32_t passes_cap;   /* entries of passes */
+	hu_gamma_pass* passes;
+	/* the report */
+	int32_t n_outer, stop;
+	double alpha_fit;
+	double rates[16];     /* HU_MAX_DGK */
+	double ll_start, ll_final;
+	int64_t n_capped;     /* hu_tree_gamma_branch_step: branches at the Newton cap; hu_tree_gamma_fit: of all rounds */
+} hu_gamma_opts;
+int hu_gamma_rates(int32_t K, double alpha, double* rates);
+int64_t hu_gamma_need(int32_t n_nodes, int32_t cs_len, int32_t K);
+void hu_gamma_default_opts(hu_gamma_opts* o);
+int hu_tree_gamma_loglik(const hu_gamma_opts* opts, int32_t n_nodes, int32_t cs_len, const int32_t* parent, const double* blen, const int8_t* seq,
+		const hu_model_desc* model, double* per_col, double* per_cat, double* ll);
+int hu_tree_gamma_branch_scores(const hu_gamma_opts* opts, int32_t n_nodes, int32_t cs_len, const int32_t* parent, const double* blen, const int8_t* seq,
+		const hu_model_desc* model, const double* t, double* f, double* d1, double* d2);
+int hu_tree_gamma_branch_step(hu_gamma_opts* opts, int32_t n_nodes, int32_t cs_len, const int32_t* parent, const double* blen, const int8_t* seq,
+		const hu_model_desc* model, double* t_star, double* f, double* d1, double* d2, uint8_t* capped);
+int hu_tree_gamma_fit(hu_gamma_opts* opts, int32_t n_nodes, int32_t cs_len, const int32_t* parent, double* blen, const int8_t* seq,
+		const hu_model_desc* model);
+int hu_gamma_timing(double* seconds /* [5] */);
+/* the phases of a round on the device, one by one and reps times each (profiles/gamma_rate.py): seconds [reps][3] = a full sweep, a step,
+ * a trial sweep with its log-likelihood, under opts->k, opts->alpha and opts->sweep_reruns; the first repetition also sends the rows */
+int hu_gamma_profile(const hu_gamma_opts* opts, int32_t n_nodes, int32_t cs_len, const int32_t* parent, const double* blen, const int8_t* seq,
+		const hu_model_desc* model, int32_t reps, double* seconds);
+
 /* ---- hmmufotu-amd-tree --ml-lengths --nni: a hill climb over nearest-neighbour interchanges ----
  * The tree, the model and the limits are those of the branch-length fit above: parent [n], blen [n], seq [n][cs_len], the fixed-rate
  * model only, one device, no column windows.
