@@ -18,6 +18,7 @@
 #define HU_MAX_INS 24            /* bases of one read outside the profile columns handled as a list */
 #define HU_TILEQ_MASK_SHIFT 16   /* an entry of a scan tile's quad list: quad (< 512) | mask of its four 32-site words << this  */
 #define HU_TILEW_QUAD (4 * HU_READ_TILE * 3)   /* dwords of a quad in a scan tile's word-major planes: four words x sixteen reads x three planes */
+#define HU_TILEINS_STRIDE (HU_READ_TILE * (HU_MAX_INS + 1))   /* dwords of a scan tile's insert list: sixteen end offsets (one per slot, the last = the count), then the entries */
 #define HU_NODE_PAD 256          /* node count is padded to a multiple of this                  */
 #define HU_MIN_LOGLIK_EXP (-510.0) /* DBL_MIN_EXP / 2 in integer arithmetic, PhyloTreeUnrooted.cpp:68 */
 #define HU_BRANCH_EPS 1e-5

@@ -2048,7 +2048,7 @@ static int ensure_read_buffers(hu_batch* b) {
 	if((rc = b->dReadSlot.ensure(std::max<size_t>(n, 1))) != HU_OK) return rc;
 	if((rc = b->dRq.ensure(std::max<size_t>(n, 1) * ((d.WQ + 31) / 32))) != HU_OK) return rc;
 	if((rc = b->dIns.ensure(std::max<size_t>(n, 1) * (HU_MAX_INS + 1))) != HU_OK) return rc;
-	if((rc = b->dTileIns.ensure(std::max<size_t>(tiles, 1) * (HU_READ_TILE * HU_MAX_INS + 1))) != HU_OK) return rc;
+	if((rc = b->dTileIns.ensure(std::max<size_t>(tiles, 1) * HU_TILEINS_STRIDE)) != HU_OK) return rc;
 	if((rc = b->dRSpan.ensure(std::max<size_t>(n, 1) * 2)) != HU_OK) return rc;
 	if((rc = b->dTileSpan.ensure(std::max<size_t>(tiles, 1) * 2)) != HU_OK) return rc;
 	return HU_OK;

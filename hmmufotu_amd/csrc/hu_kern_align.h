@@ -1263,7 +1263,8 @@ __global__ void k_tile_slots(int n, int nSlots, const uint32_t* __restrict__ sor
  * is zero and the word adds nothing to d or N, so the pair scan runs the words of the mask only); the planes of those words once
  * more, word by word in list order, tileW[tile][j][read t][plane] — what the pair scan needs of one word is then 48 consecutive
  * dwords; and the
- * reads' insert lists as one list, tileIns[tile][0] = count, [1..] = read t << 24 | (scan position << 2 | base) */
+ * reads' insert lists as one list in slot order, tileIns[tile][t] = end of slot t's entries (t = 0..15: [15] = count),
+ * [16..] = read t << 24 | (scan position << 2 | base): HU_TILEINS_STRIDE dwords per tile */
 __global__ __launch_bounds__(64) void k_tile_lists(HuDbDev db, int n, const uint32_t* __restrict__ rp, const uint32_t* __restrict__ rq, const int32_t* __restrict__ ins,
 		int32_t* __restrict__ tileQ, uint32_t* __restrict__ tileW, int32_t* __restrict__ tileIns, const int32_t* __restrict__ slotRead, const uint2* __restrict__ rspan,
 		uint2* __restrict__ tileSpan) {
@@ -1294,15 +1295,16 @@ __global__ __launch_bounds__(64) void k_tile_lists(HuDbDev db, int n, const uint
 	}
 	if(lane == 0) {
 		out[0] = cnt;
-		int32_t* til = tileIns + (size_t) tile * (HU_READ_TILE * HU_MAX_INS + 1);
+		int32_t* til = tileIns + (size_t) tile * HU_TILEINS_STRIDE;
 		int ne = 0;
 		for(int t = 0; t < HU_READ_TILE; ++t) {
 			const int r = slotRead[tile * HU_READ_TILE + t];
-			if(r < 0) continue;
-			const int32_t* il = ins + (size_t) r * (HU_MAX_INS + 1);
-			for(int e = 0; e < il[0]; ++e) til[1 + ne++] = (t << 24) | il[1 + e];
+			if(r >= 0) {
+				const int32_t* il = ins + (size_t) r * (HU_MAX_INS + 1);
+				for(int e = 0; e < il[0]; ++e) til[HU_READ_TILE + ne++] = (t << 24) | il[1 + e];
+			}
+			til[t] = ne;      /* where the entries of slot t end: the scan walks the list slot by slot */
 		}
-		til[0] = ne;
 		/* the union of the reads' position intervals, block by block */
 		uint32_t f1 = 0xffffu, l1 = 0, f2 = 0xffffu, l2 = 0; bool a1 = false, a2 = false;
 		for(int t = 0; t < HU_READ_TILE; ++t) {

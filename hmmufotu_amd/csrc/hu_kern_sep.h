@@ -9,6 +9,7 @@
 //                 (src/PhyloTreeUnrooted.cpp:879-954, 800-847, 749-798)
 #pragma once
 #include "hu_common.h"
+#include <utility>
 
 #define HU_TOPK_BINS 4097   /* bins 0..4096 = floor(4096 d/N); bin 4097 = N == 0 */
 #define HU_TOPK_CAP 4096
@@ -38,12 +39,14 @@ template<> struct HuPair<uint32_t> {
 	static constexpr int PPV = 4;      /* pairs per 16-byte vector */
 	__device__ static inline uint32_t canon(uint32_t x) { return x; }
 	__device__ static inline uint32_t pack(uint32_t c) { return c; }
+	__device__ static inline uint32_t pack2(uint32_t d, uint32_t N) { return (d << 16) | N; }
 	__device__ static inline void unpack(const uint4& v, uint32_t* o) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
 };
 template<> struct HuPair<uint16_t> {
 	static constexpr int PPV = 8;
 	__device__ static inline uint32_t canon(uint32_t x) { return ((x >> 8) << 16) | (x & 0xffu); }
 	__device__ static inline uint16_t pack(uint32_t c) { return (uint16_t)(((c >> 16) << 8) | (c & 0xffu)); }
+	__device__ static inline uint16_t pack2(uint32_t d, uint32_t N) { return (uint16_t)((d << 8) | N); }      /* N <= 255 by the batch's choice of this width */
 	__device__ static inline void unpack(const uint4& v, uint32_t* o) {
 		const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -57,11 +60,19 @@ __device__ inline uint32_t hu_pair_load(const void* pairs, size_t idx, int p16) 
 
 /* The scan with the inserts of a whole tile as ONE list (k_tile_lists): entries (read t << 24 | scan position << 2 |
  * base) read from the TRANSPOSED planes of the non-profile positions (HuDbDev::colPlanes: three wave-uniform
- * 8-byte words per insert instead of three 1-KB gathers that fetch a whole quad's lines for one bit per node) and added
- * into an LDS accumulator [read][lane] (`ds_add_u32`, so the read index may be a run-time value) in the packed
- * (d << 16 | N) form of the output.  In k_seed_pdist the per-read insert loop (scalar count -> scalar entry -> three
+ * 8-byte words per insert instead of three 1-KB gathers that fetch a whole quad's lines for one bit per node).  The list is in
+ * slot order and carries the end of every slot's entries in front (HU_TILEINS_STRIDE), so the scan walks it inside the unrolled
+ * loop over the slots and adds into the lane's own d[t] and N[t]: the mismatch mask is formed from the three words with scalar
+ * instructions (Wv & ((W0 ^ c0) | (W1 ^ c1)), c = the code's bit as wide as the wave) and each counter takes its lane's bit
+ * (v_cndmask 0, 1 of the mask + v_add per counter: with the v_readlane of the entry, five vector instructions per insert).  Until round 8 the counters of the inserts went
+ * through an LDS accumulator [read][lane] (`ds_add_u32`, 16 KB per workgroup) because the read index was a run-time value.
+ * In k_seed_pdist the per-read insert loop (scalar count -> scalar entry -> three
  * dependent gathers, sixteen times per workgroup) took 36 % of the kernel for ~1 insert per read.
- * (Staging the reads' planes in LDS instead of the scalar cache was measured: no gain.) */
+ * (Staging the reads' planes in LDS instead of the scalar cache was measured: no gain.)
+ * The tail behind the quads waits for no load of its own (profiles/r08_scan_tail.md): lane t of every wave requests slot t's read,
+ * pivot and list end and every lane one entry of the list before the quad loop, and the tail takes them with v_readlane; the
+ * stopper masks of slot t go into lane t of four registers (v_writelane) and leave in ONE 16-byte store per wave by the lanes that
+ * have a read, instead of one lane-0 store per read. */
 /* one-time: colPlanes from planes (see HuDbDev); grid (nNodesPad / 64, WQ - QM), one wave */
 __global__ __launch_bounds__(64) void k_col_planes(HuDbDev db, unsigned long long* __restrict__ col) {
 	const int nb = blockIdx.x, q = db.QM + blockIdx.y, lane = threadIdx.x;
@@ -119,7 +130,7 @@ __device__ inline uint32_t dpp_min_full(uint32_t v) {
 /* One 32-site word of a listed quad against the tile's sixteen reads: `r` = the word's 48 consecutive dwords of the tile's word-major
  * planes (k_tile_lists: [read][b0, b1, v]).  The compiler requests them in four groups of about four reads and waits once per group,
  * the rate of the quad-major form (one wait per read and quad); d[] and N[] stay in their registers (v_bcnt_u32_b32 accumulates in
- * place), 63 VGPRs under the bound of eight waves per SIMD (without the bound the requests of a word go out at once and the kernel
+ * place), 56 VGPRs (63 with the LDS accumulator of the inserts) under the bound of eight waves per SIMD (without the bound the requests of a word go out at once and the kernel
  * takes 85 VGPRs, five waves).
  * Measured and not kept: the quad-major planes with one body per mask value (fifteen instances of the read loop with the skipped
  * words compiled out, one scalar jump per quad): the counters of the fifteen bodies meet in 32 more registers (87 VGPRs, five waves
@@ -133,24 +144,37 @@ __device__ __forceinline__ void hu_scan_word(uint32_t n0, uint32_t n1, uint32_t 
 	}
 }
 
+/* slot t's four mask words into lane t of a register (v_writelane_b32 has no builtin in this compiler; the lane is an immediate) */
+template<int LANE>
+__device__ __forceinline__ void hu_writelane(uint32_t& v, uint32_t s) { asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(s), "n"(LANE)); }
+/* f(integral_constant<int, 0>) ... f(integral_constant<int, n - 1>): a loop whose index is a constant expression in the body */
+template<class F, int... I>
+__device__ __forceinline__ void hu_static_for(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+
 template<class PT, bool L0 = false>
 __global__ __launch_bounds__(256, 8) void k_seed_pdist2(HuDbDev db, const uint32_t* __restrict__ tileW,
 		const int32_t* __restrict__ tileQ, const int32_t* __restrict__ tileIns, PT* __restrict__ pairs, const int32_t* __restrict__ slotRead,
 		uint32_t* __restrict__ piv = nullptr, unsigned long long* __restrict__ l0m = nullptr) {
 	constexpr int T = HU_READ_TILE;
-	__shared__ uint32_t acc[T][256];
-	const int tile = blockIdx.x, tid = threadIdx.x;
+	static_assert(T <= 64, "slot t's read, pivot and masks live in lane t");
+	const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
 	const int node = blockIdx.y * 256 + tid;
 	const int32_t* __restrict__ ql = tileQ + (size_t) tile * (db.WQ + 1);
-	const int32_t* __restrict__ til = tileIns + (size_t) tile * (T * HU_MAX_INS + 1);
-	const int nq = ql[0], ne = til[0];
+	const int32_t* __restrict__ til = tileIns + (size_t) tile * HU_TILEINS_STRIDE;
+	const int nq = ql[0];
+	/* lane t: the read of slot t, (L0) its pivot and the end of its inserts in the tile's list; every lane: one entry of the list (always inside
+	 * the tile's HU_TILEINS_STRIDE dwords).  Requested here, so that all of it is there when the quads are done: no load of the tail waits.
+	 * The entries are loaded before the count is known, so lanes at and beyond the count read dwords of the row that k_tile_lists never wrote: on
+	 * purpose, the walk below takes a lane only below the slot's end */
+	int vread = -1, vend = 0; uint32_t vpiv = 0;
+	int vent = til[T + lane];
+	if(lane < T) {
+		vread = slotRead[tile * T + lane]; vend = til[lane];
+		if(L0 && vread >= 0) vpiv = piv[(size_t) vread * 4];
+	}
 	uint32_t d[T], N[T];
 #pragma unroll
 	for(int t = 0; t < T; ++t) { d[t] = 0; N[t] = 0; }
-	if(ne) {
-#pragma unroll
-		for(int t = 0; t < T; ++t) acc[t][tid] = 0;
-	}
 	const size_t np = (size_t) db.nNodesPad;
 	const uint32_t* __restrict__ wr = (const uint32_t*) __builtin_assume_aligned(tileW + (size_t) tile * db.WQ * HU_TILEW_QUAD, 64);      /* a word's 48 dwords: 192 bytes */
 	for(int qi = 0; qi < nq; ++qi) {
@@ -162,44 +186,58 @@ __global__ __launch_bounds__(256, 8) void k_seed_pdist2(HuDbDev db, const uint32
 		if(ent & (4 << HU_TILEQ_MASK_SHIFT)) { hu_scan_word(n0.z, n1.z, nv.z, wr, d, N); wr += T * 3; }
 		if(ent & (8 << HU_TILEQ_MASK_SHIFT)) { hu_scan_word(n0.w, n1.w, nv.w, wr, d, N); wr += T * 3; }
 	}
-	{ /* inserts: three wave-uniform 8-byte words per position (bit = node within the wave's 64) */
+	if(__builtin_amdgcn_readlane(vend, T - 1)) { /* inserts: three wave-uniform 8-byte words per position (bit = node within the wave's 64).  The list is in slot
+	                                              * order, so the counters are named statically; an entry comes out of its lane, 64 entries per load */
 		const size_t npw = np / 64;
-		const int nb = __builtin_amdgcn_readfirstlane(node >> 6), lane = tid & 63;
-		for(int e = 0; e < ne; ++e) {
-			const int ent = til[1 + e];
-			const int t = ent >> 24, pos = (ent >> 2) & 0x3fffff, code = ent & 3;
-			const unsigned long long* cp = db.colPlanes + ((size_t)(pos - db.QM * 128) * 3) * npw + nb;
-			const unsigned long long W0 = cp[0], W1 = cp[npw], Wv = cp[2 * npw];
-			const uint32_t valid = (uint32_t)(Wv >> lane) & 1u, nc = ((uint32_t)(W0 >> lane) & 1u) | (((uint32_t)(W1 >> lane) & 1u) << 1);
-			const uint32_t add = valid | ((valid & (nc != (uint32_t) code ? 1u : 0u)) << 16);
-			atomicAdd(&acc[t][tid], add);     /* own slot: no contention, a plain ds_add_u32 */
-		}
-	}
-	const bool counts = L0 && node < db.nNodes && node != db.root;      /* a place of the sort: every node but the root */
-	bool zero = false;
+		const uint32_t npw3 = (uint32_t)(3 * npw);
+		const int nb = __builtin_amdgcn_readfirstlane(node >> 6);
+		int e = 0, base = 0;
 #pragma unroll
-	for(int t = 0; t < T; ++t) {
-		const int read = slotRead[tile * T + t];
-		if(read >= 0) {
-			const uint32_t v = ((d[t] << 16) | N[t]) + (ne ? acc[t][tid] : 0u);
-			pairs[(size_t) read * np + node] = HuPair<PT>::pack(v);
-			if(L0) { /* the pivot is wave-uniform (scalar); dist(e) < dist(pivot) <=> d_e N_p < d_p N_e, exact in 32 bits */
-				const uint32_t pp = piv[(size_t) read * 4];
-				const uint32_t a = (v >> 16) * (pp & 0xffffu), bb = (pp >> 16) * (v & 0xffffu);
-				const unsigned long long mL = __ballot(counts && a >= bb), mR = __ballot(counts && bb >= a);
-				if((tid & 63) == 0) *reinterpret_cast<ulonglong2*>(l0m + ((size_t) read * (np / 64) + (size_t)(node >> 6)) * 2) = make_ulonglong2(mL, mR);
-				zero |= v == 0u;      /* d <= N: a compared-site count of zero is an all-zero pair */
+		for(int t = 0; t < T; ++t) {
+			const int end = __builtin_amdgcn_readlane(vend, t);
+			for(; e < end; ++e) {
+				if(e >= base + 64) { base += 64; vent = til[T + base + lane]; }      /* e < end <= 384: base <= 320, inside the tile's stride */
+				const int ent = __builtin_amdgcn_readlane(vent, e - base);
+				const uint32_t pos = ((uint32_t) ent >> 2) & 0x3fffffu;
+				const unsigned long long* cp = db.colPlanes + (unsigned long long)(pos - (uint32_t)(db.QM * 128)) * npw3 + nb;      /* a listed position is one of the non-profile block */
+				const unsigned long long W0 = cp[0], W1 = cp[npw], Wv = cp[2 * npw];
+				const unsigned long long c0 = (ent & 1) ? ~0ull : 0ull, c1 = (ent & 2) ? ~0ull : 0ull;      /* the code's two bits, as wide as the wave */
+				const unsigned long long mm = Wv & ((W0 ^ c0) | (W1 ^ c1));
+				N[t] += __builtin_amdgcn_inverse_ballot_w64(Wv) ? 1u : 0u;
+				d[t] += __builtin_amdgcn_inverse_ballot_w64(mm) ? 1u : 0u;
 			}
 		}
 	}
-	if(L0 && __ballot(zero && counts)) { /* a node that shares no column with some read of the tile (dist = 0 / 0: std::sort is undefined, the read takes the fallback
-	                                      * rule): rare on complete sequences, so which read it was is looked up only here */
+	const bool counts = L0 && node < db.nNodes && node != db.root;      /* a place of the sort: every node but the root */
+	const unsigned long long cm = L0 ? __ballot(counts) : 0ull;
+	uint32_t mk0 = 0, mk1 = 0, mk2 = 0, mk3 = 0;      /* lane t: slot t's !(e < pivot) and !(pivot < e) masks of this wave's 64 nodes */
+	unsigned long long zm = 0;      /* nodes with a compared-site count of zero for some read of the tile */
+	hu_static_for([&](auto tc) {
+		constexpr int t = decltype(tc)::value;
+		const int read = __builtin_amdgcn_readlane(vread, t);
+		const uint32_t pp = (uint32_t) __builtin_amdgcn_readlane((int) vpiv, t);      /* in front of the branch: taken inside it, every slot's block waits for all earlier pair stores (s_waitcnt vmcnt(0)) */
+		if(read >= 0) {
+			pairs[(size_t) read * np + node] = HuPair<PT>::pack2(d[t], N[t]);
+			if(L0) { /* the pivot is wave-uniform (scalar); dist(e) < dist(pivot) <=> d_e N_p < d_p N_e, exact in 32 bits (both factors below 2^16) */
+				const uint32_t a = __umul24(d[t], pp & 0xffffu), bb = __umul24(pp >> 16, N[t]);
+				const unsigned long long mL = __ballot(a >= bb) & cm, mR = __ballot(bb >= a) & cm;
+				hu_writelane<t>(mk0, (uint32_t) mL); hu_writelane<t>(mk1, (uint32_t)(mL >> 32));
+				hu_writelane<t>(mk2, (uint32_t) mR); hu_writelane<t>(mk3, (uint32_t)(mR >> 32));
+				zm |= __ballot(N[t] == 0u);      /* d <= N: the same condition as an all-zero pair */
+			}
+		}
+	}, std::make_integer_sequence<int, T>{});
+	if(L0) {
+		/* one store per wave: lane t puts slot t's 16 bytes into its read's row (lanes without a read hold -1) */
+		if(vread >= 0) *reinterpret_cast<uint4*>(l0m + ((size_t) vread * (np / 64) + (size_t)(node >> 6)) * 2) = make_uint4(mk0, mk1, mk2, mk3);
+		if(zm & cm) { /* a node that shares no column with some read of the tile (dist = 0 / 0: std::sort is undefined, the read takes the fallback
+		                           * rule): rare on complete sequences, so which read it was is looked up only here */
 #pragma unroll
-		for(int t = 0; t < T; ++t) {
-			const int read = slotRead[tile * T + t];
-			if(read < 0) continue;
-			const uint32_t v = ((d[t] << 16) | N[t]) + (ne ? acc[t][tid] : 0u);
-			if(__ballot(counts && v == 0u) && (tid & 63) == 0) atomicOr(&piv[(size_t) read * 4 + 3], 1u);
+			for(int t = 0; t < T; ++t) {
+				const int read = __builtin_amdgcn_readlane(vread, t);
+				if(read < 0) continue;
+				if((__ballot(N[t] == 0u) & cm) && lane == 0) atomicOr(&piv[(size_t) read * 4 + 3], 1u);
+			}
 		}
 	}
 }
