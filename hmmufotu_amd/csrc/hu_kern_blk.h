@@ -145,7 +145,11 @@ __global__ __launch_bounds__(THREADS) void k_estimate_blk(HuDbDev db, HuModelDev
  * integer exponents of the packed messages (k of 2^-k).  Relative error of the product of R mantissas is
  * <= R 2^-53, i.e. an absolute error of ~1.5e-13 on a log-likelihood of ~-1e3.
  * Pass 2 is table-driven: x_j = sum_i Q^b_i z_i with Q^b_i = pi_i (P(wnr) e_b)_i for a base b and
- * pi_i (P(wnr) pi)_i for a gap; every wave builds its own copy of the 5 x 4 table (no workgroup barrier).
+ * pi_i (P(wnr) pi)_i for a gap; ONE wave builds the 5 x 4 table for the workgroup.
+ * What depends on the slot alone runs in one wave, the BUILDER (wave blockIdx.x % NW, as k_place_blk's vt: the workgroups that share a
+ * CU put their serial work on different SIMDs): ratio and the six exponentials of the prologue, wnr, the table and the closing log.
+ * The other waves go straight to their loads and wait at a barrier, where they hold no issue slot.  Every wave passes the same four
+ * barriers: behind the load issue (the exponentials), behind the mismatch count, behind the table, in front of the output.
  * Component 0 of a message in the eigenbasis is pi . e and U(i,0) = 1, lam_0 = 0 (hu_model_prepare):
  * (P(t) e)_i = a_0 + sum_{m>0} U_im exp(lam_m t) a_m. */
 template<int CTRL>
@@ -185,8 +189,8 @@ __host__ __device__ constexpr int hu_est_waves(int spt, int occ) {
 	const int w = spt <= 2 ? 8 : spt <= 4 ? 5 : spt <= 6 ? 4 : spt <= 8 ? 3 : 2;
 	return occ > w ? occ : w;
 }
-/* DBG: diagnostic build (est_var = 98), s_memtime stamps into dbg[block][4]: the prologue up to the first vector load (the chain of scalar
- * loads and the per-wave exp), the load phase (first load issued .. last one returned), the rest, the workgroup's life */
+/* DBG: diagnostic build (est_var = 98), s_memtime stamps of the builder wave into dbg[block][4]: the prologue up to the first message load (the
+ * chain of scalar loads and the exp), the load phase (first load issued .. last one returned), the rest, the workgroup's life */
 template<int SPT, int NW, int OCC = 1, bool DBG = false>
 __global__ __launch_bounds__(64 * NW, hu_est_waves(SPT, OCC)) void k_estimate_prod(HuDbDev db, HuModelDev mdl, const int8_t* __restrict__ codes,
 		const int32_t* __restrict__ rstart, const int32_t* __restrict__ rend, const uint32_t* __restrict__ parDN,
@@ -198,34 +202,45 @@ __global__ __launch_bounds__(64 * NW, hu_est_waves(SPT, OCC)) void k_estimate_pr
 	if(DBG) { t0 = tl = (long long) __builtin_amdgcn_s_memtime(); }
 	__shared__ double redd[2 * NW];
 	__shared__ int redi[2 * NW];
-	__shared__ __attribute__((aligned(16))) double Qtab[NW][24];   /* [wave][0..3] = exp(lam_m wnr), [4 + b * 4 + i] = Q^b_i */
+	__shared__ __attribute__((aligned(16))) double Qtab[24];       /* [1..3] = exp(lam_m wnr), [4 + b * 4 + i] = Q^b_i */
+	__shared__ __attribute__((aligned(16))) double pro[12];        /* the builder's prologue: [0..2] = Eu, [3..5] = Ev, [8..11] = piw (weighted) */
+	__shared__ __attribute__((aligned(16))) double mtab[36];       /* pi, U, U1 for the table build, which indexes them by lane */
 	/* `order`: the (read, seed) slots sorted by seed NODE, so that the workgroups reading one node's messages run
 	 * together and all but the first find them in the Infinity Cache / L2 (reads of one sample share their seeds) */
 	const uint32_t slot = order ? order[hu_xcd_pos(blockIdx.x, gridDim.x, xmap)] : blockIdx.x;
-	const int read = slot / HU_MAX_SEEDS, s = slot % HU_MAX_SEEDS, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	if(s >= seedCnt[read] || hu_skip_width(db, rend[read] - rstart[read] + 1)) return;
+	const int read = slot / HU_MAX_SEEDS, s = slot % HU_MAX_SEEDS, tid = threadIdx.x, lane = tid & 63;
+	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       /* scalar: what only the builder does is a branch, not a mask */
+	const bool builder = wave == (int)(blockIdx.x % NW);
+	if(s >= seedCnt[read] || hu_skip_width(db, rend[read] - rstart[read] + 1)) return;    /* the whole workgroup, in front of every barrier */
 	const int un = seedId[(size_t) read * HU_MAX_SEEDS + s];
-	const int vn = db.parent[un];
-	const uint32_t dn = seedDN[(size_t) read * HU_MAX_SEEDS + s];
-	const uint32_t pv = parDN[(size_t) read * HU_MAX_SEEDS + s];      /* (d, N) against the parent's sequence */
-	const double cDist = (double)(dn >> 16) / (double)(dn & 0xffffu);
-	const double pDist = (double)(pv >> 16) / (double)(pv & 0xffffu);
-	double ratio = cDist / (cDist + pDist);
-	if(isnan(ratio)) ratio = 0.5;
-	const double w0 = db.blen[un];
-	const double wur = w0 * ratio, wvr = w0 - wur;
-	/* the six exponentials exp(lam_m w_ur), exp(lam_m w_vr), m = 1..3: ONE exp() per wave, lane l < 6 evaluating the l-th of them,
-	 * read back into scalar registers — every lane evaluating all six cost 5 x ~45 wave-instructions of the ~1,070 a wave executes */
-	double Eu[3], Ev[3];
-	{
+	double ratio = 0;
+	if(builder) {
+		/* the model constants of the table build, one per lane: the load is on its way while the scalar loads and the exp below run */
+		static_assert(offsetof(HuModelDev, U) == offsetof(HuModelDev, pi) + 64 && offsetof(HuModelDev, U1) == offsetof(HuModelDev, pi) + 192, "pi, logpi, U, U1 in a row");
+		const double* __restrict__ mp = reinterpret_cast<const double*>(reinterpret_cast<const char*>(&mdl) + offsetof(HuModelDev, pi));
+		const int l36 = lane < 36 ? lane : 0;
+		const double mc = mp[l36 < 4 ? l36 : l36 + 4];
+		const uint32_t dn = seedDN[(size_t) read * HU_MAX_SEEDS + s];
+		const uint32_t pv = parDN[(size_t) read * HU_MAX_SEEDS + s];      /* (d, N) against the parent's sequence */
+		const double cDist = (double)(dn >> 16) / (double)(dn & 0xffffu);
+		const double pDist = (double)(pv >> 16) / (double)(pv & 0xffffu);
+		ratio = cDist / (cDist + pDist);
+		if(isnan(ratio)) ratio = 0.5;
+		/* kept in scalar registers up to the output: the exponentials now arrive behind the loads, where every vector register is spoken for */
+		ratio = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(ratio)), __builtin_amdgcn_readfirstlane(__double2loint(ratio)));
+		const double w0 = db.blen[un];
+		const double wur = w0 * ratio, wvr = w0 - wur;
+		/* the six exponentials exp(lam_m w_ur), exp(lam_m w_vr), m = 1..3: ONE exp() per workgroup, lane l < 6 evaluating the l-th of them;
+		 * every wave takes them from LDS into scalar registers behind its loads */
 		const int l6 = lane < 6 ? lane : 0, m3 = l6 % 3;
 		const double e = exp((m3 == 0 ? mdl.lam[1] : m3 == 1 ? mdl.lam[2] : mdl.lam[3]) * (l6 < 3 ? wur : wvr));
-		const int lo = __double2loint(e), hi = __double2hiint(e);
-#pragma unroll
-		for(int k = 0; k < 3; ++k) {
-			Eu[k] = __hiloint2double(__builtin_amdgcn_readlane(hi, k), __builtin_amdgcn_readlane(lo, k));
-			Ev[k] = __hiloint2double(__builtin_amdgcn_readlane(hi, 3 + k), __builtin_amdgcn_readlane(lo, 3 + k));
+		if(lane < 6) pro[lane] = e;
+		if(weighted) { /* inferWeight(log pi) */
+			double piw[4];
+			{ double mx = max4d(mdl.logpi), sm; for(int i = 0; i < 4; ++i) piw[i] = exp(mdl.logpi[i] - mx); sm = (piw[0] + piw[2]) + (piw[1] + piw[3]); for(int i = 0; i < 4; ++i) piw[i] /= sm; }
+			if(lane < 4) pro[8 + lane] = sel4(piw, lane);
 		}
+		if(lane < 36) mtab[lane] = mc;
 	}
 	const int start = rstart[read], end = rend[read], n = end - start + 1;
 	const int8_t* __restrict__ cd = codes + (size_t) read * db.csLen + start;
@@ -237,6 +252,7 @@ __global__ __launch_bounds__(64 * NW, hu_est_waves(SPT, OCC)) void k_estimate_pr
 	 * their sums free their registers before z is built.  (Added under `j < n` inside the loop, they made each slot a block of its own
 	 * that ended in a wait for everything outstanding: six dependent round trips per workgroup at six sites per thread.) */
 	double z[SPT][4]; unsigned long long bop = 0; int ksum = 0;
+	double Eu[3], Ev[3];
 	double aU[SPT][4], aV[SPT][4];
 	/* uniform bases and a 32-bit site index: one offset register per load instead of an address pair, SPT slots of them are live at once */
 	const double* __restrict__ Ub = db.up + sOff * 4; const double* __restrict__ Vb = db.down + sOff * 4;
@@ -260,6 +276,16 @@ __global__ __launch_bounds__(64 * NW, hu_est_waves(SPT, OCC)) void k_estimate_pr
 			bop |= (unsigned long long)(b >= 0 ? b : 4) << (3 * t);
 		}
 		__builtin_amdgcn_sched_barrier(0);   /* nothing that waits for a load moves up among the loads */
+		lds_barrier();                       /* the builder's exponentials; waits for LDS and scalar loads, not for the messages */
+		{
+			const double e = pro[lane < 6 ? lane : 0];
+			const int lo = __double2loint(e), hi = __double2hiint(e);
+#pragma unroll
+			for(int k = 0; k < 3; ++k) {
+				Eu[k] = __hiloint2double(__builtin_amdgcn_readlane(hi, k), __builtin_amdgcn_readlane(lo, k));
+				Ev[k] = __hiloint2double(__builtin_amdgcn_readlane(hi, 3 + k), __builtin_amdgcn_readlane(lo, 3 + k));
+			}
+		}
 #pragma unroll
 		for(int t = 0; t < SPT; ++t) {
 			asm volatile("" : "+v"(kU[t]), "+v"(kV[t]));   /* the loads stay where they are: unconditional, ahead of the messages */
@@ -283,7 +309,7 @@ __global__ __launch_bounds__(64 * NW, hu_est_waves(SPT, OCC)) void k_estimate_pr
 	}
 	/* wnr: fraction of sites whose inferred state differs from the read's (method "unweighted"), or the
 	 * weighted form of src/PhyloTreeUnrooted.cpp:1034-1052 */
-	double wnr;
+	double wnr = 0;                                   /* the builder's */
 	if(!weighted) {
 		int nd = 0;
 #pragma unroll
@@ -294,14 +320,15 @@ __global__ __launch_bounds__(64 * NW, hu_est_waves(SPT, OCC)) void k_estimate_pr
 		}
 		if(lane == 0) redi[wave] = nd;
 		lds_barrier();
-		int tot = redi[0];
+		if(builder) {
+			int tot = redi[0];
 #pragma unroll
-		for(int w = 1; w < NW; ++w) tot += redi[w];
-		wnr = (double) tot / (double) n;
+			for(int w = 1; w < NW; ++w) tot += redi[w];
+			wnr = (double) tot / (double) n;
+		}
 	}
 	else {
-		double piw[4];
-		{ double mx = max4d(mdl.logpi), sm; for(int i = 0; i < 4; ++i) piw[i] = exp(mdl.logpi[i] - mx); sm = (piw[0] + piw[2]) + (piw[1] + piw[3]); for(int i = 0; i < 4; ++i) piw[i] /= sm; }
+		const double piwGap = pro[8 + piMax];          /* a gap site's second state is piMax */
 		double dsum = 0, nsum = 0;
 #pragma unroll
 		for(int t = 0; t < SPT; ++t) {
@@ -309,46 +336,49 @@ __global__ __launch_bounds__(64 * NW, hu_est_waves(SPT, OCC)) void k_estimate_pr
 			const int bi = (int)((bop >> (3 * t)) & 7u);
 			const int b1 = argmax4_tied_lin(z[t]), b2 = bi < 4 ? bi : piMax;
 			const double w1 = sel4(z[t], b1) / ((z[t][0] + z[t][2]) + (z[t][1] + z[t][3]));
-			const double w2 = bi < 4 ? 1.0 : piw[b2];
+			const double w2 = bi < 4 ? 1.0 : piwGap;
 			if(b1 != b2) dsum += w1 * w2;
 			nsum += w1 * w2;
 		}
 		dsum = wave_sum(dsum); nsum = wave_sum(nsum);
 		if(lane == 0) { redd[wave] = dsum; redd[NW + wave] = nsum; }
 		lds_barrier();
-		double a = redd[0], c = redd[NW];
+		if(builder) {
+			double a = redd[0], c = redd[NW];
 #pragma unroll
-		for(int w = 1; w < NW; ++w) { a += redd[w]; c += redd[NW + w]; }
-		wnr = a / c;
-		lds_barrier();   /* redd is reused below */
-	}
-	/* Q^b_i = pi_i (P(wnr) c^b)_i, c^b = e_b or pi; this wave's own copy */
-	double* Q = Qtab[wave];
-	if(lane < 3) Q[1 + lane] = exp((lane == 0 ? mdl.lam[1] : lane == 1 ? mdl.lam[2] : mdl.lam[3]) * wnr);
-	lds_wave_sync();
-	if(lane < 20) {
-		const int b = lane >> 2, i = lane & 3;
-		const double pii = sel4(mdl.pi, i);
-		double c;
-		if(wnr == 0) c = b < 4 ? (i == b ? 1.0 : 0.0) : pii;
-		else {
-			/* a = U^-1 c^b: column b of U1, or U1 . pi */
-			double a0, a1, a2, a3;
-			if(b < 4) { a0 = sel4(mdl.U1 + 0, b); a1 = sel4(mdl.U1 + 4, b); a2 = sel4(mdl.U1 + 8, b); a3 = sel4(mdl.U1 + 12, b); }
-			else {
-				a0 = (mdl.U1[0] * mdl.pi[0] + mdl.U1[1] * mdl.pi[1]) + (mdl.U1[2] * mdl.pi[2] + mdl.U1[3] * mdl.pi[3]);
-				a1 = (mdl.U1[4] * mdl.pi[0] + mdl.U1[5] * mdl.pi[1]) + (mdl.U1[6] * mdl.pi[2] + mdl.U1[7] * mdl.pi[3]);
-				a2 = (mdl.U1[8] * mdl.pi[0] + mdl.U1[9] * mdl.pi[1]) + (mdl.U1[10] * mdl.pi[2] + mdl.U1[11] * mdl.pi[3]);
-				a3 = (mdl.U1[12] * mdl.pi[0] + mdl.U1[13] * mdl.pi[1]) + (mdl.U1[14] * mdl.pi[2] + mdl.U1[15] * mdl.pi[3]);
-			}
-			const double Ui1 = i == 0 ? mdl.U[1] : i == 1 ? mdl.U[5] : i == 2 ? mdl.U[9] : mdl.U[13];
-			const double Ui2 = i == 0 ? mdl.U[2] : i == 1 ? mdl.U[6] : i == 2 ? mdl.U[10] : mdl.U[14];
-			const double Ui3 = i == 0 ? mdl.U[3] : i == 1 ? mdl.U[7] : i == 2 ? mdl.U[11] : mdl.U[15];
-			c = fmax(fma(Ui3, Q[3] * a3, fma(Ui2, Q[2] * a2, fma(Ui1, Q[1] * a1, a0))), 0.0);
+			for(int w = 1; w < NW; ++w) { a += redd[w]; c += redd[NW + w]; }
+			wnr = a / c;
 		}
-		Q[4 + b * 4 + i] = pii * c;
 	}
-	lds_wave_sync();
+	/* Q^b_i = pi_i (P(wnr) c^b)_i, c^b = e_b or pi: one copy, the builder's; pi, U, U1 by lane from mtab (indexed in the argument
+	 * segment they were five vector loads in the serial chain between the two barriers) */
+	double* Q = Qtab;
+	if(builder) {
+		if(lane < 3) Q[1 + lane] = exp((lane == 0 ? mdl.lam[1] : lane == 1 ? mdl.lam[2] : mdl.lam[3]) * wnr);
+		lds_wave_sync();
+		if(lane < 20) {
+			const int b = lane >> 2, i = lane & 3;
+			const double* mU = mtab + 4 + i * 4, * mU1 = mtab + 20 + (b & 3);
+			const double pii = mtab[i];
+			double c;
+			if(wnr == 0) c = b < 4 ? (i == b ? 1.0 : 0.0) : pii;
+			else {
+				/* a = U^-1 c^b: column b of U1, or U1 . pi */
+				double a0, a1, a2, a3;
+				if(b < 4) { a0 = mU1[0]; a1 = mU1[4]; a2 = mU1[8]; a3 = mU1[12]; }
+				else {
+					a0 = (mdl.U1[0] * mdl.pi[0] + mdl.U1[1] * mdl.pi[1]) + (mdl.U1[2] * mdl.pi[2] + mdl.U1[3] * mdl.pi[3]);
+					a1 = (mdl.U1[4] * mdl.pi[0] + mdl.U1[5] * mdl.pi[1]) + (mdl.U1[6] * mdl.pi[2] + mdl.U1[7] * mdl.pi[3]);
+					a2 = (mdl.U1[8] * mdl.pi[0] + mdl.U1[9] * mdl.pi[1]) + (mdl.U1[10] * mdl.pi[2] + mdl.U1[11] * mdl.pi[3]);
+					a3 = (mdl.U1[12] * mdl.pi[0] + mdl.U1[13] * mdl.pi[1]) + (mdl.U1[14] * mdl.pi[2] + mdl.U1[15] * mdl.pi[3]);
+				}
+				const double Ui1 = mU[1], Ui2 = mU[2], Ui3 = mU[3];
+				c = fmax(fma(Ui3, Q[3] * a3, fma(Ui2, Q[2] * a2, fma(Ui1, Q[1] * a1, a0))), 0.0);
+			}
+			Q[4 + b * 4 + i] = pii * c;
+		}
+	}
+	lds_barrier();   /* the table; redd is free again */
 	/* log-likelihood: product of the mantissas, sum of the exponents */
 	double mant = 1.0; int esum = ksum;
 #pragma unroll
@@ -364,7 +394,7 @@ __global__ __launch_bounds__(64 * NW, hu_est_waves(SPT, OCC)) void k_estimate_pr
 	esum = wave_sum_i32(esum);
 	if(lane == 0) { redd[wave] = mant; redi[NW + wave] = esum; }
 	lds_barrier();
-	if(tid == 0) {
+	if(builder && lane == 0) {
 		double m = redd[0]; long long e = redi[NW];
 #pragma unroll
 		for(int w = 1; w < NW; ++w) { m *= redd[w]; e += redi[NW + w]; }
@@ -373,7 +403,7 @@ __global__ __launch_bounds__(64 * NW, hu_est_waves(SPT, OCC)) void k_estimate_pr
 	}
 	if(DBG) {
 		stamp(2);
-		if(tid == 0) { tk[3] = tl - t0; for(int i = 0; i < 4; ++i) dbg[(size_t) blockIdx.x * 4 + i] = tk[i]; }
+		if(builder && lane == 0) { tk[3] = tl - t0; for(int i = 0; i < 4; ++i) dbg[(size_t) blockIdx.x * 4 + i] = tk[i]; }
 	}
 }
 
