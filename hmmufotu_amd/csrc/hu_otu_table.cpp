@@ -237,6 +237,10 @@ int hu_otu_subset_check(const char* fn, int64_t n_otu, int64_t n_sample, const d
 	if(opts) *eff = *opts;
 	if(eff->chunk < 1 || eff->chunk > (1 << 24)) { hu_set_error("%s: chunk %d: 1 .. %d reads per workgroup", fn, eff->chunk, 1 << 24); return HU_ERR_ARG; }
 	if(eff->key_bits < 1 || eff->key_bits > 64) { hu_set_error("%s: key_bits %d: 1 .. 64", fn, eff->key_bits); return HU_ERR_ARG; }
+	return hu_otu_cells_check(fn, n_otu, n_sample, counts, total);
+}
+
+int hu_otu_cells_check(const char* fn, int64_t n_otu, int64_t n_sample, const double* counts, std::vector<uint64_t>& total) {
 	total.assign((size_t) n_sample, 0);
 	for(int64_t i = 0; i < n_otu; ++i) for(int64_t j = 0; j < n_sample; ++j) {
 		const double v = counts[(size_t) i * n_sample + j];

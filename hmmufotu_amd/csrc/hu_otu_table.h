@@ -31,6 +31,8 @@ HU_HD inline uint64_t hu_otu_draw(const uint32_t k[2], uint64_t m, uint32_t j, u
 /* the arguments of hu_otu_subset, checked; total [n_sample]: the column sums, each < 2^32 */
 int hu_otu_subset_check(const char* fn, int64_t n_otu, int64_t n_sample, const double* counts, uint64_t size, int method, const hu_otu_opts* opts,
 		const double* out, hu_otu_opts* eff, std::vector<uint64_t>& total);
+/* the cells alone: non-negative integers, every column sum below 2^32 (hu_alpha_host.cpp asks the same of its table) */
+int hu_otu_cells_check(const char* fn, int64_t n_otu, int64_t n_sample, const double* counts, std::vector<uint64_t>& total);
 /* the host path, on checked arguments */
 void hu_otu_subset_host(int64_t n_otu, int64_t n_sample, const double* counts, const std::vector<uint64_t>& total, uint64_t size, int method, uint64_t seed,
 		int key_bits, double* out);

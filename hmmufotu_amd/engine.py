@@ -999,6 +999,70 @@ def pcoa_timing() -> dict:
     return dict(to_device=s[0], square=s[1], product=s[2], small=s[3], host_mxm=s[4], to_host=s[5])
 
 
+class AlphaOpts(C.Structure):
+    _fields_ = [("host", C.c_int32), ("chunk", C.c_int32), ("key_bits", C.c_int32), ("reserved", C.c_int32), ("draw_chunk", C.c_int64), ("mem_budget", C.c_int64)]
+
+
+ALPHA_REC = np.dtype([("reads", np.uint64), ("S", np.uint64), ("F1", np.uint64), ("F2", np.uint64), ("Q", np.uint64), ("A", np.float64), ("PD", np.float64),
+                      ("observed", np.float64), ("singles", np.float64), ("doubles", np.float64), ("chao1", np.float64), ("shannon", np.float64),
+                      ("simpson", np.float64), ("goods_coverage", np.float64), ("faith_pd", np.float64)])
+
+
+def _alpha_args(what, counts, otu_node, parent, blen, depths, host, chunk, key_bits, draw_chunk, mem_budget):
+    c, _, tree, node, keep = _unifrac_args(what, counts, otu_node, parent, blen, "unweighted", None, 0, host, 0)
+    o = AlphaOpts()
+    load_library().hu_alpha_default_opts(C.byref(o))
+    o.host = 1 if host else 0; o.key_bits = int(key_bits); o.draw_chunk = int(draw_chunk or 0); o.mem_budget = int(mem_budget or 0)
+    if chunk is not None:
+        o.chunk = int(chunk)
+    if any(int(m) < 0 or int(m) >= 2 ** 64 for m in depths):
+        raise EngineError(what + ": a depth is a whole number")
+    d = np.array([int(m) for m in depths], np.uint64)
+    return c, o, tree, node, d, keep
+
+
+def alpha_diversity(counts, otu_node=None, parent=None, blen=None, depths=(), reps=0, seed=1, device=0, host=False, chunk=None, key_bits=64, draw_chunk=0, mem_budget=0) -> dict:
+    """hu_alpha: the alpha diversity of every column of counts [otus][samples], and of its rarefied draws: dict(whole, draws), each a dict
+    of named arrays (reads, S, F1, F2, Q, A, PD, observed, singles, doubles, chao1, shannon, simpson, goods_coverage, faith_pd); whole
+    [samples], draws [samples][depths][reps].  The draw (j, m, r) is column j of otu_subset(counts, m, seed=seed + r); one that does not
+    exist (m above the sample's reads) has reads 0 and NaN.  With a tree (parent [nodes] with -1 for the root, blen [nodes], otu_node [otus])
+    PD is Faith's PD, without one NaN.  host, or device < 0: the library's host path, no device needed."""
+    c, o, tree, node, d, keep = _alpha_args("alpha_diversity", counts, otu_node, parent, blen, depths, host or int(device) < 0, chunk, key_bits, draw_chunk, mem_budget)
+    S = c.shape[1]
+    R = int(reps)
+    if S * len(d) * max(R, 0) > 2 ** 31:                            # the library's refusal, before the room for the draws is asked for
+        raise EngineError("alpha_diversity: %d depths x %d repeats x %d samples: more than 2^31 draws" % (len(d), R, S))
+    whole = np.zeros(S, ALPHA_REC); draws = np.zeros((S, len(d), max(R, 0)), ALPHA_REC)
+    _chk(load_library().hu_alpha(C.c_int(int(device)), C.byref(tree) if tree is not None else None, C.c_int64(c.shape[0]), C.c_int64(S), node, _p(c, C.c_double),
+                                 C.c_int64(len(d)), _p(d, C.c_uint64) if len(d) else None, C.c_int64(R), C.c_uint64(int(seed) & (2 ** 64 - 1)), C.byref(o),
+                                 whole.ctypes.data_as(C.c_void_p), draws.ctypes.data_as(C.c_void_p) if draws.size else None))
+    return dict(whole={f: whole[f].copy() for f in ALPHA_REC.names}, draws={f: draws[f].copy() for f in ALPHA_REC.names})
+
+
+def alpha_sizes(counts, otu_node=None, parent=None, blen=None, depths=(), reps=0, chunk=None) -> dict:
+    """hu_alpha_sizes: what alpha_need takes, for a call of alpha_diversity: dict(n_cell, n_entry, max_nnz, max_chunk, n_draw, n_branch);
+    n_draw counts the whole samples too"""
+    c, o, tree, node, d, keep = _alpha_args("alpha_sizes", counts, otu_node, parent, blen, depths, True, chunk, 64, 0, 0)
+    out = np.zeros(6, np.int64)
+    _chk(load_library().hu_alpha_sizes(C.byref(tree) if tree is not None else None, C.c_int64(c.shape[0]), C.c_int64(c.shape[1]), node, _p(c, C.c_double),
+                                       C.c_int64(len(d)), _p(d, C.c_uint64) if len(d) else None, C.c_int64(int(reps)), C.byref(o), _p(out, C.c_int64)))
+    return dict(zip(("n_cell", "n_entry", "max_nnz", "max_chunk", "n_draw", "n_branch"), (int(v) for v in out)))
+
+
+def alpha_need(n_sample: int, n_cell: int, n_entry: int, max_nnz: int, max_chunk: int, n_draw: int) -> int:
+    """hu_alpha_need: the bytes of device memory for n_draw resident draws"""
+    lib = load_library()
+    lib.hu_alpha_need.restype = C.c_int64
+    return int(lib.hu_alpha_need(*(C.c_int64(int(v)) for v in (n_sample, n_cell, n_entry, max_nnz, max_chunk, n_draw))))
+
+
+def alpha_timing() -> dict:
+    """hu_alpha_timing: the phases of this thread's last alpha_diversity on a device, in seconds"""
+    s = np.zeros(6)
+    _chk(load_library().hu_alpha_timing(_p(s, C.c_double)))
+    return dict(to_device=s[0], select=s[1], take=s[2], metrics=s[3], pd=s[4], to_host=s[5])
+
+
 class NjOpts(C.Structure):
     _fields_ = [("host", C.c_int32), ("reserved", C.c_int32), ("mem_budget", C.c_int64)]
 

@@ -1618,6 +1618,78 @@ int64_t hu_pcoa_need(int64_t n, int64_t k, int64_t oversample);
 int64_t hu_pcoa_slabs(int64_t n);
 int hu_pcoa_timing(double* seconds /* [6] */);
 
+/* ---- hmmufotu-amd-alpha: alpha diversity of the samples of an OTU table, and rarefaction curves ----
+ * Column j of counts [n_otu][n_sample] is a sample; its cells n_i are non-negative integers, N = sum n_i, 0 < N < 2^32 (the checks of
+ * hu_otu_subset; a sample without reads is refused as hu_unifrac refuses it).
+ * Integer statistics, exact, the same on host and device:
+ *     S = #{n_i > 0},  F1 = #{n_i = 1},  F2 = #{n_i = 2},  Q = sum n_i^2  (Q <= N^2 < 2^64)
+ * Float statistics:
+ *     A  = sum over n_i >= 2 of n_i ln n_i
+ *     PD = sum of b_k over the kept branches k below which the sample has a read.  The tree, the convention for reads on inner nodes and
+ *          for an OTU that is the root, and the branch numbering are hu_unifrac's.  Without a tree (tree == NULL) PD is NaN.
+ * Metrics, by hu_alpha_metrics on both paths:
+ *     observed = S, singles = F1, doubles = F2
+ *     chao1 = S + (double) F1 * (double) (F1 - 1) / (2.0 * (double) (F2 + 1))        (bias-corrected, always defined)
+ *     shannon = max(0, ln N - A / N) in nats, exactly 0 when S <= 1
+ *     simpson = 1 - (double) Q / ((double) N * (double) N)
+ *     goods_coverage = 1 - (double) F1 / (double) N
+ *     faith_pd = PD
+ * Rarefied draws: the draw (j, m, r), 1 <= m <= N_j, r = 0 .. reps - 1, is column j of hu_otu_subset(counts, m, HU_OTU_UNIFORM,
+ * seed + r) (the sum wraps at 2^64), and its metrics are that column's: a definition by names.  m = N_j is the whole sample; for
+ * m > N_j the draw does not exist: reads = 0, the integers 0 and every double NaN.  For a fixed (j, r) the kept sets are nested in m
+ * (the m smallest (key, t) of one key sequence); the tie rule and key_bits are hu_otu_subset's.
+ * hu_alpha: whole_out [n_sample], draws_out [n_sample][n_depth][reps] (may be NULL when n_depth * reps == 0).  depths [n_depth] strictly
+ * ascending, each >= 1.  opts->host, or device < 0: the host path, no device needed.  The device path uploads every sample's nonzero cells
+ * once and keeps them resident: their prefixes in table order, which numbers the reads as hu_otu_subset does, and for each cell its
+ * place in the depth-first row order of hu_unifrac's embedding, in which a draw's cells are kept; draws are processed
+ * draw_chunk at a time (0: as many as the memory holds): the cut key of every draw by the radix select of hu_otu_subset, the keys of a
+ * (sample, repeat) computed once per pass for up to 8 depths, the kept reads counted into the draw's copy of the sample's nonzero cells
+ * (never [n_otu][draws]), one kernel for S, F1, F2, Q, A and one for PD (a presence prefix over the draw's cells and the sample's branch
+ * intervals); 40 bytes per draw come back.  S, F1, F2, Q: integer sums.  A: thread x of 256 adds the draw's cells x, x + 256, ... of that order;
+ * PD: thread x adds the sample's branch entries x, x + 256, ... (ascending branch number; an absent branch adds +0); the 256 partial sums
+ * are then added as a tree: within each 64 v[l] += v[l + d] for d = 32, 16, .. 1, then (w0 + w1) + (w2 + w3).  The host path adds PD in
+ * that order (the same bits) and A in ascending cell order (libm's log: the same value within DESIGN §30's bound, not the same bits).
+ * No result depends on chunk, draw_chunk, the grid or the device.
+ * HU_ERR_ARG with the reason, before a device is asked for: the cell and total checks of hu_otu_subset, the tree checks of hu_unifrac,
+ * a sample without reads, a depth of 0, depths not strictly ascending, reps < 0, reps == 0 with depths given, n_depth * reps * n_sample
+ * above 2^31, key_bits, chunk, draw_chunk or mem_budget out of range.  HU_ERR_NOMEM naming both numbers when hu_alpha_need for the
+ * draw_chunk (for one draw when it is 0) exceeds mem_budget (checked before a device is asked for) or what the device reports free.
+ * hu_alpha_need: the bytes on the device for n_draw resident draws of a table with n_sample samples, n_cell nonzero cells, n_entry
+ * branch entries (pairs of a sample and a kept branch below which it has a nonzero cell), max_nnz the most nonzero cells of a sample
+ * and max_chunk the largest ceil(N_j / chunk):
+ *     32 n_sample + 4 (2 n_cell + n_sample) + 16 n_entry + n_draw (1136 + 4 max_nnz + 24 max_chunk) + 2^20
+ * (the samples, their prefixes and places, the entries; per draw its record, selection state, histogram, result, group, cells, tie counts and
+ * chunk list; 1 MB of slack); -1 on a negative argument.  The whole samples count as draws.
+ * hu_alpha_sizes: out [6] = n_cell, n_entry, max_nnz, max_chunk, the draws of the call (n_sample whole ones included), the kept
+ * branches B: what hu_alpha_need takes, for the same arguments and refusals as hu_alpha.  Host only.
+ * hu_alpha_metrics: the metrics of a record from its reads, S, F1, F2, Q, A and PD.
+ * hu_alpha_curve: x [n] -> *mean = (x_0 + x_1 + ...) / n added in ascending order, *sd = sqrt(sum (x - mean)^2 / (n - 1)) in the same
+ * order, NaN for n == 1; HU_ERR_ARG for n < 1.
+ * hu_alpha_timing: of this thread's last device call, seconds [6] = copies up, select, take, metrics, PD, copy back. */
+typedef struct {
+	int32_t host;         /* 0; 1: the host path, no device needed */
+	int32_t chunk;        /* 16384: reads per workgroup */
+	int32_t key_bits;     /* 64; below 64 keys tie: for the tie tests only */
+	int32_t reserved;
+	int64_t draw_chunk;   /* 0: as many draws resident as the memory holds */
+	int64_t mem_budget;   /* 0: what the device reports free */
+} hu_alpha_opts;
+typedef struct {
+	uint64_t reads;       /* N of the column: N_j, or m for a draw; 0: the draw does not exist */
+	uint64_t S, F1, F2, Q;
+	double A, PD;
+	double observed, singles, doubles, chao1, shannon, simpson, goods_coverage, faith_pd;
+} hu_alpha_rec;
+void hu_alpha_default_opts(hu_alpha_opts* o);
+int hu_alpha(int device, const hu_unifrac_tree* tree, int64_t n_otu, int64_t n_sample, const int32_t* otu_node, const double* counts,
+		int64_t n_depth, const uint64_t* depths, int64_t reps, uint64_t seed, const hu_alpha_opts* opts, hu_alpha_rec* whole_out, hu_alpha_rec* draws_out);
+int64_t hu_alpha_need(int64_t n_sample, int64_t n_cell, int64_t n_entry, int64_t max_nnz, int64_t max_chunk, int64_t n_draw);
+int hu_alpha_sizes(const hu_unifrac_tree* tree, int64_t n_otu, int64_t n_sample, const int32_t* otu_node, const double* counts,
+		int64_t n_depth, const uint64_t* depths, int64_t reps, const hu_alpha_opts* opts, int64_t* out /* [6] */);
+void hu_alpha_metrics(hu_alpha_rec* r);
+int hu_alpha_curve(int64_t n, const double* x, double* mean, double* sd);
+int hu_alpha_timing(double* seconds /* [6] */);
+
 #ifdef __cplusplus
 }
 #endif
