@@ -459,6 +459,7 @@ __device__ inline double em_branch_blk(const double (&rho)[SPT], int nvalidWave,
 	auto stamp = [&](int i) { if(st) { const long long t = (long long) __builtin_amdgcn_s_memtime(); st[i] += t - tl; tl = t; } };
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	double p0 = 1 - q0, p = p0, q = q0, rc = 0;
+	const int em0 = emIters;
 	if(lane == 0) redc[(phase & 1) * NW + wave] = (double) nvalidWave;
 	for(int it = 0; it < HU_MAX_ITER && p >= 0 && p <= 1; ++it) {
 		double s = 0;
@@ -545,6 +546,10 @@ __device__ inline double em_branch_blk(const double (&rho)[SPT], int nvalidWave,
 	}
 	double w = -hu_log_call(q);
 	if(w > maxL) w = maxL;
+	/* every term p0 / x is at most 1, and the reference's quotient never rounds above it; p0 times a rounded reciprocal can, by an ulp,
+	 * once q is below 2^-53 (a one-column read against a leaf of another base, deep tree).  The loop has then ended on p > 1 with
+	 * q = 1 - p < 0, and -log q is NaN, where the reference reads p = 1, q = 0, runs its passes out on log 0 and takes the cap */
+	if(q < 0) { w = maxL; emIters = em0 + HU_MAX_ITER; }
 	return w;
 }
 

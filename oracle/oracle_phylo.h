@@ -428,8 +428,16 @@ struct AssignOpts {
 /* the SEP part of the per-read task (src/hmmufotu.cpp:641-647,720-733); seq = DigitalSeq of
  * the alignment, [start,end] 0-based inclusive */
 inline std::vector<Placement> assignSeq(const Tree& t, const int8_t* seq, int start, int end, const AssignOpts& o,
-		std::vector<PTLoc>* seedsOut = nullptr, std::vector<Placement>* estOut = nullptr, std::vector<int>* filtOut = nullptr) {
-	std::vector<PTLoc> seeds = getSeed(t, seq, start, end, o.maxDiff, o.maxHeight, o.tieMode, (size_t) o.maxNSeed);
+		std::vector<PTLoc>* seedsOut = nullptr, std::vector<Placement>* estOut = nullptr, std::vector<int>* filtOut = nullptr,
+		const std::vector<long>* given = nullptr) {
+	std::vector<PTLoc> seeds;
+	if(!given) seeds = getSeed(t, seq, start, end, o.maxDiff, o.maxHeight, o.tieMode, (size_t) o.maxNSeed);
+	else for(long id : *given) { /* the caller's seeds in the caller's order, their distances over the region as scanSeeds counts them */
+		PTLoc l; l.start = start; l.end = end; l.id = id;
+		pdist_counts(seq, t.S(id), start, end, l.d, l.N);
+		l.dist = static_cast<double>(l.d) / l.N;
+		seeds.push_back(l);
+	}
 	if(seedsOut) *seedsOut = seeds;
 	std::vector<Placement> places;
 	for(const PTLoc& l : seeds) places.push_back(estimateSeq(t, seq, l, o.weighted != 0, o.tieTol));

@@ -172,15 +172,20 @@ class Tree:
                              C.c_double(wnr0), C.c_double(max_height), C.c_int(int(fix_root)), _p(out, C.c_double), C.byref(a), _p(it, C.c_int))
         return dict(loglik=out[0], wnr=out[1], ratio=out[2], height=out[3], aNode=a.value, iters=int(it[0]), em_iters=int(it[1]))
 
-    def assign(self, seq, start, end, opts=None):
+    def assign(self, seq, start, end, opts=None, seeds=None):
+        """seeds: node ids that take the place of getSeed's (their distances are counted over the region)"""
         opts = opts or default_opts()
         seq = np.ascontiguousarray(seq, np.int8)
-        m = max(opts.maxNSeed, 1)
+        m = max(opts.maxNSeed, 1) if seeds is None else max(len(seeds), 1)
         ni = np.zeros((m, 4), np.int32); nd = np.zeros((m, 8)); ns = C.c_int(0)
         sid = np.zeros(m, np.int64); sd = np.zeros(m, np.int64); sn = np.zeros(m, np.int64); est = np.zeros((m, 3))
         fo = np.zeros(m, np.int32)
-        n = lib().orc_assign(self.h, _p(seq, C.c_int8), C.c_int(start), C.c_int(end), C.byref(opts), _p(ni, C.c_int), _p(nd, C.c_double),
-                             C.byref(ns), _p(sid, C.c_long), _p(sd, C.c_long), _p(sn, C.c_long), _p(est, C.c_double), _p(fo, C.c_int))
+        out = (_p(ni, C.c_int), _p(nd, C.c_double), C.byref(ns), _p(sid, C.c_long), _p(sd, C.c_long), _p(sn, C.c_long), _p(est, C.c_double), _p(fo, C.c_int))
+        if seeds is None:
+            n = lib().orc_assign(self.h, _p(seq, C.c_int8), C.c_int(start), C.c_int(end), C.byref(opts), *out)
+        else:
+            given = np.ascontiguousarray(seeds, np.int64)
+            n = lib().orc_assign_given(self.h, _p(seq, C.c_int8), C.c_int(start), C.c_int(end), C.byref(opts), C.c_int(len(given)), _p(given, C.c_long), *out)
         k = ns.value
         return dict(n=n, nodes=ni[:n], vals=nd[:n], seed_ids=sid[:k], seed_d=sd[:k], seed_N=sn[:k], est=est[:k], filt_order=fo[:n])
 

@@ -1,6 +1,7 @@
-"""Regenerates tests/golden/hiprec.npz and hiprec_wide.npz: the floating-point stages of the per-read task in 50-digit arithmetic.
+"""Regenerates tests/golden/hiprec.npz, hiprec_wide.npz and hiprec_deep.npz: the floating-point stages of the per-read task in 50-digit
+arithmetic.
 
-    python tests/golden/make_hiprec_golden.py [--set narrow|wide] [--out PATH] [--workers N]
+    python tests/golden/make_hiprec_golden.py [--set narrow|wide|deep] [--out PATH] [--workers N]
 
 A second derivation, independent of oracle/ and of the engine: it is written from the reference's source (cited as file:line below)
 and the mathematics, imports neither, and works in LINEAR space with mpmath (mp.dps = 50) where both of them work in log space with
@@ -30,11 +31,41 @@ region of `cols` columns, every other site a gap), one per width class of the es
 as above, q complements for three reads.  To stay under the size cap it holds the messages and the per-column root log-likelihood at the
 MSG_COLS columns only (and the serial sum over all columns), and no P(t) block.  It costs about 65 CPU-minutes (9 minutes with 8 workers).  The conditions above hold for it with its own read seed.
 
+--set deep (hiprec_deep.npz) is the same mathematics where the two log-space implementations rescale: messages below -510
+(src/PhyloTreeUnrooted.h:1495-1510), which no message of the other two sets comes near.  Two databases of 1,024 leaves x 96 columns, 64 of
+them match columns: GTR with 4 rate categories at a mean branch length of 0.3 (19 match columns with a root message below -510, the lowest
+-766; 45 above it, the highest -44), and JC69 without dGamma at 0.15 (all 64 below, the lowest -963).  The 32 all-gap columns lie lower
+still (-1,197 / -1,420).  Asserted from the 50-digit messages themselves (change the database arguments if one fails, not the
+conditions): at least 16 match columns with a root message below -510; no message whose finite components are 200 nats or more apart (the
+largest spread is 19.3, so no component underflows under the reference's rule and the exact value is what that rule is meant to compute);
+every inner row of the data the argmax of the exact message.
+  Reads (make_deep_reads), six per database, all within the 96 columns: the whole width (a leaf with 3 % substitutions; on GTR+4 it holds
+  bases on at least 5 deep and 5 other match columns, asserted: 18 and 45), 80 columns equal to a leaf, 65 columns all gaps but the two
+  ends, 90 columns 30 % diverged, one deep match column, and two neighbouring columns of which one is a deep match column and the other is
+  not deep (JC69 has no such column: there both are deep match columns).  The columns of the two short reads are chosen with synth's float64
+  root message and asserted against the 50-digit one.
+  Candidates (cand_nodes), at most 48 per read and from the tree alone: every ancestor of the read's leaf up to a child of the root, their
+  siblings (so both children of the root), and four leaves of the other root subtree.  Asserted per read: the list holds a leaf, a branch
+  with only `down` below -510 at a column of the read, and -- for the four reads wider than two columns -- a branch with `up` and `down`
+  both below -510 at one column (up + down of a column is about its root message, so this happens at all-gap columns only, which the
+  two short reads do not hold).
+  Stored: per read and candidate what the other archives hold (`cand` [reads][W] names the nodes, -1 past the end of a list), the q
+  complements for two reads, the messages of the candidate nodes alone (msg_nodes) at the MSG_COLS columns with the lowest, a median and
+  the highest root message, the root log-likelihood of all 96 columns and its serial sum, the heights; SHA-256 digests of parent / blen /
+  seq in place of the arrays (2,047 x 96 rows do not fit the size cap), which tests/hiprec_cases.py compares with the database it rebuilds.
+  `up` is swept over all 2,047 nodes, `down` over the candidates and their ancestors, by column chunks in parallel.
+  On a deep tree a one-column read that differs from a candidate sends q = 1 - p of the 2-node EM below 1e-50 within the 100 passes (em2
+  then takes the same number without the cancellation), and a one-hot message against another base at length 0 makes the length infinite
+  in exact arithmetic too (the reference runs its passes out on log 0 and takes the cap: stored as the cap, knife-edge).  With the read
+  seed in use (2681) 0 of 180 (GTR+4) and 7 of 164 (JC69, 4.3 %) candidates are knife-edge.  Measured cost: 155 CPU-seconds, 27 s of wall
+  time with 8 workers (21 s of them the message sweeps).
+
 The archive is written with fixed zip timestamps, so a rerun reproduces it byte for byte.
 """
 from __future__ import annotations
 
 import argparse
+import hashlib
 import io
 import multiprocessing
 import os
@@ -69,7 +100,12 @@ WIDE_READS = [(512, 120), (513, 100), (1024, 256), (1024, 257), (1025, 150), (15
               (2049, 250), (3072, 500), (3073, 300)]                # (columns, base sites) of each read
 WIDE = dict(name="wide", out="hiprec_wide.npz", cases=[("GTR", 4), ("JC69", 0)], db_args=dict(n_leaves=8, cs_len=3300, n_match=None),
             read_seed=2031, q_reads=(2, 5, 10))                     # q-values for (1024, 256), (1536, 256) and (3072, 500)
-SETS = dict(narrow=NARROW, wide=WIDE)
+# --set deep: 1,024 leaves x 96 columns with long branches, so that messages lie below the -510 at which both log-space implementations rescale
+DEEP = dict(name="deep", out="hiprec_deep.npz", cases=[("GTR", 4), ("JC69", 0)], db_args=dict(n_leaves=1024, cs_len=96, n_match=64),
+            mean_blen=(0.3, 0.15), read_seed=2681, q_reads=(0, 3))  # q-values for the whole-width and the 30 % diverged read
+DEEP_LL = -510                                                   # src/PhyloTreeUnrooted.h:1495-1510: messages below it are rescaled there
+DEEP_MIN_COLS, DEEP_MAX_SPREAD, DEEP_MAX_CAND = 16, 200, 48
+SETS = dict(narrow=NARROW, wide=WIDE, deep=DEEP)
 A, C, G, T = 0, 1, 2, 3
 
 
@@ -331,6 +367,211 @@ def make_wide_reads(s):
     return reads
 
 
+# ----------------------------------------------------------------------------- the deep set
+def deep_setup(ci, cfg=DEEP):
+    """the data of a deep case, its six reads and their candidate lists; no message yet.  The columns of the two short reads are CHOSEN with
+    synth's float64 root message (data, like the rows); that they are deep or not is asserted from the 50-digit values in deep_state."""
+    from hmmufotu_amd import synth
+    name, dg_k = cfg["cases"][ci]
+    da = cfg["db_args"]
+    db = synth.make_db(da["n_leaves"], da["cs_len"], name, dg_k, n_match=da["n_match"], mean_blen=cfg["mean_blen"][ci])
+    s = DbState()
+    s.ci, s.name, s.dg_k = ci, name, dg_k
+    s.n, s.L = db.n_nodes, db.cs_len
+    s.parent = [int(x) for x in db.parent]
+    s.blen = [mpf(float(x)) for x in db.blen]
+    s.is_leaf = [bool(x) for x in db.is_leaf]
+    s.anno = [int(x) for x in db.anno_id]
+    s.rates = [mpf(float(x)) for x in db.dg_r] if dg_k > 0 else [mpf(1)]
+    s.model = ModelP(name, db.model.pi, db.model.par)
+    s.seq = np.array(db.seq, np.int8)
+    s.read_seed = cfg["read_seed"]
+    s.digests = {k: hashlib.sha256(np.ascontiguousarray(a).tobytes()).digest()
+                 for k, a in (("parent", np.asarray(db.parent, np.int32)), ("blen", np.asarray(db.blen, np.float64)), ("seq", s.seq))}
+    s.kids = [[] for _ in range(s.n)]
+    for i in range(1, s.n):
+        s.kids[s.parent[i]].append(i)
+    s.match = (s.seq[np.array(s.is_leaf)] < 0).mean(0) < 0.5    # the columns make_db drew as match columns: few leaf gaps
+    root = np.asarray(db.up[0]); mx = root.max(1)
+    s.ll_synth = mx + np.log((np.asarray(db.model.pi)[None, :] * np.exp(root - mx[:, None])).sum(1))
+    s.reads, s.src = make_deep_reads(s)
+    s.cands = [cand_nodes(s, u) for u in s.src]
+    s.msg_nodes = sorted(set(u for c in s.cands for u in c))
+    need = set()                                                 # down of a node takes its parent's: the candidates and their ancestors
+    for u in s.msg_nodes:
+        while u != 0 and u not in need:
+            need.add(u); u = s.parent[u]
+    s.need_down = sorted(need)
+    h = [None] * s.n                                             # src/PhyloTreeUnrooted.cpp:274-287
+    for u in range(s.n - 1, -1, -1):
+        h[u] = mpf(0) if s.is_leaf[u] else min(h[c] + s.blen[c] for c in s.kids[u])
+    s.height = h
+    return s
+
+
+def make_deep_reads(s):
+    """(codes [L], start, end) x 6 within the 96 columns, made as make_reads makes the narrow ones: the whole width (a leaf with 3 %
+    substitutions and its gaps), 80 columns equal to a leaf, 65 columns all gaps but the two ends, 90 columns 30 % diverged, one deep
+    match column, and two neighbouring columns of which one is a deep match column and the other is not deep.  Also each read's leaf."""
+    rng = np.random.default_rng(s.read_seed + s.ci)
+    leaves = np.flatnonzero(s.is_leaf)
+    L = s.L
+
+    def from_leaf(cols, mut, gaps, start=None):
+        u = int(leaves[rng.integers(len(leaves))])
+        if start is None:
+            start = int(rng.integers(0, L - cols + 1))
+        end = start + cols - 1
+        at = np.arange(start, end + 1)
+        b = np.where(s.seq[u, at] >= 0, s.seq[u, at], s.seq[s.parent[u], at]).astype(np.int8)
+        m = rng.random(cols) < mut
+        b[m] = (b[m] + rng.integers(1, 4, size=int(m.sum()))) % 4
+        if gaps == "leaf":
+            g = s.seq[u, at] < 0
+            g[0] = g[-1] = False
+            b[g] = GAP
+        elif gaps == "all":
+            b[1:-1] = GAP
+        codes = np.full(L, GAP, np.int8)
+        codes[at] = b
+        return codes, start, end, u
+
+    reads = [from_leaf(L, 0.03, "leaf")]
+    while True:                                                  # equal to a leaf wherever both hold a base
+        cd, st, en, u = from_leaf(80, 0.0, "leaf")
+        both = (cd >= 0) & (s.seq[u] >= 0)
+        if both.sum() >= 40:
+            assert (cd[both] == s.seq[u][both]).all()
+            reads.append((cd, st, en, u))
+            break
+    reads.append(from_leaf(65, 0.03, "all"))
+    while True:                                                  # 30 % diverged: no leaf closer than 0.25 over the compared sites
+        cd, st, en, u = from_leaf(90, 0.30, "leaf")
+        rows = s.seq[leaves][:, st:en + 1]
+        both = (cd[st:en + 1] >= 0)[None, :] & (rows >= 0)
+        diff = (both & (rows != cd[st:en + 1][None, :])).sum(1)
+        if (diff[both.sum(1) > 0] >= 0.25 * both.sum(1)[both.sum(1) > 0]).all():
+            reads.append((cd, st, en, u))
+            break
+    deep = s.match & (s.ll_synth < DEEP_LL)
+    cols = np.flatnonzero(deep)
+    reads.append(from_leaf(1, 0.03, None, start=int(cols[rng.integers(len(cols))])))
+    # a deep match column next to a column that is not deep: a shallow match column where the database has one, else any other
+    # (JC69: every match column is deep and every other column is all gaps, deeper still and without a say in a branch length: there the
+    # read takes two deep match columns)
+    pairs = [j for j in range(L - 1) if deep[j] != deep[j + 1] and s.ll_synth[j if deep[j + 1] else j + 1] > DEEP_LL]
+    pool = pairs or [j for j in range(L - 1) if deep[j] and deep[j + 1]]
+    reads.append(from_leaf(2, 0.03, None, start=int(pool[rng.integers(len(pool))])))
+    return [(r[0], r[1], r[2]) for r in reads], [r[3] for r in reads]
+
+
+def cand_nodes(s, leaf):
+    """the candidates of a read from the tree alone: every ancestor of its leaf up to a child of the root (the leaf first), each followed
+    by its sibling -- the last pair is the two children of the root --, then the four lowest-numbered leaves of the other root subtree"""
+    out = []
+    u = leaf
+    while u != 0:
+        out.append(u)
+        out += [c for c in s.kids[s.parent[u]] if c != u]
+        top, u = u, s.parent[u]
+    other = [c for c in s.kids[0] if c != top]
+    far = []
+    for v in range(1, s.n):                                      # preorder numbering: an ancestor has the smaller number
+        a = v
+        while s.parent[a] != 0:
+            a = s.parent[a]
+        if s.is_leaf[v] and a in other and v not in out:
+            far.append(v)
+            if len(far) == 4:
+                break
+    out += far
+    assert len(out) == len(set(out)) <= DEEP_MAX_CAND, "more than %d candidates: change READ_SEED" % DEEP_MAX_CAND
+    return out
+
+
+def deep_sweep(task):
+    """the 50-digit messages of one deep case at the columns `cols`: `up` of every node, `down` of the candidates and their ancestors.  Kept:
+    both messages of the candidate nodes, the root log-likelihood, and what the conditions of deep_state are asserted from."""
+    ci, cols = task
+    s = deep_setup(ci)
+    pi, dg = s.model.pi, s.dg_k > 0
+    Pn = [None] + [[s.model.P(s.blen[i] * r) for r in s.rates] for i in range(1, s.n)]
+    up = [None] * s.n; down = {}
+    spread = mpf(0)
+
+    def see(m):
+        pos = [x for x in m if x > 0]
+        return mp.log(max(pos)) - mp.log(min(pos))
+    for u in range(s.n - 1, -1, -1):                             # parents are numbered before their children
+        if s.is_leaf[u]:
+            up[u] = {j: leaf_vec(int(s.seq[u, j]), pi) for j in cols}
+        else:
+            up[u] = {j: join([(Pn[c], up[c][j]) for c in s.kids[u]], dg) for j in cols}
+            for j in cols:                                       # components equal in exact arithmetic (JC69): any of them
+                assert up[u][j][int(s.seq[u, j])] >= max(up[u][j]) * (1 - TIE), "inner row %d of the database is not the argmax of the 50-digit message" % u
+        spread = max([spread] + [see(up[u][j]) for j in cols])
+    for u in s.need_down:
+        p = s.parent[u]
+        down[u] = {j: join(([(Pn[p], down[p][j])] if p != 0 else []) + [(Pn[c], up[c][j]) for c in s.kids[p] if c != u], dg) for j in cols}
+        spread = max([spread] + [see(down[u][j]) for j in cols])
+    return dict(ci=ci, cols=list(cols), spread=spread, up={u: up[u] for u in s.msg_nodes + [0]}, down={u: down[u] for u in s.msg_nodes},
+                root_ll={j: mp.log(sum(pi[i] * up[0][j][i] for i in range(4))) for j in cols})
+
+
+def deep_state(ci, parts, cfg=DEEP):
+    """the state that candidate() reads, from the sweeps of one deep case (all columns, or those of one read), and its conditions"""
+    s = deep_setup(ci, cfg)
+    whole = sorted(j for p in parts for j in p["cols"]) == list(range(s.L))
+    s.up = [None] * s.n; s.down = [None] * s.n
+    s.root_ll = [None] * s.L
+    for p in parts:
+        for side, dst in ((p["up"], s.up), (p["down"], s.down)):
+            for u, by_col in side.items():
+                if dst[u] is None:
+                    dst[u] = [None] * s.L
+                for j, m in by_col.items():
+                    dst[u][j] = m
+        for j, x in p["root_ll"].items():
+            s.root_ll[j] = x
+    spread = max(p["spread"] for p in parts)
+    assert spread < DEEP_MAX_SPREAD, "a message with components %s nats apart: change the database arguments" % spread
+    low = lambda m: mp.log(max(m)) < DEEP_LL
+    rd = lambda ri: range(s.reads[ri][1], s.reads[ri][2] + 1)
+    for ri, (codes, st, en) in enumerate(s.reads):               # the three kinds of branch the list is to hold, at columns that are here
+        at = [j for j in rd(ri) if s.root_ll[j] is not None]
+        kinds = dict(both=any(low(s.up[u][j]) and low(s.down[u][j]) for u in s.cands[ri] for j in at),
+                     down_only=any(low(s.down[u][j]) and not low(s.up[u][j]) for u in s.cands[ri] for j in at),
+                     leaf=any(s.is_leaf[u] for u in s.cands[ri]))
+        s.kinds = getattr(s, "kinds", []) + [kinds]
+        # up + down of one column is about its root message, -1,420 at the lowest: both are below -510 only at an all-gap column, which
+        # the two short reads do not hold
+        assert not whole or (kinds["leaf"] and kinds["down_only"] and (kinds["both"] or en - st < 2)), "read %d: %s: change READ_SEED" % (ri, kinds)
+    j1 = s.reads[4][1]; j2 = s.reads[5][1]
+    is_deep = lambda j: bool(s.match[j] and s.ll_synth[j] < DEEP_LL)
+    assert is_deep(j1) and (is_deep(j2) != is_deep(j2 + 1) or (s.ll_synth < DEEP_LL).all())
+    for j in (j1, j2, j2 + 1):                                   # what the columns were chosen by holds for the 50-digit values
+        if s.root_ll[j] is not None:
+            assert (s.root_ll[j] < DEEP_LL) == bool(s.ll_synth[j] < DEEP_LL), "column %d: synth's root message and the 50-digit one differ about -510" % j
+    if not whole:
+        s.root_ll_sum = None
+        return s
+    s.root_ll_sum = sum(s.root_ll)
+    deep_cols = [j for j in range(s.L) if s.match[j] and s.root_ll[j] < DEEP_LL]
+    assert len(deep_cols) >= DEEP_MIN_COLS, "%d deep match columns: change the database arguments" % len(deep_cols)
+    on0 = [j for j in range(s.L) if s.match[j] and s.reads[0][0][j] >= 0]
+    n_deep0 = sum(1 for j in on0 if s.root_ll[j] < DEEP_LL)
+    if s.dg_k > 0:                                               # deep and shallow columns side by side under one read
+        assert n_deep0 >= 5 and len(on0) - n_deep0 >= 5, (n_deep0, len(on0))
+    order = sorted(range(s.L), key=lambda j: (s.root_ll[j], j))
+    s.msg_cols = sorted({order[0], order[s.L // 2], order[-1]})  # the lowest, a median and the highest root message
+    assert len(s.msg_cols) == MSG_COLS
+    print("%-7s %d of %d match columns below %d at the root (lowest %.1f; lowest of any column %.1f), largest spread %.1f nats, "
+          "the whole-width read on %d deep and %d other match columns, %d message nodes" %
+          (case_name(s.name, s.dg_k), len(deep_cols), int(s.match.sum()), DEEP_LL, float(min(s.root_ll[j] for j in deep_cols)),
+           float(min(s.root_ll)), float(spread), n_deep0, len(on0) - n_deep0, len(s.msg_nodes)), flush=True)
+    return s
+
+
 # ----------------------------------------------------------------------------- e. one candidate
 def pdist_counts(a, b, start, end):
     """SeqUtils::pDist (src/SeqUtils.cpp:37-54): sites where both hold a base, and those of them that differ"""
@@ -355,7 +596,7 @@ class Margin:
             self.cond = min(self.cond, abs(x - BRANCH_EPS) / (self.P_ERR * (1 / q + 1 / q0)))
 
 
-def em2(pi, Um, Vm, w0, max_l, mg):
+def em2(pi, Um, Vm, w0, max_l, mg, deep=False):
     """the 2-node EM of src/PhyloTreeUnrooted.cpp:749-798 on linear messages: A = pi . (U o V), B = (pi . U)(pi . V) per site.  A site is
     skipped there when logA or logB is NaN; with messages that are not all zero neither can be (asserted).  Returns (w, passes)."""
     q0 = mp.exp(-w0); p0 = 1 - q0
@@ -372,6 +613,11 @@ def em2(pi, Um, Vm, w0, max_l, mg):
         steps += 1
         p = sum(Bj * p0 / (Aj * q0 + Bj * p0) for Aj, Bj in AB) / n
         q = 1 - p
+        if q == 0 and deep:                                      # the same number without the cancellation: on a deep tree a one-column read
+            q = sum(Aj * q0 / (Aj * q0 + Bj * p0) for Aj, Bj in AB) / n      # that differs from a leaf sends q below 1e-50 within the 100 passes
+        if q == 0 and deep:                                      # every A is 0 (a one-hot message against another base at length 0): the length is
+            mg.cond = mpf(0)                                     # infinite in exact arithmetic too; the reference runs its passes out on log(0) and
+            return max_l, MAX_ITER                               # takes the cap.  Knife-edge: the pass count is not compared
         assert q > 0, "a branch length ran to infinity: choose other reads"
         x = abs(mp.log(q) - mp.log(q0))
         mg.see(x, q, q0)
@@ -439,17 +685,18 @@ def candidate(s, ri, u):
     wur0, wnr0 = lenUR, lenNR
     wur = lenUR
     mg = Margin()
+    deep = hasattr(s, "cands")
     outer = em = 0
     it = 0
     while it < MAX_ITER and 0 <= wur <= w0j:
         outer += 1
         PU, PV = catP(lenUR), catP(lenVR)
         RN = [join([(PU, U[j]), (PV, V[j])], dg) for j in range(n)]
-        wnr, k = em2(pi, RN, N, lenNR, mpf(1), mg); em += k
+        wnr, k = em2(pi, RN, N, lenNR, mpf(1), mg, deep); em += k
         lenNR = wnr
         PN = catP(lenNR)
         RU = [join([(PV, V[j]), (PN, N[j])], dg) for j in range(n)]
-        wur, k = em2(pi, RU, U, lenUR, w0j, mg); em += k
+        wur, k = em2(pi, RU, U, lenUR, w0j, mg, deep); em += k
         lenUR = wur
         lenVR = w0j - wur
         a, b = abs(wur - wur0), abs(wnr - wnr0)
@@ -496,11 +743,16 @@ _STATES = {}
 
 def _task(t):
     key, ri, u = t
-    return t, candidate(_STATES[key], ri, u)
+    try:
+        return t, candidate(_STATES[key], ri, u)
+    except AssertionError as e:
+        raise AssertionError("%s (case %d, read %d, node %d)" % (e, key[1], ri, u))
 
 
 def assemble(states, results, cfg=NARROW):
     """{key: array} of the whole archive"""
+    if cfg["name"] == "deep":
+        return assemble_deep(states, results, cfg)
     wide = cfg["name"] == "wide"
     da = cfg["db_args"]
     arc = {"ts": np.array(TS), "max_error": np.array(MAX_ERROR), "dps": np.array(mp.dps), "read_seed": np.array(cfg["read_seed"]),
@@ -561,6 +813,68 @@ def assemble(states, results, cfg=NARROW):
     return arc
 
 
+def assemble_deep(states, results, cfg):
+    """the deep archive: the per-candidate values of assemble() per read and entry of that read's own candidate list (`cand` [reads][W], -1
+    where a list is shorter), the messages of the candidate nodes only, and digests in place of the tree and the rows"""
+    da = cfg["db_args"]
+    arc = {"max_error": np.array(MAX_ERROR), "dps": np.array(mp.dps), "read_seed": np.array(cfg["read_seed"]),
+           "q_reads": np.array(cfg["q_reads"], np.int32), "db_args": np.array([da["n_leaves"], da["cs_len"], da["n_match"]], np.int32),
+           "mean_blen": np.array(cfg["mean_blen"]), "cases": np.array([case_name(*c) for c in cfg["cases"]])}
+    over = []
+    for s in states:
+        px = case_name(s.name, s.dg_k) + "_"
+        nr = len(s.reads)
+        W = max(len(c) for c in s.cands)
+        for k, d in s.digests.items():
+            arc[px + k + "_sha256"] = np.frombuffer(d, np.uint8)
+        arc[px + "height"] = np.array([float(x) for x in s.height])
+        arc[px + "msg_cols"] = np.array(s.msg_cols, np.int32)
+        arc[px + "msg_nodes"] = np.array(s.msg_nodes, np.int32)
+        arc[px + "up"] = np.array([[[flog(x) for x in s.up[u][j]] for j in s.msg_cols] for u in s.msg_nodes])
+        arc[px + "down"] = np.array([[[flog(x) for x in s.down[u][j]] for j in s.msg_cols] for u in s.msg_nodes])
+        arc[px + "root_ll"] = np.array([float(x) for x in s.root_ll])
+        arc[px + "root_ll_sum"] = np.array(float(s.root_ll_sum))
+        arc[px + "codes"] = np.stack([r[0] for r in s.reads])
+        arc[px + "start"] = np.array([r[1] for r in s.reads], np.int32)
+        arc[px + "end"] = np.array([r[2] for r in s.reads], np.int32)
+        arc[px + "n_cand"] = np.array([len(c) for c in s.cands], np.int32)
+        arc[px + "cand"] = np.array([c + [-1] * (W - len(c)) for c in s.cands], np.int32)
+        cand = [[results[((cfg["name"], s.ci), ri, u)] for u in s.cands[ri]] for ri in range(nr)]
+        pad = lambda row, fill: row + [fill] * (W - len(row))
+        f = lambda key, dt=np.float64, fill=0: np.array([pad([c[key] for c in row], fill) for row in cand], dt)
+        arc[px + "dN"] = f("dN", np.int16, (0, 0, 0, 0))
+        arc[px + "est_d"] = f("est_d", np.int16)
+        for key in ("est_ratio", "est_wnr_w", "est_ll", "est_ll_w", "pl_ratio", "pl_wnr", "pl_root_ll"):
+            arc[px + key] = f(key)
+        arc[px + "pl_const_ll"] = np.array([row[0]["pl_const_ll"] for row in cand])
+        arc[px + "pl_outer"] = f("pl_outer", np.uint8)
+        arc[px + "pl_em"] = f("pl_em", np.uint16)
+        arc[px + "pl_a_node"] = f("pl_a_node", np.int32)
+        for key in ("margin", "state_gap", "margin_cond"):
+            arc[px + key] = f(key, np.float32, 1.0)
+        real = arc[px + "cand"] >= 0
+        ll = f("est_ll", fill=-np.inf)
+        arc[px + "filter_in"] = real & ~(ll.max(1, keepdims=True) - ll > MAX_ERROR)             # src/HmmUFOtu_main.cpp:162-173
+        exact = [[max(c["_q"][0] for c in row) - c["_q"][0] for c in row] for row in cand]
+        fm = np.array([min(float(abs(x - mpf(MAX_ERROR))) for x in row) for row in exact])
+        arc[px + "filter_margin"] = fm.astype(np.float32)
+        for ri, row in enumerate(exact):
+            assert [bool(x) for x in arc[px + "filter_in"][ri, :len(row)]] == [not (x > mpf(MAX_ERROR)) for x in row]
+        assert fm.min() > FILTER_MARGIN, "a filter gap within %g of %g (%s): change READ_SEED" % (FILTER_MARGIN, MAX_ERROR, px)
+        knife = real & ((arc[px + "margin"] < KNIFE_MARGIN) | (arc[px + "state_gap"] < KNIFE_GAP) | (arc[px + "margin_cond"] < 1))
+        if knife.sum() > KNIFE_CAP * real.sum():
+            over.append("%s: %d knife-edge candidates of %d, per read %s" % (px[:-1], knife.sum(), real.sum(), knife.sum(1).tolist()))
+        omp = np.ones((len(cfg["q_reads"]), W, 4, 2))
+        for i, ri in enumerate(cfg["q_reads"]):
+            omp[i, :len(cand[ri])] = q_complements(cand[ri])
+        arc[px + "omp"] = omp
+        print("%-7s knife-edge %d/%d, smallest margin %.3g, conditioned %.3g, state gap %.3g, filter margin %.3g" %
+              (px[:-1], knife.sum(), real.sum(), arc[px + "margin"][real].min(), arc[px + "margin_cond"][real].min(),
+               arc[px + "state_gap"][real].min(), fm.min()), flush=True)
+    assert not over, "more than %g of a database's candidates are knife-edge: change READ_SEED (%s)" % (KNIFE_CAP, "; ".join(over))
+    return arc
+
+
 def write_archive(path, arc):
     """an .npz (deflated) with fixed member timestamps: the same arrays give the same bytes"""
     with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
@@ -579,6 +893,9 @@ def one_candidate(case, ri, u, set_name="narrow"):
     cfg = SETS[set_name]
     ci = [case_name(*c) for c in cfg["cases"]].index(case)
     key = (set_name, ci) if set_name == "narrow" else (set_name, ci, ri)
+    if key not in _STATES and set_name == "deep":                # the sweep over the whole tree at the read's own columns
+        rd = deep_setup(ci, cfg).reads[ri]
+        _STATES[key] = deep_state(ci, [deep_sweep((ci, list(range(rd[1], rd[2] + 1))))], cfg)
     if key not in _STATES:
         _STATES[key] = db_state(ci, None if set_name == "narrow" else ri, cfg)
     s = _STATES[key]
@@ -598,11 +915,20 @@ def main():
     workers = max(1, min(16, a.workers))
     ctx = multiprocessing.get_context("fork")
     n = len(cfg["cases"])
-    with ctx.Pool(min(workers, n)) as pool:
-        states = pool.starmap(db_state, [(ci, None, cfg) for ci in range(n)])
+    if a.set == "deep":                                          # the sweeps by column chunks: a column's messages depend on no other's
+        L = cfg["db_args"]["cs_len"]
+        per = max(1, workers // n)
+        chunks = [(ci, list(range(k, L, per))) for ci in range(n) for k in range(per)]
+        with ctx.Pool(min(workers, len(chunks))) as pool:
+            parts = pool.map(deep_sweep, chunks)
+        states = [deep_state(ci, [p for p in parts if p["ci"] == ci], cfg) for ci in range(n)]
+    else:
+        with ctx.Pool(min(workers, n)) as pool:
+            states = pool.starmap(db_state, [(ci, None, cfg) for ci in range(n)])
     for s in states:
         _STATES[(a.set, s.ci)] = s
-    tasks = [((a.set, s.ci), ri, u) for s in states for ri in range(len(s.reads)) for u in range(1, s.n)]
+    nodes_of = (lambda s, ri: s.cands[ri]) if a.set == "deep" else (lambda s, ri: range(1, s.n))
+    tasks = [((a.set, s.ci), ri, u) for s in states for ri in range(len(s.reads)) for u in nodes_of(s, ri)]
     tasks.sort(key=lambda t: -(states[t[0][1]].reads[t[1]][2] - states[t[0][1]].reads[t[1]][1]) * (1 + max(states[t[0][1]].dg_k, 1)))
     with ctx.Pool(workers) as pool:                              # forked after _STATES is filled: the workers inherit it
         results = dict(pool.imap_unordered(_task, tasks, chunksize=4))

@@ -1,7 +1,10 @@
-"""Shared by tests/test_hiprec_oracle.py and tests/test_hiprec_gpu.py: tests/golden/hiprec.npz and hiprec_wide.npz (the floating-point
-stages in 50-digit arithmetic, written by tests/golden/make_hiprec_golden.py --set narrow / wide) and the rules both files read them by.
-The narrow archive holds six models on regions of 1 to 190 columns; the wide one two models on twelve reads of 512 to 3,073 columns, one
-per width class of the estimate / placement dispatch (WIDE_READS)."""
+"""Shared by tests/test_hiprec_oracle.py and tests/test_hiprec_gpu.py: tests/golden/hiprec.npz, hiprec_wide.npz and hiprec_deep.npz (the
+floating-point stages in 50-digit arithmetic, written by tests/golden/make_hiprec_golden.py --set narrow / wide / deep) and the rules both
+files read them by.  The narrow archive holds six models on regions of 1 to 190 columns; the wide one two models on twelve reads of 512 to
+3,073 columns, one per width class of the estimate / placement dispatch (WIDE_READS); the deep one two models on 1,024 leaves x 96 columns
+with branches long enough that messages lie below the -510 at which the log-space implementations rescale, six reads each with a
+candidate list of its own (at most 48 nodes), the messages of those nodes only, and digests in place of the tree and the rows."""
+import hashlib
 import os
 
 import numpy as np
@@ -9,9 +12,11 @@ import numpy as np
 from conftest import get_db
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-GOLD = dict(narrow=os.path.join(GOLDEN, "hiprec.npz"), wide=os.path.join(GOLDEN, "hiprec_wide.npz"))
+GOLD = dict(narrow=os.path.join(GOLDEN, "hiprec.npz"), wide=os.path.join(GOLDEN, "hiprec_wide.npz"), deep=os.path.join(GOLDEN, "hiprec_deep.npz"))
 CASES = ["GTR4", "TN933", "HKY854", "F810", "K802", "JC690"]
 WIDE_CASES = ["GTR4", "JC690"]
+DEEP_CASES = ["GTR4", "JC690"]
+DEEP_LL = -510.0                                                 # a message whose largest component is below it is rescaled
 # (columns, base sites) of read ri of every wide case: what the tests parametrize over (the archive's read_shapes must be this)
 WIDE_READS = [(512, 120), (513, 100), (1024, 256), (1024, 257), (1025, 150), (1536, 256), (1400, 257), (1537, 200), (2048, 300),
               (2049, 250), (3072, 500), (3073, 300)]
@@ -19,7 +24,10 @@ KNIFE_MARGIN, KNIFE_GAP = 1e-6, 1e-9
 VARIANTS = {(0, 0): 0, (1, 0): 1, (0, 1): 2, (1, 1): 3}        # (prior, fix_root_loglik) -> index into omp
 MAX_Q = 250.0
 
-_ARCS = dict(narrow={}, wide={})
+_ARCS = dict(narrow={}, wide={}, deep={})
+# per-candidate arrays [reads][candidates]
+PER_CAND = ("dN", "est_d", "est_ratio", "est_wnr_w", "est_ll", "est_ll_w", "pl_ratio", "pl_wnr", "pl_root_ll", "pl_outer", "pl_em",
+            "pl_a_node", "margin", "state_gap", "margin_cond", "filter_in", "knife")
 
 
 class Case:
@@ -38,11 +46,19 @@ class Case:
         self.root_ll_sum = float(self.root_ll_sum.ravel()[0])
         n_leaves, cs_len, n_match = (int(x) for x in _ARC["db_args"])
         model, dg_k = name[:-1], int(name[-1])
-        self.db = get_db(n_leaves, cs_len, model, dg_k=dg_k, seed=97, **(dict(n_match=n_match) if n_match >= 0 else {}))
+        kw = dict(n_match=n_match) if n_match >= 0 else {}
+        if archive == "deep":
+            kw["mean_blen"] = float(_ARC["mean_blen"][DEEP_CASES.index(name)])
+        self.db = get_db(n_leaves, cs_len, model, dg_k=dg_k, seed=97, **kw)
         if archive == "wide":                                    # one read per entry of WIDE_READS, its base sites counted
             shapes = [(int(e - s + 1), int((cd[s:e + 1] >= 0).sum())) for cd, s, e in zip(self.codes, self.start, self.end)]
             assert shapes == WIDE_READS == [tuple(int(x) for x in r) for r in _ARC["read_shapes"]]
         # the same case: tree, rows and rates are the ones the 50-digit run was given
+        if archive == "deep":                                    # by digest: 2,047 nodes x 96 columns do not fit the size cap of a golden file
+            for k, dt in (("parent", np.int32), ("blen", np.float64), ("seq", np.int8)):
+                a = np.ascontiguousarray(np.asarray(getattr(self.db, k), dt))
+                assert hashlib.sha256(a.tobytes()).digest() == getattr(self, k + "_sha256").tobytes(), k
+                setattr(self, k, a)
         assert np.array_equal(self.db.parent, self.parent) and np.array_equal(self.db.blen, self.blen) and np.array_equal(self.db.seq, self.seq)
         self.rates = np.concatenate([[1.0], self.db.dg_r]) if dg_k else np.ones(1)
         self.n_reads = len(self.start)
@@ -50,13 +66,23 @@ class Case:
         # (margin_cond < 1: an EM quantity closer to 1e-5 than a relative error of 1e-14 in p moves it through q = 1 - p — an EM that does
         # not converge halves q until 1 - p has no digits left, and the pass count from there on is the arithmetic's, not the formula's)
         self.knife = (self.margin < KNIFE_MARGIN) | (self.state_gap < KNIFE_GAP) | (self.margin_cond < 1)
+        if archive == "deep":                                    # a candidate list per read: `cand` [reads][W], -1 past the end of a list
+            self.knife &= self.cand >= 0
+            self._slot = [{int(u): k for k, u in enumerate(row[:n])} for row, n in zip(self.cand, self.n_cand)]
+
+    def cands(self, ri):
+        """the candidate nodes of read ri in the order of the per-candidate arrays: every non-root node, or the read's own list (deep)"""
+        return self.cand[ri, :int(self.n_cand[ri])] if self.archive == "deep" else self.seeds
+
+    def slot(self, ri, u):
+        """the index of node u in the per-candidate arrays of read ri"""
+        return self._slot[ri][int(u)] if self.archive == "deep" else int(u) - 1
 
     def one_read(self, ri):
         """the same case with read ri alone (a batch of one read: the kernel instance then depends on that read only)"""
         import copy
         c = copy.copy(self)
-        for k in ("codes", "start", "end", "dN", "est_d", "est_ratio", "est_wnr_w", "est_ll", "est_ll_w", "pl_ratio", "pl_wnr", "pl_root_ll",
-                  "pl_const_ll", "pl_outer", "pl_em", "pl_a_node", "margin", "state_gap", "margin_cond", "filter_in", "filter_margin", "knife"):
+        for k in ("codes", "start", "end", "pl_const_ll", "filter_margin") + PER_CAND + (("cand", "n_cand", "_slot") if self.archive == "deep" else ()):
             setattr(c, k, getattr(self, k)[ri:ri + 1])
         c.n_reads = 1
         c.q_reads = [0] if ri in self.q_reads else []
@@ -85,12 +111,12 @@ class Case:
         return float(self.est_d[ri, k]) / float(self.end[ri] - self.start[ri] + 1)
 
     def placed_height(self, ri, k):
-        u = int(self.seeds[k])
+        u = int(self.cands(ri)[k])
         return float(self.height[u] + self.pl_ratio[ri, k] * self.blen[u])
 
     def q_exact(self, ri, prior, fix):
         """(q_place, q_taxon, 1 - p_place, 1 - p_taxon) [n_cand] of read ri (one of q_reads) from the exact complements"""
-        omp = self.omp[self.q_reads.index(ri), :, VARIANTS[(prior, fix)], :]
+        omp = self.omp[self.q_reads.index(ri), :len(self.cands(ri)), VARIANTS[(prior, fix)], :]
         with np.errstate(divide="ignore"):
             q = np.minimum(MAX_Q, -10.0 * np.log10(omp))
         return q[:, 0], q[:, 1], omp[:, 0], omp[:, 1]
@@ -106,3 +132,17 @@ def q_ok(q, q_exact, omp, eps):
 def ratio_half(case, ri):
     """a placed ratio within 1e-6 of 0.5 switches the taxon node: the taxon sums of that read are not comparable"""
     return bool((np.abs(case.pl_ratio[ri] - 0.5) < 1e-6).any())
+
+
+def level_shape(got, want):
+    """the depth-aware distance of log-space messages [..., 4] from the exact ones: (level, shape) with level = |max_i got_i - max_i want_i|
+    relative to max(|max_i want_i|, 1) and shape = max over the finite components of |(got_i - max got) - (want_i - max want)|, absolute.
+    |dM| / max(|M|, 1) alone allows 1.6e-8 in the linear value at |M| = 900; the shape is the linear value's relative error.  The -inf
+    pattern must be equal."""
+    got = np.asarray(got, float); want = np.asarray(want, float)
+    inf = np.isneginf(want)
+    assert np.array_equal(np.isneginf(got), inf) and np.isfinite(got[~inf]).all()
+    gm, wm = got.max(-1), want.max(-1)
+    level = (np.abs(gm - wm) / np.maximum(np.abs(wm), 1.0)).max()
+    d = np.abs((got - gm[..., None]) - (want - wm[..., None]))
+    return float(level), float(d[~inf].max())

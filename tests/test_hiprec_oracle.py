@@ -20,6 +20,14 @@ The wide set (tests/golden/hiprec_wide.npz: GTR+4 and JC69, 8 leaves x 3,300 col
 candidate) runs under the same rules and the same bounds (test_wide_*); its figures are printed as HIPREC oracle_wide_* lines and anchor
 the kernels' bounds on that set (tests/test_hiprec_gpu.py: ORACLE_WIDE).  Measured: logliks 6.2e-14 (estimate) and 5.7e-14 (root), weighted
 wnr 6.5e-15 absolute, placed ratio 1.2e-13 and wnr 1.9e-13 absolute (7.6e-12 relative to max(|x|, 1e-3)), height 6.6e-15, q eps 2.1e-10.
+The deep set (tests/golden/hiprec_deep.npz: GTR+4 and JC69, 1,024 leaves x 96 columns, root messages down to -766 / -963 on match columns
+and -1,197 / -1,420 on all-gap columns, six reads with a candidate list each, given to the oracle through Tree.assign(seeds=...); 7
+knife-edge candidates of 344, all on JC69) runs under the same rules and bounds (test_deep_*): the -510 rescaling of the oracle and of
+synth's numpy messages is exercised there and nowhere else.  Its figures are printed as HIPREC oracle_deep_* lines and anchor ORACLE_DEEP
+in tests/test_hiprec_gpu.py.  Messages are measured there by hiprec_cases.level_shape as well.  Measured: message level 2.2e-14 (synth
+1.3e-13) and shape 4.7e-12 (synth 9.3e-12), root loglik 2.8e-14, estimated and root logliks 4.9e-15, weighted wnr 2.0e-14 relative, placed
+lengths 1.3e-11 and height 7.8e-13 relative to max(|x|, 1e-3), q eps 8.0e-12; counts, filter sets and taxon nodes equal.  The oracle is
+right at depth too.
 """
 import glob
 import importlib.util
@@ -29,7 +37,7 @@ import re
 import numpy as np
 import pytest
 
-from hiprec_cases import CASES, WIDE_CASES, WIDE_READS, Case, q_ok, ratio_half
+from hiprec_cases import CASES, DEEP_CASES, DEEP_LL, WIDE_CASES, WIDE_READS, Case, level_shape, q_ok, ratio_half
 
 REL = 1e-6
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -113,7 +121,7 @@ def _estimate(c):
     worst = dict(ll=0.0, ll_w=0.0, wnr_w=0.0, wnr_w_rel=0.0)
     for ri in range(c.n_reads):
         st, en = int(c.start[ri]), int(c.end[ri])
-        for k, u in enumerate(c.seeds):
+        for k, u in enumerate(c.cands(ri)):
             e0 = T.estimate(c.codes[ri], st, en, u, c.dist(ri, k), weighted=False)
             e1 = T.estimate(c.codes[ri], st, en, u, c.dist(ri, k), weighted=True)
             assert e0["ratio"] == c.ratio_double(ri, k) == e1["ratio"]
@@ -141,7 +149,7 @@ def _place(c):
     worst = dict(ratio=0.0, wnr=0.0, height=0.0, const=0.0, root=0.0, length_rel=0.0, height_rel=0.0)
     for ri in range(c.n_reads):
         st, en = int(c.start[ri]), int(c.end[ri])
-        for k, u in enumerate(c.seeds):
+        for k, u in enumerate(c.cands(ri)):
             p = T.place(c.codes[ri], st, en, u, c.ratio_double(ri, k), c.wnr_unweighted(ri, k))
             pf = T.place(c.codes[ri], st, en, u, c.ratio_double(ri, k), c.wnr_unweighted(ri, k), fix_root=True)
             assert (pf["ratio"], pf["wnr"], pf["iters"], pf["em_iters"]) == (p["ratio"], p["wnr"], p["iters"], p["em_iters"])
@@ -175,23 +183,25 @@ def test_assign_filter_set_and_q_values(name):
 def _assign(c):
     from oracle import oracle_py as O
     _, _, T = _oracle(c)
-    n_cand = len(c.seeds)
     worst = dict(q_eps=0.0)
     for ri in range(c.n_reads):
         st, en = int(c.start[ri]), int(c.end[ri])
-        res = T.assign(c.codes[ri], st, en, O.default_opts(maxError=c.max_error))
-        assert sorted(int(x) for x in res["seed_ids"]) == sorted(int(x) for x in c.seeds)
-        assert sorted(int(x) for x in res["filt_order"]) == sorted(int(u) for u, keep in zip(c.seeds, c.filter_in[ri]) if keep), ri
+        seeds = c.cands(ri)
+        n_cand = len(seeds)
+        given = dict(seeds=seeds) if c.archive == "deep" else {}      # the deep set: the read's own list in place of getSeed's
+        res = T.assign(c.codes[ri], st, en, O.default_opts(maxError=c.max_error), **given)
+        assert sorted(int(x) for x in res["seed_ids"]) == sorted(int(x) for x in seeds)
+        assert sorted(int(x) for x in res["filt_order"]) == sorted(int(u) for u, keep in zip(seeds, c.filter_in[ri]) if keep), ri
         if ri not in c.q_reads:
             continue
         for prior in (0, 1):
             for fix in (0, 1):
-                res = T.assign(c.codes[ri], st, en, O.default_opts(maxError=1e9, prior=prior, fixRootLoglik=fix))
+                res = T.assign(c.codes[ri], st, en, O.default_opts(maxError=1e9, prior=prior, fixRootLoglik=fix), **given)
                 assert res["n"] == n_cand
                 qp, qt, op, ot = c.q_exact(ri, prior, fix)
                 for nodes, vals in zip(res["nodes"], res["vals"]):
-                    k = int(nodes[0]) - 1                        # seeds are the nodes 1 .. n - 1 in order
-                    assert int(c.seeds[k]) == int(nodes[0])
+                    k = c.slot(ri, nodes[0])                     # narrow / wide: the seeds are the nodes 1 .. n - 1 in order
+                    assert int(seeds[k]) == int(nodes[0])
                     assert q_ok(vals[4], qp[k], op[k], 1e-9), (ri, prior, fix, k, vals[4], qp[k])
                     if not ratio_half(c, ri):
                         assert q_ok(vals[5], qt[k], ot[k], 1e-9), (ri, prior, fix, k, vals[5], qt[k])
@@ -224,6 +234,56 @@ def test_wide_assign_filter_set_and_q_values(name):
     report("wide_q", name, **_assign(Case(name, "wide")))
 
 
+# ---- the deep set (tests/golden/hiprec_deep.npz): 1,024 leaves x 96 columns, messages down to -1,420, under the same rules and bounds
+def _root_ll(root, pi):
+    """treeLoglik of every column from a root message [L][4]: log(pi . exp(root message))"""
+    mx = root.max(1)
+    return mx + np.log((np.asarray(pi)[None, :] * np.exp(root - mx[:, None])).sum(1))
+
+
+@pytest.mark.parametrize("name", DEEP_CASES)
+def test_deep_messages(name):
+    """the oracle's two-pass pruning and synth's numpy messages where both rescale (src/PhyloTreeUnrooted.h:1495-1510): the old measure
+    (1e-11 relative to max(|x|, 1)) and the depth-aware pair hiprec_cases.level_shape.  Level 1e-11: the old bound on the largest
+    component.  Shape 1e-9 absolute: the relative error of the linear value that the project asks of a message of magnitude <= 1."""
+    c = Case(name, "deep")
+    O, m, _ = _oracle(c)
+    db = c.db
+    leaf_only = np.where(db.is_leaf[:, None], db.seq, 0).astype(np.int8)
+    up, down, seq, h = O.tree_evaluate(db.parent, db.blen, leaf_only, m, db.dg_r if db.dg_k else None)
+    assert np.array_equal(seq, db.seq)
+    assert np.abs(h - c.height).max() < 1e-14
+    # the archive is deep where it says: stored messages of both kinds below the rescaling level
+    assert (c.up.max(-1) < DEEP_LL).any() and (c.down.max(-1) < DEEP_LL).any() and (c.root_ll < DEEP_LL).sum() >= 16
+    worst = {}
+    for who, (u_, d_) in dict(oracle=(up, down), synth=(db.up, db.down)).items():
+        for side, got, want in (("up", u_[c.msg_nodes][:, c.msg_cols], c.up), ("down", d_[c.msg_nodes][:, c.msg_cols], c.down)):
+            level, shape = level_shape(got, want)
+            inf = np.isneginf(want)
+            old = (np.abs(got[~inf] - want[~inf]) / np.maximum(np.abs(want[~inf]), 1.0)).max()
+            worst.update({"%s_%s_level" % (who, side): level, "%s_%s_shape" % (who, side): shape, "%s_%s_rel" % (who, side): old})
+        ll = _root_ll(u_[0], m.pi)
+        worst[who + "_tree_ll"] = max((np.abs(ll - c.root_ll) / np.abs(c.root_ll)).max(), _rel(ll.sum(), c.root_ll_sum))
+    report("deep_messages", name, **worst)
+    for k, v in worst.items():
+        assert np.isfinite(v) and v < (1e-12 if k.endswith("tree_ll") else 1e-9 if k.endswith("shape") else 1e-11), (k, v)
+
+
+@pytest.mark.parametrize("name", DEEP_CASES)
+def test_deep_estimate(name):
+    report("deep_estimate", name, **_estimate(Case(name, "deep")))
+
+
+@pytest.mark.parametrize("name", DEEP_CASES)
+def test_deep_place(name):
+    report("deep_place", name, **_place(Case(name, "deep")))
+
+
+@pytest.mark.parametrize("name", DEEP_CASES)
+def test_deep_assign_filter_set_and_q_values(name):
+    report("deep_q", name, **_assign(Case(name, "deep")))
+
+
 def test_the_archive_is_the_generators_output():
     """one candidate regenerated in 50-digit arithmetic gives the stored bits"""
     pytest.importorskip("mpmath")
@@ -254,6 +314,15 @@ def test_the_archive_is_the_generators_output():
     assert (got["pl_outer"], got["pl_em"], got["pl_a_node"]) == (int(c.pl_outer[ri, k]), int(c.pl_em[ri, k]), int(c.pl_a_node[ri, k]))
     assert np.float32(got["margin"]) == c.margin[ri, k] and np.float32(got["margin_cond"]) == c.margin_cond[ri, k]
     assert got["pl_const_ll"] == c.pl_const_ll[ri]
+    # and one of the deep set: the one-column read (a sweep over the 2,047 nodes at that column) on the cheapest model
+    c = Case("JC690", "deep")
+    ri, k = 4, 3
+    got = gen.one_candidate("JC690", ri, int(c.cands(ri)[k]), "deep")
+    assert tuple(got["dN"]) == tuple(int(x) for x in c.dN[ri, k]) and got["est_d"] == int(c.est_d[ri, k])
+    for key in ("est_ratio", "est_wnr_w", "est_ll", "est_ll_w", "pl_ratio", "pl_wnr", "pl_root_ll"):
+        assert got[key] == getattr(c, key)[ri, k], key
+    assert (got["pl_outer"], got["pl_em"], got["pl_a_node"]) == (int(c.pl_outer[ri, k]), int(c.pl_em[ri, k]), int(c.pl_a_node[ri, k]))
+    assert np.float32(got["margin"]) == c.margin[ri, k] and np.float32(got["margin_cond"]) == c.margin_cond[ri, k]
 
 
 def test_only_the_generator_imports_mpmath():
