@@ -1063,6 +1063,62 @@ def alpha_timing() -> dict:
     return dict(to_device=s[0], select=s[1], take=s[2], metrics=s[3], pd=s[4], to_host=s[5])
 
 
+class DiffabundOpts(C.Structure):
+    _fields_ = [("perms", C.c_int64), ("seed", C.c_uint64), ("host", C.c_int32), ("rank_by", C.c_int32), ("min_prevalence", C.c_int64), ("chunk", C.c_int64),
+                ("mem_budget", C.c_int64)]
+
+
+DIFFABUND_REC = np.dtype([("tested", np.int32), ("best", np.int32), ("prevalence", np.int64), ("T_hi", np.uint64), ("T_lo", np.uint64), ("count_ge", np.int64),
+                          ("H", np.float64), ("p", np.float64), ("p_maxT", np.float64), ("q", np.float64)])
+RANK_BY = {"fraction": 0, "count": 1}
+
+
+def diffabund(counts, group, perms=999, seed=1, rank_by="fraction", min_prevalence=1, chunk=0, device=0, host=False, mem_budget=0) -> dict:
+    """hu_diffabund: Kruskal-Wallis per OTU of counts [n_otu][n_sample] between the labels group [n_sample] (0 .. a-1), with permutation
+    p-values, single-step maxT and Benjamini-Hochberg: dict(rec, a structured array [n_otu] of tested, best, prevalence, T_hi, T_lo, count_ge,
+    H, p, p_maxT, q (NaN and best -1 where an OTU is not tested), and max_H [perms], the largest H of every permutation).  host: the
+    library's host path, no device needed; it gives the same bits."""
+    c = np.ascontiguousarray(counts, np.float64); g = np.ascontiguousarray(group, np.int32)
+    if c.ndim != 2 or g.shape != (c.shape[1],):
+        raise EngineError("diffabund: counts [n_otu][n_sample] and group [n_sample]")
+    if rank_by not in RANK_BY:
+        raise EngineError("diffabund: rank_by is 'fraction' or 'count'")
+    lib = load_library()
+    o = DiffabundOpts()
+    lib.hu_diffabund_default_opts(C.byref(o))
+    o.perms = int(perms); o.seed = int(seed) & (2 ** 64 - 1); o.host = 1 if host else 0; o.rank_by = RANK_BY[rank_by]; o.min_prevalence = int(min_prevalence)
+    o.chunk = int(chunk or 0); o.mem_budget = int(mem_budget or 0)
+    rec = np.zeros(c.shape[0], DIFFABUND_REC)
+    mx = np.zeros(max(int(perms), 0))
+    _chk(lib.hu_diffabund(C.c_int(int(device)), C.c_int64(c.shape[0]), C.c_int64(c.shape[1]), _p(c, C.c_double), _p(g, C.c_int32), C.byref(o),
+                          rec.ctypes.data_as(C.c_void_p), _p(mx, C.c_double) if len(mx) else None))
+    return dict(rec=rec, max_H=mx)
+
+
+def diffabund_ranks(counts, rank_by="fraction") -> np.ndarray:
+    """hu_diffabund_ranks (host only): [n_otu][n_sample], the doubled mid-ranks of every OTU's cells among its samples"""
+    c = np.ascontiguousarray(counts, np.float64)
+    if c.ndim != 2 or rank_by not in RANK_BY:
+        raise EngineError("diffabund_ranks: counts [n_otu][n_sample], rank_by 'fraction' or 'count'")
+    out = np.zeros(c.shape, np.int32)
+    _chk(load_library().hu_diffabund_ranks(C.c_int64(c.shape[0]), C.c_int64(c.shape[1]), _p(c, C.c_double), C.c_int32(RANK_BY[rank_by]), _p(out, C.c_int32)))
+    return out
+
+
+def diffabund_need(n_sample: int, a: int, n_otu: int, n_cell: int, chunk: int) -> int:
+    """hu_diffabund_need: the bytes of device memory for n_otu tested OTUs with n_cell cells above 0 and `chunk` permutations per launch"""
+    lib = load_library()
+    lib.hu_diffabund_need.restype = C.c_int64
+    return int(lib.hu_diffabund_need(*(C.c_int64(int(v)) for v in (n_sample, a, n_otu, n_cell, chunk))))
+
+
+def diffabund_timing() -> dict:
+    """hu_diffabund_timing: the phases of this thread's last diffabund on a device, in seconds"""
+    s = np.zeros(4)
+    _chk(load_library().hu_diffabund_timing(_p(s, C.c_double)))
+    return dict(to_device=s[0], shuffle=s[1], sums=s[2], finish=s[3])
+
+
 class NjOpts(C.Structure):
     _fields_ = [("host", C.c_int32), ("reserved", C.c_int32), ("mem_budget", C.c_int64)]
 

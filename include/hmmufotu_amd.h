@@ -1690,6 +1690,63 @@ void hu_alpha_metrics(hu_alpha_rec* r);
 int hu_alpha_curve(int64_t n, const double* x, double* mean, double* sd);
 int hu_alpha_timing(double* seconds /* [6] */);
 
+/* ---- hmmufotu-amd-diffabund: which OTUs differ between the sample groups? (Kruskal-Wallis by permutation) ----
+ * counts [n_otu][n_sample] row-major, finite and non-negative.  group [n_sample]: a label g_j in 0 .. a-1 per sample, n_g the group
+ * sizes, N = n_sample.  Per OTU o:
+ *   values      rank_by 0 (fraction): x_j = counts[o][j] / total_j, one rounded division, total_j the column sum added in ascending OTU
+ *               order; rank_by 1 (count): x_j = counts[o][j].
+ *   ranks       doubled mid-ranks, integers: r2_j = 2 #{k : x_k < x_j} + #{k : x_k == x_j} + 1; centred e_j = r2_j - (N + 1), so
+ *               sum_j e_j = 0, and every zero cell has the same e_z.
+ *   group sums  C_g = sum_{j in g} e_j = n_g e_z + D_g, D_g = the sum of e_j - e_z over the cells of g above 0: only those are visited.
+ *   T           the integer sum_g C_g^2 (L / n_g), L = lcm(n_0 .. n_{a-1}), in unsigned 128-bit arithmetic on both paths.  A permutation
+ *               moves labels and keeps sizes, so L and the tie correction are constant per OTU and Kruskal-Wallis' H is monotone in T:
+ *               no floating-point operation decides a tie.
+ *   p           (1 + #{pi : T(pi) >= T(observed)}) / (perms + 1); count_ge is the count.
+ *   H           plain IEEE operations in this order, no fma: x = (double) T_hi * 2^64 + (double) T_lo,
+ *               tc = 1 - (double) sum_ties (t^3 - t) / (double) (N^3 - N), H = ((x / (double) L) * (3.0 / ((double) N * (double) (N + 1)))) / tc:
+ *               Kruskal-Wallis with the tie correction, for a == 2 the two-sided Wilcoxon rank-sum test; non-decreasing in T.
+ *   p_maxT      single-step maxT (Westfall-Young): M(pi) = the maximum over the tested OTUs of H_o(T_o(pi)),
+ *               p_maxT_o = (1 + #{pi : M(pi) >= H_o(observed)}) / (perms + 1).
+ *   q           Benjamini-Hochberg on the p of the m tested OTUs: sorted ascending, stable by OTU order, q = (p * (double) m) / (double) j
+ *               for the j-th (1-based), then the running minimum from the end, capped at 1.
+ *   best        the group with the largest C_g / n_g, compared by integer cross-multiplication; the first group wins a tie.
+ *   not tested  an OTU whose cells all tie (tc == 0: all zero, or all equal) or with fewer than min_prevalence nonzero cells: tested 0,
+ *               best -1, NaN in H, p, p_maxT and q; it takes no part in M or in m.
+ * Permutation p is the labelling hu_permanova_labels(n, group, seed, p) gives.  The host path (opts->host, or device < 0: one thread, no
+ * device needed) gives the same bits in every field and in maxstat_perm_out [perms] (may be NULL), which receives M(pi).
+ * HU_ERR_ARG with the reason, before a device is asked for: n_sample < 3 or > 16,384, a negative label, labels not dense in 0 .. a-1,
+ * a < 2, a > 64, a > n-1, L >= 2^64 (with the group sizes), perms < 1 or > 10^7, chunk < 0, min_prevalence < 0, rank_by not 0 or 1, a
+ * negative or non-finite cell, a sample without reads under rank_by 0, every OTU untested.  HU_ERR_NOMEM with the bytes needed and the
+ * bytes free when hu_diffabund_need exceeds mem_budget (checked before a device is asked for) or what the device reports free.
+ * chunk: permutations per launch; 0: the largest multiple of 256 that fits, 16,384 at the most and never more than perms.
+ * hu_diffabund_ranks: host only, r2_out [n_otu][n_sample] the doubled mid-ranks.
+ * hu_diffabund_need: the bytes on the device; n_otu and n_cell are the tested OTUs and their cells above 0 (the whole table's bound them).
+ * With c = chunk rounded up to 256 and b = (n_otu + 63) / 64: 4 n_cell for the cells, n_sample c for the labels, 8 b c for the partial
+ * maxima, 8 c for the maxima, n_sample + 16 a for the tables, 52 n_otu + 8 for the rows and 1 MB of slack; -1 on a bad argument.
+ * hu_diffabund_timing: of this thread's last device call, seconds [4] = copies up, shuffles, sums, finish and copy back. */
+typedef struct {
+	int64_t perms;          /* 999 */
+	uint64_t seed;          /* 1 */
+	int32_t host;           /* 0; 1: the host path, no device needed */
+	int32_t rank_by;        /* 0: fraction of the sample's reads; 1: count */
+	int64_t min_prevalence; /* 1 */
+	int64_t chunk;          /* 0: chosen from the sizes and the memory */
+	int64_t mem_budget;     /* 0: what the device reports free */
+} hu_diffabund_opts;
+typedef struct {
+	int32_t tested, best;
+	int64_t prevalence;
+	uint64_t T_hi, T_lo;
+	int64_t count_ge;
+	double H, p, p_maxT, q;
+} hu_diffabund_rec;
+void hu_diffabund_default_opts(hu_diffabund_opts* o);
+int hu_diffabund(int device, int64_t n_otu, int64_t n_sample, const double* counts, const int32_t* group, const hu_diffabund_opts* opts,
+		hu_diffabund_rec* rec_out /* [n_otu] */, double* maxstat_perm_out /* [perms] or NULL */);
+int hu_diffabund_ranks(int64_t n_otu, int64_t n_sample, const double* counts, int32_t rank_by, int32_t* r2_out /* [n_otu][n_sample] */);
+int64_t hu_diffabund_need(int64_t n_sample, int64_t a, int64_t n_otu, int64_t n_cell, int64_t chunk);
+int hu_diffabund_timing(double* seconds /* [4] */);
+
 #ifdef __cplusplus
 }
 #endif
