@@ -38,6 +38,7 @@ struct HuAlPlan {
 	std::vector<uint32_t> prefix;        /* per sample nnz + 1, the cells in table order: it numbers the reads */
 	std::vector<uint32_t> slot;          /* per sample nnz: the place of that cell among the sample's in depth-first row order */
 	std::vector<HuAlBranch> br;
+	std::vector<uint32_t> brK;           /* beside br: the number of the kept branch (hu_unifrac_rarefied's embedding) */
 	std::vector<HuAlUnit> unit;          /* the whole samples, then the existing draws by (sample, repeat, depth) */
 	int64_t maxNnz = 0, maxChunk = 0;    /* the largest nnz and the largest ceil(T / chunk) of a sample */
 };

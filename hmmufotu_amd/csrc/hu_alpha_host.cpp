@@ -110,14 +110,14 @@ int hu_al_plan(const char* fn, const hu_unifrac_tree* tree, int64_t n_otu, int64
 	}
 	for(size_t j = 0; j < S; ++j) pl.prefix[(size_t) pl.smp[j].pfx0 + pl.smp[j].nnz] = pl.smp[j].T;
 	/* the branch entries of a sample: the kept branches whose interval of rows holds one of its nonzero cells, in branch order */
-	pl.br.clear();
+	pl.br.clear(); pl.brK.clear();
 	for(size_t j = 0; j < S; ++j) {
 		HuAlSample& s = pl.smp[j];
 		s.br0 = pl.br.size();
 		const uint32_t *p0 = pos.data() + ((size_t) s.pfx0 - j), *p1 = p0 + s.nnz;
 		for(size_t k = 0; k < (size_t) pl.B; ++k) {
 			const uint32_t lo = (uint32_t)(std::lower_bound(p0, p1, (uint32_t) up.lo[k]) - p0), hi = (uint32_t)(std::lower_bound(p0, p1, (uint32_t) up.hi[k]) - p0);
-			if(hi > lo) pl.br.push_back(HuAlBranch{up.b[k], lo, hi});
+			if(hi > lo) { pl.br.push_back(HuAlBranch{up.b[k], lo, hi}); pl.brK.push_back((uint32_t) k); }
 		}
 		s.nBr = (uint32_t)(pl.br.size() - s.br0);
 	}

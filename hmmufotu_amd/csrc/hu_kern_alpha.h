@@ -56,7 +56,7 @@ __device__ inline uint64_t hu_al_isum(uint64_t v, uint64_t* lds /* [HU_AL_WAVES]
 	return lds[0] + lds[1] + lds[2] + lds[3];
 }
 
-__global__ __launch_bounds__(HU_AL_WG) void k_al_hist(const HuAlSample* smp, const HuAlGroup* grp, const HuAlChunk* chunk, const HuAlSel* sel, uint32_t* hist,
+static __global__ __launch_bounds__(HU_AL_WG) void k_al_hist(const HuAlSample* smp, const HuAlGroup* grp, const HuAlChunk* chunk, const HuAlSel* sel, uint32_t* hist,
 		int keyBits, int chunkLen, int shift, int first) {
 	__shared__ uint32_t h[HU_AL_DT][256];
 	const HuAlChunk c = chunk[blockIdx.x];
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(HU_AL_WG) void k_al_hist(const HuAlSample* smp, con
 	}
 }
 
-__global__ __launch_bounds__(64) void k_al_pick(const HuAlDraw* draw, HuAlSel* sel, uint32_t* hist) {
+static __global__ __launch_bounds__(64) void k_al_pick(const HuAlDraw* draw, HuAlSel* sel, uint32_t* hist) {
 	const int a = blockIdx.x, lane = threadIdx.x;
 	if(draw[a].m == 0) return;
 	uint4* h4 = (uint4*)(hist + (size_t) a * 256);
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(64) void k_al_pick(const HuAlDraw* draw, HuAlSel* s
 	}
 }
 
-__global__ __launch_bounds__(HU_AL_WG) void k_al_ties(const HuAlSample* smp, const HuAlGroup* grp, const HuAlChunk* chunk, const HuAlDraw* draw, const HuAlSel* sel,
+static __global__ __launch_bounds__(HU_AL_WG) void k_al_ties(const HuAlSample* smp, const HuAlGroup* grp, const HuAlChunk* chunk, const HuAlDraw* draw, const HuAlSel* sel,
 		uint32_t* tie, int keyBits, int chunkLen) {
 	const HuAlChunk c = chunk[blockIdx.x];
 	const HuAlGroup g = grp[c.g];
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(HU_AL_WG) void k_al_ties(const HuAlSample* smp, con
 	for(int i = 0; i < HU_AL_DT; ++i) if(act[i] && lane == 0) tie[draw[g.draw0 + d0 + i].tie0 + at] = n[i];
 }
 
-__global__ __launch_bounds__(64) void k_al_tie_scan(const HuAlSample* smp, const HuAlDraw* draw, const HuAlSel* sel, uint32_t* tie, int chunkLen) {
+static __global__ __launch_bounds__(64) void k_al_tie_scan(const HuAlSample* smp, const HuAlDraw* draw, const HuAlSel* sel, uint32_t* tie, int chunkLen) {
 	const int a = blockIdx.x, lane = threadIdx.x;
 	const HuAlDraw d = draw[a];
 	if(d.m == 0) return;
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(64) void k_al_tie_scan(const HuAlSample* smp, const
 	}
 }
 
-__global__ __launch_bounds__(HU_AL_WG) void k_al_take(const HuAlSample* smp, const HuAlGroup* grp, const HuAlChunk* chunk, const HuAlDraw* draw, const HuAlSel* sel,
+static __global__ __launch_bounds__(HU_AL_WG) void k_al_take(const HuAlSample* smp, const HuAlGroup* grp, const HuAlChunk* chunk, const HuAlDraw* draw, const HuAlSel* sel,
 		const uint32_t* tie, const uint32_t* prefix, const uint32_t* slot, uint32_t* out, int keyBits, int chunkLen) {
 	const HuAlChunk c = chunk[blockIdx.x];
 	const HuAlGroup g = grp[c.g];
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(HU_AL_WG) void k_al_take(const HuAlSample* smp, con
 	}
 }
 
-__global__ __launch_bounds__(HU_AL_WG) void k_al_whole(const HuAlSample* smp, const HuAlDraw* draw, const uint32_t* prefix, const uint32_t* slot, uint32_t* out) {
+static __global__ __launch_bounds__(HU_AL_WG) void k_al_whole(const HuAlSample* smp, const HuAlDraw* draw, const uint32_t* prefix, const uint32_t* slot, uint32_t* out) {
 	const HuAlDraw d = draw[blockIdx.x];
 	if(d.m != 0) return;
 	const HuAlSample s = smp[d.smp];
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(HU_AL_WG) void k_al_whole(const HuAlSample* smp, co
 	for(uint32_t c = threadIdx.x; c < s.nnz; c += HU_AL_WG) out[d.cell0 + L[c]] = P[c + 1] - P[c];
 }
 
-__global__ __launch_bounds__(HU_AL_WG) void k_al_stats(const HuAlSample* smp, const HuAlDraw* draw, const uint32_t* out, HuAlStat* stat) {
+static __global__ __launch_bounds__(HU_AL_WG) void k_al_stats(const HuAlSample* smp, const HuAlDraw* draw, const uint32_t* out, HuAlStat* stat) {
 	__shared__ uint64_t li[4][HU_AL_WAVES];
 	__shared__ double la[HU_AL_WAVES];
 	const HuAlDraw d = draw[blockIdx.x];
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(HU_AL_WG) void k_al_stats(const HuAlSample* smp, co
 }
 
 /* after k_al_stats: the draw's cells are overwritten by the inclusive prefix of their presence */
-__global__ __launch_bounds__(HU_AL_WG) void k_al_pd(const HuAlSample* smp, const HuAlBranch* br, const HuAlDraw* draw, uint32_t* out, HuAlStat* stat) {
+static __global__ __launch_bounds__(HU_AL_WG) void k_al_pd(const HuAlSample* smp, const HuAlBranch* br, const HuAlDraw* draw, uint32_t* out, HuAlStat* stat) {
 	__shared__ uint32_t ws[HU_AL_WAVES];
 	__shared__ double la[HU_AL_WAVES];
 	const HuAlDraw d = draw[blockIdx.x];

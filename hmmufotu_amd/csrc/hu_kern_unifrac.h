@@ -25,7 +25,7 @@
 
 #define HU_UF_WG 256
 
-__global__ void __launch_bounds__(256) k_unifrac_scan_sums(const double* __restrict__ C, double* __restrict__ blkSum, int64_t M, int64_t Sp) {
+static __global__ void __launch_bounds__(256) k_unifrac_scan_sums(const double* __restrict__ C, double* __restrict__ blkSum, int64_t M, int64_t Sp) {
 	const int64_t j = (int64_t) blockIdx.x * 256 + threadIdx.x, blk = blockIdx.y;
 	if(j >= Sp) return;
 	const int64_t q0 = blk * HU_UF_SCAN_ROWS, q1 = min(M, q0 + (int64_t) HU_UF_SCAN_ROWS);
@@ -34,14 +34,14 @@ __global__ void __launch_bounds__(256) k_unifrac_scan_sums(const double* __restr
 	blkSum[blk * Sp + j] = s;
 }
 
-__global__ void __launch_bounds__(256) k_unifrac_scan_offs(double* __restrict__ blkSum, int64_t nBlk, int64_t Sp) {
+static __global__ void __launch_bounds__(256) k_unifrac_scan_offs(double* __restrict__ blkSum, int64_t nBlk, int64_t Sp) {
 	const int64_t j = (int64_t) blockIdx.x * 256 + threadIdx.x;
 	if(j >= Sp) return;
 	double off = 0.0;
 	for(int64_t blk = 0; blk < nBlk; ++blk) { const double s = blkSum[blk * Sp + j]; blkSum[blk * Sp + j] = off; off += s; }
 }
 
-__global__ void __launch_bounds__(256) k_unifrac_scan_rows(double* __restrict__ C, const double* __restrict__ blkOff, int64_t M, int64_t Sp) {
+static __global__ void __launch_bounds__(256) k_unifrac_scan_rows(double* __restrict__ C, const double* __restrict__ blkOff, int64_t M, int64_t Sp) {
 	const int64_t j = (int64_t) blockIdx.x * 256 + threadIdx.x, blk = blockIdx.y;
 	if(j >= Sp) return;
 	const int64_t q0 = blk * HU_UF_SCAN_ROWS, q1 = min(M, q0 + (int64_t) HU_UF_SCAN_ROWS);
@@ -49,7 +49,7 @@ __global__ void __launch_bounds__(256) k_unifrac_scan_rows(double* __restrict__ 
 	for(int64_t q = q0; q < q1; ++q) { run += C[(q + 1) * Sp + j]; C[(q + 1) * Sp + j] = run; }
 }
 
-__global__ void __launch_bounds__(256) k_unifrac_gather(const double* __restrict__ C, const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
+static __global__ void __launch_bounds__(256) k_unifrac_gather(const double* __restrict__ C, const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
 		double* __restrict__ P, int64_t M, int64_t S, int64_t Sp, int64_t B) {
 	const int64_t j = (int64_t) blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
 	if(j >= Sp || k >= B) return;
@@ -71,17 +71,17 @@ template<int METHOD> __device__ __forceinline__ void hu_uf_term(double b, double
 	}
 }
 
-/* grid (tiles, slabs); part [slab][tile][2][64][64] */
-template<int METHOD> __global__ void __launch_bounds__(HU_UF_WG) k_unifrac_pairs(const double* __restrict__ P, const double* __restrict__ blen,
-		double* __restrict__ part, int64_t Sp, int64_t B, int64_t L, double alpha) {
+/* one workgroup's tile (of nTile) and slab; part [slab][tile][2][64][64].  hu_kern_unifrac_rarefied.h calls it once per resident draw */
+template<int METHOD> __device__ __forceinline__ void hu_uf_pairs_wg(const double* __restrict__ P, const double* __restrict__ blen,
+		double* __restrict__ part, int64_t Sp, int64_t B, int64_t L, double alpha, const int tile, const int slab, const int nTile) {
 	__shared__ __attribute__((aligned(16))) double sI[HU_UF_CHUNK][HU_UF_TILE], sJ[HU_UF_CHUNK][HU_UF_TILE];
 	__shared__ double sB[HU_UF_CHUNK];
 	const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
 	const int nt = (int)(Sp / HU_UF_TILE);
-	int t = blockIdx.x, iblk = 0;
+	int t = tile, iblk = 0;
 	while(t >= nt - iblk) { t -= nt - iblk; ++iblk; }
 	const int jblk = iblk + t;
-	const int64_t k0 = (int64_t) blockIdx.y * L, k1 = min(B, k0 + L);
+	const int64_t k0 = (int64_t) slab * L, k1 = min(B, k0 + L);
 	/* staging: thread -> row tid >> 3 of the chunk, columns 8 (tid & 7) .. + 7 of either panel */
 	const int sr = tid >> 3, sc = (tid & 7) * 8;
 	const double* gI = P + (int64_t) iblk * HU_UF_TILE + sc;
@@ -129,7 +129,7 @@ template<int METHOD> __global__ void __launch_bounds__(HU_UF_WG) k_unifrac_pairs
 				for(int c = 0; c < 4; ++c) hu_uf_term<METHOD>(b, x[r], y[c], alpha, num[r][c], den[r][c]);
 		}
 	}
-	double* out = part + ((int64_t) blockIdx.y * gridDim.x + blockIdx.x) * (2 * HU_UF_TILE * HU_UF_TILE);
+	double* out = part + ((int64_t) slab * nTile + tile) * (2 * HU_UF_TILE * HU_UF_TILE);
 #pragma unroll
 	for(int r = 0; r < 4; ++r) {
 		const int row = 2 * ty + (r & 1) + 32 * (r >> 1);
@@ -142,8 +142,14 @@ template<int METHOD> __global__ void __launch_bounds__(HU_UF_WG) k_unifrac_pairs
 	}
 }
 
+/* grid (tiles, slabs) */
+template<int METHOD> __global__ void __launch_bounds__(HU_UF_WG) k_unifrac_pairs(const double* __restrict__ P, const double* __restrict__ blen,
+		double* __restrict__ part, int64_t Sp, int64_t B, int64_t L, double alpha) {
+	hu_uf_pairs_wg<METHOD>(P, blen, part, Sp, B, L, alpha, (int) blockIdx.x, (int) blockIdx.y, (int) gridDim.x);
+}
+
 /* grid (tiles, 16): a thread per pair of the tile */
-__global__ void __launch_bounds__(256) k_unifrac_finish(const double* __restrict__ part, double* __restrict__ dist, int64_t S, int64_t Sp, int64_t nSlab, int raw) {
+static __global__ void __launch_bounds__(256) k_unifrac_finish(const double* __restrict__ part, double* __restrict__ dist, int64_t S, int64_t Sp, int64_t nSlab, int raw) {
 	const int nt = (int)(Sp / HU_UF_TILE);
 	int t = blockIdx.x, iblk = 0;
 	while(t >= nt - iblk) { t -= nt - iblk; ++iblk; }
@@ -163,7 +169,7 @@ __global__ void __launch_bounds__(256) k_unifrac_finish(const double* __restrict
 }
 
 /* grid (ceil(Sp / 256), slabs) */
-__global__ void __launch_bounds__(256) k_unifrac_pd(const double* __restrict__ P, const double* __restrict__ blen, double* __restrict__ pdPart, int64_t Sp, int64_t B, int64_t L) {
+static __global__ void __launch_bounds__(256) k_unifrac_pd(const double* __restrict__ P, const double* __restrict__ blen, double* __restrict__ pdPart, int64_t Sp, int64_t B, int64_t L) {
 	const int64_t j = (int64_t) blockIdx.x * 256 + threadIdx.x;
 	if(j >= Sp) return;
 	const int64_t k0 = (int64_t) blockIdx.y * L, k1 = min(B, k0 + L);
@@ -172,7 +178,7 @@ __global__ void __launch_bounds__(256) k_unifrac_pd(const double* __restrict__ P
 	pdPart[(int64_t) blockIdx.y * Sp + j] = acc;
 }
 
-__global__ void __launch_bounds__(256) k_unifrac_pd_finish(const double* __restrict__ pdPart, double* __restrict__ pd, int64_t S, int64_t Sp, int64_t nSlab) {
+static __global__ void __launch_bounds__(256) k_unifrac_pd_finish(const double* __restrict__ pdPart, double* __restrict__ pd, int64_t S, int64_t Sp, int64_t nSlab) {
 	const int64_t j = (int64_t) blockIdx.x * 256 + threadIdx.x;
 	if(j >= S) return;
 	double tot = 0.0;

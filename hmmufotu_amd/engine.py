@@ -1063,6 +1063,77 @@ def alpha_timing() -> dict:
     return dict(to_device=s[0], select=s[1], take=s[2], metrics=s[3], pd=s[4], to_host=s[5])
 
 
+class UnifracRarefiedOpts(C.Structure):
+    _fields_ = [("method", C.c_int32), ("host", C.c_int32), ("alpha", C.c_double), ("slab", C.c_int64), ("chunk", C.c_int32), ("key_bits", C.c_int32),
+                ("draw_chunk", C.c_int64), ("mem_budget", C.c_int64)]
+
+
+def _unifrac_rarefied_args(what, counts, otu_node, parent, blen, depth, reps, method, alpha, slab, host, chunk, key_bits, draw_chunk, mem_budget):
+    c, uo, tree, node, keep = _unifrac_args(what, counts, otu_node, parent, blen, method, alpha, slab, host, 0)
+    o = UnifracRarefiedOpts()
+    load_library().hu_unifrac_rarefied_default_opts(C.byref(o))
+    o.method = uo.method; o.host = 1 if host else 0; o.alpha = uo.alpha; o.slab = uo.slab; o.key_bits = int(key_bits)
+    o.draw_chunk = int(draw_chunk or 0); o.mem_budget = int(mem_budget or 0)
+    if chunk is not None:
+        o.chunk = int(chunk)
+    if int(depth) < 0 or int(depth) >= 2 ** 64:
+        raise EngineError(what + ": the depth is a whole number")
+    return c, o, tree, node, keep
+
+
+def unifrac_rarefied_sizes(counts, otu_node=None, parent=None, blen=None, depth=1, reps=1, method="weighted", alpha=None, slab=0, chunk=None) -> dict:
+    """hu_unifrac_rarefied_sizes (host only): what unifrac_rarefied_need takes, for a call of unifrac_rarefied: dict(n_kept, n_cell, n_entry,
+    max_nnz, max_chunk, n_branch, slab, max_depth2); max_depth2 is the largest depth that keeps 2 samples"""
+    c, o, tree, node, keep = _unifrac_rarefied_args("unifrac_rarefied_sizes", counts, otu_node, parent, blen, depth, reps, method, alpha, slab, True, chunk, 64, 0, 0)
+    out = np.zeros(8, np.int64)
+    _chk(load_library().hu_unifrac_rarefied_sizes(C.byref(tree) if tree is not None else None, C.c_int64(c.shape[0]), C.c_int64(c.shape[1]), node, _p(c, C.c_double),
+                                                  C.c_uint64(int(depth)), C.c_int64(int(reps)), C.byref(o), _p(out, C.c_int64)))
+    return dict(zip(("n_kept", "n_cell", "n_entry", "max_nnz", "max_chunk", "n_branch", "slab", "max_depth2"), (int(v) for v in out)))
+
+
+def unifrac_rarefied(counts, otu_node=None, parent=None, blen=None, depth=None, reps=None, seed=1, method="weighted", alpha=None, slab=0, device=0, host=False,
+                     chunk=None, key_bits=64, draw_chunk=0, mem_budget=0, draws=False) -> dict:
+    """hu_unifrac_rarefied: the distances of unifrac averaged over `reps` rarefied draws of `depth` reads: dict(mean [S'][S'], sd [S'][S'],
+    kept [samples] bool, and with draws=True draws [reps][S'][S']).  The S' kept samples are the columns with at least `depth` reads, in
+    table order.  Draw r is otu_subset(counts, depth, seed=seed + r) of the whole table, its distances those of unifrac on the kept columns
+    with the slab of (S', B); mean and sd follow Welford's recurrence in ascending r (sd is NaN for reps == 1).  host, or device < 0: the
+    library's host path, no device needed."""
+    if depth is None or reps is None:
+        raise EngineError("unifrac_rarefied: depth and reps are required")
+    hst = host or int(device) < 0
+    c, o, tree, node, keep = _unifrac_rarefied_args("unifrac_rarefied", counts, otu_node, parent, blen, depth, reps, method, alpha, slab, hst, chunk, key_bits, draw_chunk, mem_budget)
+    S = c.shape[1]
+    R = int(reps)
+    tot = c.sum(axis=0) if c.size else np.zeros(S)
+    Sk = int(np.count_nonzero(tot >= int(depth))) if int(depth) > 0 else S      # the room only: the library counts for itself
+    kept = np.zeros(S, np.uint8); mean = np.zeros((Sk, Sk)); sd = np.zeros((Sk, Sk))
+    dr = np.zeros((R, Sk, Sk)) if draws and 0 < R <= 100000 else None
+    _chk(load_library().hu_unifrac_rarefied(C.c_int(int(device)), C.byref(tree) if tree is not None else None, C.c_int64(c.shape[0]), C.c_int64(S), node, _p(c, C.c_double),
+                                            C.c_uint64(int(depth)), C.c_int64(R), C.c_uint64(int(seed) & (2 ** 64 - 1)), C.byref(o), _p(kept, C.c_uint8),
+                                            _p(mean, C.c_double), _p(sd, C.c_double), _p(dr, C.c_double) if dr is not None else None))
+    out = dict(mean=mean, sd=sd, kept=kept.astype(bool))
+    if draws:
+        out["draws"] = dr
+    return out
+
+
+def unifrac_rarefied_need(n_sample: int, n_kept: int, n_cell: int, n_entry: int, max_nnz: int, max_chunk: int, n_branch: int, slab: int, draw_chunk: int,
+                          want_draws: bool = False) -> int:
+    """hu_unifrac_rarefied_need: the bytes of device memory for draw_chunk resident draws"""
+    lib = load_library()
+    lib.hu_unifrac_rarefied_need.restype = C.c_int64
+    return int(lib.hu_unifrac_rarefied_need(*(C.c_int64(int(v)) for v in (n_sample, n_kept, n_cell, n_entry, max_nnz, max_chunk, n_branch, slab, draw_chunk)),
+                                            C.c_int32(1 if want_draws else 0)))
+
+
+def unifrac_rarefied_timing() -> dict:
+    """hu_unifrac_rarefied_timing: the phases of this thread's last unifrac_rarefied on a device, in seconds, and the draws that were resident at once"""
+    s = np.zeros(6)
+    n = C.c_int64(0)
+    _chk(load_library().hu_unifrac_rarefied_timing(_p(s, C.c_double), C.byref(n)))
+    return dict(to_device=s[0], draws=s[1], embed=s[2], pairs=s[3], accumulate=s[4], to_host=s[5], resident_draws=int(n.value))
+
+
 class DiffabundOpts(C.Structure):
     _fields_ = [("perms", C.c_int64), ("seed", C.c_uint64), ("host", C.c_int32), ("rank_by", C.c_int32), ("min_prevalence", C.c_int64), ("chunk", C.c_int64),
                 ("mem_budget", C.c_int64)]

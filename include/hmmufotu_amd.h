@@ -1747,6 +1747,63 @@ int hu_diffabund_ranks(int64_t n_otu, int64_t n_sample, const double* counts, in
 int64_t hu_diffabund_need(int64_t n_sample, int64_t a, int64_t n_otu, int64_t n_cell, int64_t chunk);
 int hu_diffabund_timing(double* seconds /* [4] */);
 
+/* ---- hmmufotu-amd-unifrac --rarefy: the distances averaged over rarefied draws ----
+ * The inputs of hu_unifrac, a depth M >= 1, R >= 1 repeats and a 64-bit seed.
+ * Kept samples: the columns with N_j >= M, in table order, S' of them; kept_out [n_sample] (may be NULL) is 1 for them and 0 for the
+ *     dropped ones (N_j < M).  Fewer than 2 kept samples are refused.
+ * Draw r (r = 0 .. R-1) is the table X_r: column j of X_r is column j of hu_otu_subset(counts, M, HU_OTU_UNIFORM, seed + r) of the
+ *     original table (the Philox key takes the original column index, so a dropped column does not renumber the others; seed + r wraps
+ *     at 2^64): hu_alpha's draw (j, M, r).  A sample with N_j == M is itself in every draw.  X_r keeps every row, empty ones too.
+ * D_r is hu_unifrac of X_r restricted to the kept columns, with the same otu_node, tree, method and alpha, and the slab L = opts->slab
+ *     or hu_unifrac_default_slab(S', B) when that is 0; B depends on the ids alone, so every draw has the same.  A branch below which
+ *     neither sample has a read adds +0 to every sum: D_r has the bits hu_unifrac returns for that table and that L, device against
+ *     device and host against host.
+ * Result: mean_out [S'][S'] and sd_out [S'][S'] by Welford's recurrence in ascending r, every operation rounded on its own:
+ *     mean = 0, M2 = 0; for r = 1 .. R with x = D_{r-1}[i][j]:  d = x - mean;  mean = mean + d / r;  M2 = M2 + d * (x - mean)
+ *     sd = sqrt(M2 / (R - 1)), NaN for R == 1.  The diagonal is exactly 0 in both, [j][i] is the stored copy of [i][j].
+ *     draws_out [R][S'][S'] (may be NULL) receives every D_r.
+ * All six methods; HU_UF_BRAY_CURTIS and HU_UF_JACCARD on the identity tree (tree == NULL).  Uniform draws only.  No PD: hu_alpha has it.
+ * opts->host, or device < 0: the host path (hu_otu_subset's host selection, hu_unifrac's host path per draw, the same recurrence): the
+ * same bits as the device for every method but HU_UF_GENERALIZED with 0 < alpha < 1, where the two agree as hu_unifrac's paths do.
+ * The device path uploads the table once, as hu_alpha does (every sample's nonzero cells), and no draw's table comes back: per chunk of
+ * draw_chunk repeats the select / ties / take kernels of hu_alpha draw every kept sample, one kernel turns a (sample, repeat)'s counters
+ * into its column of P_r [B][Sp] (an integer prefix over the counters, one rounded division per branch entry), hu_unifrac's pair kernel
+ * runs over (tile, slab, draw) in one launch, and one kernel adds a draw's slabs in ascending order, divides and applies the recurrence,
+ * the draws in ascending r.  No atomics in the floating-point path.  No result depends on draw_chunk, chunk, the grid or the device.
+ * HU_ERR_ARG with the reason, before a device is asked for: whatever hu_unifrac and hu_alpha refuse of the table, the tree and the
+ * options, M == 0, R < 1 or R > 100,000, fewer than 2 kept samples (the message gives the largest M that keeps 2), a NULL mean_out or
+ * sd_out.  HU_ERR_NOMEM with both numbers when hu_unifrac_rarefied_need for draw_chunk (for 1 when it is 0) exceeds mem_budget (checked
+ * before a device is asked for) or what the device reports free.
+ * hu_unifrac_rarefied_need: the bytes on the device, with Sp = 64 ceil(n_kept / 64), tiles = hu_unifrac's and slabs = ceil(n_branch / slab):
+ *     32 n_sample + 4 (2 n_cell + n_sample) + 20 n_entry + 8 n_branch                          the resident table, entries, lengths
+ *   + draw_chunk (n_kept (1096 + 4 max_nnz + 24 max_chunk) + 8 n_branch Sp + 65536 slabs tiles)  select state, counters, P, partial sums
+ *   + (want_draws ? draw_chunk : 0) 8 n_kept^2 + 16 n_kept^2 + 2^20                            the D_r of a chunk, mean and M2, slack
+ * -1 on a negative argument or slab < 1.
+ * hu_unifrac_rarefied_sizes: host only, for the arguments and refusals of hu_unifrac_rarefied: out [8] = n_kept, n_cell, n_entry, max_nnz,
+ * max_chunk, n_branch, the slab L, the largest M that keeps 2 samples.
+ * hu_unifrac_rarefied_timing: of this thread's last device call, seconds [6] = copies up, draws, embedding, pair kernels, accumulate,
+ * copy back; resident_draws (may be NULL) receives the draws that were resident at once. */
+typedef struct {
+	int32_t method;       /* HU_UF_WEIGHTED */
+	int32_t host;         /* 0; 1: the host path, no device needed */
+	double alpha;         /* 0.5; read by HU_UF_GENERALIZED only */
+	int64_t slab;         /* 0: hu_unifrac_default_slab(S', B) */
+	int32_t chunk;        /* 16384: reads per workgroup of the draw kernels */
+	int32_t key_bits;     /* 64; below 64 keys tie: for the tie tests only */
+	int64_t draw_chunk;   /* 0: as many draws resident as the memory holds */
+	int64_t mem_budget;   /* 0: what the device reports free */
+} hu_unifrac_rarefied_opts;
+#define HU_UFR_MAX_REPS 100000
+void hu_unifrac_rarefied_default_opts(hu_unifrac_rarefied_opts* o);
+int hu_unifrac_rarefied(int device, const hu_unifrac_tree* tree, int64_t n_otu, int64_t n_sample, const int32_t* otu_node, const double* counts,
+		uint64_t depth, int64_t reps, uint64_t seed, const hu_unifrac_rarefied_opts* opts, uint8_t* kept_out /* [n_sample] or NULL */,
+		double* mean_out /* [S'][S'] */, double* sd_out /* [S'][S'] */, double* draws_out /* [reps][S'][S'] or NULL */);
+int hu_unifrac_rarefied_sizes(const hu_unifrac_tree* tree, int64_t n_otu, int64_t n_sample, const int32_t* otu_node, const double* counts,
+		uint64_t depth, int64_t reps, const hu_unifrac_rarefied_opts* opts, int64_t* out /* [8] */);
+int64_t hu_unifrac_rarefied_need(int64_t n_sample, int64_t n_kept, int64_t n_cell, int64_t n_entry, int64_t max_nnz, int64_t max_chunk,
+		int64_t n_branch, int64_t slab, int64_t draw_chunk, int32_t want_draws);
+int hu_unifrac_rarefied_timing(double* seconds /* [6] */, int64_t* resident_draws);
+
 #ifdef __cplusplus
 }
 #endif
