@@ -2,7 +2,7 @@
 // step to another package, which needs a tree matched to OTU names; here the OTU ids are node numbers of <DB>.ptu.
 //   hmmufotu-amd-alpha <OTU-FILE> [--db DB] [-o FILE] [--depths a,b,c | --steps 10 [--max-depth M]] [--reps 10] [-S|--seed 1]
 //                      [--curve-out FILE] [--draws-out FILE] [--chunk N] [--mem GB] [--device N] [--host] [-v]
-// The statistics are hu_alpha's: on the device (hu_kern_alpha.h), or with --host by the library's host path; the metrics and a curve's
+// The statistics are hu_alpha's: on the device (hu_kern_draw.h, hu_kern_alpha.h), or with --host by the library's host path; the metrics and a curve's
 // mean and deviation are the library's host code on both.  Every refusal comes before a device is asked for, and the outputs are opened
 // only after the computation: a refused run leaves no file.
 #include <algorithm>

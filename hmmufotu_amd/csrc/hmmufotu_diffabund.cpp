@@ -16,6 +16,7 @@
 #include <vector>
 #include "../../include/hmmufotu_amd.h"
 #include "hu_num_format.h"
+#include "hu_groups_file.h"
 
 static void usage(const char* p) {
 	std::cerr << "Test every OTU of a table for a difference between groups of samples (Kruskal-Wallis on ranks, permutation p-values, maxT and BH)\n"
@@ -81,26 +82,8 @@ int main(int argc, char** argv) {
 	const double* cnt = hu_otu_table_counts(t);
 	std::map<std::string, int64_t> at;
 	for(int64_t j = 0; j < S; ++j) at[hu_otu_table_sample(t, j)] = j;
-	/* GROUPS: sample<TAB>group, the rules of hmmufotu-amd-permanova */
-	std::vector<std::string> groupOf((size_t) S); std::vector<char> seen((size_t) S, 0);
-	{
-		std::ifstream in(pos[1]);
-		if(!in) { std::cerr << "Unable to open group file '" << pos[1] << "'" << std::endl; return EXIT_FAILURE; }
-		std::string line; long long ln = 0, ignored = 0;
-		while(std::getline(in, line)) {
-			++ln;
-			if(!line.empty() && line.back() == '\r') line.pop_back();
-			if(line.empty() || line[0] == '#') continue;
-			const size_t tab = line.find('\t');
-			if(tab == std::string::npos || tab == 0 || tab + 1 >= line.size() || line.find('\t', tab + 1) != std::string::npos) {
-				std::cerr << pos[1] << ": line " << ln << ": expected sample<TAB>group" << std::endl; return EXIT_FAILURE; }
-			const auto it = at.find(line.substr(0, tab));
-			if(it == at.end()) { ++ignored; continue; }
-			if(seen[(size_t) it->second]) { std::cerr << "Sample '" << it->first << "' is named twice in '" << pos[1] << "'" << std::endl; return EXIT_FAILURE; }
-			seen[(size_t) it->second] = 1; groupOf[(size_t) it->second] = line.substr(tab + 1);
-		}
-		if(verbose) std::cerr << ignored << " line(s) of '" << pos[1] << "' name no sample of the table" << std::endl;
-	}
+	std::vector<std::string> groupOf, gname; std::vector<char> seen;
+	if(!hu_groups_read(pos[1], S, at, "table", verbose != 0, groupOf, seen)) return EXIT_FAILURE;
 	/* the samples of the test: all of them, or with --ignore-missing those that have a line */
 	std::vector<int64_t> col;
 	for(int64_t j = 0; j < S; ++j) {
@@ -109,14 +92,7 @@ int main(int argc, char** argv) {
 	}
 	const int64_t N = (int64_t) col.size();
 	if(verbose && ignoreMissing) std::cerr << S - N << " sample(s) of the table have no line in '" << pos[1] << "' and are left out" << std::endl;
-	/* groups in order of first appearance among the table's samples */
-	std::vector<std::string> gname; std::map<std::string, int32_t> gid; std::vector<int32_t> label((size_t) N);
-	for(int64_t k = 0; k < N; ++k) {
-		const std::string& g = groupOf[(size_t) col[(size_t) k]];
-		auto it = gid.find(g);
-		if(it == gid.end()) { it = gid.emplace(g, (int32_t) gname.size()).first; gname.push_back(g); }
-		label[(size_t) k] = it->second;
-	}
+	const std::vector<int32_t> label = hu_groups_label(groupOf, col, gname);
 	std::vector<double> sub;
 	const double* use = cnt;
 	if(N != S) {

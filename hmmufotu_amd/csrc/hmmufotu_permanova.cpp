@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 #include "../../include/hmmufotu_amd.h"
+#include "hu_groups_file.h"
 
 static void usage(const char* p) {
 	std::cerr << "Test whether groups of samples differ on a distance matrix (PERMANOVA: pseudo-F and a permutation p-value)\n"
@@ -78,35 +79,13 @@ int main(int argc, char** argv) {
 	const double* dist = hu_dist_matrix_values(m);
 	std::map<std::string, int64_t> at;
 	for(int64_t i = 0; i < n; ++i) at[hu_dist_matrix_sample(m, i)] = i;
-	/* GROUPS: sample<TAB>group */
-	std::vector<std::string> groupOf((size_t) n); std::vector<char> seen((size_t) n, 0);
-	{
-		std::ifstream in(pos[1]);
-		if(!in) { std::cerr << "Unable to open group file '" << pos[1] << "'" << std::endl; return EXIT_FAILURE; }
-		std::string line; long long ln = 0, ignored = 0;
-		while(std::getline(in, line)) {
-			++ln;
-			if(!line.empty() && line.back() == '\r') line.pop_back();
-			if(line.empty() || line[0] == '#') continue;
-			const size_t tab = line.find('\t');
-			if(tab == std::string::npos || tab == 0 || tab + 1 >= line.size() || line.find('\t', tab + 1) != std::string::npos) {
-				std::cerr << pos[1] << ": line " << ln << ": expected sample<TAB>group" << std::endl; return EXIT_FAILURE; }
-			const auto it = at.find(line.substr(0, tab));
-			if(it == at.end()) { ++ignored; continue; }
-			if(seen[(size_t) it->second]) { std::cerr << "Sample '" << it->first << "' is named twice in '" << pos[1] << "'" << std::endl; return EXIT_FAILURE; }
-			seen[(size_t) it->second] = 1; groupOf[(size_t) it->second] = line.substr(tab + 1);
-		}
-		if(verbose) std::cerr << ignored << " line(s) of '" << pos[1] << "' name no sample of the matrix" << std::endl;
-	}
-	for(int64_t i = 0; i < n; ++i) if(!seen[(size_t) i]) {
-		std::cerr << "Sample '" << hu_dist_matrix_sample(m, i) << "' of the matrix has no line in '" << pos[1] << "'" << std::endl; return EXIT_FAILURE; }
-	/* groups in order of first appearance among the matrix's samples */
-	std::vector<std::string> gname; std::map<std::string, int32_t> gid; std::vector<int32_t> label((size_t) n);
+	std::vector<std::string> groupOf, gname; std::vector<char> seen; std::vector<int64_t> every((size_t) n);
+	if(!hu_groups_read(pos[1], n, at, "matrix", verbose != 0, groupOf, seen)) return EXIT_FAILURE;
 	for(int64_t i = 0; i < n; ++i) {
-		auto it = gid.find(groupOf[(size_t) i]);
-		if(it == gid.end()) { it = gid.emplace(groupOf[(size_t) i], (int32_t) gname.size()).first; gname.push_back(groupOf[(size_t) i]); }
-		label[(size_t) i] = it->second;
+		if(!seen[(size_t) i]) { std::cerr << "Sample '" << hu_dist_matrix_sample(m, i) << "' of the matrix has no line in '" << pos[1] << "'" << std::endl; return EXIT_FAILURE; }
+		every[(size_t) i] = i;
 	}
+	const std::vector<int32_t> label = hu_groups_label(groupOf, every, gname);
 	const int dev = host ? -1 : device;
 	std::vector<std::string> lines;
 	hu_permanova_result all;

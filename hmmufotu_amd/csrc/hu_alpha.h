@@ -1,27 +1,19 @@
 // What the host half (hu_alpha_host.cpp, a plain C++ compiler) and the device half (hu_alpha.hip, hu_kern_alpha.h) of hu_alpha share
-// (DESIGN.md §30): the records both read, the plan of a call, made on the host from a checked table and one walk of the tree, and the
-// constants that fix the order in which A and PD are added.
+// (DESIGN.md §30): the records both read (those of a draw are hu_draw.h's), the plan of a call, made on the host from a checked table and
+// one walk of the tree, and the constants that fix the order in which A and PD are added.
 #pragma once
 #include <stdint.h>
 #include <vector>
 #include "hu_otu_table.h"
+#include "hu_draw.h"
 #include "hu_unifrac.h"
 
 #define HU_AL_WG 256             /* threads of every workgroup; the order of A and PD is a function of it */
 #define HU_AL_WAVES 4
-#define HU_AL_DT 8               /* depths of one (sample, repeat) that one key computation serves */
+#define HU_AL_DT 8               /* depths of one (sample, repeat) that one key computation serves: the DT of hu_kern_draw.h */
 
-/* a sample: its nnz + 1 prefixes (P[c] = reads before nonzero cell c in table order, P[nnz] = T), its nnz slots from pfx0 - col on (the
- * place of cell c in depth-first row order, in which a draw's cells are kept) and its branch entries */
-struct HuAlSample { uint64_t pfx0, br0; uint32_t nnz, T, col, nBr; };
 /* a kept branch below which the sample has a nonzero cell: its length and its cells [lo, hi), lo < hi <= nnz; ascending branch number */
 struct HuAlBranch { double b; uint32_t lo, hi; };
-/* a resident draw: its nnz cells in out[], its tie counts (4 per chunk of its sample), its sample, its depth (0: the whole sample) */
-struct HuAlDraw { uint64_t cell0, tie0; uint32_t smp, m; };
-/* the draws draw0 .. draw0 + nd - 1 of one (sample, repeat) in ascending depth; (k0, k1) is the Philox key of seed + repeat */
-struct HuAlGroup { uint64_t chunk0; uint32_t smp, k0, k1, draw0, nd, nChunk; };
-struct HuAlChunk { uint32_t g, t0; };                         /* group, first read */
-struct HuAlSel { uint64_t prefix; uint32_t rank, eq; };       /* as HuOtuSel (hu_kern_otu.h) */
 /* what comes back, one per draw */
 struct HuAlStat { uint64_t Q; double A, PD; uint32_t S, F1, F2, pad; };
 

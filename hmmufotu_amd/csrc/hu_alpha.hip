@@ -1,6 +1,6 @@
 // hu_alpha: the entry, and the device path of hmmufotu-amd-alpha.  The host makes the plan (hu_alpha_host.cpp: every
 // sample's nonzero cells, their prefixes in table order and their places in the depth-first row order of hu_unifrac's embedding, the
-// branch entries, the list of draws); the prefixes, the places and the entries go up once and stay; the draws are taken `cap` at a time through the kernels of hu_kern_alpha.h, and 40
+// branch entries, the list of draws); the prefixes, the places and the entries go up once and stay; the draws are taken `cap` at a time through the kernels of hu_kern_draw.h and hu_kern_alpha.h, and 40
 // bytes per draw come back.  The number of launches per chunk of draws does not depend on the table.
 #include <algorithm>
 #include <chrono>
@@ -66,7 +66,6 @@ static int al_device(const char* fn, int device, const HuAlPlan& pl, std::vector
 	stat.resize(U);
 	std::vector<HuAlDraw> draw; std::vector<HuAlGroup> grp; std::vector<HuAlChunk> chunk; std::vector<HuAlSel> sel;
 	const uint64_t perChunk = (uint64_t) pl.chunk;
-	const int passes = (pl.keyBits + 7) / 8;                          /* the key is below 2^key_bits: its top digit may be a short one */
 	for(size_t u0 = 0; u0 < U; u0 += D) {
 		const size_t n = std::min(D, U - u0);
 		draw.assign(n, HuAlDraw{0, 0, 0, 0}); sel.assign(n, HuAlSel{0, 0, 0}); grp.clear(); chunk.clear();
@@ -75,19 +74,14 @@ static int al_device(const char* fn, int device, const HuAlPlan& pl, std::vector
 		for(size_t a = 0; a < n; ++a) {
 			const HuAlUnit& un = pl.unit[u0 + a];
 			const HuAlSample& s = pl.smp[(size_t) un.smp];
-			const uint32_t nChunk = (uint32_t)((s.T + perChunk - 1) / perChunk);
 			draw[a] = HuAlDraw{cells, ties, (uint32_t) un.smp, un.depth < 0 ? 0u : (uint32_t) pl.depth[(size_t) un.depth]};
 			cells += s.nnz;
 			if(un.depth < 0) continue;
-			ties += (uint64_t) nChunk * HU_AL_WAVES;
+			ties += (s.T + perChunk - 1) / perChunk * HU_DRAW_WAVES;
 			sel[a] = HuAlSel{0, draw[a].m, s.T};
 			const bool cont = a > 0 && pl.unit[u0 + a - 1].depth >= 0 && pl.unit[u0 + a - 1].smp == un.smp && pl.unit[u0 + a - 1].rep == un.rep;
 			if(cont) ++grp.back().nd;
-			else {
-				const uint64_t sd = pl.seed + (uint64_t) un.rep;
-				grp.push_back(HuAlGroup{chunk.size(), (uint32_t) un.smp, (uint32_t)(sd & 0xffffffffu), (uint32_t)(sd >> 32), (uint32_t) a, 1u, nChunk});
-				for(uint32_t c = 0; c < nChunk; ++c) chunk.push_back(HuAlChunk{(uint32_t)(grp.size() - 1), (uint32_t)(c * perChunk)});
-			}
+			else hu_draw_add_group(grp, chunk, (uint32_t) un.smp, pl.seed + (uint64_t) un.rep, (uint32_t) a, 1u, s.T, perChunk);
 			maxNd = std::max(maxNd, grp.back().nd);
 		}
 		ACHK(hipMemcpy(dDraw, draw.data(), n * sizeof(HuAlDraw), hipMemcpyHostToDevice));
@@ -99,27 +93,13 @@ static int al_device(const char* fn, int device, const HuAlPlan& pl, std::vector
 		ACHK(hipMemset(dOut, 0, (size_t) cells * 4));
 		ACHK(hipDeviceSynchronize());
 		phase(0);
-		const dim3 grid((unsigned) chunk.size(), (maxNd + HU_AL_DT - 1) / HU_AL_DT);
-		if(!chunk.empty()) {
-			for(int p = 0; p < passes; ++p) {
-				k_al_hist<<<grid, HU_AL_WG>>>(dSmp, dGrp, dChunk, dSel, dHist, pl.keyBits, pl.chunk, 8 * (passes - 1 - p), p == 0);
-				ACHK(hipGetLastError());
-				k_al_pick<<<(unsigned) n, 64>>>(dDraw, dSel, dHist);
-				ACHK(hipGetLastError());
-			}
-			k_al_ties<<<grid, HU_AL_WG>>>(dSmp, dGrp, dChunk, dDraw, dSel, dTie, pl.keyBits, pl.chunk);
-			ACHK(hipGetLastError());
-			k_al_tie_scan<<<(unsigned) n, 64>>>(dSmp, dDraw, dSel, dTie, pl.chunk);
-			ACHK(hipGetLastError());
-			ACHK(hipDeviceSynchronize());
-		}
+		const HuDrawDev dv = {dSmp, dDraw, dGrp, dChunk, dSel, dHist, dTie, dPrefix, dSlot, dOut, pl.keyBits, pl.chunk};
+		ACHK(hu_draw_select<HU_AL_DT>(dv, (unsigned) n, (unsigned) chunk.size(), maxNd));
+		ACHK(hipDeviceSynchronize());
 		phase(1);
 		k_al_whole<<<(unsigned) n, HU_AL_WG>>>(dSmp, dDraw, dPrefix, dSlot, dOut);
 		ACHK(hipGetLastError());
-		if(!chunk.empty()) {
-			k_al_take<<<grid, HU_AL_WG>>>(dSmp, dGrp, dChunk, dDraw, dSel, dTie, dPrefix, dSlot, dOut, pl.keyBits, pl.chunk);
-			ACHK(hipGetLastError());
-		}
+		ACHK(hu_draw_take<HU_AL_DT>(dv, (unsigned) chunk.size(), maxNd));
 		ACHK(hipDeviceSynchronize());
 		phase(2);
 		k_al_stats<<<(unsigned) n, HU_AL_WG>>>(dSmp, dDraw, dOut, dStat);

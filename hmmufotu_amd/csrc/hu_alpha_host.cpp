@@ -170,7 +170,7 @@ void hu_al_host(const HuAlPlan& pl, std::vector<HuAlStat>& stat) {
 			stat[u++] = al_stats(pl, s, cells.data(), W);
 			continue;
 		}
-		/* the draws of one (sample, repeat): the keys once, then every depth as hu_otu_subset_host selects */
+		/* the draws of one (sample, repeat): the keys once, then every depth by hu_otu_subset_host's selection (hu_draw.h) */
 		const uint64_t sd = pl.seed + (uint64_t) un.rep;
 		const uint32_t key[2] = {(uint32_t)(sd & 0xffffffffu), (uint32_t)(sd >> 32)};
 		keys.resize(s.T);
@@ -180,20 +180,10 @@ void hu_al_host(const HuAlPlan& pl, std::vector<HuAlStat>& stat) {
 			if(m >= s.T) { for(uint32_t c = 0; c < s.nnz; ++c) cells[L[c]] = P[c + 1] - P[c]; }
 			else {
 				work = keys;
-				std::nth_element(work.begin(), work.begin() + (size_t)(m - 1), work.end());
-				const uint64_t cut = work[(size_t)(m - 1)];
-				uint64_t need = m;
-				for(uint64_t r = 0; r + 1 < m; ++r) need -= work[(size_t) r] < cut;
-				uint64_t t = 0;
-				for(uint32_t c = 0; c < s.nnz; ++c) {
-					uint32_t kept = 0;
-					for(; t < P[c + 1]; ++t) {
-						const uint64_t k = keys[(size_t) t];
-						if(k < cut) ++kept;
-						else if(k == cut && need > 0) { ++kept; --need; }
-					}
-					cells[L[c]] = kept;
-				}
+				uint64_t cut, need;
+				hu_draw_cut(work, m, cut, need);
+				hu_draw_walk(cut, need, s.nnz, [&](uint64_t c) { return (uint64_t) P[c + 1]; }, [&](uint64_t t) { return keys[(size_t) t]; },
+					[&](uint64_t c, uint64_t kept) { cells[L[c]] = (uint32_t) kept; });
 			}
 			stat[u] = al_stats(pl, s, cells.data(), W);
 		}

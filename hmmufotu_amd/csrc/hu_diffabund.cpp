@@ -88,7 +88,7 @@ static int da_device(const char* fn, int device, const HuDaPlan& pl, uint64_t* t
 	auto run = [&](int64_t first, int64_t cnt, bool observed) -> int {
 		const int64_t c = observed ? HU_DA_WG : hu_da_pad(cnt);             /* whole workgroups of this launch, <= cp */
 		double ta = since();
-		k_da_shuffle<<<(unsigned)(c / 64), 64>>>(dObs, dLab, n, cp, (uint64_t) first, pl.seed, observed ? 1 : 0);
+		k_label_shuffle<uint8_t><<<(unsigned)(c / 64), 64>>>(dObs, dLab, n, cp, (uint64_t) first, pl.seed, observed ? 1 : 0);
 		DCHK(hipGetLastError());
 		DCHK(hipDeviceSynchronize());
 		double tb = since();

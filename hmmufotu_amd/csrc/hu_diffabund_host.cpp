@@ -79,20 +79,9 @@ int hu_da_plan(const char* fn, int64_t M, int64_t N, const double* counts, const
 	if(o.chunk < 0) { hu_set_error("%s: chunk %lld below 0", fn, (long long) o.chunk); return HU_ERR_ARG; }
 	if(o.min_prevalence < 0) { hu_set_error("%s: min_prevalence %lld below 0", fn, (long long) o.min_prevalence); return HU_ERR_ARG; }
 	if(o.rank_by != 0 && o.rank_by != 1) { hu_set_error("%s: rank_by %d: 0 (fraction) or 1 (count)", fn, o.rank_by); return HU_ERR_ARG; }
-	int64_t top = -1;
-	for(int64_t i = 0; i < N; ++i) {
-		if(group[i] < 0) { hu_set_error("%s: sample %lld has the negative label %d", fn, (long long) i, group[i]); return HU_ERR_ARG; }
-		top = std::max<int64_t>(top, group[i]);
-	}
-	if(top >= N) { hu_set_error("%s: the labels are not dense in 0 .. a-1: label %lld among %lld samples", fn, (long long) top, (long long) N); return HU_ERR_ARG; }
-	const int64_t a = top + 1;
-	std::vector<int64_t> size((size_t) a, 0);
-	for(int64_t i = 0; i < N; ++i) ++size[(size_t) group[i]];
-	for(int64_t g = 0; g < a; ++g) if(size[(size_t) g] == 0) {
-		hu_set_error("%s: the labels are not dense in 0 .. a-1: label %lld is used, label %lld is not", fn, (long long) top, (long long) g); return HU_ERR_ARG; }
-	if(a < 2) { hu_set_error("%s: one group: a test needs 2 at the least", fn); return HU_ERR_ARG; }
-	if(a > N - 1) { hu_set_error("%s: %lld groups of %lld samples: every group is a single sample, no relabelling changes a sum", fn, (long long) a, (long long) N); return HU_ERR_ARG; }
-	if(a > HU_DA_MAX_GROUPS) { hu_set_error("%s: %lld groups: %d at the most", fn, (long long) a, HU_DA_MAX_GROUPS); return HU_ERR_ARG; }
+	std::vector<int64_t> size;
+	{ const int rc = hu_groups_check(fn, N, group, HU_DA_MAX_GROUPS, "no relabelling changes a sum", size); if(rc != HU_OK) return rc; }
+	const int64_t a = (int64_t) size.size();
 	unsigned __int128 L = 1;
 	for(int64_t g = 0; g < a; ++g) {
 		uint64_t x = (uint64_t) L, y = (uint64_t) size[(size_t) g];
@@ -144,10 +133,7 @@ int hu_da_plan(const char* fn, int64_t M, int64_t N, const double* counts, const
 
 void hu_da_host_shuffle(const HuDaPlan& pl, uint64_t p, uint8_t* g) {
 	std::copy(pl.lab.begin(), pl.lab.end(), g);
-	for(int64_t i = pl.n - 1; i >= 1; --i) {
-		const uint64_t j = hu_pm_partner(pl.seed, p, (uint64_t) i);
-		std::swap(g[i], g[(size_t) j]);
-	}
+	hu_pm_shuffle(pl.seed, p, pl.n, g);
 }
 
 void hu_da_host_T(const HuDaPlan& pl, int64_t r, const uint8_t* g, uint64_t* hi, uint64_t* lo, int64_t* C) {

@@ -1,9 +1,7 @@
 // The rank statistic of every tested OTU under every permutation of a chunk (hmmufotu-amd-diffabund).
 //
-//   k_da_shuffle   the byte-label twin of k_permanova_shuffle: a thread per slot of the chunk copies the observed labels into its column
-//                  of lab [n][cp] (cp = the chunk padded to whole workgroups) and runs the Fisher-Yates shuffle of permutation
-//                  first + slot on it (hu_pm_partner, the code the host runs).  Sample-major: the 64 lanes of a wave hold 64
-//                  permutations and touch 64 consecutive bytes.  With `observed` the copy alone.
+//   k_label_shuffle  (hu_kern_shuffle.h) the labelling of every permutation of the chunk as a column of lab [n][cp], byte labels: the
+//                  64 lanes of a wave hold 64 permutations and touch 64 consecutive bytes.
 //   k_da_sums      a workgroup of 256 threads takes HU_DA_BLOCK tested OTUs (blockIdx.x, table order) and 256 permutations (blockIdx.y),
 //                  one per thread.  A row's cells (sample << 16 | e_j - e_z) are staged in LDS, HU_DA_STAGE at a time and padded with
 //                  cells of 0 to a multiple of eight, and read back as two broadcast ds_read_b128; a cell is then one byte load of the
@@ -20,21 +18,7 @@
 #pragma once
 #include "hu_common.h"
 #include "hu_diffabund.h"
-
-__global__ void __launch_bounds__(64) k_da_shuffle(const uint8_t* __restrict__ obs, uint8_t* __restrict__ lab, int64_t n, int64_t cp,
-		uint64_t first, uint64_t seed, int observed) {
-	const int64_t slot = (int64_t) blockIdx.x * 64 + threadIdx.x;
-	if(slot >= cp) return;
-	uint8_t* g = lab + slot;
-	for(int64_t i = 0; i < n; ++i) g[i * cp] = obs[i];
-	if(observed) return;
-	const uint64_t p = first + (uint64_t) slot;
-	for(int64_t i = n - 1; i >= 1; --i) {
-		const int64_t j = (int64_t) hu_pm_partner(seed, p, (uint64_t) i);          /* 0 <= j <= i < n */
-		const uint8_t x = g[i * cp], y = g[j * cp];
-		g[i * cp] = y; g[j * cp] = x;
-	}
-}
+#include "hu_kern_shuffle.h"
 
 struct HuDaDev {
 	const uint32_t* cell; const int64_t* ptr; const int32_t* ez; const int32_t* dsum; const double* tc;   /* the rows */

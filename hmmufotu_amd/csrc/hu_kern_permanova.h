@@ -1,10 +1,6 @@
 // The within-group sums of squares of every permutation of a chunk (hmmufotu-amd-permanova).
 //
-//   k_permanova_shuffle   a thread per slot of the chunk: copies the observed labels into its column of lab [n][cp] (cp = the chunk
-//                         padded to whole workgroups), then runs the Fisher-Yates shuffle of permutation first + slot on that column
-//                         (hu_pm_partner: Philox4x32-10 by (seed, p, i), the code the host runs).  Sample-major, so that the threads
-//                         of a wave touch consecutive halfwords at step i and the pair kernel's staging loads are coalesced.  With
-//                         `observed` the copy alone: every slot then holds the observed labelling.
+//   k_label_shuffle       (hu_kern_shuffle.h) the labelling of every permutation of the chunk as a column of lab [n][cp], 16-bit labels.
 //   k_permanova_pairs     a workgroup of 256 threads owns one 64 x 64 tile (I <= J) of the matrix and 256 permutations, one per thread.
 //                         The tile's squares go to LDS once (32 KB; cells with j <= i or beyond n are +0, so the loop needs no index
 //                         test), the labels of the tile's 128 samples to LDS as [sample / 4][permutation] words of four labels: 16-bit
@@ -22,27 +18,13 @@
 #pragma once
 #include "hu_common.h"
 #include "hu_permanova.h"
+#include "hu_kern_shuffle.h"
 
 /* the LDS of k_permanova_pairs<BITS>: 98,304 bytes with 16-bit labels (one workgroup per CU), 65,536 with 8-bit labels (two) */
 #define HU_PM_LDS(BITS) (HU_PM_TILE * HU_PM_TILE * 8 + 2 * (HU_PM_TILE / 4) * HU_PM_WG * (BITS) / 2)
 template<int BITS> struct HuPmWord;
 template<> struct HuPmWord<16> { typedef uint64_t type; };
 template<> struct HuPmWord<8> { typedef uint32_t type; };
-
-__global__ void __launch_bounds__(64) k_permanova_shuffle(const uint16_t* __restrict__ obs, uint16_t* __restrict__ lab, int64_t n, int64_t cp,
-		uint64_t first, uint64_t seed, int observed) {
-	const int64_t slot = (int64_t) blockIdx.x * 64 + threadIdx.x;
-	if(slot >= cp) return;
-	uint16_t* g = lab + slot;
-	for(int64_t i = 0; i < n; ++i) g[i * cp] = obs[i];
-	if(observed) return;
-	const uint64_t p = first + (uint64_t) slot;
-	for(int64_t i = n - 1; i >= 1; --i) {
-		const int64_t j = (int64_t) hu_pm_partner(seed, p, (uint64_t) i);          /* 0 <= j <= i < n */
-		const uint16_t x = g[i * cp], y = g[j * cp];
-		g[i * cp] = y; g[j * cp] = x;
-	}
-}
 
 /* 1.0 or +0.0 from one select of the high word: fma(1, d, r) is the rounded r + d, fma(+0, d, r) is r for the finite d >= 0 and r >= 0 here */
 __device__ __forceinline__ double hu_pm_one_if(bool c) { return __hiloint2double(c ? 0x3ff00000 : 0, 0); }

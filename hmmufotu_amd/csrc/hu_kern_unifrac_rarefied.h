@@ -1,7 +1,7 @@
 // The distances averaged over rarefied draws on the device (hmmufotu-amd-unifrac --rarefy).
 //
 // A chunk of n repeats is resident at a time.  Unit a = z * S' + jj is kept sample jj of resident draw z; the select / ties / take
-// kernels of hu_kern_alpha.h leave its integer counters in out[], one per nonzero cell of the sample, in depth-first row order.
+// kernels of hu_kern_draw.h leave its integer counters in out[], one per nonzero cell of the sample, in depth-first row order.
 //   k_ur_reset     before a chunk's select: the keys of the groups (seed + repeat, a group per (sample, repeat) that is drawn) and the
 //                  selection state of the units, so that the host builds the lists once and only launches afterwards.
 //   k_ur_embed     one workgroup per unit: the counters become their inclusive prefix W (a workgroup scan, as k_al_pd's over presence),
@@ -43,7 +43,7 @@ static __global__ __launch_bounds__(HU_AL_WG) void k_ur_embed(const HuAlSample* 
 	uint32_t carry = 0;
 	for(uint32_t c0 = 0; c0 < s.nnz; c0 += HU_AL_WG) {
 		const uint32_t c = c0 + threadIdx.x;
-		const uint32_t v = c < s.nnz ? o[c] : 0u, incl = hu_al_wave_scan(v, lane);
+		const uint32_t v = c < s.nnz ? o[c] : 0u, incl = hu_draw_wave_scan(v, lane);
 		if(lane == 63) ws[w] = incl;
 		__syncthreads();
 		uint32_t off = 0, tot = 0;

@@ -14,6 +14,7 @@
 #include <vector>
 #include "hu_num_format.h"
 #include "hu_otu_table.h"
+#include "hu_draw.h"
 
 void hu_set_error(const char* fmt, ...);
 int hu_catch_all(const char* fn) noexcept;
@@ -266,23 +267,13 @@ void hu_otu_subset_host(int64_t n_otu, int64_t n_sample, const double* counts, c
 		if(T <= size) continue;                                            /* not enough reads to subset */
 		auto cell = [&](int64_t i) -> uint64_t { return (uint64_t) counts[(size_t) i * n_sample + j]; };
 		if(method == HU_OTU_UNIFORM) {
-			/* the key that has rank `size`, then the reads in row order: every smaller key, and the first `need` of the equal ones */
+			/* the cut (hu_draw.h), then the reads in row order */
 			keys.resize((size_t) T);
 			for(uint64_t t = 0; t < T; ++t) keys[(size_t) t] = hu_otu_key(key, t, (uint32_t) j, key_bits);
-			std::nth_element(keys.begin(), keys.begin() + (size_t)(size - 1), keys.end());
-			const uint64_t cut = keys[(size_t)(size - 1)];
-			uint64_t need = size;
-			for(uint64_t r = 0; r + 1 < size; ++r) need -= keys[(size_t) r] < cut;
-			uint64_t t = 0;
-			for(int64_t i = 0; i < n_otu; ++i) {
-				uint64_t kept = 0;
-				for(const uint64_t end = t + cell(i); t < end; ++t) {
-					const uint64_t k = hu_otu_key(key, t, (uint32_t) j, key_bits);
-					if(k < cut) ++kept;
-					else if(k == cut && need > 0) { ++kept; --need; }
-				}
-				out[(size_t) i * n_sample + j] = (double) kept;
-			}
+			uint64_t cut, need, end = 0;
+			hu_draw_cut(keys, size, cut, need);
+			hu_draw_walk(cut, need, (uint64_t) n_otu, [&](uint64_t i) { return end += cell((int64_t) i); },
+				[&](uint64_t t) { return hu_otu_key(key, t, (uint32_t) j, key_bits); }, [&](uint64_t i, uint64_t kept) { out[(size_t) i * n_sample + j] = (double) kept; });
 		}
 		else {
 			prefix.clear(); rowOf.clear();

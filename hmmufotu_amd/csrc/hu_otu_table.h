@@ -1,4 +1,4 @@
-// What the host half (hu_otu_table.cpp, a plain C++ compiler) and the device half (hu_otu_subset.cpp, hu_kern_otu.h) of hu_otu_subset
+// What the host half (hu_otu_table.cpp, a plain C++ compiler) and the device half (hu_otu_subset.cpp, hu_kern_draw.h, hu_kern_otu.h) of hu_otu_subset
 // share: the names of a read's key and of a draw, and the checks of a table before it is subsampled.
 #pragma once
 #include <stdint.h>

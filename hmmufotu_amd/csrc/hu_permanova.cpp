@@ -71,7 +71,7 @@ static int pm_device(const char* fn, int device, const HuPmPlan& pl, const doubl
 	auto run = [&](int64_t first, int64_t cnt, bool observed) -> int {
 		const int64_t c = observed ? HU_PM_WG : hu_pm_pad(cnt);             /* whole workgroups of this launch, <= cp */
 		double ta = since();
-		k_permanova_shuffle<<<(unsigned)(c / 64), 64>>>(dObs, dLab, n, c, (uint64_t) first, pl.seed, observed ? 1 : 0);
+		k_label_shuffle<uint16_t><<<(unsigned)(c / 64), 64>>>(dObs, dLab, n, c, (uint64_t) first, pl.seed, observed ? 1 : 0);
 		PCHK(hipGetLastError());
 		PCHK(hipDeviceSynchronize());
 		double tb = since();

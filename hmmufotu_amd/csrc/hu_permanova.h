@@ -1,6 +1,6 @@
 // What the host half (hu_permanova_host.cpp, a plain C++ compiler) and the device half (hu_permanova.cpp, hu_kern_permanova.h) of
 // hu_permanova share: the checked arguments of a call, the constants that fix the summation order, and the shuffle
-// that names the labelling of permutation p by (seed, p) alone.
+// that names the labelling of permutation p by (seed, p) alone.  The shuffle and the check of the group labels are hu_diffabund's too.
 #pragma once
 #include <stdint.h>
 #include <vector>
@@ -27,6 +27,35 @@ HU_HD inline uint64_t hu_pm_partner(uint64_t seed, uint64_t p, uint64_t i) {
 	uint32_t w[4];
 	hu_philox4x32_10(c, k, w);
 	return hu_pm_mulhi64(((uint64_t) w[1] << 32) | w[0], i + 1);
+}
+/* the Fisher-Yates shuffle of permutation p on the n labels g[0], g[stride], ...: the host's rows and the columns of k_label_shuffle */
+template<class T> HU_HD inline void hu_pm_shuffle(uint64_t seed, uint64_t p, int64_t n, T* g, int64_t stride = 1) {
+	for(int64_t i = n - 1; i >= 1; --i) {
+		const int64_t j = (int64_t) hu_pm_partner(seed, p, (uint64_t) i);          /* 0 <= j <= i < n */
+		const T x = g[i * stride], y = g[j * stride];
+		g[i * stride] = y; g[j * stride] = x;
+	}
+}
+
+void hu_set_error(const char* fmt, ...);
+/* the labels of n samples: none negative, dense in 0 .. a-1, 2 <= a <= min(n - 1, max_groups); size [a] receives the groups' sizes.
+ * `single` ends the refusal of groups that are all single samples with what the test would lack */
+inline int hu_groups_check(const char* fn, int64_t n, const int32_t* group, int64_t max_groups, const char* single, std::vector<int64_t>& size) {
+	int64_t top = -1;
+	for(int64_t i = 0; i < n; ++i) {
+		if(group[i] < 0) { hu_set_error("%s: sample %lld has the negative label %d", fn, (long long) i, group[i]); return HU_ERR_ARG; }
+		top = top > group[i] ? top : (int64_t) group[i];
+	}
+	if(top >= n) { hu_set_error("%s: the labels are not dense in 0 .. a-1: label %lld among %lld samples", fn, (long long) top, (long long) n); return HU_ERR_ARG; }
+	const int64_t a = top + 1;
+	size.assign((size_t) a, 0);
+	for(int64_t i = 0; i < n; ++i) ++size[(size_t) group[i]];
+	for(int64_t g = 0; g < a; ++g) if(size[(size_t) g] == 0) {
+		hu_set_error("%s: the labels are not dense in 0 .. a-1: label %lld is used, label %lld is not", fn, (long long) top, (long long) g); return HU_ERR_ARG; }
+	if(a < 2) { hu_set_error("%s: one group: a test needs 2 at the least", fn); return HU_ERR_ARG; }
+	if(a > n - 1) { hu_set_error("%s: %lld groups of %lld samples: every group is a single sample, %s", fn, (long long) a, (long long) n, single); return HU_ERR_ARG; }
+	if(a > max_groups) { hu_set_error("%s: %lld groups: %lld at the most", fn, (long long) a, (long long) max_groups); return HU_ERR_ARG; }
+	return HU_OK;
 }
 
 struct HuPmPlan {

@@ -50,20 +50,9 @@ int hu_pm_plan(const char* fn, int64_t n, const double* dist, const int32_t* gro
 	if(hu_pm_tiles(n) > 0x7fffffffll) { hu_set_error("%s: %lld samples: more tiles than a grid holds", fn, (long long) n); return HU_ERR_ARG; }
 	if(o.perms < 1 || o.perms > HU_PM_MAX_PERMS) { hu_set_error("%s: %lld permutations: between 1 and %d", fn, (long long) o.perms, HU_PM_MAX_PERMS); return HU_ERR_ARG; }
 	if(o.chunk < 0) { hu_set_error("%s: chunk %lld below 0", fn, (long long) o.chunk); return HU_ERR_ARG; }
-	int64_t top = -1;
-	for(int64_t i = 0; i < n; ++i) {
-		if(group[i] < 0) { hu_set_error("%s: sample %lld has the negative label %d", fn, (long long) i, group[i]); return HU_ERR_ARG; }
-		top = std::max<int64_t>(top, group[i]);
-	}
-	if(top >= n) { hu_set_error("%s: the labels are not dense in 0 .. a-1: label %lld among %lld samples", fn, (long long) top, (long long) n); return HU_ERR_ARG; }
-	const int64_t a = top + 1;
-	std::vector<int64_t> size((size_t) a, 0);
-	for(int64_t i = 0; i < n; ++i) ++size[(size_t) group[i]];
-	for(int64_t g = 0; g < a; ++g) if(size[(size_t) g] == 0) {
-		hu_set_error("%s: the labels are not dense in 0 .. a-1: label %lld is used, label %lld is not", fn, (long long) top, (long long) g); return HU_ERR_ARG; }
-	if(a < 2) { hu_set_error("%s: one group: a test needs 2 at the least", fn); return HU_ERR_ARG; }
-	if(a > n - 1) { hu_set_error("%s: %lld groups of %lld samples: every group is a single sample, nothing varies within", fn, (long long) a, (long long) n); return HU_ERR_ARG; }
-	if(a > HU_PM_MAX_GROUPS) { hu_set_error("%s: %lld groups: %d at the most", fn, (long long) a, HU_PM_MAX_GROUPS); return HU_ERR_ARG; }
+	std::vector<int64_t> size;
+	{ const int rc = hu_groups_check(fn, n, group, HU_PM_MAX_GROUPS, "nothing varies within", size); if(rc != HU_OK) return rc; }
+	const int64_t a = (int64_t) size.size();
 	{ const int rc = hu_pm_check_matrix(fn, n, dist); if(rc != HU_OK) return rc; }
 	pl.n = n; pl.a = a; pl.perms = o.perms; pl.chunk = o.chunk; pl.budget = o.mem_budget > 0 ? o.mem_budget : 0; pl.seed = o.seed; pl.host = o.host != 0;
 	pl.inv.resize((size_t) a); pl.lab.resize((size_t) n);
@@ -106,16 +95,9 @@ double hu_pm_host_ssw(const HuPmPlan& pl, const double* D2, const uint16_t* g) {
 	return tot;
 }
 
-template<class T> static void pm_shuffle(uint64_t seed, uint64_t p, int64_t n, T* g) {
-	for(int64_t i = n - 1; i >= 1; --i) {
-		const uint64_t j = hu_pm_partner(seed, p, (uint64_t) i);
-		std::swap(g[i], g[(size_t) j]);
-	}
-}
-
 void hu_pm_host_shuffle(const HuPmPlan& pl, uint64_t p, uint16_t* g) {
 	std::copy(pl.lab.begin(), pl.lab.end(), g);
-	pm_shuffle(pl.seed, p, pl.n, g);
+	hu_pm_shuffle(pl.seed, p, pl.n, g);
 }
 
 void hu_pm_host_run(const HuPmPlan& pl, const double* dist, double* obs, double* ssw) {
@@ -146,7 +128,7 @@ extern "C" int hu_permanova_labels(int64_t n, const int32_t* group, uint64_t see
 	for(int64_t k = 0; k < count; ++k) {
 		int32_t* g = out + k * n;
 		std::copy(group, group + n, g);
-		pm_shuffle(seed, (uint64_t)(first + k), n, g);
+		hu_pm_shuffle(seed, (uint64_t)(first + k), n, g);
 	}
 	return HU_OK;
 } catch(...) { return hu_catch_all("hu_permanova_labels"); }

@@ -1,6 +1,6 @@
 // hu_unifrac_rarefied: the entry, and the device path of hmmufotu-amd-unifrac --rarefy.  The host makes the plan
 // (hu_unifrac_rarefied_host.cpp) and the lists of one chunk of resident draws; the table goes up once and stays; per chunk the kernels of
-// hu_kern_alpha.h draw, those of hu_kern_unifrac_rarefied.h embed, add the pairs and take the recurrence's steps.  The lists of a chunk
+// hu_kern_draw.h draw, those of hu_kern_unifrac_rarefied.h embed, add the pairs and take the recurrence's steps.  The lists of a chunk
 // are the same for every chunk but for the keys, which a kernel sets: the host only launches.
 #include <algorithm>
 #include <chrono>
@@ -75,10 +75,8 @@ static int ur_device(const char* fn, int device, const HuUrPlan& pl, double* mea
 			draw[z * Sk + a] = HuAlDraw{cells, ties, col, whole ? 0u : (uint32_t) pl.depth};
 			cells += s.nnz;
 			if(whole) continue;
-			const uint32_t nChunk = (uint32_t)((s.T + perChunk - 1) / perChunk);
-			ties += (uint64_t) nChunk * HU_AL_WAVES;
-			grp.push_back(HuAlGroup{chunk.size(), col, 0u, 0u, (uint32_t)(z * Sk + a), 1u, nChunk});
-			for(uint32_t c = 0; c < nChunk; ++c) chunk.push_back(HuAlChunk{(uint32_t)(grp.size() - 1), (uint32_t)(c * perChunk)});
+			ties += (s.T + perChunk - 1) / perChunk * HU_DRAW_WAVES;
+			hu_draw_add_group(grp, chunk, col, 0, (uint32_t)(z * Sk + a), 1u, s.T, perChunk);   /* the key: k_ur_reset's */
 		}
 	}
 
@@ -121,32 +119,18 @@ static int ur_device(const char* fn, int device, const HuUrPlan& pl, double* mea
 	phase(0);
 	(void) hipGetLastError();
 
-	const int passes = (al.keyBits + 7) / 8;
+	const HuDrawDev dv = {dSmp, dDraw, dGrp, dChunk, dSel, dHist, dTie, dPrefix, dSlot, dOut, al.keyBits, al.chunk};
 	const int raw = pl.uf.method == HU_UF_WEIGHTED_RAW;
 	for(size_t r0 = 0; r0 < R; r0 += D) {
 		const size_t n = std::min(D, R - r0), nu = n * Sk, ng = n * (size_t) grp1, nc = n * (size_t) chunks1;
 		RCHK(hipMemset(dOut, 0, std::max<size_t>(n * cells1, one) * 4));
 		k_ur_reset<<<(unsigned)((nu + HU_AL_WG - 1) / HU_AL_WG), HU_AL_WG>>>(dSmp, dDraw, dSel, dGrp, (uint32_t) nu, (uint32_t) ng, (uint32_t) std::max<uint64_t>(grp1, 1), pl.seed + (uint64_t) r0);
 		RCHK(hipGetLastError());
-		const dim3 grid((unsigned) nc, 1);
-		if(nc > 0) {
-			for(int p = 0; p < passes; ++p) {
-				k_al_hist<<<grid, HU_AL_WG>>>(dSmp, dGrp, dChunk, dSel, dHist, al.keyBits, al.chunk, 8 * (passes - 1 - p), p == 0);
-				RCHK(hipGetLastError());
-				k_al_pick<<<(unsigned) nu, 64>>>(dDraw, dSel, dHist);
-				RCHK(hipGetLastError());
-			}
-			k_al_ties<<<grid, HU_AL_WG>>>(dSmp, dGrp, dChunk, dDraw, dSel, dTie, al.keyBits, al.chunk);
-			RCHK(hipGetLastError());
-			k_al_tie_scan<<<(unsigned) nu, 64>>>(dSmp, dDraw, dSel, dTie, al.chunk);
-			RCHK(hipGetLastError());
-		}
+		/* every group is one draw: the kernels that hold one depth */
+		RCHK(hu_draw_select<1>(dv, (unsigned) nu, (unsigned) nc, 1));
 		k_al_whole<<<(unsigned) nu, HU_AL_WG>>>(dSmp, dDraw, dPrefix, dSlot, dOut);
 		RCHK(hipGetLastError());
-		if(nc > 0) {
-			k_al_take<<<grid, HU_AL_WG>>>(dSmp, dGrp, dChunk, dDraw, dSel, dTie, dPrefix, dSlot, dOut, al.keyBits, al.chunk);
-			RCHK(hipGetLastError());
-		}
+		RCHK(hu_draw_take<1>(dv, (unsigned) nc, 1));
 		RCHK(hipDeviceSynchronize());
 		phase(1);
 		RCHK(hipMemset(dP, 0, n * bP1));

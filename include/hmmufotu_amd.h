@@ -983,7 +983,7 @@ int hu_otu_table_normalize(hu_otu_table* t, double Z, int64_t* zero_columns);
 
 /* hu_otu_subset: every sample (column) of counts [n_otu][n_sample] rarefied to `size` reads into out (same shape; may not alias counts),
  * OTUTable::subsetUniform / subsetMultinom (src/OTUTable.cpp:166-209).  A sample with T_j <= size reads is returned untouched, as there.
- * device < 0: the host path; otherwise the kernels of hu_kern_otu.h on that device.  Both give the same integers.
+ * device < 0: the host path; otherwise the kernels of hu_kern_draw.h (uniform) or hu_kern_otu.h (multinomial) on that device.  Both give the same integers.
  * The distributions are the reference's, the streams are not (it draws from Boost's mt11213b): the generator is Philox4x32-10
  * (hu_sim_philox) under the key (seed & 0xffffffff, seed >> 32), and a result is defined by names, not by the order of execution.
  * HU_OTU_UNIFORM, without replacement: the reads of sample j are numbered t = 0 .. T_j - 1 in row order, OTU i owns [P_i, P_i+1), P the

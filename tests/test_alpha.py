@@ -642,6 +642,32 @@ def test_device_against_the_host_path(S, kind, chunk, reps, key_bits):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("key_bits", [4, 64])
+@pytest.mark.parametrize("n_depth", [1, 8, 17])
+def test_device_depths_against_the_width_of_a_group(n_depth, key_bits):
+    """the draw kernels serve 8 depths of a (sample, repeat) per workgroup: 1 depth (seven idle), 8 (one full group) and 17 (two full groups
+    and one depth, blockIdx.y 0 .. 2) of every (sample, repeat), with keys that tie and without.  Counts of 9, 11, 12, 14 and 16 are in
+    DEVICE_CASES from ten samples on: the table of (10, "chain63", 64, 3, 4) has a sample with 9 depths and one with 16.  The host path
+    is exact in the integers and in PD; A is a sum of at most 40 terms in another order, 40 roundings apart at the most"""
+    _need_gpu()
+    rng = np.random.default_rng(7)
+    M = 40
+    parent, blen = chain(9)
+    tr = Tree(parent, blen, rows_on(parent, M, 3))
+    counts = np.zeros((M, 3))
+    for j, N in enumerate((300, 129, 65)):
+        counts[:, j] = rng.multinomial(N, rng.dirichlet(np.full(M, 0.3)))
+    depths = [33] if n_depth == 1 else sorted({int(x) for x in np.linspace(1, 65, n_depth)})   # 65: the whole of the smallest sample
+    assert len(depths) == n_depth
+    kw = dict(depths=depths, reps=2, seed=5, key_bits=key_bits, **tr.args())
+    host = E.alpha_diversity(counts, host=True, **kw)
+    dev = E.alpha_diversity(counts, chunk=64, **kw)
+    same(dev, host, skip=("A", "shannon"))
+    assert (host["draws"]["reads"] == np.array(depths)[None, :, None]).all()
+    assert np.allclose(dev["draws"]["A"], host["draws"]["A"], rtol=40 * 2.0 ** -52, atol=0)
+
+
+@pytest.mark.gpu
 def test_device_results_do_not_depend_on_the_chunking():
     _need_gpu()
     tr, counts, depths = device_case(10, "chain63", 4)
