@@ -2,8 +2,13 @@
 // reference ends at the OTU table; here the matrix of hmmufotu-amd-unifrac -o goes straight into the test.
 //   hmmufotu-amd-permanova <DIST> <GROUPS> [-o FILE] [-n|--perms 999] [-S|--seed 1] [--pairwise] [--perm-out FILE] [--chunk N] [--mem GB]
 //                          [--device N] [--host] [-v]
+//   hmmufotu-amd-permanova <DIST> --design META --terms a,b,a:b [--factor NAME]... [--strata NAME] [-o FILE] [-n -S --perm-out --chunk --mem
+//                          --device --host -v]
+// With --design the test is hu_permanova_design's: sequential sums of squares of the terms, in the order given, of a design
+// of covariates, factors and interactions of two, permuted within the blocks of --strata.  Without it nothing changes.
 // The sums are hu_permanova's: on the device (hu_kern_permanova.h), or with --host by the library's host path.  Every refusal comes
 // before a device is asked for, and the outputs are opened only after the computation: a refused run leaves no file.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +20,7 @@
 #include <vector>
 #include "../../include/hmmufotu_amd.h"
 #include "hu_groups_file.h"
+#include "hu_design_file.h"
 
 static void usage(const char* p) {
 	std::cerr << "Test whether groups of samples differ on a distance matrix (PERMANOVA: pseudo-F and a permutation p-value)\n"
@@ -25,6 +31,10 @@ static void usage(const char* p) {
 		"            -n|--perms  INT    : number of permutations [999]\n"
 		"            -S|--seed  INT     : seed of the permutations [1]\n"
 		"            --pairwise  FLAG   : also test every pair of groups on its own samples\n"
+		"            --design  FILE     : instead of GROUPS: tab-separated metadata, a header line, then one line per sample\n"
+		"            --terms  LIST      : with --design: the terms to test in order, e.g. treatment,ph,treatment:ph\n"
+		"            --factor  NAME     : with --design: read this numeric-looking column as categorical; may be given more than once\n"
+		"            --strata  NAME     : with --design: permute only within the blocks of this column\n"
 		"            --perm-out  FILE   : also write SS_within and F of every permutation of the test on all groups\n"
 		"            --chunk  INT       : permutations per launch [a function of the matrix's size and the memory]\n"
 		"            --mem  DBL         : device memory to use, in GB [what the device reports free]\n"
@@ -42,7 +52,114 @@ static std::string line_of(const std::string& name, const hu_permanova_result& r
 		num17(r.ss_among) + '\t' + num17(r.F) + '\t' + num17(r.R2) + '\t' + num17(r.p);
 }
 
+struct DesignArgs { std::string meta, terms, strata; std::vector<std::string> factor; bool haveTerms = false, haveStrata = false; };
+
+/* the run with --design: every refusal before a device is asked for, the outputs opened after the computation */
+static int run_design(const std::string& distFn, const DesignArgs& da, const hu_permanova_opts& o, int dev, const std::string& outFn, const std::string& permFn, int verbose) {
+	auto fail = [](const std::string& why) { std::cerr << why << std::endl; return EXIT_FAILURE; };
+	std::vector<std::string> termName;
+	hu_meta_split(da.terms, ',', termName);
+	std::vector<std::vector<std::string>> termVar(termName.size());
+	std::vector<std::string> used;
+	for(size_t t = 0; t < termName.size(); ++t) {
+		hu_meta_split(termName[t], ':', termVar[t]);
+		if(termVar[t].size() > 2) return fail("Term '" + termName[t] + "': an interaction of more than two variables is not supported");
+		for(const auto& v : termVar[t]) {
+			if(v.empty()) return fail("--terms '" + da.terms + "': an empty name");
+			if(std::find(used.begin(), used.end(), v) == used.end()) used.push_back(v);
+		}
+	}
+	if(verbose) std::cerr << "Loading distance matrix" << std::endl;
+	hu_dist_matrix* m = nullptr;
+	if(hu_dist_matrix_read(distFn.c_str(), &m) != HU_OK) return fail(hu_last_error());
+	int64_t n = 0;
+	hu_dist_matrix_dims(m, &n);
+	const double* dist = hu_dist_matrix_values(m);
+	std::vector<std::string> sample((size_t) n);
+	for(int64_t i = 0; i < n; ++i) sample[(size_t) i] = hu_dist_matrix_sample(m, i);
+	HuMeta meta; std::string err;
+	if(!hu_meta_read(da.meta, sample, meta, err)) return fail(err);
+	if(verbose) std::cerr << meta.ignored << " line(s) of '" << da.meta << "' name no sample of the matrix" << std::endl;
+	auto isColumn = [&](const std::string& c) { return std::find(meta.column.begin(), meta.column.end(), c) != meta.column.end(); };
+	for(const auto& v : used) if(!isColumn(v)) return fail("--terms: '" + v + "' is no column of '" + da.meta + "'");
+	for(const auto& v : da.factor) if(!isColumn(v)) return fail("--factor: '" + v + "' is no column of '" + da.meta + "'");
+	if(da.haveStrata && !isColumn(da.strata)) return fail("--strata: '" + da.strata + "' is no column of '" + da.meta + "'");
+	std::vector<HuMetaVar> mv(used.size());
+	std::vector<hu_design_var> var(used.size());
+	for(size_t v = 0; v < used.size(); ++v) {
+		const bool factor = std::find(da.factor.begin(), da.factor.end(), used[v]) != da.factor.end();
+		if(!hu_meta_variable(meta, sample, used[v], factor, mv[v], err)) return fail(err);
+		var[v].kind = mv[v].numeric ? 0 : 1; var[v].reserved = 0; var[v].value = mv[v].numeric ? mv[v].value.data() : nullptr; var[v].label = mv[v].numeric ? nullptr : mv[v].label.data();
+	}
+	HuMetaVar strata;
+	if(da.haveStrata && !hu_meta_variable(meta, sample, da.strata, true, strata, err)) return fail(err);
+	const int64_t T = (int64_t) termName.size();
+	std::vector<hu_design_term> term((size_t) T);
+	std::vector<const char*> tn((size_t) T);
+	for(int64_t t = 0; t < T; ++t) {
+		auto at = [&](const std::string& v) { return (int32_t)(std::find(used.begin(), used.end(), v) - used.begin()); };
+		term[(size_t) t].a = at(termVar[(size_t) t][0]); term[(size_t) t].b = termVar[(size_t) t].size() == 2 ? at(termVar[(size_t) t][1]) : -1;
+		tn[(size_t) t] = termName[(size_t) t].c_str();
+	}
+	const int64_t raw = hu_design_raw_columns(n, (int64_t) var.size(), var.data(), T, term.data());
+	if(raw < 0) return fail(hu_last_error());
+	std::vector<double> Q((size_t)(n * raw));
+	std::vector<int64_t> termStart((size_t) T + 1), df((size_t) T), dropped((size_t) T);
+	int64_t q = 0;
+	if(hu_design_build(n, (int64_t) var.size(), var.data(), T, term.data(), tn.data(), Q.data(), &q, termStart.data(), df.data(), dropped.data()) != HU_OK) return fail(hu_last_error());
+	if(verbose) for(int64_t t = 0; t < T; ++t) std::cerr << "term '" << termName[(size_t) t] << "': " << df[(size_t) t] << " column(s) kept, " << dropped[(size_t) t] << " dropped" << std::endl;
+	hu_permanova_design_opts d;
+	hu_permanova_design_default_opts(&d);
+	d.perms = o.perms; d.seed = o.seed; d.host = o.host; d.chunk = o.chunk; d.mem_budget = o.mem_budget;
+	std::vector<hu_permanova_design_term> res((size_t) T);
+	std::vector<double> ss(permFn.empty() ? 0 : (size_t)(o.perms * T));
+	if(hu_permanova_design(dev, n, dist, Q.data(), q, T, termStart.data(), da.haveStrata ? strata.label.data() : nullptr, &d, res.data(), permFn.empty() ? nullptr : ss.data()) != HU_OK)
+		return fail(hu_last_error());
+	if(verbose) {
+		for(int64_t t = 0; t < T; ++t) std::cerr << "term '" << termName[(size_t) t] << "': " << res[(size_t) t].count_nan << " permutation(s) with F = NaN" << std::endl;
+		if(dev >= 0) {
+			double s[4];
+			hu_permanova_design_timing(s);
+			std::cerr << "copies up " << s[0] << " s, shuffles " << s[1] << " s, quadratic forms " << s[2] << " s, finish and copy back " << s[3] << " s" << std::endl;
+		}
+	}
+	const hu_permanova_design_term& r0 = res[0];
+	auto writeAll = [&](std::ostream& out) {
+		out << "term\tdf\tSS\tR2\tF\tp\n";
+		for(int64_t t = 0; t < T; ++t) { const auto& r = res[(size_t) t]; out << termName[(size_t) t] << '\t' << r.df << '\t' << num17(r.ss) << '\t' << num17(r.R2) << '\t' << num17(r.F) << '\t' << num17(r.p) << '\n'; }
+		out << "Residual\t" << r0.df_res << '\t' << num17(r0.ss_res) << '\t' << num17(r0.ss_res / r0.ss_total) << "\tNA\tNA\n";
+		out << "Total\t" << n - 1 << '\t' << num17(r0.ss_total) << '\t' << num17(1.0) << "\tNA\tNA\n";
+		out << "# perms: " << o.perms << "\n# seed: " << o.seed << '\n';
+		if(da.haveStrata) out << "# strata: " << da.strata << " (" << strata.level.size() << " blocks)\n";
+	};
+	if(outFn.empty()) writeAll(std::cout);
+	else {
+		std::ofstream f(outFn);
+		if(!f) return fail("Unable to write to '" + outFn + "'");
+		writeAll(f);
+	}
+	if(!permFn.empty()) {
+		std::ofstream f(permFn);
+		if(!f) return fail("Unable to write to '" + permFn + "'");
+		f << "perm";
+		for(int64_t t = 0; t < T; ++t) f << "\tSS_" << termName[(size_t) t] << "\tF_" << termName[(size_t) t];
+		f << '\n';
+		for(long long p = 0; p < o.perms; ++p) {
+			const double* row = ss.data() + p * T;
+			double sum = 0.0;
+			for(int64_t t = 0; t < T; ++t) sum += row[t];
+			const double resid = r0.ss_total - sum;                                /* the library's order: the terms ascending, then one subtraction */
+			f << p;
+			for(int64_t t = 0; t < T; ++t) f << '\t' << num17(row[t]) << '\t' << num17((row[t] / (double) res[(size_t) t].df) / (resid / (double) r0.df_res));
+			f << '\n';
+		}
+	}
+	hu_dist_matrix_free(m);
+	return EXIT_SUCCESS;
+}
+
 int main(int argc, char** argv) {
+	DesignArgs da; bool haveDesign = false;
 	std::vector<std::string> pos; std::string outFn, permFn; bool host = false, pairwise = false; int device = 0, verbose = 0;
 	hu_permanova_opts o;
 	hu_permanova_default_opts(&o);
@@ -57,6 +174,10 @@ int main(int argc, char** argv) {
 		else if(a == "-n" || a == "--perms") perms = atoll(val());
 		else if(a == "-S" || a == "--seed") o.seed = strtoull(val(), nullptr, 10);
 		else if(a == "--pairwise") pairwise = true;
+		else if(a == "--design") { da.meta = val(); haveDesign = true; }
+		else if(a == "--terms") { da.terms = val(); da.haveTerms = true; }
+		else if(a == "--factor") da.factor.push_back(val());
+		else if(a == "--strata") { da.strata = val(); da.haveStrata = true; }
 		else if(a == "--chunk") { chunk = atoll(val()); haveChunk = true; }
 		else if(a == "--mem") { memGB = atof(val()); haveMem = true; }
 		else if(a == "--device") device = atoi(val()); else if(a == "--host") host = true;
@@ -64,13 +185,18 @@ int main(int argc, char** argv) {
 		else if(a[0] == '-' && a.size() > 1) { std::cerr << "Error: unknown option " << a << std::endl; return EXIT_FAILURE; }
 		else pos.push_back(a);
 	}
-	if(pos.size() != 2) { std::cerr << "Error:" << std::endl; usage(argv[0]); return EXIT_FAILURE; }
+	if(!haveDesign && (da.haveTerms || da.haveStrata || !da.factor.empty())) { std::cerr << "--terms, --factor and --strata need --design" << std::endl; return EXIT_FAILURE; }
+	if(haveDesign && pos.size() == 2) { std::cerr << "--design takes the place of the GROUPS file: give one of them" << std::endl; return EXIT_FAILURE; }
+	if(haveDesign && pairwise) { std::cerr << "--pairwise tests groups: it does not go with --design" << std::endl; return EXIT_FAILURE; }
+	if(haveDesign && (!da.haveTerms || da.terms.empty())) { std::cerr << "--design needs --terms: the terms to test, in order" << std::endl; return EXIT_FAILURE; }
+	if(pos.size() != (haveDesign ? 1u : 2u)) { std::cerr << "Error:" << std::endl; usage(argv[0]); return EXIT_FAILURE; }
 	if(perms < 1 || perms > 10000000) { std::cerr << "--perms must lie between 1 and 10000000" << std::endl; return EXIT_FAILURE; }
 	if(haveChunk && chunk < 1) { std::cerr << "--chunk must be at least 1" << std::endl; return EXIT_FAILURE; }
 	if(haveMem && !(memGB > 0 && memGB < 1e6)) { std::cerr << "--mem must be a positive number of GB" << std::endl; return EXIT_FAILURE; }
 	if(device < 0) { std::cerr << "--device must be non-negative; --host runs without one" << std::endl; return EXIT_FAILURE; }
 	o.perms = perms; o.chunk = chunk; o.host = host ? 1 : 0; o.mem_budget = haveMem ? (int64_t)(memGB * 1073741824.0) : 0;
 	if(haveMem && o.mem_budget < 1) o.mem_budget = 1;
+	if(haveDesign) return run_design(pos[0], da, o, host ? -1 : device, outFn, permFn, verbose);
 	if(verbose) std::cerr << "Loading distance matrix" << std::endl;
 	hu_dist_matrix* m = nullptr;
 	if(hu_dist_matrix_read(pos[0].c_str(), &m) != HU_OK) { std::cerr << hu_last_error() << std::endl; return EXIT_FAILURE; }

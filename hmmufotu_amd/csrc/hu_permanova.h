@@ -21,13 +21,16 @@ HU_HD inline uint64_t hu_pm_mulhi64(uint64_t x, uint64_t y) {
 	return (uint64_t)(((unsigned __int128) x * y) >> 64);
 #endif
 }
-/* the partner j in [0, i] of position i in the shuffle of permutation p: no rejection, so j is off the uniform by (i + 1) / 2^64 at the most */
-HU_HD inline uint64_t hu_pm_partner(uint64_t seed, uint64_t p, uint64_t i) {
-	const uint32_t c[4] = {(uint32_t) i, (uint32_t)(i >> 32), (uint32_t) p, (uint32_t)(p >> 32)}, k[2] = {(uint32_t) seed, (uint32_t)(seed >> 32)};
+/* a partner in [0, range) drawn under the counter (counter, p): no rejection, so it is off the uniform by range / 2^64 at the most.  The
+ * stratified shuffle of hu_permanova_design.h names a step by the sample it moves (the counter) and draws among the step's candidates */
+HU_HD inline uint64_t hu_pm_partner_in(uint64_t seed, uint64_t p, uint64_t counter, uint64_t range) {
+	const uint32_t c[4] = {(uint32_t) counter, (uint32_t)(counter >> 32), (uint32_t) p, (uint32_t)(p >> 32)}, k[2] = {(uint32_t) seed, (uint32_t)(seed >> 32)};
 	uint32_t w[4];
 	hu_philox4x32_10(c, k, w);
-	return hu_pm_mulhi64(((uint64_t) w[1] << 32) | w[0], i + 1);
+	return hu_pm_mulhi64(((uint64_t) w[1] << 32) | w[0], range);
 }
+/* the partner j in [0, i] of position i in the shuffle of permutation p */
+HU_HD inline uint64_t hu_pm_partner(uint64_t seed, uint64_t p, uint64_t i) { return hu_pm_partner_in(seed, p, i, i + 1); }
 /* the Fisher-Yates shuffle of permutation p on the n labels g[0], g[stride], ...: the host's rows and the columns of k_label_shuffle */
 template<class T> HU_HD inline void hu_pm_shuffle(uint64_t seed, uint64_t p, int64_t n, T* g, int64_t stride = 1) {
 	for(int64_t i = n - 1; i >= 1; --i) {

@@ -931,6 +931,113 @@ def permanova_timing() -> dict:
     return dict(to_device=s[0], shuffle=s[1], pairs=s[2], finish=s[3])
 
 
+class DesignVar(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("value", C.POINTER(C.c_double)), ("label", C.POINTER(C.c_int32))]
+
+
+class DesignTerm(C.Structure):
+    _fields_ = [("a", C.c_int32), ("b", C.c_int32)]
+
+
+class PermanovaDesignOpts(C.Structure):
+    _fields_ = [("perms", C.c_int64), ("seed", C.c_uint64), ("host", C.c_int32), ("index32", C.c_int32), ("chunk", C.c_int64), ("mem_budget", C.c_int64)]
+
+
+class PermanovaDesignTerm(C.Structure):
+    _fields_ = [("df", C.c_int64), ("df_res", C.c_int64), ("ss", C.c_double), ("ss_res", C.c_double), ("ss_total", C.c_double), ("R2", C.c_double),
+                ("F", C.c_double), ("count_ge", C.c_int64), ("count_nan", C.c_int64), ("p", C.c_double)]
+
+
+def design_build(variables: dict, terms, factors=()) -> dict:
+    """hu_design_build (host only): the orthonormal, centred basis of a design.  variables: name -> values [n]; a variable is numeric when
+    its values are numbers and its name is not in `factors`, otherwise categorical, its levels numbered in order of first appearance.
+    terms: names, an interaction as 'a:b'.  dict(Q [n][q], q, term_start [T + 1], df [T], dropped [T])."""
+    names = list(variables)
+    if not names or not terms:
+        raise EngineError("design_build: variables and one term at the least")
+    keep, cvars = [], (DesignVar * len(names))()
+    n = len(variables[names[0]])
+    for k, name in enumerate(names):
+        vals = list(variables[name])
+        if len(vals) != n:
+            raise EngineError("design_build: variable '%s' has %d of %d values" % (name, len(vals), n))
+        numeric = name not in factors and all(isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool) for x in vals)
+        if numeric:
+            a = np.ascontiguousarray(vals, np.float64)
+            cvars[k].kind = 0; cvars[k].value = _p(a, C.c_double)
+        else:
+            first = {}
+            a = np.ascontiguousarray([first.setdefault(x, len(first)) for x in vals], np.int32)
+            cvars[k].kind = 1; cvars[k].label = _p(a, C.c_int32)
+        keep.append(a)
+    cterms = (DesignTerm * len(terms))()
+    for t, term in enumerate(terms):
+        parts = str(term).split(":")
+        if len(parts) > 2 or any(p not in names for p in parts):
+            raise EngineError("design_build: term '%s': one variable, or two joined by ':'" % term)
+        cterms[t].a = names.index(parts[0]); cterms[t].b = names.index(parts[1]) if len(parts) == 2 else -1
+    lib = load_library()
+    lib.hu_design_raw_columns.restype = C.c_int64
+    T = len(terms)
+    raw = int(lib.hu_design_raw_columns(C.c_int64(n), C.c_int64(len(names)), cvars, C.c_int64(T), cterms))
+    if raw < 0:
+        _chk(-1)
+    Q = np.zeros(max(n * raw, 1)); q = C.c_int64()
+    ts = np.zeros(T + 1, np.int64); df = np.zeros(T, np.int64); dropped = np.zeros(T, np.int64)
+    tn = (C.c_char_p * T)(*[str(t).encode() for t in terms])
+    _chk(lib.hu_design_build(C.c_int64(n), C.c_int64(len(names)), cvars, C.c_int64(T), cterms, tn, _p(Q, C.c_double), C.byref(q), _p(ts, C.c_int64), _p(df, C.c_int64),
+                             _p(dropped, C.c_int64)))
+    return dict(Q=Q[:n * q.value].reshape(n, q.value).copy(), q=q.value, term_start=ts, df=df, dropped=dropped)
+
+
+def permanova_perms(n: int, strata=None, seed=1, first=0, count=1) -> np.ndarray:
+    """hu_permanova_perms (host only): [count][n], the index arrays of permutations first .. first + count - 1: the design row of sample i
+    is row out[p][i] of the basis.  strata [n]: dense labels; a sample moves within its stratum only."""
+    s = None if strata is None else np.ascontiguousarray(strata, np.int32)
+    if s is not None and s.shape != (int(n),):
+        raise EngineError("permanova_perms: strata [n]")
+    out = np.zeros((int(count), int(n)), np.int64)
+    _chk(load_library().hu_permanova_perms(C.c_int64(int(n)), _p(s, C.c_int32) if s is not None else None, C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_int64(int(first)),
+                                           C.c_int64(int(count)), _p(out, C.c_int64)))
+    return out
+
+
+def permanova_design(dist, Q, term_start, strata=None, perms=999, seed=1, chunk=0, device=0, host=False, mem_budget=0, index32=False) -> dict:
+    """hu_permanova_design: sequential PERMANOVA of the terms of the basis Q [n][q] (design_build) on the distance matrix dist [n][n]:
+    dict(terms [T] of dict(df, df_res, ss, ss_res, ss_total, R2, F, count_ge, count_nan, p), ss_total, ss_res, df_res, ss_perm [perms][T]).
+    host: the library's host path, no device needed; the two paths agree within the bound of DESIGN.md §33, not in their bits."""
+    d = np.ascontiguousarray(dist, np.float64); B = np.ascontiguousarray(Q, np.float64); ts = np.ascontiguousarray(term_start, np.int64)
+    s = None if strata is None else np.ascontiguousarray(strata, np.int32)
+    if d.ndim != 2 or d.shape[0] != d.shape[1] or B.ndim != 2 or B.shape[0] != d.shape[0] or ts.ndim != 1 or len(ts) < 2 or (s is not None and s.shape != (d.shape[0],)):
+        raise EngineError("permanova_design: dist [n][n], Q [n][q], term_start [T + 1] and strata [n]")
+    lib = load_library()
+    o = PermanovaDesignOpts()
+    lib.hu_permanova_design_default_opts(C.byref(o))
+    o.perms = int(perms); o.seed = int(seed) & (2 ** 64 - 1); o.host = 1 if host else 0; o.index32 = 1 if index32 else 0; o.chunk = int(chunk or 0)
+    o.mem_budget = int(mem_budget or 0)
+    T = len(ts) - 1
+    res = (PermanovaDesignTerm * T)()
+    ss = np.zeros((max(int(perms), 0), T))
+    _chk(lib.hu_permanova_design(C.c_int(int(device)), C.c_int64(d.shape[0]), _p(d, C.c_double), _p(B, C.c_double), C.c_int64(B.shape[1]), C.c_int64(T), _p(ts, C.c_int64),
+                                 _p(s, C.c_int32) if s is not None else None, C.byref(o), res, _p(ss, C.c_double) if ss.size else None))
+    terms = [{k: getattr(r, k) for k, _ in PermanovaDesignTerm._fields_} for r in res]
+    return dict(terms=terms, ss_total=terms[0]["ss_total"], ss_res=terms[0]["ss_res"], df_res=terms[0]["df_res"], ss_perm=ss)
+
+
+def permanova_design_need(n: int, q: int, T: int, chunk: int, index32=False) -> int:
+    """hu_permanova_design_need: the bytes of device memory that n samples, q design columns in T terms and `chunk` permutations per launch take"""
+    lib = load_library()
+    lib.hu_permanova_design_need.restype = C.c_int64
+    return int(lib.hu_permanova_design_need(C.c_int64(int(n)), C.c_int64(int(q)), C.c_int64(int(T)), C.c_int64(int(chunk)), C.c_int32(1 if index32 else 0)))
+
+
+def permanova_design_timing() -> dict:
+    """hu_permanova_design_timing: the phases of this thread's last permanova_design on a device, in seconds"""
+    s = np.zeros(4)
+    _chk(load_library().hu_permanova_design_timing(_p(s, C.c_double)))
+    return dict(to_device=s[0], shuffle=s[1], quad=s[2], finish=s[3])
+
+
 def dist_matrix_read(path) -> dict:
     """hu_dist_matrix_read (host only): the matrix hmmufotu-amd-unifrac -o writes, as dict(samples, dist [n][n])"""
     lib = load_library()

@@ -1118,6 +1118,85 @@ int hu_dist_matrix_dims(const hu_dist_matrix* m, int64_t* n);
 const char* hu_dist_matrix_sample(const hu_dist_matrix* m, int64_t i);
 const double* hu_dist_matrix_values(const hu_dist_matrix* m);     /* [n][n], row-major */
 
+/* ---- hmmufotu-amd-permanova --design: covariates, several terms, strata (sequential sums of squares) ----
+ * dist [n][n] as hu_permanova takes it, D2_ij = d_ij * d_ij (one rounded product).  An ordered list of T >= 1 terms, each a numeric
+ * variable (one column), a categorical variable of L levels (L - 1 indicator columns, of the labels 1 .. L-1: the caller numbers the
+ * levels in order of first appearance) or an interaction A:B of two variables (every product of a raw column of A with a raw column
+ * of B, A's columns the outer loop).  An optional stratum label per sample.
+ * hu_design_build (host): every raw column is centred, and one that holds a numeric variable is divided by its centred 2-norm.  The
+ * columns are walked in term order: each is orthogonalised against all kept columns by modified Gram-Schmidt, applied twice, centred
+ * again and normalised; a column whose norm after projection is below 1e-10 of its norm before is dropped.  Q [n][q] row-major: its
+ * columns are orthonormal and orthogonal to the vector of ones.  df_t = the kept columns of term t, columns term_start[t] ..
+ * term_start[t + 1] - 1; df_res = n - 1 - q.  Every inner product and every sum of the builder is compensated (two-product, two-sum), so
+ * that max |Q'Q - I| <= q 2^-50 and max |1'Q| <= n 2^-52 hold (§33).  Q must have room for n * hu_design_raw_columns doubles; the first
+ * n * q of them are the result.  HU_ERR_ARG by name (term_name [T], may be NULL: then by number) for a term with df_t = 0 ("adds nothing
+ * to the terms before it"), for df_res < 1, for a value that is not finite, for labels that are negative or not dense.
+ * Statistic, for a permutation pi of the sample indices (the design row of sample i is row pi(i) of Q), v_c[i] = Q[pi(i)][c]:
+ *     s_c = v_c' D2 v_c,  SS_t = -1/2 sum_{c of term t, ascending} s_c,  SS_res = SS_T - (sum_t SS_t, t ascending),  SS_T = hu_permanova's,
+ *     F_t = (SS_t / df_t) / (SS_res / df_res),  R2_t = SS_t(observed) / SS_T,
+ *     p_t = (1 + #{pi : F_t(pi) >= F_t(obs) - 2^-26 |F_t(obs)|}) / (perms + 1).
+ * The raw data are permuted (as vegan's adonis2(by = "terms")).  The observed statistic is the identity run through the same code.  The
+ * tolerance 2^-26 is vegan's sqrt(eps) convention, not a measurement: a relabelling that keeps a categorical design's column space gives
+ * the same F in exact arithmetic but other vectors and so other bits.  A permutation whose F_t is NaN does not count (count_nan).
+ * Permutation p is a function of (seed, p, strata) alone: from the identity index array, for every stratum with members m_0 < ... <
+ * m_{k-1}, for t = k-1 down to 1: x = Philox4x32-10 of the counter (m_t, p) under the key seed, packed as hu_permanova packs (i, p),
+ * j = the high 64 bits of x (t + 1), swap idx[m_t] and idx[m_j].  Without strata these are hu_permanova's swaps: group[idx[i]] equals
+ * hu_permanova_labels(n, group, seed, p)[i].
+ * Order of sums: the bits of s_c are a function of (n, D2, v_c) alone.  On the device the rows go in blocks of 64 and the columns of D2
+ * in the K slabs of hu_pcoa (a function of n); a cell of D2 v is accumulated by v_mfma_f64_16x16x4_f64 over its slab in ascending steps
+ * of 4; over the block's 64 rows the cells times v_i are added in a fixed order: the 4 rows of a lane ascending by fma from +0, then by
+ * plain adds the 4 lane groups ascending, the 4 waves ascending, the slabs ascending and the row blocks ascending.  Neither chunk, nor the column's place in a
+ * launch, nor the grid enters.  The host path (opts->host, or device < 0: one thread, straight loops, no device needed) is held to the
+ * same derived error bound as the device, |SS_t - exact| <= df_t n^3 2^-50 max D2, not to its bits: the matrix instruction's inner
+ * order is not documented.
+ * hu_permanova_design: Q, q, term_start as hu_design_build gives them (any orthonormal centred basis is taken); result [T];
+ * ss_perm (may be NULL) [perms][T] receives SS_t of every permutation.  index32: 32-bit entries of the index array on the device where
+ * 16-bit ones would do (n <= 65,536); the results are the same bits.
+ * HU_ERR_ARG with the reason, before a device is asked for: the matrix refusals of hu_permanova, n < 3, q < 1, df_res < 1, a Q that is
+ * not finite, term_start not ascending from 0 to q, a stratum label that is negative or not dense, every stratum a single sample,
+ * perms < 1 or > 10^7, chunk < 0.  HU_ERR_NOMEM with the bytes needed and the bytes free when hu_permanova_design_need exceeds
+ * mem_budget (checked before a device is asked for) or what the device reports free.
+ * hu_permanova_design_need: with c = chunk rounded up to 64, e = 2 (n <= 65,536 and no index32) or 4, w = c q rounded up to 64,
+ * b = ceil(n / 64) and s the K slabs of n: 8 n^2 for the matrix, e n c for the index array, 8 n q for Q, 8 b s w for the partial sums,
+ * 8 w + 8 c T for the outputs, 4 (2 n + 1) for the strata and 1 MB of slack; -1 on a bad argument.  chunk 0 in the options: the largest
+ * multiple of 64 that fits, 16,384 at the most.
+ * hu_permanova_design_timing: of this thread's last device call, seconds [4] = copies up (with the squares), shuffles, quadratic-form
+ * kernel, finish and copy back.
+ * hu_permanova_perms: host only, out [count][n] the index arrays of permutations first .. first + count - 1. */
+typedef struct {
+	int32_t kind;         /* 0: numeric (value [n]); 1: categorical (label [n], dense in 0 .. L-1) */
+	int32_t reserved;
+	const double* value;
+	const int32_t* label;
+} hu_design_var;
+typedef struct {
+	int32_t a, b;         /* the variables of the term; b < 0: the variable a alone */
+} hu_design_term;
+typedef struct {
+	int64_t perms;        /* 999 */
+	uint64_t seed;        /* 1 */
+	int32_t host;         /* 0; 1: the host path, no device needed */
+	int32_t index32;      /* 0; 1: 32-bit index entries on the device at any n */
+	int64_t chunk;        /* 0: chosen from n, q and the memory */
+	int64_t mem_budget;   /* 0: what the device reports free */
+} hu_permanova_design_opts;
+typedef struct {
+	int64_t df, df_res;
+	double ss, ss_res, ss_total, R2, F;
+	int64_t count_ge, count_nan;
+	double p;
+} hu_permanova_design_term;
+int64_t hu_design_raw_columns(int64_t n, int64_t n_var, const hu_design_var* var, int64_t T, const hu_design_term* term);
+int hu_design_build(int64_t n, int64_t n_var, const hu_design_var* var, int64_t T, const hu_design_term* term, const char* const* term_name,
+		double* Q, int64_t* q, int64_t* term_start /* [T + 1] */, int64_t* df /* [T] */, int64_t* dropped /* [T] */);
+void hu_permanova_design_default_opts(hu_permanova_design_opts* o);
+int hu_permanova_perms(int64_t n, const int32_t* strata /* [n] or NULL */, uint64_t seed, int64_t first, int64_t count, int64_t* out /* [count][n] */);
+int hu_permanova_design(int device, int64_t n, const double* dist, const double* Q, int64_t q, int64_t T, const int64_t* term_start,
+		const int32_t* strata /* [n] or NULL */, const hu_permanova_design_opts* opts, hu_permanova_design_term* result /* [T] */,
+		double* ss_perm /* [perms][T] or NULL */);
+int64_t hu_permanova_design_need(int64_t n, int64_t q, int64_t T, int64_t chunk, int32_t index32);
+int hu_permanova_design_timing(double* seconds /* [4] */);
+
 /* ---- hmmufotu-amd-tree: a neighbour-joining tree from the MSA ----
  * Plain neighbour joining (Saitou and Nei 1987, in the form of Studier and Keppler 1988) on the pairwise distances of the alignment's
  * rows: not a maximum-likelihood search.  rows [n][cs_len]: the pruned alignment in the codes of hu_msa_encode_table (0..3 = A C G T, a
