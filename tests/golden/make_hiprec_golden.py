@@ -1,7 +1,7 @@
-"""Regenerates tests/golden/hiprec.npz, hiprec_wide.npz and hiprec_deep.npz: the floating-point stages of the per-read task in 50-digit
-arithmetic.
+"""Regenerates tests/golden/hiprec.npz, hiprec_wide.npz, hiprec_deep.npz and hiprec_deepwide.npz: the floating-point stages of the per-read
+task in 50-digit arithmetic.
 
-    python tests/golden/make_hiprec_golden.py [--set narrow|wide|deep] [--out PATH] [--workers N]
+    python tests/golden/make_hiprec_golden.py [--set narrow|wide|deep|deepwide] [--out PATH] [--workers N]
 
 A second derivation, independent of oracle/ and of the engine: it is written from the reference's source (cited as file:line below)
 and the mathematics, imports neither, and works in LINEAR space with mpmath (mp.dps = 50) where both of them work in log space with
@@ -60,6 +60,34 @@ every inner row of the data the argmax of the exact message.
   seed in use (2681) 0 of 180 (GTR+4) and 7 of 164 (JC69, 4.3 %) candidates are knife-edge.  Measured cost: 155 CPU-seconds, 27 s of wall
   time with 8 workers (21 s of them the message sweeps).
 
+--set deepwide (hiprec_deepwide.npz) is the deep set at the wide set's width: what every production read is.  GTR with 4 rate categories at
+a mean branch length of 0.3 and JC69 without dGamma at 0.15, on 1,029 leaves x 3,300 columns of which 1,200 are match columns.  Two
+database arguments differ from the deep and the wide set's, both because a condition below cannot hold otherwise.  With 1,024 leaves the
+children of the root hold 735 and 289 leaves, and among a read's twelve candidates no branch then has `up` and `down` both below -510 (up +
+down of a column is about its root message, -1,204 / -1,420 at the lowest: the subtree must hold 42 to 58 % of the leaves); with 1,029
+leaves they hold 534 and 495.  With the default 601 match columns a read of 256 base sites holds bases on about 47 of them, and under
+GTR+4 a column is deep by its rate category, one in four at any branch length: about 11 deep columns per read, never 16 for all seven.
+  Asserted from the 50-digit values (change READ_SEED or the database arguments if one fails, not the conditions): 301 (GTR+4) and 1,200
+  (JC69) match columns with a root message below -510 (the lowest -841 / -986, the highest of a match column -41 / -777; the lowest of any
+  column -1,208 / -1,427); the largest spread between the finite components of a message 17.7 nats (below 200); every inner row the argmax of
+  the exact message.
+  Reads (DEEPWIDE_READS), seven per database, made exactly as make_wide_reads makes them: (columns, base sites) = (1024, 256), (1024, 257),
+  (1536, 256), (1400, 257), (2048, 300), (3072, 500), (3073, 300), one per pair of shipped estimate / placement instances above the 4-site
+  class.  Asserted per read: bases on at least 16 match columns with a root message below -510 and, on GTR+4, on at least 16 above it
+  (GTR+4: 21 to 40 deep and 59 to 136 other; JC69: 82 to 175 deep).
+  Candidates (cand_nodes(short=True)), twelve per read and from the tree alone, a prefix and a suffix of the deep set's list: the read's
+  leaf, its sibling and the next three ancestors each with its sibling; the two children of the root; the two lowest-numbered leaves of the
+  other root subtree (fewer under a shallow leaf, never fewer than 8).  Asserted per read, as for the deep set: a leaf, a branch with only
+  `down` below -510 at a column of the read, a branch with `up` and `down` both below -510 at one column.
+  Stored as the deep archive is: digests of parent / blen / seq, `cand` / `n_cand`, every per-candidate value, the q complements for the
+  (1024, 256) and the (3072, 500) read, both messages of the 62 candidate nodes at the MSG_COLS columns with the lowest, a median and the
+  highest root message, the root log-likelihood at those three columns and its serial sum over all 3,300, the heights, `read_shapes`.
+  The sweeps run by column chunks of at least 64 columns (16 chunks per database with 8 workers).  A subtree whose leaves are all gaps at a
+  column sends the same message at every such column, so that message is formed once per node and chunk and shared (the same operations on
+  the same numbers: the deep archive is reproduced byte for byte); at a sparse column of 1,029 leaves only the ancestors of the one or two
+  leaves with a base are left.  With the read seed in use (2711) none of the 2 x 84 candidates is knife-edge.  Measured cost: 21.4
+  CPU-minutes, 3 minutes 12 s of wall time with 8 workers.
+
 The archive is written with fixed zip timestamps, so a rerun reproduces it byte for byte.
 """
 from __future__ import annotations
@@ -105,7 +133,13 @@ DEEP = dict(name="deep", out="hiprec_deep.npz", cases=[("GTR", 4), ("JC69", 0)],
             mean_blen=(0.3, 0.15), read_seed=2681, q_reads=(0, 3))  # q-values for the whole-width and the 30 % diverged read
 DEEP_LL = -510                                                   # src/PhyloTreeUnrooted.h:1495-1510: messages below it are rescaled there
 DEEP_MIN_COLS, DEEP_MAX_SPREAD, DEEP_MAX_CAND = 16, 200, 48
-SETS = dict(narrow=NARROW, wide=WIDE, deep=DEEP)
+# --set deepwide: the deep set's tree at the wide set's width, one read per pair of shipped instances above the 4-site class
+DEEPWIDE_READS = [(1024, 256), (1024, 257), (1536, 256), (1400, 257), (2048, 300), (3072, 500), (3073, 300)]
+DEEPWIDE = dict(name="deepwide", out="hiprec_deepwide.npz", cases=[("GTR", 4), ("JC69", 0)],
+                db_args=dict(n_leaves=1029, cs_len=3300, n_match=1200), mean_blen=(0.3, 0.15), read_seed=2711, q_reads=(0, 5),
+                read_shapes=DEEPWIDE_READS)                         # q-values for (1024, 256) and (3072, 500)
+DEEPWIDE_MIN_CAND, DEEPWIDE_CHUNK = 8, 64
+SETS = dict(narrow=NARROW, wide=WIDE, deep=DEEP, deepwide=DEEPWIDE)
 A, C, G, T = 0, 1, 2, 3
 
 
@@ -347,15 +381,17 @@ def make_reads(s):
     return [(r[0], r[1], r[2]) for r in reads]
 
 
-def make_wide_reads(s):
-    """(codes [L], start, end) per entry of WIDE_READS, made as tests/test_loads_batched.py makes its reads: a random leaf's row (its
+def make_wide_reads(s, shapes=WIDE_READS, src=None):
+    """(codes [L], start, end) per entry of `shapes` (src: a list that takes each read's leaf), made as tests/test_loads_batched.py makes its reads: a random leaf's row (its
     parent's inferred base where the leaf has a gap) with 3 % substitutions, `bases` base sites, the two ends among them, in a region of
     `cols` columns; every other site a gap"""
     rng = np.random.default_rng(s.read_seed + s.ci)
     leaves = np.flatnonzero(s.is_leaf)
     reads = []
-    for cols, bases in WIDE_READS:
+    for cols, bases in shapes:
         u = int(leaves[rng.integers(len(leaves))])
+        if src is not None:
+            src.append(u)
         start = int(rng.integers(20, s.L - cols - 20)); end = start + cols - 1
         at = np.concatenate([[start, end], start + 1 + rng.choice(cols - 2, size=bases - 2, replace=False)])
         b = np.where(s.seq[u, at] >= 0, s.seq[u, at], s.seq[s.parent[u], at]).astype(np.int8)
@@ -368,9 +404,21 @@ def make_wide_reads(s):
 
 
 # ----------------------------------------------------------------------------- the deep set
+_SETUPS = {}
+
+
 def deep_setup(ci, cfg=DEEP):
-    """the data of a deep case, its six reads and their candidate lists; no message yet.  The columns of the two short reads are CHOSEN with
-    synth's float64 root message (data, like the rows); that they are deep or not is asserted from the 50-digit values in deep_state."""
+    """the data of a deep (or deepwide) case, its reads and their candidate lists; no message yet.  Built once per process and set (a pool
+    forked after the first call inherits it); every caller gets a shallow copy to hang its messages on."""
+    import copy
+    if (cfg["name"], ci) not in _SETUPS:
+        _SETUPS[(cfg["name"], ci)] = _deep_setup(ci, cfg)
+    return copy.copy(_SETUPS[(cfg["name"], ci)])
+
+
+def _deep_setup(ci, cfg):
+    """The columns of the deep set's two short reads are CHOSEN with synth's float64 root message (data, like the rows); that they are deep
+    or not is asserted from the 50-digit values in deep_state."""
     from hmmufotu_amd import synth
     name, dg_k = cfg["cases"][ci]
     da = cfg["db_args"]
@@ -394,8 +442,13 @@ def deep_setup(ci, cfg=DEEP):
     s.match = (s.seq[np.array(s.is_leaf)] < 0).mean(0) < 0.5    # the columns make_db drew as match columns: few leaf gaps
     root = np.asarray(db.up[0]); mx = root.max(1)
     s.ll_synth = mx + np.log((np.asarray(db.model.pi)[None, :] * np.exp(root - mx[:, None])).sum(1))
-    s.reads, s.src = make_deep_reads(s)
-    s.cands = [cand_nodes(s, u) for u in s.src]
+    if "read_shapes" in cfg:                                     # deepwide: the wide set's reads, twelve candidates each
+        s.src = []
+        s.reads = make_wide_reads(s, cfg["read_shapes"], s.src)
+        s.cands = [cand_nodes(s, u, short=True) for u in s.src]
+    else:
+        s.reads, s.src = make_deep_reads(s)
+        s.cands = [cand_nodes(s, u) for u in s.src]
     s.msg_nodes = sorted(set(u for c in s.cands for u in c))
     need = set()                                                 # down of a node takes its parent's: the candidates and their ancestors
     for u in s.msg_nodes:
@@ -465,9 +518,11 @@ def make_deep_reads(s):
     return [(r[0], r[1], r[2]) for r in reads], [r[3] for r in reads]
 
 
-def cand_nodes(s, leaf):
+def cand_nodes(s, leaf, short=False):
     """the candidates of a read from the tree alone: every ancestor of its leaf up to a child of the root (the leaf first), each followed
-    by its sibling -- the last pair is the two children of the root --, then the four lowest-numbered leaves of the other root subtree"""
+    by its sibling -- the last pair is the two children of the root --, then the four lowest-numbered leaves of the other root subtree.
+    short (deepwide): a prefix and a suffix of that list, twelve nodes -- the leaf, its sibling and the next three ancestors each with its
+    sibling; the two children of the root; the first two of the far leaves -- or, under a shallow leaf, what there is of them"""
     out = []
     u = leaf
     while u != 0:
@@ -484,6 +539,10 @@ def cand_nodes(s, leaf):
             far.append(v)
             if len(far) == 4:
                 break
+    if short:
+        out = out[:8] + [u for u in out[-2:] if u not in out[:8]] + far[:2]
+        assert len(out) == len(set(out)) >= DEEPWIDE_MIN_CAND, "fewer than %d candidates: change READ_SEED" % DEEPWIDE_MIN_CAND
+        return out
     out += far
     assert len(out) == len(set(out)) <= DEEP_MAX_CAND, "more than %d candidates: change READ_SEED" % DEEP_MAX_CAND
     return out
@@ -492,8 +551,8 @@ def cand_nodes(s, leaf):
 def deep_sweep(task):
     """the 50-digit messages of one deep case at the columns `cols`: `up` of every node, `down` of the candidates and their ancestors.  Kept:
     both messages of the candidate nodes, the root log-likelihood, and what the conditions of deep_state are asserted from."""
-    ci, cols = task
-    s = deep_setup(ci)
+    ci, cols = task[0], task[1]                                  # (case, columns[, set]): the deep set unless the task names another
+    s = deep_setup(ci, SETS[task[2]] if len(task) > 2 else DEEP)
     pi, dg = s.model.pi, s.dg_k > 0
     Pn = [None] + [[s.model.P(s.blen[i] * r) for r in s.rates] for i in range(1, s.n)]
     up = [None] * s.n; down = {}
@@ -502,14 +561,28 @@ def deep_sweep(task):
     def see(m):
         pos = [x for x in m if x > 0]
         return mp.log(max(pos)) - mp.log(min(pos))
+    # A subtree whose leaves are all gaps at a column sends the same message at every such column: formed once per node, by the same
+    # operations on the same numbers, and shared.  At a sparse column of 1,000 leaves only the ancestors of the one or two leaves with a
+    # base are left to compute.
+    below = np.zeros((s.n, len(cols)), bool)                     # [node][k]: every leaf under it is a gap at cols[k]
+    gap_up = [None] * s.n; gap_spread = [None] * s.n; gap_arg = {}
     for u in range(s.n - 1, -1, -1):                             # parents are numbered before their children
         if s.is_leaf[u]:
-            up[u] = {j: leaf_vec(int(s.seq[u, j]), pi) for j in cols}
+            below[u] = s.seq[u, cols] < 0
+            gap_up[u] = leaf_vec(GAP, pi)
+            up[u] = {j: gap_up[u] if below[u, k] else leaf_vec(int(s.seq[u, j]), pi) for k, j in enumerate(cols)}
         else:
-            up[u] = {j: join([(Pn[c], up[c][j]) for c in s.kids[u]], dg) for j in cols}
-            for j in cols:                                       # components equal in exact arithmetic (JC69): any of them
-                assert up[u][j][int(s.seq[u, j])] >= max(up[u][j]) * (1 - TIE), "inner row %d of the database is not the argmax of the 50-digit message" % u
-        spread = max([spread] + [see(up[u][j]) for j in cols])
+            below[u] = np.logical_and.reduce([below[c] for c in s.kids[u]])
+            gap_up[u] = join([(Pn[c], gap_up[c]) for c in s.kids[u]], dg)
+            up[u] = {j: gap_up[u] if below[u, k] else join([(Pn[c], up[c][j]) for c in s.kids[u]], dg) for k, j in enumerate(cols)}
+            for k, j in enumerate(cols):                         # components equal in exact arithmetic (JC69): any of them
+                code = int(s.seq[u, j])
+                if below[u, k] and (u, code) not in gap_arg:
+                    gap_arg[(u, code)] = gap_up[u][code] >= max(gap_up[u]) * (1 - TIE)
+                ok = gap_arg[(u, code)] if below[u, k] else up[u][j][code] >= max(up[u][j]) * (1 - TIE)
+                assert ok, "inner row %d of the database is not the argmax of the 50-digit message" % u
+        gap_spread[u] = see(gap_up[u]) if below[u].any() else mpf(0)
+        spread = max([spread, gap_spread[u]] + [see(up[u][j]) for k, j in enumerate(cols) if not below[u, k]])
     for u in s.need_down:
         p = s.parent[u]
         down[u] = {j: join(([(Pn[p], down[p][j])] if p != 0 else []) + [(Pn[c], up[c][j]) for c in s.kids[p] if c != u], dg) for j in cols}
@@ -521,6 +594,7 @@ def deep_sweep(task):
 def deep_state(ci, parts, cfg=DEEP):
     """the state that candidate() reads, from the sweeps of one deep case (all columns, or those of one read), and its conditions"""
     s = deep_setup(ci, cfg)
+    wide = "read_shapes" in cfg
     whole = sorted(j for p in parts for j in p["cols"]) == list(range(s.L))
     s.up = [None] * s.n; s.down = [None] * s.n
     s.root_ll = [None] * s.L
@@ -546,18 +620,23 @@ def deep_state(ci, parts, cfg=DEEP):
         # up + down of one column is about its root message, -1,420 at the lowest: both are below -510 only at an all-gap column, which
         # the two short reads do not hold
         assert not whole or (kinds["leaf"] and kinds["down_only"] and (kinds["both"] or en - st < 2)), "read %d: %s: change READ_SEED" % (ri, kinds)
-    j1 = s.reads[4][1]; j2 = s.reads[5][1]
-    is_deep = lambda j: bool(s.match[j] and s.ll_synth[j] < DEEP_LL)
-    assert is_deep(j1) and (is_deep(j2) != is_deep(j2 + 1) or (s.ll_synth < DEEP_LL).all())
-    for j in (j1, j2, j2 + 1):                                   # what the columns were chosen by holds for the 50-digit values
-        if s.root_ll[j] is not None:
-            assert (s.root_ll[j] < DEEP_LL) == bool(s.ll_synth[j] < DEEP_LL), "column %d: synth's root message and the 50-digit one differ about -510" % j
+    if wide:
+        assert [(en - st + 1, int((cd[st:en + 1] >= 0).sum())) for cd, st, en in s.reads] == cfg["read_shapes"]
+    else:
+        j1 = s.reads[4][1]; j2 = s.reads[5][1]
+        is_deep = lambda j: bool(s.match[j] and s.ll_synth[j] < DEEP_LL)
+        assert is_deep(j1) and (is_deep(j2) != is_deep(j2 + 1) or (s.ll_synth < DEEP_LL).all())
+        for j in (j1, j2, j2 + 1):                               # what the columns were chosen by holds for the 50-digit values
+            if s.root_ll[j] is not None:
+                assert (s.root_ll[j] < DEEP_LL) == bool(s.ll_synth[j] < DEEP_LL), "column %d: synth's root message and the 50-digit one differ about -510" % j
     if not whole:
         s.root_ll_sum = None
         return s
     s.root_ll_sum = sum(s.root_ll)
     deep_cols = [j for j in range(s.L) if s.match[j] and s.root_ll[j] < DEEP_LL]
     assert len(deep_cols) >= DEEP_MIN_COLS, "%d deep match columns: change the database arguments" % len(deep_cols)
+    if wide:
+        return deepwide_conditions(s, deep_cols, spread)
     on0 = [j for j in range(s.L) if s.match[j] and s.reads[0][0][j] >= 0]
     n_deep0 = sum(1 for j in on0 if s.root_ll[j] < DEEP_LL)
     if s.dg_k > 0:                                               # deep and shallow columns side by side under one read
@@ -569,6 +648,28 @@ def deep_state(ci, parts, cfg=DEEP):
           "the whole-width read on %d deep and %d other match columns, %d message nodes" %
           (case_name(s.name, s.dg_k), len(deep_cols), int(s.match.sum()), DEEP_LL, float(min(s.root_ll[j] for j in deep_cols)),
            float(min(s.root_ll)), float(spread), n_deep0, len(on0) - n_deep0, len(s.msg_nodes)), flush=True)
+    return s
+
+
+def deepwide_conditions(s, deep_cols, spread):
+    """what deep_state asserts of a deepwide case beyond the deep set's conditions: every read holds bases on at least DEEP_MIN_COLS match
+    columns with a root message below -510 and, with dGamma, on as many above it: deep and shallow columns side by side in one region"""
+    counts = []
+    for ri, (codes, st, en) in enumerate(s.reads):
+        on = [j for j in range(st, en + 1) if s.match[j] and codes[j] >= 0]
+        n_deep = sum(1 for j in on if s.root_ll[j] < DEEP_LL)
+        assert n_deep >= DEEP_MIN_COLS, "read %d: bases on %d deep match columns: change READ_SEED or the database arguments" % (ri, n_deep)
+        if s.dg_k > 0:
+            assert len(on) - n_deep >= DEEP_MIN_COLS, "read %d: bases on %d other match columns: change READ_SEED or the database arguments" % (ri, len(on) - n_deep)
+        counts.append("%d+%d" % (n_deep, len(on) - n_deep))
+    order = sorted(range(s.L), key=lambda j: (s.root_ll[j], j))
+    s.msg_cols = sorted({order[0], order[s.L // 2], order[-1]})  # the lowest, a median and the highest root message
+    assert len(s.msg_cols) == MSG_COLS
+    print("%-7s %d of %d match columns below %d at the root (lowest %.1f, highest of any match column %.1f; lowest of any column %.1f), "
+          "largest spread %.1f nats, reads on deep+other match columns %s, candidates per read %s, %d message nodes" %
+          (case_name(s.name, s.dg_k), len(deep_cols), int(s.match.sum()), DEEP_LL, float(min(s.root_ll[j] for j in deep_cols)),
+           float(max(s.root_ll[j] for j in range(s.L) if s.match[j])), float(min(s.root_ll)), float(spread), " ".join(counts),
+           [len(c) for c in s.cands], len(s.msg_nodes)), flush=True)
     return s
 
 
@@ -751,7 +852,7 @@ def _task(t):
 
 def assemble(states, results, cfg=NARROW):
     """{key: array} of the whole archive"""
-    if cfg["name"] == "deep":
+    if cfg["name"] in ("deep", "deepwide"):
         return assemble_deep(states, results, cfg)
     wide = cfg["name"] == "wide"
     da = cfg["db_args"]
@@ -820,6 +921,9 @@ def assemble_deep(states, results, cfg):
     arc = {"max_error": np.array(MAX_ERROR), "dps": np.array(mp.dps), "read_seed": np.array(cfg["read_seed"]),
            "q_reads": np.array(cfg["q_reads"], np.int32), "db_args": np.array([da["n_leaves"], da["cs_len"], da["n_match"]], np.int32),
            "mean_blen": np.array(cfg["mean_blen"]), "cases": np.array([case_name(*c) for c in cfg["cases"]])}
+    wide = "read_shapes" in cfg                                  # deepwide: the root log-likelihood at the MSG_COLS columns only
+    if wide:
+        arc["read_shapes"] = np.array(cfg["read_shapes"], np.int32)
     over = []
     for s in states:
         px = case_name(s.name, s.dg_k) + "_"
@@ -832,7 +936,7 @@ def assemble_deep(states, results, cfg):
         arc[px + "msg_nodes"] = np.array(s.msg_nodes, np.int32)
         arc[px + "up"] = np.array([[[flog(x) for x in s.up[u][j]] for j in s.msg_cols] for u in s.msg_nodes])
         arc[px + "down"] = np.array([[[flog(x) for x in s.down[u][j]] for j in s.msg_cols] for u in s.msg_nodes])
-        arc[px + "root_ll"] = np.array([float(x) for x in s.root_ll])
+        arc[px + "root_ll"] = np.array([float(s.root_ll[j]) for j in (s.msg_cols if wide else range(s.L))])
         arc[px + "root_ll_sum"] = np.array(float(s.root_ll_sum))
         arc[px + "codes"] = np.stack([r[0] for r in s.reads])
         arc[px + "start"] = np.array([r[1] for r in s.reads], np.int32)
@@ -915,10 +1019,15 @@ def main():
     workers = max(1, min(16, a.workers))
     ctx = multiprocessing.get_context("fork")
     n = len(cfg["cases"])
-    if a.set == "deep":                                          # the sweeps by column chunks: a column's messages depend on no other's
+    deep = a.set in ("deep", "deepwide")
+    if deep:                                                     # the sweeps by column chunks: a column's messages depend on no other's
         L = cfg["db_args"]["cs_len"]
         per = max(1, workers // n)
-        chunks = [(ci, list(range(k, L, per))) for ci in range(n) for k in range(per)]
+        if a.set == "deepwide":                                  # chunks of DEEPWIDE_CHUNK columns or more: a worker's P(t) of every branch are amortised
+            per = max(1, min(L // DEEPWIDE_CHUNK, 4 * workers // n))
+            for ci in range(n):                                  # built here, inherited by the forked workers
+                deep_setup(ci, cfg)
+        chunks = [(ci, list(range(k, L, per)), a.set) for ci in range(n) for k in range(per)]
         with ctx.Pool(min(workers, len(chunks))) as pool:
             parts = pool.map(deep_sweep, chunks)
         states = [deep_state(ci, [p for p in parts if p["ci"] == ci], cfg) for ci in range(n)]
@@ -927,11 +1036,11 @@ def main():
             states = pool.starmap(db_state, [(ci, None, cfg) for ci in range(n)])
     for s in states:
         _STATES[(a.set, s.ci)] = s
-    nodes_of = (lambda s, ri: s.cands[ri]) if a.set == "deep" else (lambda s, ri: range(1, s.n))
+    nodes_of = (lambda s, ri: s.cands[ri]) if deep else (lambda s, ri: range(1, s.n))
     tasks = [((a.set, s.ci), ri, u) for s in states for ri in range(len(s.reads)) for u in nodes_of(s, ri)]
     tasks.sort(key=lambda t: -(states[t[0][1]].reads[t[1]][2] - states[t[0][1]].reads[t[1]][1]) * (1 + max(states[t[0][1]].dg_k, 1)))
     with ctx.Pool(workers) as pool:                              # forked after _STATES is filled: the workers inherit it
-        results = dict(pool.imap_unordered(_task, tasks, chunksize=4))
+        results = dict(pool.imap_unordered(_task, tasks, chunksize=1 if a.set == "deepwide" else 4))
     write_archive(out, assemble(states, results, cfg))
     print("wrote %s: %d bytes" % (out, os.path.getsize(out)))
 

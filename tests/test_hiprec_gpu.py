@@ -99,15 +99,72 @@ one-column read against a leaf of another base).  em_branch_blk forms p as p0 ti
 once q is below 2^-53; q = 1 - p was then negative and -log q NaN, where the reference's quotient never rounds above 1, reads q = 0 and
 takes the cap.  p is now clamped to 1 (no other output changes: the case gave NaN before).
 With tree_conv's scale forced to 0 test_deep_tree_messages_and_loglik fails on both databases, with TreeAcc::finish's on GTR+4 alone, and
-every other test of this file passes on both builds.  Not covered: the wide instances at depth (1,024 leaves x 3,300
-columns at 50 digits is about an hour and a half of CPU).
+every other test of this file passes on both builds.
+
+The deepwide set (tests/golden/hiprec_deepwide.npz, test_deepwide_*): the wide instances at depth, the regime of every production read.
+GTR+4 (mean branch length 0.3) and JC69 (0.15) on 1,029 leaves x 3,300 columns, 1,200 of them match columns: 301 / 1,200 of the match
+columns have a root message below -510 (the lowest -841 / -986), the sparse columns reach -1,208 / -1,427, so the packing exponents are
+about -2,000 per site and the carried sum of a read about -1e6 to -6e6, with deep and shallow columns side by side among one thread's sites
+on GTR+4.  Seven reads per database (DEEPWIDE_READS: the rows of WIDE_INSTANCES above the 4-site class that differ in their pair of
+instances), each in a batch of its own against a database uploaded once, with twelve candidates given through Batch.get_seed_given (the
+read's leaf and three ancestors with their siblings, the children of the root, two leaves of the other root subtree; the (d, N) of the
+given seeds are asserted).  The instance is asserted from the trace lines against the row of WIDE_INSTANCES / WIDE_KNOB_FORMS with the
+read's shape, and every test first asserts from the rebuilt database's own root message that its read holds bases on at least 16 match
+columns below -510.  Bounds by the wide and deep rule from the CPU's distances (ORACLE_DEEPWIDE), fixed before a kernel ran on this set.
+
+  quantity (deepwide set)                          oracle    narrow bound  bound     kernels' worst (MI355X, over every instance)
+  estimated loglik, relative                       2.1e-14   2.1e-13       2.1e-13   1.4e-15
+  weighted wnr, relative to max(|x|, 1e-3)         4.6e-14   2.9e-13       4.6e-13   4.1e-15
+  placed ratio, wnr, relative to max(|x|, 1e-3)    5.8e-12   4.5e-10       4.5e-10   2.5e-12
+  placed height, relative to max(|x|, 1e-3)        5.7e-13   1.7e-11       1.7e-11   7.3e-13
+  intended root loglik, relative                   1.9e-14   4.8e-14       1.9e-13   1.5e-15
+  the reference's constant loglik, relative        1.6e-16   1e-12         1e-12     1.6e-16
+  q-values, eps of the conditioned bound           2.4e-11   1.2e-11       2.4e-10   1.3e-12
+  counts, ratio, unweighted wnr, iteration counts, filter sets, taxon nodes                    exact (no knife-edge candidate among 168)
+
+  per instance (deepwide set, both databases)      reads (columns)                     est. loglik   weighted wnr
+  k_estimate_prod<4,4>                             1,024 (256 and 257 bases)           1.2e-15       3.8e-15
+  k_estimate_prod<6,4,4>                           1,400, 1,536                        1.4e-15       4.1e-15
+  k_estimate_prod<8,4>                             2,048                               1.3e-15       2.5e-15
+  k_estimate_prod<6,8,2>                           3,072                               1.4e-15       2.8e-15
+  k_estimate_prod<12,4> (est_var = 4)              3,072                               1.4e-15
+  k_estimate_blk<4 .. 12,256> (est_var = 2)        1,024, 1,536, 2,048, 3,072          1.4e-15
+  k_estimate (streaming)                           3,073; 1,024 under streaming_sep    1.3e-15       2.4e-15
+                                                                                       ratio, wnr    height     root loglik
+  k_place_blk<8,2,3,0,3,false,3,6> (v in LDS)      1,024 (256 bases)                   2.5e-12       7.3e-13    1.2e-15
+  k_place_blk<8,2,3,0,2,false,0,6> (place_var 6)   1,024 (256 bases)                   2.5e-12       7.3e-13
+  k_place_blk<8,2,3,0,2>                           1,024 (257 bases; place_nosplit)    2.5e-12       7.3e-13    1.2e-15
+  k_place_blk<12,2,3,0,2,false,1,10>               1,536                               1.0e-12       2.4e-13    1.4e-15
+  k_place_blk<12,2,3,0,2,false,1>                  1,400 (257 bases; place_nosplit)    1.1e-12       2.4e-13    1.2e-15
+  k_place_blk<12,2,1,0,2> (place_var 6)            1,024 and 1,400 (257 bases)         1.1e-12       4.6e-13
+  k_place_blk<12,2,3,0,2> (place_var 7)            1,536                               1.0e-12       2.4e-13
+  k_place_blk<8,4,3,0,1>                           2,048                               1.5e-12       7.5e-14    1.5e-15
+  k_place_blk<12,4,3,0,2,false,1>                  3,072                               1.2e-12       6.6e-13    1.4e-15
+  k_place_blk<12,4,3,0,1> (place_var 9)            3,072                               1.2e-12       6.6e-13
+  k_place (streaming)                              3,073; 1,024 under streaming_sep    1.9e-12       2.9e-13    1.3e-15
+
+All 80 tests passed on their first run: no kernel bug was found at depth and width.  What the set can and cannot see, on three scratch
+builds run against the wide, deep and deepwide tests:
+  (a) `ksum` of k_estimate_prod accumulated in an int16_t: every test passes, the deepwide ones included.  A site's two exponents add up
+      to about its root message over ln 2, at most -2,059 here, and a thread holds at most twelve sites: -24,700, inside 16 bits.  The
+      per-thread sum could leave 16 bits only on a tree of about 1,400 leaves or more; this set does not reach that.
+  (b) the guard of em_branch_blk for p > 1 removed: the four deep tests of JC69's one-column read fail with NaN, as when the bug was found;
+      no deepwide (or wide) instance returns NaN.  p exceeds 1 only once q is below 2^-53, which takes a read that contradicts the
+      candidate at every base site; a read of 256 or more base sites never does.  The guard stands after the EM loop of the one
+      em_branch_blk template that every instance is built from, so the deep set's two instances stand for the others there.
+  (c) the wave's exponent sum of k_estimate_prod truncated to 16 bits before the waves are added: all 38 deepwide tests that compare an
+      estimated loglik of a k_estimate_prod instance fail (every shipped instance and every knob form, both databases; k_estimate_blk and
+      the streaming kernel, which carry the exponent their own way, pass), the deep set fails on k_estimate_prod<2,4>, and all 126 wide
+      tests pass: a wave's sum is about -1e6 here and about -1e4 on the wide set.
+So the set holds the carried exponent of every wide instance to the exact values from the wave level upwards, and the placement
+instances to the exact lengths on rescaled messages; it does not reach a thread's own 32-bit sum, nor the p > 1 corner.
 """
 import re
 
 import numpy as np
 import pytest
 
-from hiprec_cases import CASES, DEEP_CASES, DEEP_LL, WIDE_CASES, WIDE_READS, Case, level_shape, q_ok, ratio_half
+from hiprec_cases import CASES, DEEP_CASES, DEEP_LL, DEEPWIDE_CASES, DEEPWIDE_READS, WIDE_CASES, WIDE_READS, Case, level_shape, q_ok, ratio_half
 
 pytestmark = pytest.mark.gpu
 
@@ -213,7 +270,7 @@ def _run(c, knobs=None, stop_after=None, D=None, **opts_kw):
         B.set_knob(k, v)
     B.set_aligned(c.codes, c.start, c.end)
     opts = E.default_opts(**dict(dict(max_error=1e9), **opts_kw))
-    if c.archive == "deep":                                      # the read's own candidate list, given: the seeds come back in its order
+    if c.deep:                                      # the read's own candidate list, given: the seeds come back in its order
         B.get_seed_given(c.n_cand, c.cand)
         cnt, ids, sd, sN = B.seeds()
         n_cand = c.cand.shape[1]
@@ -606,4 +663,120 @@ def test_deep_streaming_kernels(deep, capfd, name):
     c, out, ran = _deep_run(deep, capfd, name, knobs=dict(streaming_sep=1), fix_root_loglik=1)
     _check_estimates(c, name, out["est"], False, "deep_estimate_streaming", bound_deep)
     _check_places(c, name, out, "deep_place_streaming", 0, 1, bound_deep)
+    assert ran == ("k_estimate", "k_place", "column order")
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# The deepwide set (tests/golden/hiprec_deepwide.npz): the deep set's models and branch lengths on 1,029 leaves x 3,300 columns, 1,200 of them
+# match columns, and seven of the wide set's read shapes (DEEPWIDE_READS: one per pair of shipped instances above the 4-site class), each
+# with twelve candidates given through Batch.get_seed_given and each in a batch of its own.  Every instance therefore runs on messages whose
+# packing exponents are in the thousands, deep and shallow columns side by side among one thread's sites (GTR+4) or deep everywhere (JC69).
+# The instance a read must select is the row of WIDE_INSTANCES / WIDE_KNOB_FORMS with its shape: looked up, not copied.
+#
+# the oracle's worst distance from the 50-digit values over both databases, measured on the CPU before any kernel ran on this set
+# (tests/test_hiprec_oracle.py, the HIPREC oracle_deepwide_* lines)
+ORACLE_DEEPWIDE = dict(est_ll=2.1e-14, est_wnr_w=4.6e-14, length=5.8e-12, height=5.7e-13, root_ll=1.9e-14, q_eps=2.4e-11)
+INSTANCE_OF = {w[0]: w[1:] for w in WIDE_INSTANCES}
+DEEPWIDE_INSTANCES = [(shape,) + INSTANCE_OF[shape] for shape in DEEPWIDE_READS]
+DEEPWIDE_KNOB_FORMS = [w for w in WIDE_KNOB_FORMS if w[0] in DEEPWIDE_READS]
+DEEPWIDE_Q_SHAPES = [(1024, 256), (3072, 500)]                  # the reads whose q complements the archive holds
+
+
+def bound_deepwide(key):
+    """the wide and deep rule: min(project floor, max(the narrow bound, 10 x the CPU's worst distance over the deepwide set))"""
+    return min(FLOOR[FLOOR_OF[key]], max(TEN_X[key], 10.0 * ORACLE_DEEPWIDE[key]))
+
+
+@pytest.fixture(scope="module")
+def deepwide():
+    """(case, uploaded database, the deep match columns) of a deepwide case, shared by the tests of this module: the upload of 2,057 nodes x
+    3,300 columns is the only part that takes seconds.  The columns are found from the rebuilt database's own root message, as the
+    generator's deep_setup forms it."""
+    held = {}
+
+    def get(name):
+        if name not in held:
+            c = Case(name, "deepwide")
+            db = c.db
+            match = (db.seq[db.is_leaf] < 0).mean(0) < 0.5
+            root = np.asarray(db.up[0]); mx = root.max(1)
+            ll = mx + np.log((np.asarray(db.model.pi)[None, :] * np.exp(root - mx[:, None])).sum(1))
+            held[name] = (c, _engine().Database.from_synth(db), match & (ll < DEEP_LL))
+        return held[name]
+    yield get
+    for _, D, _ in held.values():
+        D.close()
+
+
+def _deepwide_run(deepwide, capfd, name, shape, knobs=None, **kw):
+    c, D, deep_cols = deepwide(name)
+    ri = DEEPWIDE_READS.index(shape)
+    # a quietly shallower database fails here: the read holds bases on at least 16 match columns whose root message is rescaled
+    assert int((deep_cols & (c.codes[ri] >= 0)).sum()) >= 16
+    one = c.one_read(ri)
+    assert (ri in c.q_reads) == (shape in DEEPWIDE_Q_SHAPES)
+    capfd.readouterr()
+    out = _run(one, knobs=dict(knobs or {}, trace=1), D=D, **kw)
+    return one, out, _instances(capfd.readouterr().err, shape[0])
+
+
+@pytest.mark.parametrize("name", DEEPWIDE_CASES)
+@pytest.mark.parametrize("shape,est_k,place_k,order", DEEPWIDE_INSTANCES, ids=_shape_id)
+def test_deepwide_estimate_place_q(deepwide, capfd, name, shape, est_k, place_k, order):
+    """default knobs: the unweighted estimate, the placement with the constant loglik, q-values where the archive holds them; the (d, N)
+    of the given seeds are asserted in _run"""
+    one, out, ran = _deepwide_run(deepwide, capfd, name, shape)
+    tag = "%s:%dx%d" % ((name,) + shape)
+    print("HIPREC deepwide_instance %s %s %s (%s)" % ((tag,) + ran))
+    _check_estimates(one, "%s:%s" % (tag, ran[0]), out["est"], False, "deepwide_estimate", bound_deepwide)
+    _check_places(one, "%s:%s" % (tag, ran[1]), out, "deepwide_place", bound=bound_deepwide)
+    assert ran == (est_k, place_k, order)
+
+
+@pytest.mark.parametrize("name", DEEPWIDE_CASES)
+@pytest.mark.parametrize("shape,est_k,place_k,order", DEEPWIDE_INSTANCES, ids=_shape_id)
+def test_deepwide_estimate_weighted(deepwide, capfd, name, shape, est_k, place_k, order):
+    one, out, ran = _deepwide_run(deepwide, capfd, name, shape, stop_after="estimate", weighted=1)
+    _check_estimates(one, "%s:%dx%d:%s" % (name, shape[0], shape[1], ran[0]), out["est"], True, "deepwide_estimate_weighted", bound_deepwide)
+    assert ran[0] == est_k
+
+
+@pytest.mark.parametrize("name", DEEPWIDE_CASES)
+@pytest.mark.parametrize("shape,est_k,place_k,order", DEEPWIDE_INSTANCES, ids=_shape_id)
+def test_deepwide_fixed_root_loglik(deepwide, capfd, name, shape, est_k, place_k, order):
+    """fix_root_loglik = 1: k_root_loglik over regions of up to 3,073 rescaled columns; the two q reads with prior HEIGHT as well"""
+    for prior in (0, 1) if shape in DEEPWIDE_Q_SHAPES else (0,):
+        one, out, ran = _deepwide_run(deepwide, capfd, name, shape, prior=prior, fix_root_loglik=1)
+        _check_places(one, "%s:%dx%d:%s" % (name, shape[0], shape[1], ran[1]), out, "deepwide_place_prior%d_fix1" % prior, prior, 1, bound_deepwide)
+        assert ran == (est_k, place_k, order)
+
+
+@pytest.mark.parametrize("name", DEEPWIDE_CASES)
+@pytest.mark.parametrize("shape,est_k,place_k,order", DEEPWIDE_INSTANCES, ids=_shape_id)
+def test_deepwide_filter_set_at_the_default_max_error(deepwide, capfd, name, shape, est_k, place_k, order):
+    one, out, ran = _deepwide_run(deepwide, capfd, name, shape, max_error=deepwide(name)[0].max_error)
+    got = sorted(int(x) for x in out["cand"]["c_node"][int(out["offs"][0]):int(out["offs"][1])])
+    assert got == sorted(int(u) for u, keep in zip(one.cands(0), one.filter_in[0]) if keep)
+    assert ran == (est_k, place_k, order)
+
+
+@pytest.mark.parametrize("name", DEEPWIDE_CASES)
+@pytest.mark.parametrize("shape,knobs,est_k,place_k,order", DEEPWIDE_KNOB_FORMS,
+                         ids=["%dx%d-%s" % (w[0] + ("-".join("%s%d" % kv for kv in sorted(w[1].items())),)) for w in DEEPWIDE_KNOB_FORMS])
+def test_deepwide_knob_forms(deepwide, capfd, name, shape, knobs, est_k, place_k, order):
+    """the instances that only a comparison knob reaches, on rescaled messages"""
+    one, out, ran = _deepwide_run(deepwide, capfd, name, shape, knobs=knobs)
+    tag = "%s:%dx%d" % ((name,) + shape)
+    print("HIPREC deepwide_instance %s %s %s (%s)" % ((tag,) + ran))
+    _check_estimates(one, "%s:%s" % (tag, ran[0]), out["est"], False, "deepwide_knob_estimate", bound_deepwide)
+    _check_places(one, "%s:%s" % (tag, ran[1]), out, "deepwide_knob_place", bound=bound_deepwide)
+    assert ran == (est_k, place_k, order)
+
+
+@pytest.mark.parametrize("name", DEEPWIDE_CASES)
+def test_deepwide_streaming_kernels(deepwide, capfd, name):
+    """streaming_sep = 1 on the (1024, 256) read: the one-wave kernels carry the exponent their own way over 1,024 columns"""
+    one, out, ran = _deepwide_run(deepwide, capfd, name, (1024, 256), knobs=dict(streaming_sep=1), fix_root_loglik=1)
+    _check_estimates(one, "%s:1024x256:%s" % (name, ran[0]), out["est"], False, "deepwide_estimate_streaming", bound_deepwide)
+    _check_places(one, "%s:1024x256:%s" % (name, ran[1]), out, "deepwide_place_streaming", 0, 1, bound_deepwide)
     assert ran == ("k_estimate", "k_place", "column order")

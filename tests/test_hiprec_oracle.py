@@ -28,6 +28,13 @@ in tests/test_hiprec_gpu.py.  Messages are measured there by hiprec_cases.level_
 1.3e-13) and shape 4.7e-12 (synth 9.3e-12), root loglik 2.8e-14, estimated and root logliks 4.9e-15, weighted wnr 2.0e-14 relative, placed
 lengths 1.3e-11 and height 7.8e-13 relative to max(|x|, 1e-3), q eps 8.0e-12; counts, filter sets and taxon nodes equal.  The oracle is
 right at depth too.
+The deepwide set (tests/golden/hiprec_deepwide.npz: GTR+4 and JC69 at the deep set's branch lengths on 1,029 leaves x 3,300 columns, 1,200 of
+them match columns; seven of the wide set's read shapes, 1,024 to 3,073 columns, with twelve given candidates each; no knife-edge candidate
+among the 168) runs under the same rules and bounds (test_deepwide_*).  Its figures are printed as HIPREC oracle_deepwide_* lines and anchor
+ORACLE_DEEPWIDE in tests/test_hiprec_gpu.py; they were measured before any kernel ran on this set.  Measured: message level 9.6e-15 (synth
+1.4e-14) and shape 1.6e-12 (synth 8.4e-12), root loglik 6.8e-15 (synth 9.6e-15), estimated logliks 2.1e-14, weighted wnr 9.0e-15 absolute
+(4.6e-14 relative), intended root loglik 1.9e-14, placed ratio 1.6e-13 and wnr 6.5e-13 absolute (5.8e-12 relative to max(|x|, 1e-3)),
+height 5.7e-13 relative, q eps 2.4e-11; counts, filter sets and taxon nodes equal.
 """
 import glob
 import importlib.util
@@ -37,7 +44,7 @@ import re
 import numpy as np
 import pytest
 
-from hiprec_cases import CASES, DEEP_CASES, DEEP_LL, WIDE_CASES, WIDE_READS, Case, level_shape, q_ok, ratio_half
+from hiprec_cases import CASES, DEEP_CASES, DEEP_LL, DEEPWIDE_CASES, DEEPWIDE_READS, WIDE_CASES, WIDE_READS, Case, level_shape, q_ok, ratio_half
 
 REL = 1e-6
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -188,7 +195,7 @@ def _assign(c):
         st, en = int(c.start[ri]), int(c.end[ri])
         seeds = c.cands(ri)
         n_cand = len(seeds)
-        given = dict(seeds=seeds) if c.archive == "deep" else {}      # the deep set: the read's own list in place of getSeed's
+        given = dict(seeds=seeds) if c.deep else {}      # the deep set: the read's own list in place of getSeed's
         res = T.assign(c.codes[ri], st, en, O.default_opts(maxError=c.max_error), **given)
         assert sorted(int(x) for x in res["seed_ids"]) == sorted(int(x) for x in seeds)
         assert sorted(int(x) for x in res["filt_order"]) == sorted(int(u) for u, keep in zip(seeds, c.filter_in[ri]) if keep), ri
@@ -246,7 +253,11 @@ def test_deep_messages(name):
     """the oracle's two-pass pruning and synth's numpy messages where both rescale (src/PhyloTreeUnrooted.h:1495-1510): the old measure
     (1e-11 relative to max(|x|, 1)) and the depth-aware pair hiprec_cases.level_shape.  Level 1e-11: the old bound on the largest
     component.  Shape 1e-9 absolute: the relative error of the linear value that the project asks of a message of magnitude <= 1."""
-    c = Case(name, "deep")
+    _deep_messages(Case(name, "deep"), "deep_messages")
+
+
+def _deep_messages(c, test):
+    name = c.name
     O, m, _ = _oracle(c)
     db = c.db
     leaf_only = np.where(db.is_leaf[:, None], db.seq, 0).astype(np.int8)
@@ -254,7 +265,9 @@ def test_deep_messages(name):
     assert np.array_equal(seq, db.seq)
     assert np.abs(h - c.height).max() < 1e-14
     # the archive is deep where it says: stored messages of both kinds below the rescaling level
-    assert (c.up.max(-1) < DEEP_LL).any() and (c.down.max(-1) < DEEP_LL).any() and (c.root_ll < DEEP_LL).sum() >= 16
+    whole = len(c.root_ll) == db.cs_len                          # the deepwide archive holds the root log-likelihood at msg_cols only
+    assert (c.up.max(-1) < DEEP_LL).any() and (c.down.max(-1) < DEEP_LL).any()
+    assert (c.root_ll < DEEP_LL).sum() >= 16 if whole else (c.root_ll.min() < DEEP_LL and (_root_ll(up[0], m.pi) < DEEP_LL).sum() >= 16)
     worst = {}
     for who, (u_, d_) in dict(oracle=(up, down), synth=(db.up, db.down)).items():
         for side, got, want in (("up", u_[c.msg_nodes][:, c.msg_cols], c.up), ("down", d_[c.msg_nodes][:, c.msg_cols], c.down)):
@@ -263,8 +276,8 @@ def test_deep_messages(name):
             old = (np.abs(got[~inf] - want[~inf]) / np.maximum(np.abs(want[~inf]), 1.0)).max()
             worst.update({"%s_%s_level" % (who, side): level, "%s_%s_shape" % (who, side): shape, "%s_%s_rel" % (who, side): old})
         ll = _root_ll(u_[0], m.pi)
-        worst[who + "_tree_ll"] = max((np.abs(ll - c.root_ll) / np.abs(c.root_ll)).max(), _rel(ll.sum(), c.root_ll_sum))
-    report("deep_messages", name, **worst)
+        worst[who + "_tree_ll"] = max((np.abs((ll if whole else ll[c.msg_cols]) - c.root_ll) / np.abs(c.root_ll)).max(), _rel(ll.sum(), c.root_ll_sum))
+    report(test, name, **worst)
     for k, v in worst.items():
         assert np.isfinite(v) and v < (1e-12 if k.endswith("tree_ll") else 1e-9 if k.endswith("shape") else 1e-11), (k, v)
 
@@ -282,6 +295,30 @@ def test_deep_place(name):
 @pytest.mark.parametrize("name", DEEP_CASES)
 def test_deep_assign_filter_set_and_q_values(name):
     report("deep_q", name, **_assign(Case(name, "deep")))
+
+
+# ---- the deepwide set (tests/golden/hiprec_deepwide.npz): the deep set's branch lengths on 1,029 leaves x 3,300 columns, seven of the wide
+# set's read shapes with twelve given candidates each, under the same rules and bounds
+@pytest.mark.parametrize("name", DEEPWIDE_CASES)
+def test_deepwide_messages(name):
+    _deep_messages(Case(name, "deepwide"), "deepwide_messages")
+
+
+@pytest.mark.parametrize("name", DEEPWIDE_CASES)
+def test_deepwide_estimate(name):
+    c = Case(name, "deepwide")
+    assert c.n_reads == len(DEEPWIDE_READS) and (c.n_cand >= 8).all() and (c.n_cand <= 12).all()
+    report("deepwide_estimate", name, **_estimate(c))
+
+
+@pytest.mark.parametrize("name", DEEPWIDE_CASES)
+def test_deepwide_place(name):
+    report("deepwide_place", name, **_place(Case(name, "deepwide")))
+
+
+@pytest.mark.parametrize("name", DEEPWIDE_CASES)
+def test_deepwide_assign_filter_set_and_q_values(name):
+    report("deepwide_q", name, **_assign(Case(name, "deepwide")))
 
 
 def test_the_archive_is_the_generators_output():
@@ -323,6 +360,18 @@ def test_the_archive_is_the_generators_output():
         assert got[key] == getattr(c, key)[ri, k], key
     assert (got["pl_outer"], got["pl_em"], got["pl_a_node"]) == (int(c.pl_outer[ri, k]), int(c.pl_em[ri, k]), int(c.pl_a_node[ri, k]))
     assert np.float32(got["margin"]) == c.margin[ri, k] and np.float32(got["margin_cond"]) == c.margin_cond[ri, k]
+    # and of the deepwide set one message column, the median one of JC69, swept again over its 2,057 nodes: the stored messages of the
+    # candidate nodes and the root log-likelihood of that column.  No candidate of that set is regenerated here: its sweep over the 1,024
+    # or more columns of a read is a quarter of a CPU-hour.
+    c = Case("JC690", "deepwide")
+    k = 1
+    j = int(c.msg_cols[k])
+    part = gen.deep_sweep((DEEPWIDE_CASES.index("JC690"), [j], "deepwide"))
+    assert sorted(part["down"]) == [int(u) for u in c.msg_nodes]
+    for x, u in enumerate(c.msg_nodes):
+        assert [gen.flog(v) for v in part["up"][int(u)][j]] == c.up[x, k].tolist(), u
+        assert [gen.flog(v) for v in part["down"][int(u)][j]] == c.down[x, k].tolist(), u
+    assert float(part["root_ll"][j]) == c.root_ll[k]
 
 
 def test_only_the_generator_imports_mpmath():
